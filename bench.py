@@ -15,11 +15,23 @@ reference's `accelerator.gather_for_metrics` (audiozen/trainer.py:511,555).
 
 `python bench.py --gpus N` without a launcher re-executes itself under torch.distributed.run (one rank per GPU).
 
-Phases: S -- one forward at a time (THE STRICT B=64 FIGURE, `config.single_stream`), then the same forward as whole-sequence
-launches with per-kernel HIP-event timers (the roofline figures of the strict schedule); K -- the scan kernels of the timed
-region's geometry, each alone on the chip; B -- the timed region: `--inflight` independent batches in flight, each lane on its
-OWN input batch (seeded per lane), EXACTLY K steps between barrier + synchronize on both sides, max over ranks -> `value`;
-then 2,000 one-frame hops of a B=1 streaming session (BASELINE configs[4]) -> `config.streaming`.
+A plain run does what the headline needs and nothing else: set up (one untimed forward on the default stream first, so that the
+engine's side streams exist before the lanes' -- see phase B), warm up, B -- the timed region: `--inflight` independent
+batches in flight, each lane on its OWN input batch (seeded per lane), EXACTLY K steps (dealt round-robin over the lanes) between
+barrier + synchronize on both sides, max over ranks -> `value` and `ms_per_step`; then `--dump-outputs DIR` if given, and the line.
+
+    --dump-outputs DIR  after the timed steps, what the last timed step returned to its caller (enh_stft as [..., 2] re / im,
+                        enh_mag, every fb_all / sb_all tensor, ...) as DIR/<name>.npy in float32: arrays above a per-array cap as a
+                        fixed sample (flat indices drawn with a seed derived from the name), 64 MB at most in all.  Inputs and weights
+                        are seeded, so two builds run with the same arguments can be compared output for output.
+    --full              everything else the benchmark measures, before and behind the timed region:
+                        S -- one forward at a time (THE STRICT B=64 FIGURE, `config.single_stream`), then the same forward as
+                        whole-sequence launches with per-kernel HIP-event timers (the roofline figures of the strict schedule);
+                        K -- the scan kernels of the timed region's geometry, each alone on the chip; a device-to-device copy (the
+                        roof as the box delivers it); behind the region the lean (`config.no_layer_outputs`), 16-bit-weight
+                        (`config.w16`), streaming (`config.streaming`, 2,000 one-frame hops of a B=1 session, BASELINE configs[4])
+                        and training (`config.training`) legs, `roofline`, and `cpu_baseline`.  The `--no-*` options below switch
+                        single legs of a --full run off.
 
 Prints ONE JSON line on rank 0 (see the task contract), carrying
   roofline      -- top level: the JOB -- algorithmic bytes of one forward (whole path) / ms_per_step of the timed region,
@@ -33,6 +45,7 @@ Prints ONE JSON line on rank 0 (see the task contract), carrying
                    (source hash) on this workload (B, T, geometry, forwards in flight);
   cpu_baseline  -- the CPU oracle (oracle/, a C restatement of the reference) timed on this host's cores on the whole workload
                    (all B clips x all T frames, groups of clips side by side; rank 0, N=1 only).
+Both are null in a run without --full, as are the `config` fields of the phases and legs it adds.
 """
 from __future__ import annotations
 
@@ -148,7 +161,12 @@ def main():
     ap.add_argument("--no-w16-leg", action="store_true", help="skip the 16-bit-weight report leg (config.w16) behind the timed region")
     ap.add_argument("--weight-bits", type=int, default=24, choices=(24, 16), help="16: the WHOLE line in the 16-bit-weight mode (module.weight_bits = 16; a report mode, not the parity gate)")
     ap.add_argument("--no-streaming-leg", action="store_true", help="skip the 2,000-hop streaming measurement (config.streaming) behind the timed region")
+    ap.add_argument("--full", action="store_true", help="also run the phases and legs beside the headline (strict forward, per-kernel and roofline "
+                                                        "figures, lean / w16 / streaming / training legs, CPU baseline); off: the timed region alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned as DIR/<name>.npy (float32, "
+                                                                        "large arrays as a fixed seeded sample, 64 MB at most in all)")
     args = ap.parse_args()
+    phase_a = args.full and not args.no_phase_a  # the untimed phases S / K and every leg behind the region
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -239,17 +257,19 @@ def main():
         return dt
 
     # ---- the roof as this box delivers it: a 1 GiB device-to-device copy (read + write), next to the 8 TB/s spec number
-    src_ = torch.empty((1 << 28,), dtype=torch.float32, device=dev)
-    dst_ = torch.empty_like(src_)
-    for _ in range(3):
-        dst_.copy_(src_)
-    torch.cuda.synchronize()
-    t_c = time.perf_counter()
-    for _ in range(10):
-        dst_.copy_(src_)
-    torch.cuda.synchronize()
-    copy_gbps = 10 * 2 * src_.numel() * 4 / (time.perf_counter() - t_c) / 1e9
-    del src_, dst_
+    copy_gbps = None
+    if phase_a:
+        src_ = torch.empty((1 << 28,), dtype=torch.float32, device=dev)
+        dst_ = torch.empty_like(src_)
+        for _ in range(3):
+            dst_.copy_(src_)
+        torch.cuda.synchronize()
+        t_c = time.perf_counter()
+        for _ in range(10):
+            dst_.copy_(src_)
+        torch.cuda.synchronize()
+        copy_gbps = 10 * 2 * src_.numel() * 4 / (time.perf_counter() - t_c) / 1e9
+        del src_, dst_
 
     scan_tags = None if args.time_all else {"scan:sb", "scan:fb", "stack:sb", "stack:fb", "scanx:sb", "scanf:sb"}
     geom_b = tuple(int(v) for v in args.rpw.split(",")) if args.rpw else (8, 16)
@@ -261,20 +281,16 @@ def main():
         eng.rows_per_wg = g
         eng.stack_rows_fb_auto = g[0] if g[0] in (4, 8, 16) else 4
     n_lanes = 1 if args.sequential else max(1, min(args.inflight, args.steps))  # (--steps 20: 12 lanes measured 36-37 M, 10 lanes 34.5-35.8 M frames/s)
-    # The timed region deals its steps round-robin over the lanes: a step count that is not a multiple of the lanes leaves some lanes one
-    # forward short, i.e. the region ends in a drain where part of the chip idles (--steps 20 on 12 lanes = 12 + 8: the driver's line
-    # sat 2.4 % under the 60-step one, round-5 review).  The count is rounded UP to a multiple of the lanes; the line says so
-    # (`steps` = the steps actually timed, `config.steps_requested` = the command line's) and `value` counts exactly the timed steps.
+    # The timed region deals its steps round-robin over the lanes and times exactly `--steps` of them: a count that is not a multiple
+    # of the lanes leaves some lanes one forward short, i.e. the region ends in a drain where part of the chip idles (--steps 20 on
+    # 12 lanes = 12 + 8: 2.4 % under the 60-step line, round-5 review) -- a cost that shrinks as the count grows.
     steps_requested = args.steps
-    if n_lanes > 1 and args.steps % n_lanes:
-        args.steps = -(-args.steps // n_lanes) * n_lanes
-        print(f"bench.py: --steps {steps_requested} rounded up to {args.steps} (a multiple of the {n_lanes} lanes in flight)", file=sys.stderr)
 
     # ---- phase S (untimed for `value`): THE STRICT NUMBER -- one forward at a time on one stream, B clips x T frames per step,
     #      nothing else in flight.  Launch geometry = the engine's default for a forward alone (full-band stack in one
     #      layer-pipelined launch, sub-band layers as full-chip launches at 4 rows per workgroup).
     single, t_s, t_k = None, {}, {}
-    if not args.no_phase_a:
+    if phase_a:
         set_geometry((0, 0))
         ka = max(2, min(args.steps, 8))
         dt_a = timed_region(forward, ka, min(args.warmup, 2) + 1)
@@ -313,6 +329,14 @@ def main():
     #      scans and time-parallel kernels fill the rest of the chip.  Every step is one complete pass over one batch.
     t_b = {}
     ov_default = eng.overlap_chunks
+    if n_lanes > 1 and not phase_a:
+        # (set-up, untimed) one forward of the engine's default schedule on the default stream BEFORE the lanes' streams exist, as phase S
+        # runs it: it creates the engine's side streams (the overlapped schedule's pair, the error-word stream) ahead of the lanes'.
+        # Created after them, the region measured 17 % slower (28.5-29.5 against 34.7-35.0 M frames/s, 240 steps, GPU_MAX_HW_QUEUES=4):
+        # the creation order decides which hardware queues the lanes share.
+        set_geometry((0, 0))
+        forward()
+        torch.cuda.synchronize()
     if n_lanes > 1:
         eng.overlap_chunks = 0  # the full-band / sub-band overlap of ONE forward only pays when nothing else fills the chip
         set_geometry(geom_b)
@@ -336,11 +360,19 @@ def main():
     else:
         set_geometry(tuple(int(v) for v in args.rpw.split(",")) if args.rpw else (0, 0))
         step = forward
-    dt = timed_region(step, args.steps, args.warmup)
+    last = [None]  # (--dump-outputs: what the last timed step handed its caller)
+
+    def step_kept():
+        last[0] = step()
+    dt = timed_region(step_kept if args.dump_outputs else step, args.steps, args.warmup)
     if eng.timers is not None:
         t_b = eng.timer_summary()
         eng.timers = None
     eng.check_stack_errors()
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, last[0])
+    last[0] = None
 
     # ---- the mode the reference's LIVE recipe runs (recipes/intel_ndns/spiking_fullsubnet/trainer.py:31,52 star-unpack and discard the
     #      per-layer lists; only the frozen trainer reads them, and only to reduce them to SynOPs / NeuronOPs, audiozen/metric.py:303-340):
@@ -348,7 +380,7 @@ def main():
     #      is launched.  Behind the timed region of `value` (which stays API-faithful), same steps: the strict forward, the sub-band
     #      launch alone, and the region with the same lanes.  -> config.no_layer_outputs
     lean = None
-    if want_layers and not args.no_phase_a and not args.sequential:
+    if want_layers and phase_a and not args.sequential:
         eng.lean_skips_proj = True  # (this leg only: the coefficient rows stay in LDS -- sfsn_proj_deepfilter with proj = NULL)
 
         def forward_lean(x=None):
@@ -392,7 +424,7 @@ def main():
     #      `value`): the strict forward, the sub-band launch and the per-layer sub-band scan in both modes, and what the rounding does to
     #      the spike trains and the output on the same input.  -> config.w16
     w16 = None
-    if rank == 0 and want_layers and not args.no_phase_a and not args.no_w16_leg and args.weight_bits == 24:
+    if rank == 0 and want_layers and phase_a and not args.no_w16_leg and args.weight_bits == 24:
         try:
             m16 = pkg.SpikingFullSubNet(**kw)
             m16.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
@@ -461,7 +493,7 @@ def main():
     # ---- BASELINE configs[4] behind the timed region: 2,000 one-frame hops of a B=1 streaming session (about 70 ms), so that the
     #      driver's record of the default command carries the streaming latency too (python bench.py --streaming prints the full line)
     streaming = None
-    if rank == 0 and not args.no_streaming_leg and not args.no_phase_a:
+    if rank == 0 and not args.no_streaming_leg and phase_a:
         try:
             streaming = streaming_measure(model, dev, 1, 1, 2000, 200, None, True, "auto")
         except Exception as e:  # the streaming leg is reported, never required for the headline
@@ -470,7 +502,7 @@ def main():
     # ---- SURVEY 8f-4 behind the timed region too: three training steps (forward in train() mode + backward) of a COPY of the model at
     #      this batch, so that the driver's record of the default command carries the figure (python bench.py --training prints the line)
     training_leg = None
-    if rank == 0 and not args.no_training_leg and not args.no_phase_a:
+    if rank == 0 and not args.no_training_leg and phase_a:
         try:
             m2 = pkg.SpikingFullSubNet(**kw)  # (a fresh module with the same weights: the measured model's engine and buffers stay untouched)
             m2.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
@@ -636,7 +668,7 @@ def main():
                                    "next product reads -- bytes the minimal figure does not count; the fraction is small because the mode is "
                                    "bound by the T-step dependency chain, not by these bytes (per-step us are the figures to read)"))
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cpu = cpu_baseline(kw, sd, stft)
         line = dict(metric="STFT frames/sec at B=64 T=1000 F=257 (hot path: noisy STFT -> enhanced STFT + magnitude)",
                     value=round(frames / dt, 1), unit="frames/s", n_gpus=world, steps=args.steps, warmup=args.warmup,
@@ -649,7 +681,7 @@ def main():
                                 layer_outputs="api-faithful (fp32 spikes returned)" if want_layers else "skipped",
                                 in_flight=n_lanes, scan_rows_per_workgroup=list(eng.rows_per_wg), steps_requested=steps_requested,
                                 single_stream=single, streaming=streaming, training=training_leg, no_layer_outputs=lean_obj, w16=w16,
-                                weight_bits=args.weight_bits,
+                                weight_bits=args.weight_bits, full=args.full, dumped_outputs=dumped,
                                 visible_gpus=torch.cuda.device_count(),
                                 world_size=(dist.get_world_size() if dist is not None else 1), backend=(backend if dist is not None else None),
                                 library=dict(abi=_lib.ABI_VERSION, source_hash=_lib.source_hash(), stack_scan=str(eng.stack_scan)),
@@ -659,6 +691,53 @@ def main():
         JSON_OUT.flush()
     if dist is not None:
         dist.destroy_process_group()
+
+
+DUMP_BUDGET_BYTES = 60_000_000  # all files of --dump-outputs together (under 64 MB in either reading of MB)
+DUMP_MAX_ELEMS = 1 << 20         # per array: at most this many entries (rows of 2 for complex tensors); above, a fixed sample
+
+
+def dump_outputs(out_dir, res):
+    """--dump-outputs: every tensor the timed path handed its caller (the forward's result dict: enh_stft, enh_mag, fb_all[i],
+    sb_all[g][i], ...; None and never-written meta entries skipped) as out_dir/<name>.npy -- complex tensors as [..., 2] (re, im),
+    integer / bool as float32, float64 kept.  An array above the per-array cap is written as a sample: flat indices drawn without
+    replacement by a generator seeded with the crc32 of the name, sorted -- the same entries on every run with the same arguments."""
+    import zlib
+    flat = []
+
+    def walk(name, v):
+        if isinstance(v, torch.Tensor):
+            if v.device.type != "meta":
+                flat.append((name, v))
+        elif isinstance(v, (list, tuple)):
+            for i, e in enumerate(v):
+                walk(f"{name}.{i}", e)
+        elif isinstance(v, dict):
+            for k, e in v.items():
+                walk(f"{name}.{k}" if name else str(k), e)
+    walk("", res)
+    torch.cuda.synchronize()
+    # one entry count for every array: bytes per entry of all arrays together x count + 4 kB per file (npy header) <= the budget
+    row_bytes = sum((8 if t.dtype == torch.float64 else 4) * (2 if t.is_complex() else 1) for _, t in flat)
+    cap = max(1, min(DUMP_MAX_ELEMS, (DUMP_BUDGET_BYTES - 4096 * len(flat)) // max(1, row_bytes)))
+    os.makedirs(out_dir, exist_ok=True)
+    total, sampled = 0, []  # (total: the files' sizes)
+    for name, t in flat:
+        a = torch.view_as_real(t) if t.is_complex() else t
+        a = a.detach().reshape(-1, 2) if t.is_complex() else a.detach().reshape(-1)
+        if a.dtype != torch.float64:
+            a = a.float()
+        if a.shape[0] > cap:
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(a.shape[0], cap, replace=False))
+            a = a[torch.from_numpy(idx).to(a.device)]
+            sampled.append(name)
+        else:
+            a = a.reshape(tuple(t.shape) + ((2,) if t.is_complex() else ()))
+        path = os.path.join(out_dir, f"{name}.npy")
+        np.save(path, a.cpu().numpy())
+        total += os.path.getsize(path)
+    assert total <= DUMP_BUDGET_BYTES, total
+    return dict(dir=out_dir, arrays=len(flat), bytes=total, sampled=sampled, entries_per_sampled_array=cap)
 
 
 def streaming_measure(model, dev, B, hop, steps, warmup, rpw, graph, one_launch):

@@ -10,8 +10,8 @@ rm -rf $OUT && mkdir -p $OUT
 timeout 420 python scripts/diag_region_r05.py > $OUT/clock_digest.txt 2> $OUT/clock.err; echo "diag rc=$?"
 cat $OUT/clock_digest.txt
 B="python bench.py --no-cpu-baseline --no-phase-a --no-streaming-leg"
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/region -o r -- $B --steps 36 --warmup 12 > $OUT/region.log 2>&1
-SFSN_OVERLAP_CHUNKS=0 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/alone -o a -- $B --sequential --rpw 8,16 --steps 6 --warmup 2 > $OUT/alone.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/region -o r -- $B --full --steps 36 --warmup 12 > $OUT/region.log 2>&1
+SFSN_OVERLAP_CHUNKS=0 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/alone -o a -- $B --full --sequential --rpw 8,16 --steps 6 --warmup 2 > $OUT/alone.log 2>&1
 python scripts/ledger_r05.py $OUT/region/r_kernel_trace.csv 36 $OUT/alone/a_kernel_trace.csv > $OUT/ledger.json 2> $OUT/ledger.err
 head -c 1200 $OUT/ledger.json
 # the same region without the fp32 spike tensors (the mode the live recipe runs): value, strict forward

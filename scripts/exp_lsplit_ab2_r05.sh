@@ -1,5 +1,5 @@
 cd $GRAFT_REPO_ROOT
-run() { env $1 timeout 200 python bench.py --no-cpu-baseline --no-streaming-leg --no-training-leg $2 2>/dev/null | tail -1 | python -c "
+run() { env $1 timeout 200 python bench.py --full --no-cpu-baseline --no-streaming-leg --no-training-leg $2 2>/dev/null | tail -1 | python -c "
 import sys,json
 d=json.loads(sys.stdin.read()); s=d['config'].get('single_stream') or {}; nl=(d['config'].get('no_layer_outputs') or {})
 print('$1 $2: value %.2f M, ms %.3f, strict %s, nl strict %s, nl region %s' % (d['value']/1e6, d['ms_per_step'], s.get('ms_per_step'), (nl.get('single_stream') or {}).get('ms_per_step'), ((nl.get('timed_region') or {}).get('value'))))"; }

@@ -7,7 +7,7 @@ OUT=gpurun_out/region_T_r05
 rm -rf $OUT && mkdir -p $OUT
 B="python bench.py --no-cpu-baseline --no-phase-a --no-streaming-leg"
 for T in 500 1000 2000; do
-  timeout 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/T$T -o r -- $B --frames $T --steps 36 --warmup 12 > $OUT/T$T.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/T$T -o r -- $B --full --frames $T --steps 36 --warmup 12 > $OUT/T$T.log 2>&1
   python scripts/ledger_r05.py $OUT/T$T/r_kernel_trace.csv 36 > $OUT/ledger_T$T.json 2> $OUT/ledger_T$T.err
   rm -f $OUT/T$T/r_kernel_trace.csv
 done

@@ -4,6 +4,6 @@ cd $GRAFT_REPO_ROOT/spiking_fullsubnet_amd/csrc && cp libsfsn_hip.so /tmp/keep.s
 cd $GRAFT_REPO_ROOT
 for r in 16 8 4; do
 for v in 3 51; do
-  SFSN_SCAN_RPW=$r SFSN_SCAN_DEBUG_OUT=$v python bench.py --steps 4 --warmup 1 --no-cpu-baseline 2>&1 | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('RPW=$r OUT=$v', 'sb', d['roofline']['launch_ms'], 'fb', d['roofline']['other_kernels_ms']['scan:fb'], 'total', d['ms_per_step'])"
+  SFSN_SCAN_RPW=$r SFSN_SCAN_DEBUG_OUT=$v python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline 2>&1 | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('RPW=$r OUT=$v', 'sb', d['roofline']['launch_ms'], 'fb', d['roofline']['other_kernels_ms']['scan:fb'], 'total', d['ms_per_step'])"
 done; done
 cp /tmp/keep.so spiking_fullsubnet_amd/csrc/libsfsn_hip.so

@@ -2,7 +2,7 @@ cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/prof_pipe
 rm -rf $OUT && mkdir -p $OUT
-rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -o q -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --pipeline > $OUT/trace.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -o q -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --pipeline > $OUT/trace.log 2>&1
 python - <<'PY'
 import csv, collections
 rows=list(csv.DictReader(open('gpurun_out/prof_pipe/trace/q_kernel_trace.csv')))

@@ -10,7 +10,7 @@ rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/single -o s -- $B -
 # (1b) the same without the chunk overlap: every scan is ONE whole-sequence launch (the durations the roofline figures use)
 SFSN_OVERLAP_CHUNKS=0 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/single_whole -o s -- $B --sequential --steps 8 --warmup 3 --no-phase-a > $OUT/single_whole.log 2>&1
 # (2) the default command (phases S, K and the timed region with 12 forwards in flight)
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/default -o d -- $B > $OUT/default.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/default -o d -- $B --full > $OUT/default.log 2>&1
 # (3) PMC passes, whole-sequence launches, one forward at a time
 for c in "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY" "SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD GRBM_GUI_ACTIVE"; do
   tag=$(echo $c | cut -d' ' -f1)
@@ -26,7 +26,7 @@ for c in FETCH_SIZE WRITE_SIZE; do
   SFSN_OVERLAP_CHUNKS=0 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/nl_$c -o p -- $B --sequential --no-layer-outputs --steps 2 --warmup 1 --no-phase-a > $OUT/nl_$c.log 2>&1
   SFSN_OVERLAP_CHUNKS=0 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/nljob_$c -o p -- $B --sequential --no-layer-outputs --rpw 8,16 --steps 3 --warmup 1 --no-phase-a > $OUT/nljob_$c.log 2>&1
 done
-python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 python bench.py --streaming --no-cpu-baseline > $OUT/bench_streaming.json 2>> $OUT/bench_default.err
 python bench.py --streaming --waveform --host-io > $OUT/bench_streaming_waveform_host.json 2>> $OUT/bench_default.err
 # (5) the training step: the line at the recipe's batch, kernel stats of one step at B = 16

@@ -431,6 +431,30 @@ def main():
     if not only or "frozen_m_zoo" in only:
         # the trained baseline_m generator (the sizes bench.py runs: full-band 320, sub-band 224, deep-filter orders 5/3/1)
         frozen_case("frozen_m_zoo.npz", rw.FROZEN_M, zoo_weights("baseline_m"), 1, 100, False, True)
+    if not only or "plugin_init" in only:
+        plugin_init_case(meta)
+
+
+def plugin_init_case(meta, seed=1234):
+    """plugin_init_baseline_m.json: the live recipe's [model] section (baseline_m.toml) and what the reference's own loader,
+    audiozen.utils.instantiate, builds from it under torch.manual_seed(seed) -- the name, shape, dtype and sha256 of every
+    state-dict entry and the parameter order (the checkpoint contract of audiozen/trainer.py:225), without the values."""
+    import hashlib
+    import json
+    import tomli
+    import torch
+    from audiozen.utils import instantiate
+    cfg = tomli.load(open(f"{REF}/recipes/intel_ndns/spiking_fullsubnet/baseline_m.toml", "rb"))["model"]
+    torch.manual_seed(seed)
+    ref = instantiate(cfg["path"], args=cfg["args"])
+    state = [dict(name=k, shape=list(v.shape), dtype=str(v.dtype).replace("torch.", ""),
+                  sha256=hashlib.sha256(v.detach().contiguous().numpy().tobytes()).hexdigest()) for k, v in ref.state_dict().items()]
+    out = dict(recipe="recipes/intel_ndns/spiking_fullsubnet/baseline_m.toml", path=cfg["path"], args=cfg["args"], seed=seed,
+               state_dict=state, parameters=[n for n, _ in ref.named_parameters()], meta=meta)
+    with open(os.path.join(HERE, "plugin_init_baseline_m.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print("plugin_init_baseline_m.json", len(state))
 
 
 if __name__ == "__main__":

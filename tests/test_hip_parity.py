@@ -1966,3 +1966,36 @@ def test_bench_rccl_path_with_a_single_rank():
     assert len(lines) == 1, out.stdout[-2000:]
     d = json.loads(lines[0])
     assert d["config"]["backend"] == "nccl" and d["config"]["world_size"] == 1 and d["n_gpus"] == 1 and d["value"] > 0
+
+
+def test_bench_plain_run_times_exactly_its_steps_and_dumps_the_last_steps_outputs(tmp_path):
+    """bench.py without --full: the timed region alone (no strict forward, legs, roofline or CPU baseline), EXACTLY --steps timed
+    steps also when they are not a multiple of the lanes in flight, `ms_per_step` = the region's time per step; --dump-outputs writes
+    what the last timed step returned (64 MB at most) -- the same files, bit for bit, from two runs with the same arguments."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for k in range(2):
+        d_ = tmp_path / f"run{k}"
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--inflight", "2",
+                              "--dump-outputs", str(d_)], capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = out.stdout.splitlines()
+        assert len(lines) == 1, out.stdout[-2000:]
+        d = json.loads(lines[0])
+        c = d["config"]
+        assert d["steps"] == 5 and d["warmup"] == 2 and c["in_flight"] == 2 and d["unit"] == "frames/s" and d["dtype"] == "f32"
+        assert abs(d["value"] * d["ms_per_step"] / 1e3 - 64 * 1000) < 0.01 * 64 * 1000  # value = B*T frames per ms_per_step
+        assert c["single_stream"] is None and c["no_layer_outputs"] is None and c["w16"] is None and c["streaming"] is None
+        assert c["training"] is None and d["roofline"] is None and d["cpu_baseline"] is None and c["full"] is False
+        files = sorted(os.listdir(d_))
+        assert {"enh_stft.npy", "enh_mag.npy", "fb_all.1.npy", "sb_all.0.1.npy"} <= set(files), files
+        assert sum(os.path.getsize(d_ / f) for f in files) <= 64e6 and c["dumped_outputs"]["arrays"] == len(files)
+        arrs = {f: np.load(d_ / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrs.values())
+        dumps.append(arrs)
+    assert dumps[0].keys() == dumps[1].keys()
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
