@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SFSN_ABI_VERSION 19 /* bumped on every struct / signature change: a stale .so must not load */
+#define SFSN_ABI_VERSION 20 /* bumped on every struct / signature change: a stale .so must not load */
 
 #define SFSN_OK 0
 #define SFSN_EINVAL (-1)       /* malformed argument (NULL where required, size <= 0, misaligned pointer)      */
@@ -557,6 +557,17 @@ typedef struct sfsn_hop_desc {
                                       SFSN_NORM_CUMLAPLACE's denominator                                             */
     int unshared;                  /* non-zero: separate forget / cell gate weights (shared_weights = False, NEURON:137-139): every
                                       layer's w_hh / w_ih images and dq vectors cover 2H rows, forget rows first (ABI 15)      */
+    const unsigned* clip_start;    /* nullable, [B] (ABI 20): per-clip utterances.  clip_start[b] = the launch index at which clip b's
+                                      utterance began (its frame 0); the launch with index k gives clip b frame index k - clip_start[b]
+                                      and (k - clip_start[b]) * hop frames before it (unsigned differences: wrap-safe) instead of
+                                      frame_index / frames_before.  In the launch k == clip_start[b] every stage reads clip b's
+                                      carried state as zero (h, c, cum, hist_ri, ola_state) instead of loading it, so that one clip
+                                      restarts while the others go on.  Waveform mode: in the launch k == clip_start[b] - 1 (the
+                                      clip's first call, no frame yet) the STFT stage leaves [0 x 384 | the new samples] in the clip's
+                                      wave_state; wave_out of clip b is zero while its frame index is < 2.  The caller writes an entry
+                                      only where no launch that is already queued reads it (a stream-ordered fill); the resident
+                                      kernel reads the array (then pinned host memory) after each doorbell.  NULL: the session-wide
+                                      frame_index / frames_before, no restarts                                            */
 } sfsn_hop_desc;
 
 size_t sfsn_hop_scratch_bytes(const sfsn_hop_desc* desc /* host */);
@@ -572,7 +583,8 @@ int sfsn_stream_hop(const sfsn_hop_desc* desc /* host */, void* stream);
  * launch): the kernel never outlives its caller by more than that.  The caller keeps `stream` free of other work while
  * the kernel is resident (it holds the hop's workgroups -- 23 of 256 CUs for the M model at B = 1) and adds the hops served to
  * its own launch / frame counters afterwards; doorbell[1] (zeroed by the caller before the call) is set to 1 by the kernel when it
- * leaves.  Same results as the launches, bit for bit. */
+ * leaves.  Same results as the launches, bit for bit.  desc->clip_start, if set, may be pinned host memory: hop k reads it after
+ * its doorbell, so the host may change entries for hop k + 1 once hop k's done words are in and before it rings hop k + 1. */
 int sfsn_stream_hop_resident(const sfsn_hop_desc* desc /* host */, void* doorbell /* pinned host, u32[2] */, unsigned idle_ms,
                              void* stream);
 /* Diagnostic: the launch's stages in block order, out[4 * i] = {sequence (0 = full-band, 1 + g = group g), layer (-1 = projection

@@ -109,6 +109,7 @@ struct HopParams {
     float* mag;
     unsigned* cnt;    // [0] error word
     unsigned long long* dbg;  // -DSFSN_HOP_STAMPS builds + SFSN_HOP_DEBUG: 8 time stamps (100 MHz) per wave
+    const unsigned* clip_start;  // optional [B]: the launch index at which clip b's utterance began (frame 0); NULL = the counters above
 };
 
 // what changes from hop to hop (a launch takes them from its kernel arguments; the resident kernel counts them up itself)
@@ -140,6 +141,17 @@ __device__ __forceinline__ unsigned long long ld64_agent(const void* p) {
 }
 __device__ __forceinline__ void st64_agent(void* p, unsigned long long v) {
     __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// ---- per-clip utterances (desc.clip_start) -------------------------------------------------------------------------------
+// Clip b's launches since its utterance began, k = launch - clip_start[b] (unsigned: wrap-safe): its frame index, k * hop frames
+// before this launch, and k == 0 marks the launch that restarts it -- every role then reads the clip's carried state as zero instead
+// of loading it.  Waveform mode: k == -1 is the clip's first call (no frame yet: its samples only enter the STFT state; whatever the
+// model stages write for the clip is discarded by the next launch's zero-read).  Uncached loads: the resident kernel reads the
+// origins from pinned host memory, which the host writes before it rings the hop; its (one-frame) roles read them before they
+// publish anything, so a write for the next hop cannot reach a role of this one.
+__device__ __forceinline__ int hop_clip_k(const HopParams& p, const HopStep& hs, int b) {
+    return (int)(hs.launch - __hip_atomic_load(p.clip_start + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM));
 }
 
 // ---- hand-off: data-tagged granules (MI355X_MICROARCH.md, price list row handoff-1to1) ------------------------------------
@@ -269,12 +281,13 @@ __device__ __forceinline__ void hop_layer_role(const HopParams& p, const HopStep
     // operands first
     const int8_t* hprev = L.h[hs.launch & 1u];
     int8_t* hnext = L.h[(hs.launch + 1u) & 1u];
+    const bool fresh = p.clip_start && hop_clip_k(p, hs, rowc / sq.N) == 0;  // my row's clip restarts here: (h, c) read as zero
     v4i h0[HOP_KS_MAX];  // h of the last frame of the previous launch (plain bytes 0/1)
     v4i Whh[3][HOP_KS_MAX], Wih[3][HOP_KS_MAX];
 #pragma unroll
     for (int ks = 0; ks < HOP_KS_MAX; ++ks) {
         h0[ks] = v4i{0, 0, 0, 0};
-        if (ks < KS) h0[ks] = *reinterpret_cast<const v4i*>(hprev + (size_t)rowc * HP + ks * 64 + q * 16);
+        if (ks < KS && !fresh) h0[ks] = *reinterpret_cast<const v4i*>(hprev + (size_t)rowc * HP + ks * 64 + q * 16);
     }
 #pragma unroll
     for (int d = 0; d < 3; ++d)
@@ -283,7 +296,8 @@ __device__ __forceinline__ void hop_layer_role(const HopParams& p, const HopStep
             Whh[d][ks] = v4i{0, 0, 0, 0};
             if (ks < KS) Whh[d][ks] = *reinterpret_cast<const v4i*>(L.w_hh + ((((size_t)d * (G * NT) + tile) * KS + ks) * 64 + lane) * 16);
         }
-    v4f c = *reinterpret_cast<const v4f*>(L.c + (size_t)rowc * H + cc);
+    v4f c = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (!fresh) c = *reinterpret_cast<const v4f*>(L.c + (size_t)rowc * H + cc);
     const v4f dq = *reinterpret_cast<const v4f*>(L.w_hh_dq + cc);
     const v4f bf = *reinterpret_cast<const v4f*>(L.bias + cc);
     const v4f bg = *reinterpret_cast<const v4f*>(L.bias + H + cc);
@@ -338,13 +352,20 @@ __device__ __forceinline__ void hop_layer_role(const HopParams& p, const HopStep
     unsigned pk = 0;
     // cumulative_laplace_norm: the running sums of my rows (every workgroup of the row tile computes the same sequence; the first
     // one stores it for the next launch, into the other half of the double buffer)
+    // (per-clip utterances: the row's own frame count, and a zero sum in the launch that restarts its clip)
     float cumr[HOP_ROWS_PER_WAVE];
+    int fbr[HOP_ROWS_PER_WAVE];
 #pragma unroll
     for (int ri = 0; ri < HOP_ROWS_PER_WAVE; ++ri) {
         const int frow = 16 * rt + wave + HOP_WAVES * ri;
-        // (agent-scope load: in the resident form the previous hop's sum was written by ANOTHER workgroup of the same launch --
-        //  no launch boundary has made it visible to this CU's L1 / this XCD's L2)
-        cumr[ri] = (L0 && sq.norm == SFSN_NORM_CUMLAPLACE && frow < R) ? __uint_as_float(ld_agent(&sq.cum[hs.launch & 1u][frow])) : 0.0f;
+        cumr[ri] = 0.0f;
+        fbr[ri] = hs.frames_before;
+        if (L0 && sq.norm == SFSN_NORM_CUMLAPLACE && frow < R) {
+            if (p.clip_start) fbr[ri] = hop_clip_k(p, hs, frow / sq.N) * hop;
+            // (agent-scope load: in the resident form the previous hop's sum was written by ANOTHER workgroup of the same launch --
+            //  no launch boundary has made it visible to this CU's L1 / this XCD's L2)
+            if (!p.clip_start || fbr[ri] != 0) cumr[ri] = __uint_as_float(ld_agent(&sq.cum[hs.launch & 1u][frow]));
+        }
     }
 
     for (int t = 0; t < hop; ++t) {
@@ -482,7 +503,7 @@ __device__ __forceinline__ void hop_layer_role(const HopParams& p, const HopStep
                     // cumlap_rowsum_kernel / cumlap_scan_kernel's arithmetic: fp32 row sum (same lanes, same reduction), fp32
                     // running sum, mean over everything the row has seen, x / (mean + eps)
                     cumr[ri] += wave_sum(sum);
-                    const float den = cumr[ri] / (float)((double)I * (hs.frames_before + t + 1)) + 2.220446049250313e-16f;
+                    const float den = cumr[ri] / (float)((double)I * (fbr[ri] + t + 1)) + 2.220446049250313e-16f;
 #pragma unroll
                     for (int u = 0; u < HOP_NU_MAX; ++u) y[u] = v[ri][u] / den;
                 } else {
@@ -649,10 +670,11 @@ __device__ __forceinline__ void hop_proj_role(const HopParams& p, const HopStep&
             const int frow = 16 * rt + rl, b_ = frow / sq.N, k = frow - b_ * sq.N;
             const int f = sq.lo + k * fc + fci;
             const float* hrow = p.hist + ((size_t)b_ * F + f) * D * 2;
+            const bool fresh = p.clip_start && hop_clip_k(p, hs, b_) == 0;  // the clip restarts here: its history reads as zero
 #pragma unroll
             for (int i = 0; i < HOP_DF_MAX; ++i) {
                 tap[it][i] = make_float2(0.0f, 0.0f);
-                if (i < D) tap[it][i] = *reinterpret_cast<const float2*>(hrow + 2 * i);
+                if (i < D && !fresh) tap[it][i] = *reinterpret_cast<const float2*>(hrow + 2 * i);
                 if (i == D) tap[it][i] = hop_in_bin(p, b_, f, 0, 1, tagw, ok);
             }
         }
@@ -724,11 +746,12 @@ __device__ __forceinline__ void hop_proj_role(const HopParams& p, const HopStep&
             const float* pr = pbuf + rl * LDP;
             const float* hrow = p.hist + ((size_t)b_ * F + f) * D * 2;
             const float* irow = p.inp + ((size_t)b_ * F + f) * hop * 2;
+            const bool fresh = p.clip_start && hop_clip_k(p, hs, b_) == 0;
             for (int s = 0; s < S; ++s) {
                 float yr = 0.0f, yi = 0.0f;
                 for (int d = 0; d < df; ++d) {
                     const int ti = D + t - (df - 1) + d;
-                    const float2 xv = ti < D ? *reinterpret_cast<const float2*>(hrow + 2 * ti)
+                    const float2 xv = ti < D ? (fresh ? make_float2(0.0f, 0.0f) : *reinterpret_cast<const float2*>(hrow + 2 * ti))
                                              : *reinterpret_cast<const float2*>(irow + 2 * (ti - D));
                     const float cr = pr[((0 * fc + fci) * df + d) * S + s];
                     const float ci = pr[((1 * fc + fci) * df + d) * S + s];
@@ -751,9 +774,11 @@ __device__ __forceinline__ void hop_proj_role(const HopParams& p, const HopStep&
         const int f = sq.lo + k * fc + fci;
         float* hrow = p.hist + ((size_t)b_ * F + f) * D * 2;
         const float* irow = p.inp + ((size_t)b_ * F + f) * hop * 2;
+        const bool fresh = p.clip_start && hop_clip_k(p, hs, b_) == 0;
         for (int i = 0; i < D; ++i) {
             const int src = i + hop;
-            const float2 v = src < D ? *reinterpret_cast<const float2*>(hrow + 2 * src) : *reinterpret_cast<const float2*>(irow + 2 * (src - D));
+            const float2 v = src < D ? (fresh ? make_float2(0.0f, 0.0f) : *reinterpret_cast<const float2*>(hrow + 2 * src))
+                                     : *reinterpret_cast<const float2*>(irow + 2 * (src - D));
             *reinterpret_cast<float2*>(hrow + 2 * i) = v;
         }
     }
@@ -775,6 +800,9 @@ __device__ __forceinline__ void hop_stft_role(const HopParams& p, const HopStep&
     fill_unit_table(unit, tid, HOP_THREADS);
     __syncthreads();
     const Twiddles tw = make_twiddles<false>(unit, lane);
+    // bit ci: clip 16 rt + ci makes its first call in this launch (its state reads as zero).  Read once, before anything leaves
+    // this workgroup: the resident kernel's host may write the origins of the next hop as soon as this hop's samples are out.
+    const unsigned long long first = p.clip_start ? __ballot(lane < nclip && hop_clip_k(p, hs, 16 * rt + lane) == -1) : 0ull;
     float2 win[4], wk[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -786,11 +814,13 @@ __device__ __forceinline__ void hop_stft_role(const HopParams& p, const HopStep&
         const int b = 16 * rt + ci;
         const float* ws = p.wave_state + (size_t)b * FFT_NFFT;
         const float* wn = p.wave_in + (size_t)b * 128;
+        const bool zero = (first >> ci) & 1ull;
         float2 v[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int j = 2 * (lane + 64 * r);  // sample j of the frame: state[128 + j] for j < 384, then the new samples
-            const float2 x = j < 384 ? *reinterpret_cast<const float2*>(ws + 128 + j) : *reinterpret_cast<const float2*>(wn + j - 384);
+            const float2 x = j < 384 ? (zero ? make_float2(0.0f, 0.0f) : *reinterpret_cast<const float2*>(ws + 128 + j))
+                                     : *reinterpret_cast<const float2*>(wn + j - 384);
             v[r] = make_float2(x.x * win[r].x, x.y * win[r].y);
         }
         fft256<false>(v, fbuf[wave], lane, tw);
@@ -800,14 +830,15 @@ __device__ __forceinline__ void hop_stft_role(const HopParams& p, const HopStep&
         for (int r = 0; r < 4; ++r) hop_put_cplx(p.spec_g + ((size_t)b * p.F + lane + 64 * r) * 4, X[r], tagw);
         if (lane == 0) hop_put_cplx(p.spec_g + ((size_t)b * p.F + FFT_N) * 4, nyq, tagw);
     }
-    // the state moves on by one hop (every sample is read before any is written)
+    // the state moves on by one hop (every sample is read before any is written; a clip's first call leaves [0 x 384 | samples])
     float keep[16];
 #pragma unroll
     for (int ci = 0; ci < 16; ++ci) {
         keep[ci] = 0.0f;
         if (ci < nclip) {
             const int b = 16 * rt + ci;
-            keep[ci] = tid < 384 ? p.wave_state[(size_t)b * FFT_NFFT + 128 + tid] : p.wave_in[(size_t)b * 128 + tid - 384];
+            if (tid >= 384) keep[ci] = p.wave_in[(size_t)b * 128 + tid - 384];
+            else if (!((first >> ci) & 1ull)) keep[ci] = p.wave_state[(size_t)b * FFT_NFFT + 128 + tid];
         }
     }
     __syncthreads();
@@ -835,6 +866,9 @@ __device__ __forceinline__ void hop_istft_role(const HopParams& p, const HopStep
     __syncthreads();
     if (pair >= p.B * p.S) return;
     const Twiddles tw = make_twiddles<true>(unit, lane);
+    // the clip's own frame index (per-clip utterances): its accumulator reads as zero in the launch that restarts it, and its
+    // output is zero until its frame 2 (calls 0 .. 2 of the utterance)
+    const int fi = p.clip_start ? hop_clip_k(p, hs, pair / p.S) : hs.frame_index;
     float2 win[4], wk[4], ola[4];
     float* os = p.ola_state + (size_t)pair * FFT_NFFT;
 #pragma unroll
@@ -842,7 +876,8 @@ __device__ __forceinline__ void hop_istft_role(const HopParams& p, const HopStep
         const int n = 2 * (lane + 64 * r);
         win[r] = make_float2(p.window[n], p.window[n + 1]);
         wk[r] = unit_at<true>(unit, lane + 64 * r);
-        ola[r] = *reinterpret_cast<const float2*>(os + n);
+        ola[r] = make_float2(0.0f, 0.0f);
+        if (!p.clip_start || fi != 0) ola[r] = *reinterpret_cast<const float2*>(os + n);
     }
     bool ok = true;
     const float* eg = p.enh_g + (size_t)pair * p.F * 4;
@@ -868,11 +903,12 @@ __device__ __forceinline__ void hop_istft_role(const HopParams& p, const HopStep
     float2 env = make_float2(0.0f, 0.0f);
 #pragma unroll
     for (int q = 3; q >= 0; --q)
-        if (hs.frame_index - q >= 0) {
+        if (fi - q >= 0) {
             env.x += win[q].x * win[q].x;
             env.y += win[q].y * win[q].y;
         }
-    const float2 out = make_float2(env.x > 1e-11f ? acc[0].x / env.x : 0.0f, env.y > 1e-11f ? acc[0].y / env.y : 0.0f);
+    float2 out = make_float2(env.x > 1e-11f ? acc[0].x / env.x : 0.0f, env.y > 1e-11f ? acc[0].y / env.y : 0.0f);
+    if (p.clip_start && fi < 2) out = make_float2(0.0f, 0.0f);
     *reinterpret_cast<float2*>(p.wave_out + (size_t)pair * 128 + 2 * lane) = out;
     if (p.done) {
         // wave_out (and this word) may be host memory the device can reach: a caller that keeps its samples on the host spins on
@@ -1045,6 +1081,7 @@ static int hop_plan(HopParams& p, size_t& lds, const sfsn_hop_desc* d) {
         p.window = d->window; p.spec_g = d->spec_g; p.enh_g = d->enh_g; p.frame_index = d->frame_index;
         p.done = d->done;
     }
+    p.clip_start = d->clip_start;
     p.nseq = 1 + d->n_groups;
     int rc = hop_fill_seq(p.seq[0], d->fb, d->B, d->F, d->S, true, 0);
     if (rc != SFSN_OK) return rc;

@@ -17,6 +17,11 @@ hop = 1 that step is launch-bound, not compute-bound.  Both are bit-identical to
 The frozen front-end (``model_low_freq.Separator``) with ``offline_laplace_norm`` normalises with utterance-level means
 (model_low_freq.py:147-169), which are not causal: a session on it raises ``NotImplementedError``.  With
 ``cumulative_laplace_norm`` (every row by its own running mean) it streams, through the one-launch hop only.
+
+Per-clip utterances: ``reset(clips=[...])`` starts a new utterance on some clips of a batched session while the others go on,
+bit for bit.  The one-launch hop gives every clip its own origin (``sfsn_hop_desc.clip_start``: the launch at which its utterance
+began) and reads a restarted clip's state as zero in that launch -- no synchronisation, and a resident launch keeps running.  The
+per-kernel sequence zeroes the clips' rows of the states and the history with stream-ordered fills.
 """
 from __future__ import annotations
 
@@ -26,6 +31,7 @@ import os
 import time
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 
 from ._lib import DfGroup, HopDesc, HOP_MAX_GROUPS, HOP_MAX_LAYERS, NORM_CUMLAPLACE, check
@@ -90,6 +96,9 @@ class StreamingSession:
         self.fg_fb = engine._feature_groups("fb", [self.x_fb], None)
         self.fg_sb = engine._feature_groups("sb", self.xs, None)
         self.frames_done = 0
+        # per-clip utterances: the session's frame / call count at which each clip's utterance began (clip_frames = the difference)
+        self._clip_f0 = np.zeros(batch, dtype=np.int64)
+        self._clip_c0 = np.zeros(batch, dtype=np.int64)
         self._graph: Optional[torch.cuda.CUDAGraph] = None
         self._dev_index = self.dev.index if self.dev.index is not None else torch.cuda.current_device()
         self._hop = None
@@ -269,6 +278,9 @@ class StreamingSession:
             host["done_np"] = host["done"].numpy()
             host["bell"] = torch.zeros((16,), dtype=torch.int32).pin_memory()  # the resident kernel's doorbell (word 0)
             host["bell_np"] = host["bell"].numpy().view("uint32")
+            if self.resident:  # the clips' origins, read by the resident kernel after each doorbell (see reset(clips))
+                host["origin"] = torch.zeros((B,), dtype=torch.int32).pin_memory()
+                host["origin_np"] = host["origin"].numpy().view("uint32")
         parts = []
         for b0 in range(0, B, per):
             nb = min(per, B - b0)
@@ -282,12 +294,17 @@ class StreamingSession:
                 desc.wave_in, desc.wave_out = probe.data_ptr(), ptr(wave_out[b0:])  # (wave_in: set per call)
                 if host is not None:
                     desc.wave_out, desc.done = ptr(host["out"][b0:]), ptr(host["done"][b0 * S:])
+            # the clips' origins (launch index of each clip's frame 0): written by stream-ordered fills, handed to the launches from
+            # the first reset(clips) on (until then the session-wide counters serve); a resident session reads pinned host memory
+            origin = torch.zeros((nb,), dtype=torch.int32, device=dev)
+            if self.resident:
+                desc.clip_start = ptr(host["origin"][b0:])
             nbytes = L.sfsn_hop_scratch_bytes(ctypes.byref(desc))
             assert nbytes, "the sizing call accepted this geometry"
             scratch = torch.zeros((nbytes // 4 + 1,), dtype=torch.int32, device=dev)  # word 0: the error flag
             desc.scratch, desc.scratch_bytes = ptr(scratch), nbytes
             # the error word of a launch is looked at, without blocking, at a later step (pinned copy behind the launch)
-            parts.append(dict(desc=desc, ref=ctypes.byref(desc), b0=b0, nb=nb, st=st, spool=spool.buf, scratch=scratch,
+            parts.append(dict(desc=desc, ref=ctypes.byref(desc), b0=b0, nb=nb, st=st, spool=spool.buf, scratch=scratch, origin=origin,
                               err=torch.zeros((1,), dtype=torch.int32).pin_memory(), err_pending=False))
         return dict(parts=parts, desc=parts[0]["desc"], scratch=parts[0]["scratch"], wpool=wpool.buf, enh=torch.view_as_complex(enh),
                     mag=mag, wave_out=wave_out, host=host)
@@ -321,8 +338,19 @@ class StreamingSession:
                 part["err_pending"] = True
 
     # -----------------------------------------------------------------------------------------------------------------
-    def reset(self) -> None:
-        """Back to the start of an utterance: zero (h, c) (modeling_spiking_fullsubnet.py:100-106) and zero history."""
+    def reset(self, clips=None) -> None:
+        """Back to the start of an utterance: zero (h, c) (modeling_spiking_fullsubnet.py:100-106) and zero history.
+
+        ``clips`` (a sequence or 1-D tensor of clip indices; duplicates allowed, empty = nothing): only these clips start a new
+        utterance, at their next call; the others go on as if nothing happened.  A restarted clip then behaves exactly like a fresh
+        session fed the same input (waveform mode: zeros for its first three calls, then the samples of three calls earlier; the
+        cumulative norm divides by its own frame count).  Ordered with the steps on torch's current stream: no synchronisation, and
+        a resident launch keeps running.  ``clips=None``: every clip, the whole session (ends a resident launch; also checks that the
+        module's parameters have not changed since the session packed them -- a walk over the state dict that a per-clip restart,
+        issued between hops, does not pay)."""
+        if clips is not None:
+            self._reset_clips(clips)
+            return
         owner = self._owner() if self._owner is not None else None
         if owner is not None and owner.engine() is not self.eng:
             raise RuntimeError("the module's parameters (or device) changed after this streaming session was created: its packed "
@@ -338,8 +366,76 @@ class StreamingSession:
             self.check_errors()
             for part in self._hop["parts"]:
                 part["spool"].zero_()  # (h, c), tagged spike buffers, history, waveform state: one fill per part
+                part["origin"].fill_(self._as_i32(part["desc"].launch_index))  # every clip's frame 0 is the next launch
+            if self.resident:
+                self._hop["host"]["origin_np"][:] = self._hop["parts"][0]["desc"].launch_index  # (the kernel has ended)
             self._wave_calls = 0
         self.frames_done = 0
+        self._clip_f0[:] = 0
+        self._clip_c0[:] = 0
+
+    @staticmethod
+    def _as_i32(v: int) -> int:  # a launch index (uint32) as the int32 a fill writes
+        v &= 0xFFFFFFFF
+        return v - (1 << 32) if v >= 1 << 31 else v
+
+    def _reset_clips(self, clips) -> None:
+        if isinstance(clips, (torch.Tensor, np.ndarray)) and clips.ndim != 1:
+            raise TypeError("clips: a 1-D tensor or a sequence of clip indices")
+        items = clips.tolist() if isinstance(clips, (torch.Tensor, np.ndarray)) else list(clips)
+        if any(isinstance(i, bool) or not isinstance(i, (int, np.integer)) for i in items):
+            raise TypeError("clips: integer clip indices")
+        idx = [int(i) for i in items]
+        bad = [i for i in idx if not 0 <= i < self.B]
+        if bad:
+            raise IndexError(f"clip index {bad[0]} out of range for a session of {self.B} clips")
+        idx = sorted(set(idx))
+        if not idx:
+            return
+        self._clip_f0[idx] = self.frames_done
+        self._clip_c0[idx] = self._wave_calls
+        if self._hop is None:  # the per-kernel sequence: zero the clips' rows of the states and their history, in stream order
+            spec = self.eng.spec
+            for d, units in ((self.fb, [1]), (self.sb, [spec.units(g) for g in range(spec.n_groups)])):
+                for layer in d["states"]:
+                    for (h, c), u in zip(layer, units):
+                        for b in idx:
+                            h[b * u:(b + 1) * u].zero_()
+                            c[b * u:(b + 1) * u].zero_()
+            for b in idx:
+                self.hist[b].zero_()
+            return
+        # the launch that will compute each clip's frame 0: the next one -- in waveform mode the one after (the next call is the
+        # clip's first, which has no frame yet), unless the session itself is at its first call (which launches nothing)
+        h = self._hop
+        nxt = h["parts"][0]["desc"].launch_index + (self._res["k"] if self._res is not None else 0)
+        org = nxt + (1 if self.waveform and self._wave_calls > 0 else 0)
+        if self.resident:
+            # pinned host memory: the previous hop's done words are in, and the next doorbell orders this write before the hop
+            h["host"]["origin_np"][idx] = org & 0xFFFFFFFF
+            return
+        for part in h["parts"]:
+            mine = [b - part["b0"] for b in idx if part["b0"] <= b < part["b0"] + part["nb"]]
+            for i in mine:  # (a fill behind the queued launches: none of them sees the new origin)
+                part["origin"][i:i + 1].fill_(self._as_i32(org))
+            part["desc"].clip_start = part["origin"].data_ptr()  # from now on the launches take the clips' own origins
+
+    @property
+    def clip_frames(self) -> np.ndarray:
+        """int64 [B] (read-only copy): the frames each clip has seen since its own utterance began."""
+        if self.waveform:
+            out = np.maximum(self.clip_calls - 1, 0)
+        else:
+            out = self.frames_done - self._clip_f0
+        out.flags.writeable = False
+        return out
+
+    @property
+    def clip_calls(self) -> np.ndarray:
+        """Waveform sessions: int64 [B] (read-only copy), the step_wave / step_wave_host calls of each clip's utterance."""
+        out = self._wave_calls - self._clip_c0
+        out.flags.writeable = False
+        return out
 
     def check_errors(self) -> None:
         """Raise if a hand-off wait of an earlier one-launch hop expired (blocks until the hops enqueued so far have finished)."""
