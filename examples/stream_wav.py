@@ -33,6 +33,7 @@ def main():
     ap.add_argument("inp")
     ap.add_argument("out")
     ap.add_argument("--ckpt", default=None, help="an Accelerate checkpoint directory of the live recipe (pytorch_model.bin / model.safetensors)")
+    ap.add_argument("--synops", action="store_true", help="count the spikes while streaming and print the clip's SynOPs / NeuronOPs")
     args = ap.parse_args()
     with wave.open(args.inp, "rb") as w:
         assert w.getnchannels() == 1 and w.getsampwidth() == 2 and w.getframerate() == 16000, "16 kHz mono 16-bit PCM expected"
@@ -42,7 +43,7 @@ def main():
         from spiking_fullsubnet_amd.checkpoint import load_checkpoint
         load_checkpoint(model, args.ckpt)
     model = model.to("cuda").eval()
-    sess = model.streaming(batch=1, waveform=True, host_io=True)
+    sess = model.streaming(batch=1, waveform=True, host_io=True, count_spikes=args.synops)
     n_hops = -(-len(x) // 128) + 3  # + the 3 hops of algorithmic delay
     xp = np.zeros(n_hops * 128, np.float32)
     xp[:len(x)] = x
@@ -63,6 +64,12 @@ def main():
     lat = np.sort(np.asarray(lat[10:])) * 1e6
     print(f"{len(x) / 16000:.2f} s of audio, {n_hops} hops: per-hop latency p50 {lat[len(lat) // 2]:.1f} us, p99 {lat[int(len(lat) * 0.99)]:.1f} us "
           f"({8000.0 / lat[len(lat) // 2]:.0f} x real time)")
+    if args.synops:  # the utterance as streamed: every frame the session computed (the zero-padded tail included)
+        from spiking_fullsubnet_amd import metric
+        for b in range(sess.B):
+            fb_b, sb_b = sess.spike_summary([b])
+            print(f"clip {b}: {int(sess.clip_frames[b])} frames, SynOPs {metric.compute_synops(fb_b, sb_b, BASELINE_M['shared_weights']):.6g}, "
+                  f"NeuronOPs {metric.compute_neuronops(fb_b, sb_b):.6g}")
 
 
 if __name__ == "__main__":

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SFSN_ABI_VERSION 20 /* bumped on every struct / signature change: a stale .so must not load */
+#define SFSN_ABI_VERSION 21 /* bumped on every struct / signature change: a stale .so must not load */
 
 #define SFSN_OK 0
 #define SFSN_EINVAL (-1)       /* malformed argument (NULL where required, size <= 0, misaligned pointer)      */
@@ -568,9 +568,20 @@ typedef struct sfsn_hop_desc {
                                       only where no launch that is already queued reads it (a stream-ordered fill); the resident
                                       kernel reads the array (then pinned host memory) after each doorbell.  NULL: the session-wide
                                       frame_index / frames_before, no restarts                                            */
+    unsigned* spike_slots;         /* nullable, sfsn_hop_spike_slots(desc) words (ABI 21): running spike counts, zeroed by the caller
+                                      to reset.  Layout: the full-band model, then groups 0 .. n_groups - 1; within a sequence layer
+                                      by layer; within a layer [R][H / 4]: slot (row, j) counts the spikes of neurons 4j .. 4j + 3 of
+                                      row `row` (clip row / feat.n_units).  One lane of the launch owns each slot and adds, once per
+                                      launch, the spikes of the `hop` frames it computed (plain per-lane load + store: no atomics).
+                                      With clip_start: in the launch that restarts the row's clip the slot reads as zero instead of
+                                      being loaded; in a waveform clip's first call (no frame yet) the slot is written as zero.  May be
+                                      pinned host memory: the resident kernel writes a hop's slots before it releases that hop's done
+                                      words, so the host may read them for every hop whose done words it has seen.  NULL: no counting */
 } sfsn_hop_desc;
 
 size_t sfsn_hop_scratch_bytes(const sfsn_hop_desc* desc /* host */);
+/* Words of desc->spike_slots: sum over the sequences and their layers of R * H / 4 (0 for a descriptor the launch refuses). */
+size_t sfsn_hop_spike_slots(const sfsn_hop_desc* desc /* host */);
 int sfsn_stream_hop(const sfsn_hop_desc* desc /* host */, void* stream);
 
 /* The RESIDENT form of the waveform hop (BASELINE.json configs[4] names a "persistent kernel"; round 3).  One launch serves hop
@@ -610,6 +621,20 @@ typedef struct sfsn_count_tensor {
 } sfsn_count_tensor;
 
 int sfsn_spike_count(const sfsn_count_tensor* tensors /* host */, int n_tensors, void* stream);
+
+/* Per-clip spike counts of a streaming step run by the per-kernel sequence (the graph-replayed fallback of sfsn_stream_hop):
+ * for every tensor, rows are grouped by clip (R = clips * rows_per_clip, row b * rows_per_clip + k) and
+ *     counts[b] += #{ spikes_i8[t][r][c] != 0 : t0 <= t < t0 + nt, r in clip b, c < HP }
+ * (pad columns are zero).  One workgroup owns each counter (plain load + store, no atomics): capturable in a HIP graph.
+ * SFSN_EINVAL: NULL pointers, n_tensors outside 1 .. SFSN_MAX_COUNT_TENSORS, T, R, HP, rows_per_clip, nt <= 0, t0 < 0,
+ * t0 + nt > T, R % rows_per_clip != 0, HP % 16 != 0 or a misaligned spike pointer. */
+typedef struct sfsn_row_count {
+    const int8_t* spikes_i8;     /* device, [T][R][HP] int8 spikes 0/1, 16-byte aligned (frame t at t * R * HP) */
+    int T, R, HP, rows_per_clip;
+    unsigned long long* counts;  /* device, [R / rows_per_clip], accumulated */
+} sfsn_row_count;
+
+int sfsn_spike_count_rows(const sfsn_row_count* tensors /* host */, int n_tensors, int t0, int nt, void* stream);
 
 /* ----------------------------------------------------------------------------------------------------
  * The two edges of the path -- replace audiozen/acoustics/audio_feature.py:236-347 as the models call them

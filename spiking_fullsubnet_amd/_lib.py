@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(CSRC, "libsfsn_hip.so")
 SFSN_OK, SFSN_EINVAL, SFSN_EUNSUPPORTED, SFSN_EHIP, SFSN_EDIVISIBLE = 0, -1, -2, -3, -4
 NORM_NONE, NORM_LAYERNORM, NORM_LAPLACE, NORM_CUMLAPLACE, NORM_GAUSSIAN = 0, 1, 2, 3, 4
 MAX_SEGMENTS, MAX_GROUPS, MAX_HIDDEN = 8, 8, 320
-ABI_VERSION = 20  # = SFSN_ABI_VERSION of include/sfsn.h; bumped with every struct / signature change
+ABI_VERSION = 21  # = SFSN_ABI_VERSION of include/sfsn.h; bumped with every struct / signature change
 
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -66,6 +66,10 @@ class CountTensor(ctypes.Structure):
     _fields_ = [("spikes_i8", _P), ("n_bytes", ctypes.c_ulonglong), ("count", _P)]
 
 
+class RowCount(ctypes.Structure):  # sfsn_row_count
+    _fields_ = [("spikes_i8", _P), ("T", _I), ("R", _I), ("HP", _I), ("rows_per_clip", _I), ("counts", _P)]
+
+
 class TrainSeqFwd(ctypes.Structure):  # SfsnTrainSeqFwd: one layer call of a multi-call training launch
     _fields_ = [("z", _P), ("w_hh", _P), ("bias", _P), ("bn_w", _P), ("bn_b", _P), ("running_mean", _P), ("running_var", _P),
                 ("momentum", _F), ("eps", _F), ("R", _I), ("spikes", _P), ("u", _P), ("xhat", _P), ("f", _P), ("g", _P), ("invstd", _P),
@@ -98,7 +102,7 @@ class HopDesc(ctypes.Structure):
                 ("D", _I), ("fdrc", _F), ("inp_ri", _P), ("hist_ri", _P), ("enh_ri", _P), ("enh_mag", _P),
                 ("scratch", _P), ("scratch_bytes", ctypes.c_size_t), ("launch_index", ctypes.c_uint), ("wave_in", _P), ("wave_state", _P),
                 ("ola_state", _P), ("wave_out", _P), ("window", _P), ("spec_g", _P), ("enh_g", _P), ("frame_index", _I), ("done", _P), ("frames_before", _I), ("unshared", _I),
-                ("clip_start", _P)]
+                ("clip_start", _P), ("spike_slots", _P)]
 
 
 def _sources():
@@ -237,6 +241,8 @@ def lib() -> ctypes.CDLL:
     L.sfsn_cum_laplace_norm.argtypes = [_P, _I, _I, _I, _P, _I, _P, _P]
     L.sfsn_hop_scratch_bytes.restype = ctypes.c_size_t
     L.sfsn_hop_scratch_bytes.argtypes = [ctypes.POINTER(HopDesc)]
+    L.sfsn_hop_spike_slots.restype = ctypes.c_size_t
+    L.sfsn_hop_spike_slots.argtypes = [ctypes.POINTER(HopDesc)]
     L.sfsn_hop_stages.restype = _I
     L.sfsn_hop_stages.argtypes = [ctypes.POINTER(HopDesc), ctypes.POINTER(_I), _I]
     L.sfsn_stream_hop.restype = _I
@@ -245,6 +251,8 @@ def lib() -> ctypes.CDLL:
     L.sfsn_stream_hop_resident.argtypes = [ctypes.POINTER(HopDesc), _P, ctypes.c_uint, _P]
     L.sfsn_spike_count.restype = _I
     L.sfsn_spike_count.argtypes = [ctypes.POINTER(CountTensor), _I, _P]
+    L.sfsn_spike_count_rows.restype = _I
+    L.sfsn_spike_count_rows.argtypes = [ctypes.POINTER(RowCount), _I, _I, _I, _P]
     L.sfsn_stft.restype = _I
     L.sfsn_stft.argtypes = [_P, _I, _I, _I, _I, _P, _P, _I, _P]
     L.sfsn_istft.restype = _I
@@ -262,7 +270,8 @@ EXPORTS = ("sfsn_abi_version", "sfsn_source_hash", "sfsn_strerror", "sfsn_device
            "sfsn_gsn_train_seq_fwd", "sfsn_gsn_train_seq_bwd", "sfsn_gsn_layer_scan_w16", "sfsn_gsn_train_check", "sfsn_gsn_stack_scan_x", "sfsn_train_seq_scratch_bytes", "sfsn_gsn_train_multi_check",
            "sfsn_gsn_train_seq_fwd_multi", "sfsn_gsn_train_seq_bwd_multi", "sfsn_features_z", "sfsn_gaussian_stats", "sfsn_gsn_train_step_check",
            "sfsn_spike_proj_multi", "sfsn_input_proj_f32_multi", "sfsn_features_proj",
-           "sfsn_scan_split_scratch_bytes", "sfsn_gsn_layer_scan_split", "sfsn_proj_deepfilter", "sfsn_gsn_stack_scan_x_w16")
+           "sfsn_scan_split_scratch_bytes", "sfsn_gsn_layer_scan_split", "sfsn_proj_deepfilter", "sfsn_gsn_stack_scan_x_w16",
+           "sfsn_hop_spike_slots", "sfsn_spike_count_rows")
 
 
 def check(rc: int, what: str = "") -> None:

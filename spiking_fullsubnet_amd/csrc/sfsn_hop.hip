@@ -74,6 +74,7 @@ struct HopSeqDev {
     const float* ln_b;
     float* cum[2];  // SFSN_NORM_CUMLAPLACE: running sum of every row, double-buffered by launch parity
     int nl, H, P, R, KS, NT, PT, I, I1, KC;
+    int slot0;      // desc.spike_slots: this sequence's first slot (layer l, row r, column group j at slot0 + (l R + r) H / 4 + j)
     int lo, N, ctr, nbr, ctr_fb, nbr_fb, norm, df, fc;
     float eps;
 };
@@ -110,12 +111,16 @@ struct HopParams {
     unsigned* cnt;    // [0] error word
     unsigned long long* dbg;  // -DSFSN_HOP_STAMPS builds + SFSN_HOP_DEBUG: 8 time stamps (100 MHz) per wave
     const unsigned* clip_start;  // optional [B]: the launch index at which clip b's utterance began (frame 0); NULL = the counters above
+    unsigned* slots;  // optional: running spike counts, one word per (sequence, layer, row, 4-neuron column group) -- desc.spike_slots
 };
 
 // what changes from hop to hop (a launch takes them from its kernel arguments; the resident kernel counts them up itself)
 struct HopStep {
     unsigned launch;
     int frame_index, frames_before;
+    // resident kernel with spike slots: the inverse-STFT waves release their done words once every other workgroup has counted
+    // itself finished with this hop (scratch word 2) -- its stores of the hop, the spike slots included, have completed
+    int wait_fin;
 };
 
 #ifdef SFSN_HOP_STAMPS
@@ -281,7 +286,9 @@ __device__ __forceinline__ void hop_layer_role(const HopParams& p, const HopStep
     // operands first
     const int8_t* hprev = L.h[hs.launch & 1u];
     int8_t* hnext = L.h[(hs.launch + 1u) & 1u];
-    const bool fresh = p.clip_start && hop_clip_k(p, hs, rowc / sq.N) == 0;  // my row's clip restarts here: (h, c) read as zero
+    // my row's clip: restarts here ((h, c) and its spike slot read as zero) / makes its first call (waveform mode: no frame yet)
+    const int kclip = p.clip_start ? hop_clip_k(p, hs, rowc / sq.N) : 1;
+    const bool fresh = kclip == 0, first = kclip < 0;
     v4i h0[HOP_KS_MAX];  // h of the last frame of the previous launch (plain bytes 0/1)
     v4i Whh[3][HOP_KS_MAX], Wih[3][HOP_KS_MAX];
 #pragma unroll
@@ -595,6 +602,16 @@ __device__ __forceinline__ void hop_layer_role(const HopParams& p, const HopStep
     if (active && row < R) {
         *reinterpret_cast<v4f*>(L.c + (size_t)row * H + cc) = c;
         st_agent(hnext + (size_t)row * HP + cc, pk);  // (write-through: the resident form has no launch boundary to write L2 back)
+        if (p.slots) {
+            // my slot: += the spikes of this launch's frames (bytes 0/1: a popcount).  Read as zero where the clip restarts, written
+            // as zero in a waveform clip's first call.  System scope: the slots may be pinned host memory the host reads
+            unsigned* slot = p.slots + sq.slot0 + ((size_t)l * R + row) * (H >> 2) + (cc >> 2);
+            unsigned nspk = __builtin_popcount(pk);
+            for (int t = 0; t < hop - 1; ++t)  // (hop > 1: the earlier frames' words, as this lane published them -- tag bits masked)
+                nspk += __builtin_popcount(ld_agent(L.spikes + ((size_t)t * R + row) * HP + cc) & 0x01010101u);
+            const unsigned prev = (fresh || first) ? 0u : __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(slot, first ? 0u : prev + nspk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
     }
     if (L0 && sq.norm == SFSN_NORM_CUMLAPLACE && wgl - rt * wpr == 0 && lane == 0) {
 #pragma unroll
@@ -910,6 +927,18 @@ __device__ __forceinline__ void hop_istft_role(const HopParams& p, const HopStep
     float2 out = make_float2(env.x > 1e-11f ? acc[0].x / env.x : 0.0f, env.y > 1e-11f ? acc[0].y / env.y : 0.0f);
     if (p.clip_start && fi < 2) out = make_float2(0.0f, 0.0f);
     *reinterpret_cast<float2*>(p.wave_out + (size_t)pair * 128 + 2 * lane) = out;
+    if (hs.wait_fin) {
+        // (resident kernel, spike slots: each other workgroup counts itself finished after s_waitcnt(0) -- once all have, the slots
+        //  of this hop are in memory, and the done words below may tell the host so; the inverse STFT is the last stage)
+        const unsigned need = (hs.launch - p.launch + 1u) * gridDim.x - (unsigned)sd.nwg;
+        for (unsigned spins = 0; ok && (int)(ld_agent(p.cnt + 2) - need) < 0; ++spins) {
+            if (spins > HOP_SPIN_LIMIT) {
+                st_agent(p.cnt, 1u);
+                ok = false;
+            }
+            __builtin_amdgcn_s_sleep(1);
+        }
+    }
     if (p.done) {
         // wave_out (and this word) may be host memory the device can reach: a caller that keeps its samples on the host spins on
         // the word instead of synchronising the stream -- the samples are there when it changes (system-scope release)
@@ -958,6 +987,7 @@ __global__ __launch_bounds__(HOP_THREADS) void stream_hop_kernel(const HopParams
     HOP_STAMP(0);
     HopStep hs;
     hs.launch = p.launch; hs.frame_index = p.frame_index; hs.frames_before = p.frames_before;
+    hs.wait_fin = 0;
     hop_dispatch<ONE, G>(p, hs, smem);
     HOP_STAMP(7);
 }
@@ -1010,6 +1040,7 @@ __global__ __launch_bounds__(HOP_THREADS) void stream_hop_resident_kernel(const 
 #endif
         HopStep hs;
         hs.launch = p.launch + k; hs.frame_index = p.frame_index + (int)k; hs.frames_before = p.frames_before + (int)k * p.hop;
+        hs.wait_fin = p.slots != nullptr;
         hop_dispatch<true, G>(p, hs, smem);
 #ifdef SFSN_HOP_STAMPS
         HOP_STAMP(7);
@@ -1082,6 +1113,7 @@ static int hop_plan(HopParams& p, size_t& lds, const sfsn_hop_desc* d) {
         p.done = d->done;
     }
     p.clip_start = d->clip_start;
+    p.slots = d->spike_slots;
     p.nseq = 1 + d->n_groups;
     int rc = hop_fill_seq(p.seq[0], d->fb, d->B, d->F, d->S, true, 0);
     if (rc != SFSN_OK) return rc;
@@ -1096,6 +1128,10 @@ static int hop_plan(HopParams& p, size_t& lds, const sfsn_hop_desc* d) {
     }
     if (dmax - 1 > d->D || fcov > d->F) return SFSN_EINVAL;
     p.fcov = fcov;
+    for (int i = 0, o = 0; i < p.nseq; ++i) {  // (spike slots: sequences in descriptor order, layers, rows, column groups)
+        p.seq[i].slot0 = o;
+        o += p.seq[i].nl * p.seq[i].R * (p.seq[i].H / 4);
+    }
     if (p.seq[0].PT > HOP_WAVES) return SFSN_EUNSUPPORTED;  // the sub-band layer-0 workgroups compute it with one tile per wave
     // stages in dependency order: producers get the lower block indices.  Sub-band stages go layer by layer over all groups
     // (the groups' layer-0 workgroups all wait for the same full-band layer).
@@ -1167,6 +1203,15 @@ extern "C" size_t sfsn_hop_scratch_bytes(const sfsn_hop_desc* desc) {
     if (hop_plan(p, lds, desc) != SFSN_OK) return 0;
     if (hop_fits_device(p.nblocks) == SFSN_EUNSUPPORTED) return 0;  // (no device at all: the launch reports it)
     return hop_counter_bytes(p) + (size_t)p.nblocks * HOP_WAVES * 8 * sizeof(unsigned long long);
+}
+
+extern "C" size_t sfsn_hop_spike_slots(const sfsn_hop_desc* desc) {
+    HopParams p;
+    size_t lds;
+    if (hop_plan(p, lds, desc) != SFSN_OK) return 0;
+    size_t n = 0;
+    for (int i = 0; i < p.nseq; ++i) n += (size_t)p.seq[i].nl * p.seq[i].R * (p.seq[i].H / 4);
+    return n;
 }
 
 extern "C" int sfsn_hop_stages(const sfsn_hop_desc* desc, int* out, int cap) {

@@ -1793,6 +1793,41 @@ __global__ __launch_bounds__(256) void spike_count_kernel(const CountParams p) {
     if (threadIdx.x == 0) atomicAdd(p.dst[ti], (unsigned long long)(part[0] + part[1] + part[2] + part[3]));
 }
 
+// Per-clip counts of a streaming step (sfsn_spike_count_rows): one workgroup per (tensor, clip) sums the clip's rows over the
+// frames and is the only writer of its counter -- a plain load + store, no atomics.  A clip's rows of one frame are contiguous.
+struct RowCountParams {
+    const int8_t* src[SFSN_MAX_COUNT_TENSORS];
+    unsigned long long* dst[SFSN_MAX_COUNT_TENSORS];
+    int R[SFSN_MAX_COUNT_TENSORS], HP[SFSN_MAX_COUNT_TENSORS], rpc[SFSN_MAX_COUNT_TENSORS];
+    int blk0[SFSN_MAX_COUNT_TENSORS + 1];  // first workgroup (= clip 0) of each tensor
+    int n, t0, nt;
+};
+
+__global__ __launch_bounds__(256) void spike_count_rows_kernel(const RowCountParams p) {
+    int ti = 0;
+    while (ti + 1 < p.n && (int)blockIdx.x >= p.blk0[ti + 1]) ++ti;
+    const int b = (int)blockIdx.x - p.blk0[ti];
+    const size_t nvec = (size_t)p.rpc[ti] * p.HP[ti] / 16;  // 16-byte vectors of one frame of the clip
+    unsigned cnt = 0;
+    for (int t = p.t0; t < p.t0 + p.nt; ++t) {
+        const v4i* src = reinterpret_cast<const v4i*>(p.src[ti] + ((size_t)t * p.R[ti] + (size_t)b * p.rpc[ti]) * p.HP[ti]);
+        for (size_t i = threadIdx.x; i < nvec; i += 256) {
+            const v4i v = src[i];
+            cnt += __builtin_popcount((unsigned)v.x) + __builtin_popcount((unsigned)v.y) + __builtin_popcount((unsigned)v.z) +
+                   __builtin_popcount((unsigned)v.w);
+        }
+    }
+    __shared__ unsigned part[4];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long* d = p.dst[ti] + b;
+        *d = *d + (unsigned long long)(part[0] + part[1] + part[2] + part[3]);
+    }
+}
+
 // ---- Laplace means -----------------------------------------------------------------------------------
 // rs[b][f] = sum_t mag[b][f][t] (f < nf), then rs[b][nf + f'] = sum_t fb[t][b][f'].  One wave per row.
 // (rs2 non-null: also the row sums of squares, as doubles -- offline_gaussian_norm's second moment)
@@ -2868,6 +2903,26 @@ extern "C" int sfsn_spike_count(const sfsn_count_tensor* tensors, int n_tensors,
     }
     p.blk0[n_tensors] = (int)blocks;
     hipLaunchKernelGGL(spike_count_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), p);
+    return hip_ok(hipGetLastError());
+}
+
+extern "C" int sfsn_spike_count_rows(const sfsn_row_count* tensors, int n_tensors, int t0, int nt, void* stream) {
+    if (!tensors || n_tensors <= 0 || n_tensors > SFSN_MAX_COUNT_TENSORS || t0 < 0 || nt <= 0) return SFSN_EINVAL;
+    RowCountParams p;
+    p.n = n_tensors; p.t0 = t0; p.nt = nt;
+    long long blocks = 0;
+    for (int i = 0; i < n_tensors; ++i) {
+        const sfsn_row_count& t = tensors[i];
+        if (!t.spikes_i8 || !t.counts || t.T <= 0 || t.R <= 0 || t.HP <= 0 || t.rows_per_clip <= 0 || (long long)t0 + nt > t.T ||
+            t.R % t.rows_per_clip || t.HP % 16 || (reinterpret_cast<uintptr_t>(t.spikes_i8) & 15))
+            return SFSN_EINVAL;
+        p.src[i] = t.spikes_i8; p.dst[i] = t.counts; p.R[i] = t.R; p.HP[i] = t.HP; p.rpc[i] = t.rows_per_clip;
+        p.blk0[i] = (int)blocks;
+        blocks += t.R / t.rows_per_clip;
+    }
+    if (blocks > 0x7fffffffLL) return SFSN_EUNSUPPORTED;
+    p.blk0[n_tensors] = (int)blocks;
+    hipLaunchKernelGGL(spike_count_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), p);
     return hip_ok(hipGetLastError());
 }
 

@@ -22,6 +22,12 @@ Per-clip utterances: ``reset(clips=[...])`` starts a new utterance on some clips
 bit for bit.  The one-launch hop gives every clip its own origin (``sfsn_hop_desc.clip_start``: the launch at which its utterance
 began) and reads a restarted clip's state as zero in that launch -- no synchronisation, and a resident launch keeps running.  The
 per-kernel sequence zeroes the clips' rows of the states and the history with stream-ordered fills.
+
+Spike counts: a session opened with ``count_spikes=True`` counts every layer's spikes per clip as it runs, and
+``spike_summary(clips)`` returns them in the form of the offline forward's ``layer_outputs="counts"`` lists, so that
+``metric.compute_synops`` / ``compute_neuronops`` give each clip's current utterance's SynOPs and NeuronOPs.  The one-launch hop
+adds each launch's spikes into per-lane slots (``sfsn_hop_desc.spike_slots``; a restarted clip's slots read as zero); the
+per-kernel sequence adds a per-clip count launch (``sfsn_spike_count_rows``) to its graph.
 """
 from __future__ import annotations
 
@@ -34,8 +40,8 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from ._lib import DfGroup, HopDesc, HOP_MAX_GROUPS, HOP_MAX_LAYERS, NORM_CUMLAPLACE, check
-from .engine import Engine, _ptr
+from ._lib import DfGroup, HopDesc, HOP_MAX_GROUPS, HOP_MAX_LAYERS, MAX_COUNT_TENSORS, NORM_CUMLAPLACE, RowCount, check
+from .engine import Engine, SpikeSummary, _ptr
 
 
 def _raw_stream(device_index: int) -> int:
@@ -50,7 +56,8 @@ class StreamingSession:
     """``step(frames [B, F, hop] complex64) -> (enh_stft [B, S, F, hop], enh_mag [B, S, F, hop])`` with state carried."""
 
     def __init__(self, engine: Engine, batch: int = 1, hop: int = 1, graph: bool = True, rows_per_wg=None, owner=None,
-                 one_launch="auto", waveform: bool = False, host_io: bool = False, resident: bool = False, idle_ms: int = 1000):
+                 one_launch="auto", waveform: bool = False, host_io: bool = False, resident: bool = False, idle_ms: int = 1000,
+                 count_spikes: bool = False):
         spec = engine.spec
         # the module the engine was packed from: reset() checks that its parameters have not changed since (the session's
         # captured graph holds pointers to THIS engine's packed weights)
@@ -93,6 +100,10 @@ class StreamingSession:
         for g in range(ng):
             self.dfg[g].proj, self.dfg[g].n_units = _ptr(self.sb["proj"][g]), spec.units(g)
             self.dfg[g].fc, self.dfg[g].df = spec.ctr[g], spec.df[g]
+        # count_spikes: per-clip spike counts of every layer (spike_summary); the per-kernel sequence keeps them in `_rows`
+        # [fb layers + groups x sb layers, B] int64, filled by one sfsn_spike_count_rows launch per step (captured with the rest)
+        self.count_spikes = bool(count_spikes)
+        self._rows = None
         self.fg_fb = engine._feature_groups("fb", [self.x_fb], None)
         self.fg_sb = engine._feature_groups("sb", self.xs, None)
         self.frames_done = 0
@@ -128,6 +139,17 @@ class StreamingSession:
             self._hop = self._build_hop()
             if self._hop is None and one_launch is True:
                 raise NotImplementedError("sfsn_stream_hop does not cover this model / batch (see include/sfsn.h)")
+        if self._hop is None and self.count_spikes:
+            self._rows = torch.zeros((spec.fb_layers + ng * spec.sb_layers, B), dtype=torch.int64, device=dev)
+            tens = [(self.fb["s8"][l][0], 1) for l in range(spec.fb_layers)] + \
+                   [(self.sb["s8"][l][g], spec.units(g)) for g in range(ng) for l in range(spec.sb_layers)]
+            self._row_jobs = []
+            for i0 in range(0, len(tens), MAX_COUNT_TENSORS):
+                arr = (RowCount * len(tens[i0:i0 + MAX_COUNT_TENSORS]))()
+                for j, (t, rpc) in enumerate(tens[i0:i0 + MAX_COUNT_TENSORS]):
+                    arr[j].spikes_i8, arr[j].T, arr[j].R, arr[j].HP, arr[j].rows_per_clip = _ptr(t), t.shape[0], t.shape[1], t.shape[2], rpc
+                    arr[j].counts = _ptr(self._rows[i0 + j])
+                self._row_jobs.append(arr)
         if self._hop is None and graph:
             self._capture()
 
@@ -301,10 +323,16 @@ class StreamingSession:
                 desc.clip_start = ptr(host["origin"][b0:])
             nbytes = L.sfsn_hop_scratch_bytes(ctypes.byref(desc))
             assert nbytes, "the sizing call accepted this geometry"
+            slots = None
+            if self.count_spikes:  # running spike counts, one word per lane that writes 4 neurons of a row (include/sfsn.h)
+                n = L.sfsn_hop_spike_slots(ctypes.byref(desc))
+                # (resident: pinned host memory, read by the host while the launch runs; otherwise device memory, summed in stream order)
+                slots = torch.zeros((n,), dtype=torch.int32).pin_memory() if self.resident else torch.zeros((n,), dtype=torch.int32, device=dev)
+                desc.spike_slots = ptr(slots)
             scratch = torch.zeros((nbytes // 4 + 1,), dtype=torch.int32, device=dev)  # word 0: the error flag
             desc.scratch, desc.scratch_bytes = ptr(scratch), nbytes
             # the error word of a launch is looked at, without blocking, at a later step (pinned copy behind the launch)
-            parts.append(dict(desc=desc, ref=ctypes.byref(desc), b0=b0, nb=nb, st=st, spool=spool.buf, scratch=scratch, origin=origin,
+            parts.append(dict(desc=desc, ref=ctypes.byref(desc), b0=b0, nb=nb, st=st, spool=spool.buf, scratch=scratch, origin=origin, slots=slots,
                               err=torch.zeros((1,), dtype=torch.int32).pin_memory(), err_pending=False))
         return dict(parts=parts, desc=parts[0]["desc"], scratch=parts[0]["scratch"], wpool=wpool.buf, enh=torch.view_as_complex(enh),
                     mag=mag, wave_out=wave_out, host=host)
@@ -367,9 +395,13 @@ class StreamingSession:
             for part in self._hop["parts"]:
                 part["spool"].zero_()  # (h, c), tagged spike buffers, history, waveform state: one fill per part
                 part["origin"].fill_(self._as_i32(part["desc"].launch_index))  # every clip's frame 0 is the next launch
+                if part["slots"] is not None:
+                    part["slots"].zero_()  # (pinned: the resident launch has ended)
             if self.resident:
                 self._hop["host"]["origin_np"][:] = self._hop["parts"][0]["desc"].launch_index  # (the kernel has ended)
             self._wave_calls = 0
+        if self._rows is not None:
+            self._rows.zero_()
         self.frames_done = 0
         self._clip_f0[:] = 0
         self._clip_c0[:] = 0
@@ -404,6 +436,8 @@ class StreamingSession:
                             c[b * u:(b + 1) * u].zero_()
             for b in idx:
                 self.hist[b].zero_()
+                if self._rows is not None:
+                    self._rows[:, b].zero_()
             return
         # the launch that will compute each clip's frame 0: the next one -- in waveform mode the one after (the next call is the
         # clip's first, which has no frame yet), unless the session itself is at its first call (which launches nothing)
@@ -436,6 +470,70 @@ class StreamingSession:
         out = self._wave_calls - self._clip_c0
         out.flags.writeable = False
         return out
+
+    def spike_summary(self, clips=None):
+        """``(fb_all, sb_all)`` of the selected clips' current utterances (``clips=None``: every clip), shaped like the offline
+        forward's ``layer_outputs="counts"`` lists over ``clip_frames`` frames: input and projection entries are shape-only (meta
+        tensors), spike entries ``SpikeSummary`` objects with the exact spike count of the selected clips.  Counts are summed on
+        the device (nothing synchronises until they are read); a resident session reads them from pinned host memory.  So
+        ``metric.compute_synops(*session.spike_summary([b]), shared_weights=...)`` is clip b's SynOPs.  The selected clips must
+        have seen the same number of frames (``ValueError`` otherwise); the session must have been opened with
+        ``count_spikes=True`` (``RuntimeError``)."""
+        if not self.count_spikes:
+            raise RuntimeError("open the session with count_spikes=True to count spikes")
+        if clips is None:
+            idx = list(range(self.B))
+        else:
+            if isinstance(clips, (torch.Tensor, np.ndarray)) and clips.ndim != 1:
+                raise TypeError("clips: a 1-D tensor or a sequence of clip indices")
+            items = clips.tolist() if isinstance(clips, (torch.Tensor, np.ndarray)) else list(clips)
+            if any(isinstance(i, bool) or not isinstance(i, (int, np.integer)) for i in items):
+                raise TypeError("clips: integer clip indices")
+            idx = sorted(set(int(i) for i in items))
+            bad = [i for i in idx if not 0 <= i < self.B]
+            if bad:
+                raise IndexError(f"clip index {bad[0]} out of range for a session of {self.B} clips")
+            if not idx:
+                raise ValueError("clips: no clip selected")
+        frames = self.clip_frames[idx]
+        if (frames != frames[0]).any():
+            raise ValueError(f"spike_summary: the selected clips have seen different numbers of frames {frames.tolist()}; select "
+                             "clips whose utterances are equally long")
+        T, nb = int(frames[0]), len(idx)
+        spec, eng = self.eng.spec, self.eng
+        ng, nl_fb, nl_sb = spec.n_groups, spec.fb_layers, spec.sb_layers
+        if self._hop is None:
+            counts = self._rows[:, idx].sum(1)
+        else:
+            counts = None
+            seqs = [eng.fb] + list(eng.sb)
+            units = [1] + [spec.units(g) for g in range(ng)]
+            for part in self._hop["parts"]:
+                mine = [b - part["b0"] for b in idx if part["b0"] <= b < part["b0"] + part["nb"]]
+                if not mine:
+                    continue
+                slots = part["slots"]
+                if self.resident:
+                    slots = torch.from_numpy(slots.numpy().copy())  # (a snapshot: the launch may be serving the next hop)
+                per, off = [], 0
+                for seq, u in zip(seqs, units):  # (include/sfsn.h: sequences, layers, rows = clip * units + unit, column groups)
+                    n = part["nb"] * u * (seq.H // 4)
+                    for _ in seq.cells:
+                        per.append(slots[off:off + n].view(part["nb"], -1)[mine].sum(dtype=torch.int64))
+                        off += n
+                c = torch.stack(per)
+                counts = c if counts is None else counts + c
+        fb_sh = [(T, nb, eng.fb.H)] * nl_fb
+        sb_sh = [(T, nb * spec.units(g), eng.sb[g].H) for g in range(ng) for _ in range(nl_sb)]
+        summ = [SpikeSummary(counts[i], shp) for i, shp in enumerate(fb_sh + sb_sh)]
+
+        def meta(*shape):
+            return torch.empty(shape, dtype=torch.float32, device="meta")
+
+        fb_all = [meta(T, nb, spec.fb_in)] + summ[:nl_fb] + [meta(T, nb, eng.fb.P)]
+        sb_all = [[meta(T, nb * spec.units(g), spec.sb_input_size(g))] + summ[nl_fb + g * nl_sb:nl_fb + (g + 1) * nl_sb] +
+                  [meta(T, nb * spec.units(g), eng.sb[g].P)] for g in range(ng)]
+        return fb_all, sb_all
 
     def check_errors(self) -> None:
         """Raise if a hand-off wait of an earlier one-launch hop expired (blocks until the hops enqueued so far have finished)."""
@@ -502,6 +600,9 @@ class StreamingSession:
         model(eng.sb, self.sb, self.xs, "sb", rpw_sb)
         check(L.sfsn_deepfilter(_ptr(ri), B, F, Th, S, self.dfg, ng, _ptr(torch.view_as_real(self.enh)), _ptr(self.enh_mag), D, hop, st),
               "sfsn_deepfilter")
+        if self._rows is not None:  # every layer's spikes of frames [D, D + hop), per clip
+            for arr in self._row_jobs:
+                check(L.sfsn_spike_count_rows(arr, len(arr), D, hop, st), "sfsn_spike_count_rows")
 
     def _capture(self) -> None:
         side = torch.cuda.Stream(device=self.dev)
