@@ -651,6 +651,46 @@ int sfsn_stft(const float* wave /* [B][L] */, int B, int L, int n_fft, int hop, 
 int sfsn_istft(const float* stft_ri /* [B][n_fft/2+1][T][2] */, int B, int T, int n_fft, int hop, const float* window,
                float* wave /* [B][length] */, int length, void* stream);
 
+/* ----------------------------------------------------------------------------------------------------
+ * The cIRM-GSN model (CIRM = audiozen/models/cirm_gsn/modeling_cirm_gsn.py, recipes/intel_ndns/cirm_gsn): one full-band GSN stack
+ * on ALL F = n_fft/2 + 1 bins and a full-spectrum deep filter.  Its GSN layers run on sfsn_gsn_stack_scan; these are its two ends
+ * and its layer-0 input product.
+ *
+ * sfsn_fullband_features -- CIRM:220-226 + SequenceModel.forward's transpose and pre_layer_norm (CIRM:101-106):
+ *     x[t][b][f] = LayerNorm_f(|X[b][f][t]|^fdrc),  f < F (Nyquist included; sfsn_features drops it)
+ *     with sfsn_features' magnitude and LayerNorm expressions.  ln_w = ln_b = NULL: no LayerNorm.  F <= 320.
+ *
+ * sfsn_fullband_input_proj -- layer 0's input term for rows wider than sfsn_input_proj_f32 covers (K > 192: the full-spectrum rows
+ * have K = F = 257): z[m][n] = sum_k x[m][k] * w[n][k] (+ bias[n]) as one fp32 fmaf chain in k order, then + bias; arguments as for
+ * sfsn_input_proj_f32 (any M, K, N; ldz >= N; 4-byte aligned).
+ *
+ * sfsn_fullband_proj_deepfilter -- SequenceModel's proj + output activation (CIRM:113-120), the (c d s f) re-index (CIRM:230) and
+ * deepfiltering (CIRM:125-157) over all F bins, in one launch:
+ *     v[t][b][n] = dq'[n'] * sum_k s[t][b][k] Wq'[n'][k] + bias'[n']   (sfsn_spike_proj's arithmetic: the same value, bit for bit)
+ *     C[d][s] = act(v[.][((0 * df + d) * S + s) * F + f]) + i act(v[.][((1 * df + d) * S + s) * F + f])
+ *     Y[b][s][f][t] = sum_{d<df} X[b][f][t-(df-1)+d] * C[d][s]   (zero before frame 0; d ascending)
+ * The projection weights are packed with their rows BIN-MAJOR: W' [NFB * NCT * 16][H] with NFB = ceil(F / 16), NCT = 2 * df * S,
+ *     W'[(fb * NCT + (c * df + d) * S + s) * 16 + i] = W[((c * df + d) * S + s) * F + fb * 16 + i]   (zero rows for bins >= F)
+ * and passed as sfsn_w3_pack(W', NFB * NCT * 16, H); bias' (nullable, 16-byte aligned) in the same row order.  Every row is its own
+ * exact sum, so the permutation changes no bit.  `proj` (nullable) receives the pre-activation rows in the reference's column order
+ * n = ((c * df + d) * S + s) * F + f, [T][B][2 * df * S * F]; they are not written anywhere when it is NULL.  enh_mag (nullable)
+ * = hypot(re, im) rounded as glibc's hypotf.  Frames [t0, t0 + nt) are produced (the filter reads earlier frames of stft_ri).
+ * pad64(H) <= 320, F <= 1025, S <= 4, df <= 16: SFSN_EUNSUPPORTED otherwise.  (ABI 21 additions.)
+ * ---------------------------------------------------------------------------------------------------- */
+#define SFSN_ACT_NONE 0    /* anything but the exact strings below: nn.Identity (CIRM:54-61) */
+#define SFSN_ACT_TANH 1
+#define SFSN_ACT_SIGMOID 2
+#define SFSN_ACT_RELU 3
+
+int sfsn_fullband_features(const float* stft_ri /* [B][F][T][2] */, int B, int F, int T, float fdrc, const float* ln_w /* [F] */,
+                           const float* ln_b /* [F] */, float ln_eps, float* x /* [T][B][F] */, int t0, int nt, void* stream);
+int sfsn_fullband_input_proj(const float* x /* [M][K] */, const float* w /* [N][K] */, const float* bias /* [N], nullable */,
+                             float* z /* [M][ldz] */, int M, int K, int N, int ldz, void* stream);
+int sfsn_fullband_proj_deepfilter(const float* stft_ri /* [B][F][T][2] */, const int8_t* spikes_i8 /* [T][B][pad64(H)] */, int H,
+                                  const int8_t* w_packed, const float* w_dq, const float* bias, int act, int B, int F, int T, int S,
+                                  int df, float* proj /* [T][B][2 df S F], nullable */, float* enh_ri /* [B][S][F][T][2] */,
+                                  float* enh_mag /* [B][S][F][T], nullable */, int t0, int nt, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,7 @@ Drop-in modules (same constructor keywords, state-dict names and forward() tuple
 
 * ``spiking_fullsubnet_amd.modeling_spiking_fullsubnet.SpikingFullSubNet``  (live recipes)
 * ``spiking_fullsubnet_amd.model_low_freq.Separator``                        (frozen recipe / model_zoo checkpoints)
+* ``spiking_fullsubnet_amd.modeling_cirm_gsn.Model``                         (the cIRM-GSN baseline recipe)
 
 All compute between ``stft`` and ``istft`` runs in hand-written gfx950 kernels behind the C ABI of
 ``include/sfsn.h`` (``csrc/libsfsn_hip.so``).  There is no CPU fallback.
@@ -13,6 +14,7 @@ from .engine import Engine, PathSpec, SpikeSummary  # noqa: F401
 from . import checkpoint, metric  # noqa: F401
 from .model_low_freq import Separator  # noqa: F401
 from .modeling_spiking_fullsubnet import SpikingFullSubNet  # noqa: F401
+from .modeling_cirm_gsn import Model  # noqa: F401
 from .streaming import StreamingSession  # noqa: F401
 
-__all__ = ["SpikingFullSubNet", "Separator", "Engine", "PathSpec", "StreamingSession"]
+__all__ = ["SpikingFullSubNet", "Separator", "Engine", "PathSpec", "StreamingSession", "Model"]

@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(CSRC, "libsfsn_hip.so")
 
 SFSN_OK, SFSN_EINVAL, SFSN_EUNSUPPORTED, SFSN_EHIP, SFSN_EDIVISIBLE = 0, -1, -2, -3, -4
 NORM_NONE, NORM_LAYERNORM, NORM_LAPLACE, NORM_CUMLAPLACE, NORM_GAUSSIAN = 0, 1, 2, 3, 4
+ACT_NONE, ACT_TANH, ACT_SIGMOID, ACT_RELU = 0, 1, 2, 3  # SFSN_ACT_* (sfsn_fullband_proj_deepfilter)
 MAX_SEGMENTS, MAX_GROUPS, MAX_HIDDEN = 8, 8, 320
 ABI_VERSION = 21  # = SFSN_ABI_VERSION of include/sfsn.h; bumped with every struct / signature change
 
@@ -109,7 +110,7 @@ def _sources():
     """The files the library is made of, in the order the Makefile hashes them (SRCS)."""
     return [os.path.join(_HERE, "..", "include", "sfsn.h")] + [
         os.path.join(CSRC, f) for f in ("sfsn_scan_dev.h", "sfsn_scan3_dev.h", "sfsn_scan3i_dev.h", "sfsn_scan3x_dev.h", "sfsn_scan3w_dev.h", "sfsn_scan3j_dev.h", "sfsn_scan3g_dev.h", "sfsn_feat_dev.h", "sfsn_fft_dev.h", "sfsn_kernels.hip", "sfsn_stack.hip", "sfsn_hop.hip", "sfsn_fft.hip", "sfsn_train.hip",
-                                  "sfsn_featproj.hip", "sfsn_projdf.hip", "sfsn_pack.cpp")]
+                                  "sfsn_featproj.hip", "sfsn_projdf.hip", "sfsn_fullband.hip", "sfsn_pack.cpp")]
 
 
 def source_hash() -> str:
@@ -257,6 +258,12 @@ def lib() -> ctypes.CDLL:
     L.sfsn_stft.argtypes = [_P, _I, _I, _I, _I, _P, _P, _I, _P]
     L.sfsn_istft.restype = _I
     L.sfsn_istft.argtypes = [_P, _I, _I, _I, _I, _P, _P, _I, _P]
+    L.sfsn_fullband_features.restype = _I
+    L.sfsn_fullband_features.argtypes = [_P, _I, _I, _I, _F, _P, _P, _F, _P, _I, _I, _P]
+    L.sfsn_fullband_input_proj.restype = _I
+    L.sfsn_fullband_input_proj.argtypes = [_P, _P, _P, _P, _I, _I, _I, _I, _P]
+    L.sfsn_fullband_proj_deepfilter.restype = _I
+    L.sfsn_fullband_proj_deepfilter.argtypes = [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _P]
     if L.sfsn_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH}: ABI version {L.sfsn_abi_version()} != {ABI_VERSION}; rebuild (make -C {CSRC})")
     _lib = L
@@ -271,7 +278,8 @@ EXPORTS = ("sfsn_abi_version", "sfsn_source_hash", "sfsn_strerror", "sfsn_device
            "sfsn_gsn_train_seq_fwd_multi", "sfsn_gsn_train_seq_bwd_multi", "sfsn_features_z", "sfsn_gaussian_stats", "sfsn_gsn_train_step_check",
            "sfsn_spike_proj_multi", "sfsn_input_proj_f32_multi", "sfsn_features_proj",
            "sfsn_scan_split_scratch_bytes", "sfsn_gsn_layer_scan_split", "sfsn_proj_deepfilter", "sfsn_gsn_stack_scan_x_w16",
-           "sfsn_hop_spike_slots", "sfsn_spike_count_rows")
+           "sfsn_hop_spike_slots", "sfsn_spike_count_rows", "sfsn_fullband_features", "sfsn_fullband_input_proj",
+           "sfsn_fullband_proj_deepfilter")
 
 
 def check(rc: int, what: str = "") -> None:

@@ -1,0 +1,89 @@
+"""Drop-in for ``audiozen.models.cirm_gsn.modeling_cirm_gsn.Model``, the cIRM-GSN baseline of the Intel N-DNS challenge recipes
+(``recipes/intel_ndns/cirm_gsn/default.toml``).
+
+Same constructor keywords and defaults (modeling_cirm_gsn.py:162-204), same state-dict names (``fb_model`` is this package's
+``modeling_spiking_fullsubnet.SequenceModel``), same initialisation under a fixed seed and the same ``forward(input[B, samples])``
+return values (:206-245).  A recipe switches over by changing only
+
+    [model]
+    path = "spiking_fullsubnet_amd.modeling_cirm_gsn.Model"
+
+In ``eval()`` mode a GSN model runs everything between ``stft`` and ``istft`` on the gfx950 kernels through ``FullbandEngine``; an
+LSTM model runs its sequence model on ATen (``training.sequence_model``) and the deep filter as torch operations.  Training is not
+covered: ``forward()`` in training mode, or with an input that requires grad, raises ``NotImplementedError``.
+"""
+from __future__ import annotations
+
+import torch
+import torch.nn as nn
+
+from .fullband_engine import FullbandEngine, FullbandSpec, activation_code
+from .modeling_spiking_fullsubnet import SequenceModel, _EngineMixin
+
+
+def deep_filter_torch(cmp: torch.Tensor, coef: torch.Tensor, df: int, S: int) -> torch.Tensor:
+    """deepfiltering (modeling_cirm_gsn.py:125-157) with the coefficients in the projection's column order:
+    cmp complex [B, F, T], coef [B, 2 df S F, T] -> [B, S, F, T], Y[f, t] = sum_d X[f, t - (df - 1) + d] C[d]."""
+    B, F, T = cmp.shape
+    c = coef.reshape(B, 2, df, S, F, T)
+    cc = torch.complex(c[:, 0], c[:, 1])                                          # [B, df, S, F, T]
+    taps = torch.nn.functional.pad(cmp, (df - 1, 0)).unfold(2, T, 1).permute(0, 2, 1, 3)  # [B, df, F, T]
+    return (taps[:, :, None] * cc).sum(1)
+
+
+class Model(_EngineMixin, nn.Module):
+    def __init__(self, n_fft, hop_length, win_length, fdrc, input_size, hidden_size, num_layers, proj_size, output_activate_function,
+                 df_order, use_pre_layer_norm_fb=True, bn=False, shared_weights=False, sequence_model="LSTM", num_spks=2):
+        super().__init__()
+        self.fb_model = SequenceModel(input_size=input_size, hidden_size=hidden_size, num_layers=num_layers,
+                                      shared_weights=shared_weights, sequence_model=sequence_model,
+                                      proj_size=proj_size * num_spks * df_order * 2, output_activate_function=output_activate_function,
+                                      bn=bn, use_pre_layer_norm=use_pre_layer_norm_fb)
+        self.fb_input_size, self.n_fft, self.hop_length, self.win_length = input_size, n_fft, hop_length, win_length
+        self.fdrc, self.df_order, self.num_spks = fdrc, df_order, num_spks
+        F = n_fft // 2 + 1
+        if input_size != F or proj_size != F:
+            # the reference feeds all F bins to the model and re-indexes its output as (c d s f) over F bins (:220-230): any other
+            # size fails there inside einops; refuse up front
+            raise ValueError(f"input_size ({input_size}) and proj_size ({proj_size}) must both equal n_fft // 2 + 1 = {F}")
+        self._fb_spec = FullbandSpec(n_fft=n_fft, fdrc=float(fdrc), hidden=hidden_size, layers=num_layers, df=df_order,
+                                     num_spks=num_spks, shared=bool(shared_weights), bn=bool(bn), ln=bool(use_pre_layer_norm_fb),
+                                     act=activation_code(output_activate_function))
+
+    def _make_engine(self, state_dict, device):
+        return FullbandEngine(self._fb_spec, state_dict, device, weight_bits=self.weight_bits)
+
+    def streaming(self, *args, **kwargs):
+        raise NotImplementedError("cIRM-GSN has no streaming session: the one-launch hop covers the Spiking-FullSubNet models only")
+
+    def forward(self, input):
+        assert input.ndim == 2, f"Input tensor must be 2D, but got {input.ndim}D."
+        if self.training or input.requires_grad:
+            raise NotImplementedError("training the cIRM-GSN model is not supported by spiking_fullsubnet_amd: call .eval() and pass an "
+                                      "input that does not require grad (inference only)")
+        with torch.no_grad():
+            if self.fb_model.sequence_model_name == "LSTM":
+                return self._forward_lstm(input)
+            return self._forward_gsn(input)
+
+    def _finish(self, enh_stft, enh_mag, layers, batch_size, sequence_length):
+        if self.num_spks > 1:
+            enh_y = self._istft(enh_stft.reshape(batch_size * self.num_spks, *enh_stft.shape[2:]), length=sequence_length)
+            # the reference returns `_` here, rebound by `fb_output, *_ = self.fb_model(...)` to [all_layer_outputs] (:228, :239)
+            return enh_y.reshape(batch_size, self.num_spks, -1), [layers]
+        enh_y = self._istft(enh_stft[:, 0], length=sequence_length)
+        return enh_y, enh_mag
+
+    def _forward_gsn(self, input):
+        batch_size, sequence_length = input.shape
+        res = self.engine().forward_stft(self._stft(input), want_layers=self.num_spks > 1)
+        mag = res["enh_mag"][:, 0] if res["enh_mag"] is not None else None
+        return self._finish(res["enh_stft"], mag, res["all_layers"], batch_size, sequence_length)
+
+    def _forward_lstm(self, input):
+        from . import training
+        batch_size, sequence_length = input.shape
+        cmp = self._stft(input)
+        coef, layers = training.sequence_model(self.fb_model, torch.abs(cmp) ** self.fdrc, training=False)  # [B, P, T]
+        enh = deep_filter_torch(cmp, coef, self.df_order, self.num_spks)
+        return self._finish(enh, torch.abs(enh[:, 0]), layers, batch_size, sequence_length)

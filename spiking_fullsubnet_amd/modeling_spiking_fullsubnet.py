@@ -195,9 +195,12 @@ class _EngineMixin:
             if dev.type != "cuda":
                 raise RuntimeError("spiking_fullsubnet_amd has no CPU path: move the module to a HIP device (`.to('cuda')`) first")
             sd = {k: t.detach().cpu().numpy() for k, t in tensors}
-            self._engine = Engine(self._spec(), sd, dev, weight_bits=self.weight_bits)
+            self._engine = self._make_engine(sd, dev)
             self._engine_key = key
         return self._engine
+
+    def _make_engine(self, state_dict, device):
+        return Engine(self._spec(), state_dict, device, weight_bits=self.weight_bits)
 
     def streaming(self, batch: int = 1, hop: int = 1, graph: bool = True, rows_per_wg=None, one_launch="auto", waveform: bool = False,
                   host_io: bool = False, resident: bool = False, idle_ms: int = 1000, count_spikes: bool = False):
