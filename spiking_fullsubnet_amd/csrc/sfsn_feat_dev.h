@@ -33,4 +33,18 @@ __device__ __forceinline__ float wave_sum(float v) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
 
+// wave_sum() is a balanced tree of adjacent pairs over the 64 lane values: row_shr 1/2/4/8 pair lanes, pairs of lanes, ... inside
+// each 16-lane row (lane 15 of a row = its sum), the two broadcasts give (R3 + R2) + (R1 + R0) in lane 63.  The same association
+// over 16 values held by ONE lane: four of these and tree4() are bit for bit wave_sum() of the 64 values (fp32 addition is
+// commutative, the library is built with -ffp-contract=off).
+__device__ __forceinline__ float tree16(const float (&a)[16]) {
+    float b[8], c[4];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) b[i] = a[2 * i + 1] + a[2 * i];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) c[i] = b[2 * i + 1] + b[2 * i];
+    return (c[3] + c[2]) + (c[1] + c[0]);
+}
+__device__ __forceinline__ float tree4(const float (&r)[4]) { return (r[3] + r[2]) + (r[1] + r[0]); }
+
 #endif

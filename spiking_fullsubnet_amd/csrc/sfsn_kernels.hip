@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <type_traits>
 
@@ -1544,19 +1545,172 @@ struct FeatParams {
 
 #define FEAT_TT 32  // frames per workgroup
 
-// grid (ceil(T/32), B), 256 threads.  LDS: magnitude tile [f_cnt][33] + full-band tile [32][FB] + a gather table of the
-// current unit chunk + one staging segment per wave.
+// grid (ceil(T/32), B), 256 threads.  LDS: magnitude tile [f_cnt][33] + full-band tile [FB][33] (both column-major with an odd
+// stride: 32 lanes reading 32 frames of one bin hit 32 banks) + the gather table of the current unit chunk (byte offsets into
+// the two tiles, unit k at k * IP with IP = I rounded up to 16, the padding pointing at a row of zeros) + the chunk's LayerNorm
+// statistics [unit][33] (mean, rstd) + the 32 zeros.
 //
-// A wave owns a frame.  For every unit of the chunk it gathers the row from the tiles (per-lane LDS offsets from the
-// table, built once per chunk by the whole workgroup), normalises it with two DPP wave reductions and parks it in its
-// staging segment; the units of one (frame, clip) are contiguous in x, so the segment then leaves as one contiguous run
-// (1.1-1.3 KB at baseline_m) with every lane storing -- rows of 38/94/158 floats written one by one were partial-line
-// writes 78 KB apart.  NU = ceil(I/64) feature slots per lane is a template parameter: no work for absent slots.
-#define FEAT_CHUNK 512  // floats per staging segment / gather-table entries: units per chunk = FEAT_CHUNK / I
+// The units of one (frame, clip) are contiguous in x, so a chunk of nk units leaves as one contiguous run of nk * I floats per
+// frame (1.1-1.3 KB at baseline_m) -- rows of 38/94/158 floats written one by one were partial-line writes 78 KB apart.
+//
+// Default mapping, two phases per chunk (32-frame tile: a 64-frame one is twice the LDS, one workgroup per CU):
+//  (S) LayerNorm only.  A LANE owns a (frame, unit) row: lanes 0-31 of a wave are the 32 frames of one unit, lanes 32-63
+//      those of the next (separate LDS lane groups, so both halves read conflict-free).  The lane walks the row's elements
+//      (table entry = a broadcast read, value = a stride-1 read) and adds them in wave_sum()'s association: leaf l = slots
+//      l, l + 64, ... in order, balanced adjacent-pair tree over the 64 leaves (tree16 / tree4 of sfsn_feat_dev.h), 16 leaves
+//      at a time.  No DPP, no readlane, no idle lanes for I < 64; (mean, rstd) go to the statistics area.
+//  (O) A wave owns a frame (as before) and its lanes the elements of the run: gather again from the tile, normalise with
+//      the row's statistics, store -- the run leaves straight from registers, coalesced, with no staging copy in LDS.  A
+//      transposing staging area [32][nk * I + 1] for lane-per-row outputs would be 40 KB for a 316-float run: one workgroup per
+//      CU, or chunks of a unit or two that leave three waves of four idle in (S); without it the kernel needs 48.8 KB at
+//      baseline_m (three workgroups per CU).  Per-lane constants of (O) (table entry, unit, ln_w, ln_b) are set up once per chunk.
+// Every expression is the one of the wave-per-row body below, which stays as the reference (SFSN_FEAT_ROWS=wave): a wave owns a
+// frame, gathers each row, normalises it with two DPP wave reductions and parks it in its staging segment.
+// NU = ceil(I/64) feature slots per leaf / lane is a template parameter: no work for absent slots.
+#define FEAT_CHUNK 512  // elements of a chunk's run (floats per staging segment of the wave-per-row body): units per chunk = FEAT_CHUNK / I
+#define FEAT_KMAX 16    // ... and at most this many (statistics area; table padding)
+#define FEAT_TAB (FEAT_CHUNK + 16 * FEAT_KMAX)  // table entries
+#define FEAT_STATS (2 * FEAT_KMAX * 33 + 32)    // floats: statistics and the zero row
 
+__device__ __forceinline__ float feat_lds(const char* smem_b, int byte_off) { return *reinterpret_cast<const float*>(smem_b + byte_off); }
+
+// Sixteen leaves of a row's tree-sum for the lane that owns the row, summed: leaf i = slots u = 0 .. NS - 1 of element 16 blk + i
+// in order, from the literal 0.0f.  SQ = false: the elements; SQ = true: (v - mean)^2.  te: the unit's table entries of the
+// block, ttb = 4 * frame of the tile.  PAD: the last of the NS slots may end inside this block, its table entries past I then
+// point at the zero row: the first pass adds the 0.0f read there as the wave-per-row body adds its literal, the second adds
+// +0.0f to a sum of squares in place of skipping the element: the same bits.  Straight-line code: with a branch inside, the
+// compiler keeps every loaded value and adds late (196 VGPRs).
+template <int NS, bool SQ, bool PAD>
+__device__ __forceinline__ float feat_leaves16(const char* smem_b, const int* te, int ttb, int zrow, float mean) {
+    float leaf[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) leaf[i] = 0.0f;
+#pragma unroll
+    for (int u = 0; u < NS; ++u) {
+        int o[16];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const v4i o4 = *reinterpret_cast<const v4i*>(te + 64 * u + 4 * q);
+            o[4 * q] = o4.x; o[4 * q + 1] = o4.y; o[4 * q + 2] = o4.z; o[4 * q + 3] = o4.w;
+        }
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const float v = feat_lds(smem_b, o[i] + ttb);
+            if constexpr (SQ) {
+                const float d = v - mean;
+                leaf[i] += (PAD && u == NS - 1 && o[i] == zrow) ? 0.0f : d * d;
+            } else {
+                leaf[i] += v;
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);  // 16 table entries + 16 values in flight, not those of every slot (registers)
+    }
+    return tree16(leaf);
+}
+
+// One tree-sum over a row.  Slots u < NU - 1 are complete; the last holds rem = I - 64 (NU - 1) elements, so a block of 16
+// leaves either has it whole, or in part, or not at all: then nothing is added for it -- the wave-per-row body adds a literal
+// 0.0f there in the first pass, to a leaf that is either the literal 0.0f it started from (NU = 1) or 0.0f + v + ..., never
+// -0.0f: the same bits.
+template <int NU, bool SQ>
+__device__ __forceinline__ float feat_row_tree(const char* smem_b, const int* tabk, int I, int ttb, int zrow, float mean) {
+    const int rem = I - 64 * (NU - 1);
+    float part[4];
+#pragma unroll
+    for (int blk = 0; blk < 4; ++blk) {
+        const int* te = tabk + 16 * blk;
+        const int n = rem - 16 * blk;  // wave-uniform
+        if (n >= 16) part[blk] = feat_leaves16<NU, SQ, false>(smem_b, te, ttb, zrow, mean);
+        else if (n > 0) part[blk] = feat_leaves16<NU, SQ, true>(smem_b, te, ttb, zrow, mean);
+        else part[blk] = feat_leaves16<NU - 1, SQ, false>(smem_b, te, ttb, zrow, mean);
+    }
+    return tree4(part);
+}
+
+// Phase (S): (mean, rstd) of the chunk's 32 * nk rows, a lane per row.
+template <int NU>
+__device__ __forceinline__ void feat_lane_stats(const FeatGroupDev& g, const char* smem_b, const int* tab, v2f* stats, int nk, int IP,
+                                                int zrow, int tid) {
+    const float inv_I = 1.0f / (float)g.I;
+    for (int r0 = 0; r0 < 32 * nk; r0 += 256) {
+        if (r0 + (tid & ~63) >= 32 * nk) break;  // wave-uniform: no row left for this wave
+        const int r = r0 + tid, tt = r & 31;
+        const bool live = (r >> 5) < nk;
+        const int k = live ? r >> 5 : nk - 1;  // the idle half of a wave repeats the last unit and stores nothing
+        const int* tabk = tab + k * IP;
+        const float mean = feat_row_tree<NU, false>(smem_b, tabk, g.I, tt * 4, zrow, 0.0f) * inv_I;
+        asm volatile("" ::: "memory");  // the second pass reads the table again: up to 256 entries kept in registers cost the occupancy
+        const float rstd = __builtin_amdgcn_rsqf(feat_row_tree<NU, true>(smem_b, tabk, g.I, tt * 4, zrow, mean) * inv_I + g.eps);
+        if (live) stats[k * 33 + tt] = v2f{mean, rstd};
+    }
+}
+
+// Phase (O): the chunk's run of every frame, a wave per frame, lane + 64 m = element of the run.
+template <int NORM, int MM>
+__device__ __forceinline__ void feat_store_runs_m(const FeatGroupDev& g, const char* smem_b, const int* tab, const v2f* stats, int k0, int nk,
+                                                int IP, int b, int B, int t0, int tend, int lane, int wave) {
+    const int seg = nk * g.I;  // (MM - 1) * 64 < seg <= MM * 64: straight-line code, the loads of a frame issue together
+    const float lap_den = NORM == SFSN_NORM_LAPLACE ? g.mu[b] + 2.220446049250313e-16f : 1.0f;
+    const float gau_mu = NORM == SFSN_NORM_GAUSSIAN ? g.mu[b] : 0.0f;
+    const float gau_den = NORM == SFSN_NORM_GAUSSIAN ? g.ln_w[b] + 2.220446049250313e-16f : 1.0f;
+    const float r_I = 1.0f / (float)g.I;
+    int ob[MM], ks[MM];
+    float lw[MM], lb[MM];
+#pragma unroll
+    for (int m = 0; m < MM; ++m) {
+        lw[m] = 0.0f; lb[m] = 0.0f;
+        {
+            const int i = min(lane + 64 * m, seg - 1);
+            // unit of element i: (i + 0.5) / I is at least 1 / 512 away from an integer (I <= 256), the fp32 error is below 1e-4
+            const int k = (int)(((float)i + 0.5f) * r_I), j = i - k * g.I;
+            ob[m] = tab[k * IP + j];
+            ks[m] = k * 33;
+            if constexpr (NORM == SFSN_NORM_LAYERNORM) {
+                lw[m] = g.ln_w[j];
+                lb[m] = g.ln_b[j];
+            }
+        }
+    }
+    for (int tt = wave; tt < FEAT_TT; tt += 4) {
+        const int t = t0 + tt;
+        if (t >= tend) break;  // wave-uniform
+        float* out = g.x + ((size_t)t * B * g.N + (size_t)b * g.N + k0) * g.I;
+#pragma unroll
+        for (int m = 0; m < MM; ++m) {
+            {
+                const float v = feat_lds(smem_b, ob[m] + tt * 4);
+                float y;
+                if constexpr (NORM == SFSN_NORM_LAYERNORM) {
+                    const v2f s = stats[ks[m] + tt];
+                    y = ((v - s.x) * s.y) * lw[m] + lb[m];
+                } else if constexpr (NORM == SFSN_NORM_LAPLACE) {
+                    y = v / lap_den;
+                } else if constexpr (NORM == SFSN_NORM_GAUSSIAN) {
+                    y = (v - gau_mu) / gau_den;
+                } else {
+                    y = v;
+                }
+                const int i = lane + 64 * m;
+                if (m < MM - 1 || i < seg) out[i] = y;
+            }
+        }
+    }
+}
+
+template <int NORM>
+__device__ __forceinline__ void feat_store_runs(const FeatGroupDev& g, const char* smem_b, const int* tab, const v2f* stats, int k0, int nk,
+                                                int IP, int b, int B, int t0, int tend, int lane, int wave) {
+    switch ((nk * g.I + 63) >> 6) {  // <= FEAT_CHUNK / 64
+#define FEAT_M(M_) case M_: feat_store_runs_m<NORM, M_>(g, smem_b, tab, stats, k0, nk, IP, b, B, t0, tend, lane, wave); break;
+        FEAT_M(1) FEAT_M(2) FEAT_M(3) FEAT_M(4) FEAT_M(5) FEAT_M(6) FEAT_M(7) FEAT_M(8)
+#undef FEAT_M
+    }
+}
+
+// The wave-per-row body (reference; SFSN_FEAT_ROWS=wave).
 template <int NU, int NORM>
-__device__ __forceinline__ void feat_chunk_rows(const FeatGroupDev& g, const float* magT, const float* fbT, const int* offs,
-                                                float* stage, int k0, int nk, int b, int B, int FB, int t0, int tend, int lane, int wave) {
+__device__ __forceinline__ void feat_chunk_rows(const FeatGroupDev& g, const char* smem_b, const int* offs, int IP,
+                                                float* stage, int k0, int nk, int b, int B, int t0, int tend, int lane, int wave) {
     float lw[NU], lb[NU];
 #pragma unroll
     for (int u = 0; u < NU; ++u) {
@@ -1582,8 +1736,7 @@ __device__ __forceinline__ void feat_chunk_rows(const FeatGroupDev& g, const flo
             for (int u = 0; u < NU; ++u) {
                 const int j = lane + 64 * u;
                 have[u] = j < g.I;
-                const int o = have[u] ? offs[k * g.I + j] : 0;
-                v[u] = !have[u] ? 0.0f : (o < 0 ? fbT[tt * FB + (-1 - o)] : magT[o + tt]);
+                v[u] = have[u] ? feat_lds(smem_b, offs[k * IP + j] + tt * 4) : 0.0f;
                 sum += v[u];
             }
             float y[NU];
@@ -1621,6 +1774,8 @@ __device__ __forceinline__ void feat_chunk_rows(const FeatGroupDev& g, const flo
 // (zero_ptr, zero_n16): rows blockIdx.y >= B of the grid carry no feature tile -- they zero `zero_n16` 16-byte pieces at `zero_ptr`:
 // the zero initial state of a forward's scans (MODEL:100-106), written by the first launch of the forward's chain instead of by a
 // fill kernel of its own (round 3: 217 fill launches averaging 149 us each in the timed region, queued behind scan workgroups).
+// WAVE_ROWS: the wave-per-row reference body instead of the two phases.
+template <bool WAVE_ROWS>
 __global__ __launch_bounds__(256) void features_kernel(const float* __restrict__ stft, const float* __restrict__ fb,
                                                         const FeatParams p, float* __restrict__ zero_ptr, const size_t zero_n16) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -1636,11 +1791,16 @@ __global__ __launch_bounds__(256) void features_kernel(const float* __restrict__
     }
     const int nf = p.F - 1, T = p.T, B = p.B, FB = p.FB;
     float* magT = smem;                                         // [f_cnt][33]
-    float* fbT = smem + (size_t)p.f_cnt * 33;                   // [32][FB]
-    int* offs = reinterpret_cast<int*>(fbT + FEAT_TT * (FB > 0 ? FB : 1));  // [FEAT_CHUNK]
+    float* fbT = smem + (size_t)p.f_cnt * 33;                   // [FB][33]
+    const int fbt_off = p.f_cnt * 33, tab_off = (fbt_off + (FB > 0 ? FB : 1) * 33 + 3) & ~3;
+    int* offs = reinterpret_cast<int*>(smem + tab_off);         // [FEAT_TAB], 16-byte aligned
+    const char* smem_b = reinterpret_cast<const char*>(smem);
     const int b = blockIdx.y, t0 = p.t0 + blockIdx.x * FEAT_TT;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    float* stage = reinterpret_cast<float*>(offs + FEAT_CHUNK) + wave * FEAT_CHUNK;
+    v2f* stats = reinterpret_cast<v2f*>(offs + FEAT_TAB);       // [FEAT_KMAX][33]; the wave-per-row body's staging segments instead
+    float* stage = reinterpret_cast<float*>(offs + FEAT_TAB) + wave * FEAT_CHUNK;
+    const int zrow = 4 * (tab_off + FEAT_TAB + 2 * FEAT_KMAX * 33);  // byte offset of 32 floats of +0.0f: what an absent element reads
+    if (!WAVE_ROWS && tid < 32) smem[tab_off + FEAT_TAB + 2 * FEAT_KMAX * 33 + tid] = 0.0f;
     const int tend = p.t1;
 
     // Tile loads in batches of eight independent requests per thread (a load -> wait -> store loop costs one HBM round
@@ -1681,40 +1841,62 @@ __global__ __launch_bounds__(256) void features_kernel(const float* __restrict__
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 const int idx = i0 + 256 * i;
-                if (idx < nfb) fbT[idx] = (t0 + idx / FB < tend) ? v[i] : 0.0f;
+                const int tt = idx / FB, f = idx - tt * FB;
+                if (idx < nfb) fbT[f * 33 + tt] = (t0 + tt < tend) ? v[i] : 0.0f;
             }
         }
     }
 
     for (int gi = 0; gi < p.ng; ++gi) {
         const FeatGroupDev g = p.g[gi];
-        const int kch = FEAT_CHUNK / g.I;  // units per chunk (>= 1: I <= 256)
+        const int IP = (g.I + 15) & ~15;
+        int kch = FEAT_CHUNK / g.I;  // units per chunk (>= 1: I <= 256)
+        if (kch > FEAT_KMAX) kch = FEAT_KMAX;
         for (int k0 = 0; k0 < g.N; k0 += kch) {
             const int nk = (g.N - k0 < kch) ? g.N - k0 : kch;
-            // tiles loaded / previous chunk's table no longer read: LDS traffic only, so a raw barrier behind lgkmcnt(0) -- __syncthreads()
-            // is a workgroup-scope release and made every chunk's row stores retire in HBM before the next chunk began (round 5)
+            // tiles loaded / previous chunk's table and statistics no longer read: LDS traffic only, so a raw barrier behind lgkmcnt(0) --
+            // __syncthreads() is a workgroup-scope release and made every chunk's row stores retire in HBM before the next chunk began (round 5)
             __builtin_amdgcn_s_waitcnt(0xc07f);
             __builtin_amdgcn_s_barrier();
-            // gather table of the chunk: entry >= 0 = offset of the bin's row in magT, < 0 = -1 - full-band column
-            for (int idx = tid; idx < nk * g.I; idx += 256) {
-                const int k = idx / g.I, j = idx - k * g.I, ku = k0 + k;
-                offs[idx] = j < g.I1 ? (reflect_bin(g.lo + ku * g.ctr - g.nbr + j, nf) - p.f_lo) * 33
-                                     : -1 - reflect_bin(g.lo + ku * g.ctr_fb - g.nbr_fb + (j - g.I1), nf) % FB;
+            // gather table of the chunk: byte offset of the bin's row in magT or of the full-band column in fbT (the lane adds 4 * frame)
+            for (int idx = tid; idx < nk * IP; idx += 256) {
+                const int k = idx / IP, j = idx - k * IP, ku = k0 + k;
+                if (j >= g.I)
+                    offs[idx] = zrow;
+                else
+                    offs[idx] = 4 * (j < g.I1 ? (reflect_bin(g.lo + ku * g.ctr - g.nbr + j, nf) - p.f_lo) * 33
+                                              : fbt_off + (reflect_bin(g.lo + ku * g.ctr_fb - g.nbr_fb + (j - g.I1), nf) % FB) * 33);
             }
             __builtin_amdgcn_s_waitcnt(0xc07f);
             __builtin_amdgcn_s_barrier();
+            if constexpr (WAVE_ROWS) {
 #define FEAT_ROWS(NU_)                                                                                                             \
     do {                                                                                                                           \
-        if (g.norm == SFSN_NORM_LAYERNORM) feat_chunk_rows<NU_, SFSN_NORM_LAYERNORM>(g, magT, fbT, offs, stage, k0, nk, b, B, FB, t0, tend, lane, wave); \
-        else if (g.norm == SFSN_NORM_LAPLACE) feat_chunk_rows<NU_, SFSN_NORM_LAPLACE>(g, magT, fbT, offs, stage, k0, nk, b, B, FB, t0, tend, lane, wave); \
-        else if (g.norm == SFSN_NORM_GAUSSIAN) feat_chunk_rows<NU_, SFSN_NORM_GAUSSIAN>(g, magT, fbT, offs, stage, k0, nk, b, B, FB, t0, tend, lane, wave); \
-        else feat_chunk_rows<NU_, SFSN_NORM_NONE>(g, magT, fbT, offs, stage, k0, nk, b, B, FB, t0, tend, lane, wave);               \
+        if (g.norm == SFSN_NORM_LAYERNORM) feat_chunk_rows<NU_, SFSN_NORM_LAYERNORM>(g, smem_b, offs, IP, stage, k0, nk, b, B, t0, tend, lane, wave); \
+        else if (g.norm == SFSN_NORM_LAPLACE) feat_chunk_rows<NU_, SFSN_NORM_LAPLACE>(g, smem_b, offs, IP, stage, k0, nk, b, B, t0, tend, lane, wave); \
+        else if (g.norm == SFSN_NORM_GAUSSIAN) feat_chunk_rows<NU_, SFSN_NORM_GAUSSIAN>(g, smem_b, offs, IP, stage, k0, nk, b, B, t0, tend, lane, wave); \
+        else feat_chunk_rows<NU_, SFSN_NORM_NONE>(g, smem_b, offs, IP, stage, k0, nk, b, B, t0, tend, lane, wave);               \
     } while (0)
-            if (g.I <= 64) FEAT_ROWS(1);
-            else if (g.I <= 128) FEAT_ROWS(2);
-            else if (g.I <= 192) FEAT_ROWS(3);
-            else FEAT_ROWS(4);
+                if (g.I <= 64) FEAT_ROWS(1);
+                else if (g.I <= 128) FEAT_ROWS(2);
+                else if (g.I <= 192) FEAT_ROWS(3);
+                else FEAT_ROWS(4);
 #undef FEAT_ROWS
+            } else if (g.norm == SFSN_NORM_LAYERNORM) {
+                if (g.I <= 64) feat_lane_stats<1>(g, smem_b, offs, stats, nk, IP, zrow, tid);
+                else if (g.I <= 128) feat_lane_stats<2>(g, smem_b, offs, stats, nk, IP, zrow, tid);
+                else if (g.I <= 192) feat_lane_stats<3>(g, smem_b, offs, stats, nk, IP, zrow, tid);
+                else feat_lane_stats<4>(g, smem_b, offs, stats, nk, IP, zrow, tid);
+                __builtin_amdgcn_s_waitcnt(0xc07f);  // the statistics are in LDS
+                __builtin_amdgcn_s_barrier();
+                feat_store_runs<SFSN_NORM_LAYERNORM>(g, smem_b, offs, stats, k0, nk, IP, b, B, t0, tend, lane, wave);
+            } else if (g.norm == SFSN_NORM_LAPLACE) {
+                feat_store_runs<SFSN_NORM_LAPLACE>(g, smem_b, offs, stats, k0, nk, IP, b, B, t0, tend, lane, wave);
+            } else if (g.norm == SFSN_NORM_GAUSSIAN) {
+                feat_store_runs<SFSN_NORM_GAUSSIAN>(g, smem_b, offs, stats, k0, nk, IP, b, B, t0, tend, lane, wave);
+            } else {
+                feat_store_runs<SFSN_NORM_NONE>(g, smem_b, offs, stats, k0, nk, IP, b, B, t0, tend, lane, wave);
+            }
         }
     }
 }
@@ -2828,19 +3010,25 @@ extern "C" int sfsn_features_z(const float* stft_ri, const float* fb_tbf, int B,
     if (rc != SFSN_OK) return rc;
     for (int i = 0; i < n_groups; ++i)
         if (groups[i].ctr_fb > 0 && !fb_tbf) return SFSN_EINVAL;
-    const size_t lds = ((size_t)p.f_cnt * 33 + (size_t)FEAT_TT * (FB > 0 ? FB : 1) + 5 * FEAT_CHUNK) * sizeof(float);
+    // A/B runs and tests: SFSN_FEAT_ROWS=wave selects the wave-per-row reference body (read on every call)
+    const char* rows_env = getenv("SFSN_FEAT_ROWS");
+    const bool wave_rows = rows_env && strcmp(rows_env, "wave") == 0;
+    const size_t tab_off = (((size_t)p.f_cnt + (FB > 0 ? FB : 1)) * 33 + 3) & ~(size_t)3;
+    const size_t lds = (tab_off + FEAT_TAB + (wave_rows ? 4 * FEAT_CHUNK : FEAT_STATS)) * sizeof(float);
     if (lds > 150 * 1024) return SFSN_EUNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
+    const void* kern = wave_rows ? reinterpret_cast<const void*>(features_kernel<true>) : reinterpret_cast<const void*>(features_kernel<false>);
     if (lds > 64 * 1024) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(features_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds) != hipSuccess)
-            return SFSN_EHIP;
+        if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return SFSN_EHIP;
     }
     const unsigned gx = (unsigned)((nt + FEAT_TT - 1) / FEAT_TT);
     const size_t n16 = zero_bytes / 16, zblocks = (n16 + 8 * 256 - 1) / (8 * 256);
     const size_t zrows = (zblocks + gx - 1) / gx;
     if ((size_t)B + zrows > 65535) return SFSN_EUNSUPPORTED;
-    hipLaunchKernelGGL(features_kernel, dim3(gx, (unsigned)(B + zrows)), dim3(256), lds, st, stft_ri, fb_tbf, p, zero_ptr, n16);
+    if (wave_rows)
+        hipLaunchKernelGGL(features_kernel<true>, dim3(gx, (unsigned)(B + zrows)), dim3(256), lds, st, stft_ri, fb_tbf, p, zero_ptr, n16);
+    else
+        hipLaunchKernelGGL(features_kernel<false>, dim3(gx, (unsigned)(B + zrows)), dim3(256), lds, st, stft_ri, fb_tbf, p, zero_ptr, n16);
     return hip_ok(hipGetLastError());
 }
 
