@@ -351,6 +351,9 @@ int sfsn_spike_proj(const int8_t* s, const int8_t* w_packed, const float* w_dq, 
  *     j >= ctr+2nbr : fb[t][b][reflect(lo + k*ctr_fb - nbr_fb + j') % FB]  (the tiled full-band output, MODEL:442-443)
  * with mag = |stft|^fdrc on bins 0..nf-1 (nf = F-1).  The full-band model's own input is the group
  * {lo=0, n_units=1, ctr=FB, nbr=0, ctr_fb=0}.
+ * Input domain: every |stft| is 0 or lies in [2^-60, 2^60] -- the magnitude is sqrt(fma(re, re, im * im)) in fp32 without range
+ * scaling (sfsn_feat_dev.h), so values outside it may lose bits to underflow or overflow of the squares.  The same domain holds for
+ * sfsn_laplace_means, sfsn_gaussian_stats and the enh_mag outputs of the deep-filter entry points.
  * ---------------------------------------------------------------------------------------------------- */
 #define SFSN_NORM_NONE 0
 #define SFSN_NORM_LAYERNORM 1 /* (x - mean) * rstd * ln_w + ln_b over the I features, eps inside the sqrt       */

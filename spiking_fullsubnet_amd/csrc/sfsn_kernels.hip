@@ -3161,7 +3161,10 @@ extern "C" int sfsn_deepfilter(const float* stft_ri, int B, int F, int T, int S,
     p.fcov = lo;
     hipStream_t st = static_cast<hipStream_t>(stream);
     {   // pass-structured kernel: every P a multiple of 4 (16-byte coefficient loads), tiles within 48 KB of LDS
-        static const bool no_pass = getenv("SFSN_DF_GENERIC") != nullptr;  // diagnostic: force the unit-by-unit kernel
+        // (tests/frontback.py df_dispatch() restates this block's arithmetic to label which kernel a test case ran: keep the two together)
+        // diagnostic: force the unit-by-unit kernel.  Read ONCE per process (static), so tests must not depend on it: the shapes of
+        // tests/frontback.py reach that kernel on their own (P % 4 != 0, an unaligned proj, > DF_MAX_PASSES passes, a tile > 48 KB).
+        static const bool no_pass = getenv("SFSN_DF_GENERIC") != nullptr;
         DfPassParams pp;
         pp.base = p;
         pp.npass = 0;
