@@ -694,6 +694,26 @@ int sfsn_fullband_proj_deepfilter(const float* stft_ri /* [B][F][T][2] */, const
                                   int df, float* proj /* [T][B][2 df S F], nullable */, float* enh_ri /* [B][S][F][T][2] */,
                                   float* enh_mag /* [B][S][F][T], nullable */, int t0, int nt, void* stream);
 
+/* ----------------------------------------------------------------------------------------------------
+ * The cIRM-GSN deep filter for TRAINING (training.FullbandDeepFilterFn): the coefficients are the projection's (activated) output in
+ * its own layout, coef [T][B][P] with P = 2 * df * S * F and channel p = ((c * df + d) * S + s) * F + f, read / written exactly once.
+ *
+ * sfsn_fullband_deepfilter_fwd:
+ *     Y[b][s][f][t] = sum_{d<df} X[b][f][t-(df-1)+d] * (coef[t][b][(0,d,s,f)] + i coef[t][b][(1,d,s,f)])
+ *     X = 0 left of frame 0; d ascending; yr += xr * cr - xi * ci, yi += xr * ci + xi * cr (no contraction).
+ * sfsn_fullband_deepfilter_bwd (the gradient with respect to coef for a cotangent g of Y; none with respect to X):
+ *     d_coef[t][b][(0,d,s,f)] = xr * gr + xi * gi,  d_coef[t][b][(1,d,s,f)] = xr * gi - xi * gr,  x = X[b][f][t-(df-1)+d]
+ *     Every element of d_coef is written exactly once: no zero fill is needed before the launch.
+ * One workgroup = (clip, 32 frames, 32 bins): coefficient rows are read / written in runs of 32 bins (128 bytes), spectrum, output and
+ * cotangent rows in runs of 32 frames (256 bytes), turned in LDS.  No atomics, no waits between workgroups, nothing per launch but the
+ * launch (capturable).  B, T free; F <= 320, S <= 4, df <= 16: SFSN_EUNSUPPORTED otherwise.  spec_ri / enh_ri / g_ri 8-byte aligned.
+ * (Added without an ABI bump: no struct or signature changed.)
+ * ---------------------------------------------------------------------------------------------------- */
+int sfsn_fullband_deepfilter_fwd(const float* spec_ri /* [B][F][T][2] */, const float* coef /* [T][B][2 df S F] */, int B, int F, int T,
+                                 int S, int df, float* enh_ri /* [B][S][F][T][2] */, void* stream);
+int sfsn_fullband_deepfilter_bwd(const float* spec_ri /* [B][F][T][2] */, const float* g_ri /* [B][S][F][T][2] */, int B, int F, int T,
+                                 int S, int df, float* d_coef /* [T][B][2 df S F] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

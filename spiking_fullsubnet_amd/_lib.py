@@ -110,7 +110,7 @@ def _sources():
     """The files the library is made of, in the order the Makefile hashes them (SRCS)."""
     return [os.path.join(_HERE, "..", "include", "sfsn.h")] + [
         os.path.join(CSRC, f) for f in ("sfsn_scan_dev.h", "sfsn_scan3_dev.h", "sfsn_scan3i_dev.h", "sfsn_scan3x_dev.h", "sfsn_scan3w_dev.h", "sfsn_scan3j_dev.h", "sfsn_scan3g_dev.h", "sfsn_feat_dev.h", "sfsn_fft_dev.h", "sfsn_kernels.hip", "sfsn_stack.hip", "sfsn_hop.hip", "sfsn_fft.hip", "sfsn_train.hip",
-                                  "sfsn_featproj.hip", "sfsn_projdf.hip", "sfsn_fullband.hip", "sfsn_pack.cpp")]
+                                  "sfsn_featproj.hip", "sfsn_projdf.hip", "sfsn_fullband.hip", "sfsn_fullband_train.hip", "sfsn_pack.cpp")]
 
 
 def source_hash() -> str:
@@ -264,6 +264,10 @@ def lib() -> ctypes.CDLL:
     L.sfsn_fullband_input_proj.argtypes = [_P, _P, _P, _P, _I, _I, _I, _I, _P]
     L.sfsn_fullband_proj_deepfilter.restype = _I
     L.sfsn_fullband_proj_deepfilter.argtypes = [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _P]
+    L.sfsn_fullband_deepfilter_fwd.restype = _I  # spec_ri, coef | B, F, T, S, df | enh_ri, stream
+    L.sfsn_fullband_deepfilter_fwd.argtypes = [_P, _P, _I, _I, _I, _I, _I, _P, _P]
+    L.sfsn_fullband_deepfilter_bwd.restype = _I  # spec_ri, g_ri | B, F, T, S, df | d_coef, stream
+    L.sfsn_fullband_deepfilter_bwd.argtypes = [_P, _P, _I, _I, _I, _I, _I, _P, _P]
     if L.sfsn_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH}: ABI version {L.sfsn_abi_version()} != {ABI_VERSION}; rebuild (make -C {CSRC})")
     _lib = L
@@ -279,7 +283,7 @@ EXPORTS = ("sfsn_abi_version", "sfsn_source_hash", "sfsn_strerror", "sfsn_device
            "sfsn_spike_proj_multi", "sfsn_input_proj_f32_multi", "sfsn_features_proj",
            "sfsn_scan_split_scratch_bytes", "sfsn_gsn_layer_scan_split", "sfsn_proj_deepfilter", "sfsn_gsn_stack_scan_x_w16",
            "sfsn_hop_spike_slots", "sfsn_spike_count_rows", "sfsn_fullband_features", "sfsn_fullband_input_proj",
-           "sfsn_fullband_proj_deepfilter")
+           "sfsn_fullband_proj_deepfilter", "sfsn_fullband_deepfilter_fwd", "sfsn_fullband_deepfilter_bwd")
 
 
 def check(rc: int, what: str = "") -> None:

@@ -9,8 +9,14 @@ return values (:206-245).  A recipe switches over by changing only
     path = "spiking_fullsubnet_amd.modeling_cirm_gsn.Model"
 
 In ``eval()`` mode a GSN model runs everything between ``stft`` and ``istft`` on the gfx950 kernels through ``FullbandEngine``; an
-LSTM model runs its sequence model on ATen (``training.sequence_model``) and the deep filter as torch operations.  Training is not
-covered: ``forward()`` in training mode, or with an input that requires grad, raises ``NotImplementedError``.
+LSTM model runs its sequence model on ATen (``training.sequence_model``) and the deep filter as torch operations.
+
+In ``train()`` mode -- or in ``eval()`` mode with grad enabled and an input that requires grad (or ``autograd_in_eval = True``) --
+``forward()`` takes the differentiable path ``training.forward_cirm``: the GSN stack on the one-launch training layer calls of
+``csrc/sfsn_train.hip`` (a hidden size that is not a multiple of 16, the recipe's 268, padded to the next one with silent neurons:
+``training.PaddedStack``), the deep filter and its backward as one HIP launch each
+(``csrc/sfsn_fullband_train.hip``), the rest as ATen operations.  HIP tensors only: on CPU tensors that path raises
+``NotImplementedError``.
 """
 from __future__ import annotations
 
@@ -53,14 +59,17 @@ class Model(_EngineMixin, nn.Module):
     def _make_engine(self, state_dict, device):
         return FullbandEngine(self._fb_spec, state_dict, device, weight_bits=self.weight_bits)
 
+    def _kernel_path(self) -> bool:
+        return True  # (eval mode without gradients: the engine for GSN, _forward_lstm for LSTM -- both below)
+
     def streaming(self, *args, **kwargs):
         raise NotImplementedError("cIRM-GSN has no streaming session: the one-launch hop covers the Spiking-FullSubNet models only")
 
     def forward(self, input):
         assert input.ndim == 2, f"Input tensor must be 2D, but got {input.ndim}D."
-        if self.training or input.requires_grad:
-            raise NotImplementedError("training the cIRM-GSN model is not supported by spiking_fullsubnet_amd: call .eval() and pass an "
-                                      "input that does not require grad (inference only)")
+        if self._wants_autograd(input):
+            from . import training
+            return training.forward_cirm(self, input)
         with torch.no_grad():
             if self.fb_model.sequence_model_name == "LSTM":
                 return self._forward_lstm(input)

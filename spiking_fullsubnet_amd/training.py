@@ -320,8 +320,10 @@ class GSNLayerTrainFn(torch.autograd.Function):
         fg, gg = torch.empty((T, R, H), **f32), torch.empty((T, R, H), **f32)
         if fold:
             rm, rv = stats[0].float(), stats[1].float()
-            alpha = bn_w.detach().float() / torch.sqrt(rv + eps)
+            inv = 1.0 / torch.sqrt(rv + eps)
+            alpha = bn_w.detach().float() * inv
             beta = bn_b.detach().float() - rm * alpha
+            ctx.fold = (beta, inv, rm)  # (backward: the gradients of gamma / beta through the folded map)
         xhat = torch.empty((T, R, H), **f32) if (use_bn and not fold) else None
         invstd = torch.empty((T, H), **f32) if (use_bn and not fold) else None
         zero = torch.zeros((R, H), **f32)
@@ -414,6 +416,10 @@ class GSNLayerTrainFn(torch.autograd.Function):
         if _debug_scratch is not None:
             _debug_scratch.append(("bwd", R, H, T, scr))
         dh_rec = dc = None
+        want_bn = fold and (ctx.needs_input_grad[4] or ctx.needs_input_grad[5])
+        if want_bn:
+            f_beta, f_inv, f_rm = ctx.fold
+            g_alpha, g_beta = torch.zeros((H,), **f32), torch.zeros((H,), **f32)
         if seq:
             with torch.cuda.device(dev), _Logged("bwd", T, [(R, H, GH)]):
                 check(L.sfsn_gsn_train_seq_bwd(P(pw), P(pdy), P(pu), P(pxh) if bn_kernel else None, P(pf), P(pg), P(pis) if bn_kernel else None, a_bw,
@@ -432,6 +438,9 @@ class GSNLayerTrainFn(torch.autograd.Function):
                     du = dh * tri
                     if dc is not None:
                         du = du + dc
+                    if want_bn:  # u = alpha c' + beta: dL/dalpha = sum du c' with c' = (u - beta) / alpha (alpha = 0: a padded neuron, no gradient)
+                        g_alpha += (du * torch.where(alpha != 0, (u[t] - f_beta) / alpha, torch.zeros_like(alpha))).sum(0)
+                        g_beta += du.sum(0)
                     dcy = (du * alpha).contiguous()
                     rc = bwd(None, None, None, None, _p(dcy), P(pu + t * sRH), None, P(pf + t * sRH), P(pg + t * sRH), p_cp, None, None, R, H, sh,
                              P(pdg + t * s2H), P(pdz + t * sRG) if shared else None, P(pdc[t & 1]), None, None, p_scr, T - t, st)
@@ -463,7 +472,8 @@ class GSNLayerTrainFn(torch.autograd.Function):
         if not use_bn:
             d_bn_w = d_bn_b = None
         elif fold:
-            d_bn_w = d_bn_b = None  # (eval-mode gradients of gamma / beta are not produced: parameters are frozen in eval use)
+            # alpha = gamma inv, beta_folded = beta - mean gamma inv (the running statistics are constants in eval mode)
+            d_bn_w, d_bn_b = (((g_alpha - f_rm * g_beta) * f_inv).add_(poison), g_beta + poison) if want_bn else (None, None)
         return dx, dw_ih, dw_hh, dbias, d_bn_w, d_bn_b, None, None, None, None, None
 
 
@@ -1128,6 +1138,169 @@ def forward_live(model, wave: torch.Tensor):
     if S > 1:
         return enh_y.reshape(B, S, -1), fb_all, sb_all
     return enh_y, enh_stft[:, 0].abs(), fb_all, sb_all
+
+
+# ---- the cIRM-GSN model (modeling_cirm_gsn.Model) ----------------------------------------------------------------------------------
+# The model's deep filter as ONE HIP launch per direction (csrc/sfsn_fullband_train.hip) on the projection's own [T, B, P] layout;
+# SFSN_TRAIN_FULLBAND_DF=0: modeling_cirm_gsn.deep_filter_torch (measurement and cross-checks: scripts/exp_cirm_train.py).
+TRAIN_FULLBAND_DF = os.environ.get("SFSN_TRAIN_FULLBAND_DF", "1") != "0"
+
+
+def ceil16(h: int) -> int:
+    return (h + 15) // 16 * 16
+
+
+def pad_cell_tensors(w_ih, w_hh, bias, bn_w, bn_b, H: int, Hp: int, in_pad: int, shared: bool):
+    """fullband_engine.pad_cell out of differentiable operations on the module's parameters: w_ih [G H, I] -> [G Hp, in_pad], w_hh
+    [G H, H] -> [G Hp, Hp] (per gate block zero rows; zero input / recurrent columns), bias [2 H] -> [2 Hp] (padded neurons: forget
+    half 0, cell half -1), BatchNorm gamma / beta (or None) -> 0 / -1.  The gradient of a padded tensor is the slice of its cotangent.
+    Hp == H returns the tensors as they are."""
+    if Hp == H and in_pad == w_ih.shape[1]:
+        return w_ih, w_hh, bias, bn_w, bn_b
+    G, I, n = (1 if shared else 2), w_ih.shape[1], Hp - H
+    wi = torch.cat([F.pad(w_ih[g * H:(g + 1) * H], (0, in_pad - I, 0, n)) for g in range(G)])
+    wh = torch.cat([F.pad(w_hh[g * H:(g + 1) * H], (0, n, 0, n)) for g in range(G)])
+    b = torch.cat([F.pad(bias[:H], (0, n)), F.pad(bias[H:], (0, n), value=-1.0)])
+    if bn_w is not None:
+        bn_w, bn_b = F.pad(bn_w, (0, n)), F.pad(bn_b, (0, n), value=-1.0)
+    return wi, wh, b, bn_w, bn_b
+
+
+class _Shim:
+    """Attribute bag standing in for a StackedGSU / GSULayer / GSUCell / BatchNorm1d: gsn_stack, _stack_chunks, _pipelined_stacks and
+    _cell_args read a stack only through attributes."""
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+class PaddedStack:
+    """A StackedGSU whose hidden size H is not a multiple of 16, as the training layer calls take it at Hp = ceil16(H):
+    `.layers[l].cell` carries pad_cell_tensors of the module's parameters (non-leaf tensors: the gradients flow back into the module's
+    own [H]-shaped parameters), the BatchNorm running statistics as padded temporaries (mean 0, variance 1 for the padded neurons: with
+    gamma = 0 and beta = -1 their membrane is -1 in training and in eval mode, the triangle surrogate is 0 there and no gradient passes)
+    and the module's own num_batches_tracked.  The kernels update the temporaries in place; `commit()` copies their first H entries back
+    into the module's buffers on the current stream (no host synchronisation: the step stays capturable)."""
+
+    def __init__(self, stack):
+        cells = [layer.cell for layer in stack.layers]
+        H = cells[0].weight_hh.shape[1]
+        Hp = ceil16(H)
+        if Hp > _lib.MAX_HIDDEN:
+            raise NotImplementedError(f"hidden size {H} (padded {Hp}): the gfx950 scan holds W_hh register-resident up to {_lib.MAX_HIDDEN}")
+        self.H, self.Hp, self._stats, self.layers = H, Hp, [], []
+        for l, cell in enumerate(cells):
+            bn = getattr(cell, "batchnorm", None) if cell.use_bn else None
+            shared = bool(cell.shared_weights)
+            wi, wh, b, bw, bb = pad_cell_tensors(cell.weight_ih, cell.weight_hh, cell.bias_ih, None if bn is None else bn.weight,
+                                                 None if bn is None else bn.bias, H, Hp, cell.weight_ih.shape[1] if l == 0 else Hp, shared)
+            shim_bn = None
+            if bn is not None:
+                with torch.no_grad():
+                    rm, rv = F.pad(bn.running_mean, (0, Hp - H)), F.pad(bn.running_var, (0, Hp - H), value=1.0)
+                self._stats.append((bn, rm, rv))
+                shim_bn = _Shim(weight=bw, bias=bb, running_mean=rm, running_var=rv, num_batches_tracked=bn.num_batches_tracked,
+                                momentum=bn.momentum, eps=bn.eps)
+            self.layers.append(_Shim(cell=_Shim(weight_ih=wi, weight_hh=wh, bias_ih=b, shared_weights=shared, use_bn=bn is not None,
+                                                batchnorm=shim_bn)))
+
+    def commit(self) -> None:
+        with torch.no_grad():
+            for bn, rm, rv in self._stats:
+                bn.running_mean.copy_(rm[:self.H])
+                bn.running_var.copy_(rv[:self.H])
+
+
+class FullbandDeepFilterFn(torch.autograd.Function):
+    """deepfiltering (modeling_cirm_gsn.py:125-157) of the cIRM-GSN model on the projection's own layout: coef [T, B, 2 df S F]
+    (activated, contiguous, channel ((c df + d) S + s) F + f), spec_ri [B, F, T, 2] = view_as_real of the noisy spectrum (data: no
+    gradient) -> enh_ri [B, S, F, T, 2].  One launch per direction (sfsn_fullband_deepfilter_fwd / _bwd): the coefficients and their
+    gradient are read / written once."""
+
+    @staticmethod
+    def forward(ctx, coef, spec_ri, S, df):
+        if not coef.is_cuda:
+            raise RuntimeError("spiking_fullsubnet_amd has no CPU path: move the module and its input to a HIP device")
+        L = _lib.lib()
+        B, Fq, T, _ = spec_ri.shape
+        if tuple(coef.shape) != (T, B, 2 * df * S * Fq) or coef.dtype != torch.float32 or spec_ri.dtype != torch.float32:
+            raise ValueError(f"expected float32 coef [{T}, {B}, {2 * df * S * Fq}] and spec_ri [B, F, T, 2], got {tuple(coef.shape)} "
+                             f"{coef.dtype} and {tuple(spec_ri.shape)} {spec_ri.dtype}")
+        coef, spec_ri = coef.contiguous(), spec_ri.detach().contiguous()
+        enh = torch.empty((B, S, Fq, T, 2), dtype=torch.float32, device=coef.device)
+        with torch.cuda.device(coef.device):
+            check(L.sfsn_fullband_deepfilter_fwd(_p(spec_ri), _p(coef), B, Fq, T, S, df, _p(enh),
+                                                 ctypes.c_void_p(torch.cuda.current_stream(coef.device).cuda_stream)), "sfsn_fullband_deepfilter_fwd")
+        ctx.save_for_backward(spec_ri)
+        ctx.geo = (B, Fq, T, S, df)
+        return enh
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        spec_ri, = ctx.saved_tensors
+        B, Fq, T, S, df = ctx.geo
+        g = g.contiguous().float()
+        d_coef = torch.empty((T, B, 2 * df * S * Fq), dtype=torch.float32, device=g.device)
+        with torch.cuda.device(g.device):
+            check(_lib.lib().sfsn_fullband_deepfilter_bwd(_p(spec_ri), _p(g), B, Fq, T, S, df, _p(d_coef),
+                                                          ctypes.c_void_p(torch.cuda.current_stream(g.device).cuda_stream)),
+                  "sfsn_fullband_deepfilter_bwd")
+        return d_coef, None, None, None
+
+
+def _cirm_sequence_model(seq, x: torch.Tensor, training: bool):
+    """SequenceModel.forward of the cIRM-GSN model's GSN stack on time-major rows x [T, B, F]: (activated coefficients [T, B, P]
+    contiguous, [x_norm, S1, ..., SL, proj]) with H columns in every spike tensor.  A hidden size that is not a multiple of 16 runs
+    padded (PaddedStack); the projection then reads the padded spikes against zero weight columns (a column slice of [T, B, Hp] is
+    not contiguous, and _LinearTN's split weight-gradient GEMM wants contiguous rows)."""
+    if seq.use_pre_layer_norm:
+        x = _pre_ln(seq.pre_layer_norm, x)
+    x = x.contiguous()
+    stack = seq.sequence_model
+    H = stack.layers[0].cell.weight_hh.shape[1]
+    if H % 16 == 0:
+        outs = gsn_stack(x, stack, training)
+        y = _proj(seq.proj, outs[-1])
+    else:
+        padded = PaddedStack(stack)
+        outs = gsn_stack(x, padded, training)
+        if training:
+            padded.commit()
+        y = _LinearTN.apply(outs[-1], F.pad(seq.proj.weight, (0, padded.Hp - H)), seq.proj.bias)
+        outs = [outs[0]] + [s[:, :, :H] for s in outs[1:]]
+    return seq.output_activate_function(y).contiguous(), outs + [y]
+
+
+def forward_cirm(model, wave: torch.Tensor):
+    """modeling_cirm_gsn.Model.forward (audiozen/models/cirm_gsn/modeling_cirm_gsn.py:206-245) on differentiable operations: the
+    return values of eval mode, (enh_y [B, L], |enh_stft| [B, F, T]) for one speaker, (enh_y [B, S, L], [all_layer_outputs]) for
+    several."""
+    assert wave.ndim == 2, f"Input tensor must be 2D, but got {wave.ndim}D."
+    if not wave.is_cuda or not next(model.parameters()).is_cuda:
+        raise NotImplementedError("training the cIRM-GSN model (train() mode, or an input that requires grad) has no CPU path: move the "
+                                  "module and its input to a HIP device")
+    from .modeling_cirm_gsn import deep_filter_torch
+    B, length = wave.shape
+    window = torch.hann_window(model.n_fft, device=wave.device)
+    noisy = torch.stft(wave, model.n_fft, model.hop_length, model.win_length, window=window, return_complex=True, pad_mode="constant")
+    Fq, T = noisy.shape[1], noisy.shape[2]
+    S, df, seq = model.num_spks, model.df_order, model.fb_model
+    mag_t = (noisy.abs() ** model.fdrc).permute(2, 0, 1)            # [T, B, F]: all bins, the Nyquist bin included
+    if seq.sequence_model_name == "LSTM":
+        coef_bpt, layers = sequence_model(seq, mag_t, model.training, time_major=True)    # [B, P, T], []
+        coef = None
+    else:
+        coef, layers = _cirm_sequence_model(seq, mag_t, model.training)                   # [T, B, P]
+        coef_bpt = coef.permute(1, 2, 0)
+    if (TRAIN_FULLBAND_DF and coef is not None and not noisy.requires_grad and noisy.dtype == torch.complex64
+            and Fq <= 320 and S <= 4 and df <= 16):
+        enh = torch.view_as_complex(FullbandDeepFilterFn.apply(coef, torch.view_as_real(noisy), S, df))   # [B, S, F, T]
+    else:
+        enh = deep_filter_torch(noisy, coef_bpt, df, S)
+    enh_y = _istft(enh.reshape(B * S, Fq, T), model.n_fft, model.hop_length, model.win_length, window, length)
+    if S > 1:
+        return enh_y.reshape(B, S, -1), [layers]
+    return enh_y, enh[:, 0].abs()
 
 
 _LAPLACE_EPS = 2.220446049250313e-16  # audiozen/constant.py:11 (np.finfo(np.float32).eps is NOT what the reference adds)
