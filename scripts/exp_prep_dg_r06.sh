@@ -1,5 +1,6 @@
 #!/bin/bash
-# strict forward: prep-ahead (full-band features + input products of all chunks up front) with deeper full-band rings (exp libs dg6 / dg9)
+# strict forward with deeper full-band rings (exp libs dg6 / dg9; their combination with the prep of all chunks ahead was measured
+# with a switch that is gone: profiles/EXPERIMENTS.md)
 run() { # name, env...
   n=$1; shift
   env "$@" python bench.py --full --steps 24 --no-cpu-baseline --no-training-leg --no-streaming-leg --no-w16-leg 2>/dev/null | python -c "
@@ -7,9 +8,6 @@ import json,sys; l=json.loads(sys.stdin.readline()); c=l['config']; print('$n', 
 }
 for i in 1 2; do
   run base X=1
-  run prep SFSN_PREP_AHEAD=1
   run dg6 SFSN_LIB_PATH=$PWD/spiking_fullsubnet_amd/csrc_dg6/libsfsn_hip.so
-  run dg6+prep SFSN_LIB_PATH=$PWD/spiking_fullsubnet_amd/csrc_dg6/libsfsn_hip.so SFSN_PREP_AHEAD=1
   run dg9 SFSN_LIB_PATH=$PWD/spiking_fullsubnet_amd/csrc_dg9/libsfsn_hip.so
-  run dg9+prep SFSN_LIB_PATH=$PWD/spiking_fullsubnet_amd/csrc_dg9/libsfsn_hip.so SFSN_PREP_AHEAD=1
 done

@@ -25,6 +25,7 @@
 #include "sfsn.h"
 #include "sfsn_scan_dev.h"  // v4f, bf8, split3
 #include "sfsn_feat_dev.h"  // reflect_bin, compress_mag, wave_sum
+#include "sfsn_host.h"
 
 typedef int v2i __attribute__((ext_vector_type(2)));
 
@@ -417,20 +418,13 @@ __global__ __launch_bounds__(512) void featproj_kernel(const float* __restrict__
 // =====================================================================================================
 // host
 // =====================================================================================================
-static int fp_cu_count() {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    return (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-}
-
 extern "C" int sfsn_features_proj(const float* stft_ri, const float* fb_tbf, int B, int F, int T, int FB, float fdrc,
                                   const sfsn_featproj_job* jobs, int n_jobs, int t0, int nt, float* zero_ptr, size_t zero_bytes,
                                   void* stream) {
     if (!stft_ri || !jobs || n_jobs <= 0 || n_jobs > FP_MAX_JOBS || B <= 0 || F < 2 || T <= 0 || FB < 0) return SFSN_EINVAL;
     if (t0 < 0 || nt <= 0 || t0 + nt > T) return SFSN_EINVAL;
     if ((zero_bytes != 0 && !zero_ptr) || (zero_bytes & 15) || (reinterpret_cast<uintptr_t>(zero_ptr) & 15)) return SFSN_EINVAL;
-    static const bool no_bf3 = getenv("SFSN_INPROJ_F32") != nullptr;  // (the diagnostic switch of sfsn_input_proj_f32)
-    if (no_bf3) return SFSN_EUNSUPPORTED;
+    if (sfsn_knob_set("SFSN_INPROJ_F32")) return SFSN_EUNSUPPORTED;  // (the diagnostic switch of sfsn_input_proj_f32)
     if (FB > 0 && (FP_TT * FB > 512 * FP_NFB || 512 % FB != 0)) return SFSN_EUNSUPPORTED;
     if ((double)B * F * T * 2 >= 2147483648.0 || (double)T * B * (FB > 0 ? FB : 1) >= 2147483648.0) return SFSN_EUNSUPPORTED;  // 32-bit offsets
     const int nf = F - 1;
@@ -506,9 +500,9 @@ extern "C" int sfsn_features_proj(const float* stft_ri, const float* fb_tbf, int
     if (nu_max > 3 || tpw_max * ks_max > 12 || (ks_max == 6 && tpw_max > 1) || (ks_max == 5 && tpw_max > 2)) return SFSN_EUNSUPPORTED;
     if (lds > 150 * 1024) return SFSN_EUNSUPPORTED;
     // persistent workgroups dealt in proportion to the jobs' estimated cycles
-    static const int blocks_env = getenv("SFSN_FP_BLOCKS") ? atoi(getenv("SFSN_FP_BLOCKS")) : 0;
+    const int blocks_env = sfsn_knob("SFSN_FP_BLOCKS", 0);
     const int per_cu = lds <= 78 * 1024 ? 2 : 1;
-    const int total = blocks_env > 0 ? blocks_env : fp_cu_count() * per_cu;
+    const int total = blocks_env > 0 ? blocks_env : cu_count() * per_cu;
     double sum = 0;
     for (int i = 0; i < n_jobs; ++i) sum += wt[i];
     int blocks = 0;
@@ -524,22 +518,9 @@ extern "C" int sfsn_features_proj(const float* stft_ri, const float* fb_tbf, int
     p.zero_ptr = zero_ptr;
     p.zero_n16 = zero_bytes / 16;
     blocks += (int)((p.zero_n16 + 8 * 512 - 1) / (8 * 512));
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
-#define FP_LAUNCH(TPW_, KSM_)                                                                                                    \
-    if (tpw_max == TPW_ && ks_max == KSM_) {                                                                                     \
-        static int lds_seen[64] = {0};                                                                                           \
-        auto kern = featproj_kernel<TPW_, KSM_>;                                                                                 \
-        if ((int)lds > lds_seen[dev]) {                                                                                          \
-            if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                                      \
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)      \
-                return SFSN_EHIP;                                                                                                \
-            lds_seen[dev] = (int)lds;                                                                                            \
-        }                                                                                                                        \
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(512), lds, st, stft_ri, fb_tbf, p);                                \
-        return hipGetLastError() == hipSuccess ? SFSN_OK : SFSN_EHIP;                                                            \
-    }
+#define FP_LAUNCH(TPW_, KSM_) \
+    if (tpw_max == TPW_ && ks_max == KSM_) return launch_lds<featproj_kernel<TPW_, KSM_>>(dim3((unsigned)blocks), dim3(512), lds, st, stft_ri, fb_tbf, p);
     FP_LAUNCH(1, 2) FP_LAUNCH(2, 2) FP_LAUNCH(3, 2) FP_LAUNCH(1, 3) FP_LAUNCH(2, 3) FP_LAUNCH(3, 3) FP_LAUNCH(1, 5) FP_LAUNCH(2, 5)
     FP_LAUNCH(1, 6)
 #undef FP_LAUNCH

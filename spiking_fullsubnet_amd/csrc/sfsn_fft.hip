@@ -15,6 +15,7 @@
 #include "sfsn.h"
 
 #include "sfsn_fft_dev.h"
+#include "sfsn_host.h"
 
 namespace {
 
@@ -168,8 +169,6 @@ __global__ __launch_bounds__(IFFT_WAVES * 64) void istft_kernel(const float* __r
     }
 }
 
-inline int hip_rc(hipError_t e) { return e == hipSuccess ? SFSN_OK : SFSN_EHIP; }
-
 }  // namespace
 
 extern "C" int sfsn_stft(const float* wave, int B, int L, int n_fft, int hop, const float* window, float* stft_ri, int T, void* stream) {
@@ -178,7 +177,7 @@ extern "C" int sfsn_stft(const float* wave, int B, int L, int n_fft, int hop, co
     if (T != 1 + L / hop || (reinterpret_cast<uintptr_t>(stft_ri) & 7)) return SFSN_EINVAL;
     hipLaunchKernelGGL(stft_kernel, dim3((T + FFT_TT - 1) / FFT_TT, B), dim3(256), 0, static_cast<hipStream_t>(stream), wave, window,
                        stft_ri, B, L, T, hop);
-    return hip_rc(hipGetLastError());
+    return hip_ok(hipGetLastError());
 }
 
 extern "C" int sfsn_istft(const float* stft_ri, int B, int T, int n_fft, int hop, const float* window, float* wave, int length,
@@ -187,9 +186,6 @@ extern "C" int sfsn_istft(const float* stft_ri, int B, int T, int n_fft, int hop
     if (n_fft != FFT_NFFT || FFT_NFFT % hop != 0 || FFT_NFFT / hop > IFFT_HALO + 1) return SFSN_EUNSUPPORTED;
     if (length > (T - 1) * hop + FFT_NFFT / 2 || (reinterpret_cast<uintptr_t>(stft_ri) & 7)) return SFSN_EINVAL;
     const int nblk = (length + FFT_NFFT / 2 + FFT_TT * hop - 1) / (FFT_TT * hop);
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(istft_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, IFFT_LDS) != hipSuccess)
-        return SFSN_EHIP;
-    hipLaunchKernelGGL(istft_kernel, dim3(nblk, B), dim3(IFFT_WAVES * 64), IFFT_LDS, static_cast<hipStream_t>(stream), stft_ri, window,
-                       wave, B, T, hop, length);
-    return hip_rc(hipGetLastError());
+    return launch_lds<istft_kernel>(dim3(nblk, B), dim3(IFFT_WAVES * 64), IFFT_LDS, static_cast<hipStream_t>(stream), stft_ri, window, wave,
+                                    B, T, hop, length);
 }

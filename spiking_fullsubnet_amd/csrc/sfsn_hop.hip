@@ -37,6 +37,7 @@
 #include "sfsn_scan_dev.h"
 #include "sfsn_feat_dev.h"
 #include "sfsn_fft_dev.h"
+#include "sfsn_host.h"
 
 #define HOP_THREADS 512
 #define HOP_WAVES 8
@@ -1236,27 +1237,14 @@ extern "C" int sfsn_stream_hop(const sfsn_hop_desc* desc, void* stream) {
     local.frames_before = desc->frames_before;
     // per-wave time stamps behind the control words (written by -DSFSN_HOP_STAMPS builds only; scripts/exp_hop.py reads them)
     local.dbg = reinterpret_cast<unsigned long long*>(static_cast<char*>(desc->scratch) + hop_counter_bytes(local));
-    int dev = 0;
     const int fit = hop_fits_device(local.nblocks);
     if (fit != SFSN_OK) return fit;
-    if (hipGetDevice(&dev) != hipSuccess) return SFSN_EHIP;
-    static int lds_set[2][2][64];  // per kernel instantiation (hop == 1 or not, one or two gate matrices) and device (round-4 advisor finding)
-    const int one = local.hop == 1 ? 1 : 0;
-    const bool g2 = local.G == 2;
-    const void* kern = one ? (g2 ? reinterpret_cast<const void*>(stream_hop_kernel<true, 2>) : reinterpret_cast<const void*>(stream_hop_kernel<true, 1>))
-                           : (g2 ? reinterpret_cast<const void*>(stream_hop_kernel<false, 2>) : reinterpret_cast<const void*>(stream_hop_kernel<false, 1>));
-    if (lds > 64 * 1024 && (dev < 0 || dev >= 64 || !lds_set[one][g2 ? 1 : 0][dev])) {  // (devices beyond the cache: set on every launch)
-        if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return SFSN_EHIP;
-        if (dev >= 0 && dev < 64) lds_set[one][g2 ? 1 : 0][dev] = 1;
-    }
     if (lds > 160 * 1024) return SFSN_EUNSUPPORTED;
-    if (one)
-        if (g2) hipLaunchKernelGGL((stream_hop_kernel<true, 2>), dim3(local.nblocks), dim3(HOP_THREADS), lds, static_cast<hipStream_t>(stream), local);
-        else hipLaunchKernelGGL((stream_hop_kernel<true, 1>), dim3(local.nblocks), dim3(HOP_THREADS), lds, static_cast<hipStream_t>(stream), local);
-    else
-        if (g2) hipLaunchKernelGGL((stream_hop_kernel<false, 2>), dim3(local.nblocks), dim3(HOP_THREADS), lds, static_cast<hipStream_t>(stream), local);
-        else hipLaunchKernelGGL((stream_hop_kernel<false, 1>), dim3(local.nblocks), dim3(HOP_THREADS), lds, static_cast<hipStream_t>(stream), local);
-    return hipGetLastError() == hipSuccess ? SFSN_OK : SFSN_EHIP;
+    const bool one = local.hop == 1, g2 = local.G == 2;
+    const dim3 grid(local.nblocks), block(HOP_THREADS);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (one) return g2 ? launch_lds<stream_hop_kernel<true, 2>>(grid, block, lds, st, local) : launch_lds<stream_hop_kernel<true, 1>>(grid, block, lds, st, local);
+    return g2 ? launch_lds<stream_hop_kernel<false, 2>>(grid, block, lds, st, local) : launch_lds<stream_hop_kernel<false, 1>>(grid, block, lds, st, local);
 }
 
 extern "C" int sfsn_stream_hop_resident(const sfsn_hop_desc* desc, void* doorbell, unsigned idle_ms, void* stream) {
@@ -1274,12 +1262,11 @@ extern "C" int sfsn_stream_hop_resident(const sfsn_hop_desc* desc, void* doorbel
     if (fit != SFSN_OK) return fit;
     if (lds > 160 * 1024) return SFSN_EUNSUPPORTED;
     const bool g2 = local.G == 2;
-    const void* kern = g2 ? reinterpret_cast<const void*>(stream_hop_resident_kernel<2>) : reinterpret_cast<const void*>(stream_hop_resident_kernel<1>);
-    if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return SFSN_EHIP;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (hipMemsetAsync(local.cnt + 1, 0, 2 * sizeof(unsigned), st) != hipSuccess) return SFSN_EHIP;  // (word 2: the hop-finished count)
     const unsigned polls = (idle_ms > 30000u ? 30000u : idle_ms) * 100000u;  // ticks of the 100 MHz wall clock
-    if (g2) hipLaunchKernelGGL(stream_hop_resident_kernel<2>, dim3(local.nblocks), dim3(HOP_THREADS), lds, st, local, static_cast<unsigned*>(doorbell), polls);
-    else hipLaunchKernelGGL(stream_hop_resident_kernel<1>, dim3(local.nblocks), dim3(HOP_THREADS), lds, st, local, static_cast<unsigned*>(doorbell), polls);
-    return hipGetLastError() == hipSuccess ? SFSN_OK : SFSN_EHIP;
+    const dim3 grid(local.nblocks), block(HOP_THREADS);
+    unsigned* bell = static_cast<unsigned*>(doorbell);
+    return g2 ? launch_lds<stream_hop_resident_kernel<2>>(grid, block, lds, st, local, bell, polls)
+              : launch_lds<stream_hop_resident_kernel<1>>(grid, block, lds, st, local, bell, polls);
 }

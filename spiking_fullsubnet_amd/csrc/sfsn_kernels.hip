@@ -28,6 +28,7 @@
 #include "sfsn_scan3j_dev.h"
 #include "sfsn_scan3g_dev.h"
 #include "sfsn_feat_dev.h"
+#include "sfsn_host.h"
 
 // G = 1: shared gate weights (W [H][*] used for both gates); G = 2: separate forget / cell weights.
 // KS = 64-wide k steps; NW = waves per workgroup; TPW = tiles owned by the first (NT - NW*(TPW-1)) waves, the
@@ -2275,35 +2276,6 @@ __global__ __launch_bounds__(DFP_THREADS) void deepfilter_pass_kernel(const floa
 // =====================================================================================================
 // host side: argument checks, dispatch on compile-time shapes, launches
 // =====================================================================================================
-static inline int hip_ok(hipError_t e) { return e == hipSuccess ? SFSN_OK : SFSN_EHIP; }
-// Per-DEVICE caches: one process may drive several GPUs (the function attribute below and the CU count are per device).
-#define SFSN_MAX_DEVICES 64
-static int current_device() {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= SFSN_MAX_DEVICES) dev = 0;
-    return dev;
-}
-static int cu_count() {  // compute units of the current device (256 on MI355X); 256 if the query fails
-    static int n[SFSN_MAX_DEVICES] = {0};
-    const int dev = current_device();
-    if (n[dev] == 0) {
-        int v = 0;
-        n[dev] = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-    }
-    return n[dev];
-}
-// hipFuncAttributeMaxDynamicSharedMemorySize raised to `bytes` on the current device (idempotent; a benign race between host
-// threads sets it twice at worst).  `seen` is the caller's per-kernel table of the largest size set per device.
-static int raise_lds(const void* kern, int bytes, int* seen) {
-    const int dev = current_device();
-    if (bytes > seen[dev]) {
-        if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return SFSN_EHIP;
-        seen[dev] = bytes;
-    }
-    return SFSN_OK;
-}
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 extern "C" int sfsn_abi_version(void) { return SFSN_ABI_VERSION; }
 
 // Test hook (not part of include/sfsn.h): wave n of a 64-wave launch runs wait_vmcnt_n's computed jump with n in its probe form (every
@@ -2371,15 +2343,9 @@ extern "C" int sfsn_device_count(void) {
 template <int G, int KS, int NW, int TPW, int OUT, int LP>
 static int launch_scan_variant(const ScanParams& p, int tiles, hipStream_t st) {
     using C = ScanCfg<G, KS, NW, TPW, OUT, LP>;
-    auto kern = gsn_scan_kernel<G, KS, NW, TPW, OUT, LP>;
-    if (C::LDS_BYTES > 64 * 1024) {
-        static int seen[SFSN_MAX_DEVICES] = {0};
-        if (raise_lds(reinterpret_cast<const void*>(kern), C::LDS_BYTES, seen) != SFSN_OK) return SFSN_EHIP;
-    }
     ScanParams q = p;
     q.wg_times = sfsn_wgprobe_take(1, tiles);
-    hipLaunchKernelGGL(kern, dim3(tiles), dim3(NW * 64), C::LDS_BYTES, st, q);
-    return hip_ok(hipGetLastError());
+    return launch_lds<gsn_scan_kernel<G, KS, NW, TPW, OUT, LP>>(dim3(tiles), dim3(NW * 64), C::LDS_BYTES, st, q);
 }
 
 template <int G, int KS, int NW, int TPW, int LP>
@@ -2410,22 +2376,8 @@ template <int KS, int RPW, int OUT>
 static int launch_scan3_variant(const ScanParams& p, int tiles, hipStream_t st) {
     using C = Scan3Cfg<KS, RPW, 0>;
     const int lds = C::lds_bytes(p.NT);
-    if (p.w16) {
-        auto k16 = gsn_scan3_kernel<KS, RPW, OUT, 1>;
-        if (lds > 64 * 1024) {
-            static int seen16[SFSN_MAX_DEVICES] = {0};
-            if (raise_lds(reinterpret_cast<const void*>(k16), lds, seen16) != SFSN_OK) return SFSN_EHIP;
-        }
-        hipLaunchKernelGGL(k16, dim3(tiles), dim3(1024), lds, st, p);
-        return hip_ok(hipGetLastError());
-    }
-    auto kern = gsn_scan3_kernel<KS, RPW, OUT>;
-    if (lds > 64 * 1024) {
-        static int seen[SFSN_MAX_DEVICES] = {0};
-        if (raise_lds(reinterpret_cast<const void*>(kern), lds, seen) != SFSN_OK) return SFSN_EHIP;
-    }
-    hipLaunchKernelGGL(kern, dim3(tiles), dim3(1024), lds, st, p);
-    return hip_ok(hipGetLastError());
+    if (p.w16) return launch_lds<gsn_scan3_kernel<KS, RPW, OUT, 1>>(dim3(tiles), dim3(1024), lds, st, p);
+    return launch_lds<gsn_scan3_kernel<KS, RPW, OUT>>(dim3(tiles), dim3(1024), lds, st, p);
 }
 
 static int launch_scan3(const ScanParams& p, int tiles, int out, int KS, hipStream_t st) {
@@ -2445,7 +2397,7 @@ static int layer_scan_impl(const sfsn_scan_segment* segs, int n_segs, int T, int
     ScanParams p;
     p.wg_times = nullptr;
     p.w16 = w16;
-    p.lsplit = sfsn_s3_lsplit_host();
+    p.lsplit = s3_lsplit_knob();
     // rows per workgroup: as few as it takes to spread the launch over ~all 256 CUs (see the kernel comment)
     int rows_total = 0;
     for (int i = 0; i < n_segs; ++i) rows_total += segs[i].R > 0 ? segs[i].R : 0;
@@ -2470,17 +2422,10 @@ static int layer_scan_impl(const sfsn_scan_segment* segs, int n_segs, int T, int
     if (out == 6) return SFSN_EUNSUPPORTED;  // membranes are a test output: request them together with fp32 spikes
     for (int i = 0; i < n_segs; ++i) {
         const sfsn_scan_segment& s = segs[i];
-        if (!s.spikes_i8 || (s.spikes_f32 != nullptr) != ((out & 1) != 0) || (s.membrane != nullptr) != ((out & 4) != 0))
-            return SFSN_EINVAL;
-        if (s.R <= 0 || !s.zin || !s.w_hh || !s.w_dq || !s.bias || !s.bn_alpha || !s.bn_beta || !s.h_state || !s.c_state)
-            return SFSN_EINVAL;
-        if (!aligned16(s.zin) || !aligned16(s.w_hh) || !aligned16(s.h_state) || !aligned16(s.c_state) ||
-            !aligned16(s.spikes_f32) || !aligned16(s.spikes_i8) || !aligned16(s.membrane))
-            return SFSN_EINVAL;
+        if (check_segment(s, out, SEG_NEED_ZIN | SEG_MEMBRANE) != SFSN_OK) return SFSN_EINVAL;
         ScanSegDev& d = p.seg[i];
-        d.zin = s.zin; d.w_hh = s.w_hh; d.w_dq = s.w_dq; d.bias = s.bias; d.bn_alpha = s.bn_alpha; d.bn_beta = s.bn_beta;
-        d.h_state = s.h_state; d.c_state = s.c_state; d.spikes_f32 = s.spikes_f32; d.spikes_i8 = s.spikes_i8; d.count = s.spike_count;
-        d.membrane = s.membrane; d.R = s.R; d.tile0 = tiles;
+        copy_segment(d, s, 0);
+        d.membrane = s.membrane; d.tile0 = tiles;
         tiles += (s.R + rpw - 1) / rpw;
     }
     p.nseg = n_segs; p.T = T; p.H = H; p.NT = H / 16;
@@ -2494,8 +2439,7 @@ static int layer_scan_impl(const sfsn_scan_segment* segs, int n_segs, int T, int
     if (streamed) {
         const int HPs = KS * 64;
         const size_t lds = (size_t)2 * 16 * (HPs + 32) + (size_t)5 * HPs * 4;
-        hipLaunchKernelGGL(gsn_scan_stream_kernel<2>, dim3(tiles), dim3(512), lds, st, p);
-        return hip_ok(hipGetLastError());
+        return launch_lds<gsn_scan_stream_kernel<2>>(dim3(tiles), dim3(512), lds, st, p);
     }
     // shared gates, at most 14 output tiles (two of the 16 waves are free for the input ring and the spike stores), no membrane
     // output: the scan with IO-specialised waves (sfsn_scan3_dev.h).  SFSN_SCAN_V2=1 keeps round 2's body (A/B runs, tests).
@@ -2509,13 +2453,7 @@ static int layer_scan_impl(const sfsn_scan_segment* segs, int n_segs, int T, int
 #define SCAN3G_CASE(KS_, OUT_)                                                                                            \
     if (KS == KS_ && out == OUT_) {                                                                                       \
         const int lds = Scan3gCfg<KS_>::lds_bytes(NT);                                                                     \
-        if (lds <= 160 * 1024 - 64) {                                                                                     \
-            auto kern = gsn_scan3g_kernel<KS_, OUT_>;                                                                     \
-            static int seen[SFSN_MAX_DEVICES] = {0};                                                                      \
-            if (raise_lds(reinterpret_cast<const void*>(kern), lds, seen) != SFSN_OK) return SFSN_EHIP;                   \
-            hipLaunchKernelGGL(kern, dim3(tiles), dim3(1024), lds, st, p);                                                \
-            return hip_ok(hipGetLastError());                                                                             \
-        }                                                                                                                 \
+        if (lds <= 160 * 1024 - 64) return launch_lds<gsn_scan3g_kernel<KS_, OUT_>>(dim3(tiles), dim3(1024), lds, st, p); \
     }
         SCAN3G_CASE(1, 2) SCAN3G_CASE(1, 3) SCAN3G_CASE(2, 2) SCAN3G_CASE(2, 3) SCAN3G_CASE(3, 2) SCAN3G_CASE(3, 3) SCAN3G_CASE(4, 2) SCAN3G_CASE(4, 3)
 #undef SCAN3G_CASE
@@ -2562,10 +2500,7 @@ extern "C" int sfsn_gsn_layer_scan_split(const sfsn_scan_segment* segs, int n_se
     const sfsn_scan_segment& s = segs[0];
     const int out = 2 | (s.spikes_f32 ? 1 : 0) | (s.membrane ? 4 : 0);
     if (out == 6) return SFSN_EUNSUPPORTED;
-    if (s.R <= 0 || !s.spikes_i8 || !s.zin || !s.w_hh || !s.w_dq || !s.bias || !s.bn_alpha || !s.bn_beta || !s.h_state || !s.c_state) return SFSN_EINVAL;
-    if (!aligned16(s.zin) || !aligned16(s.w_hh) || !aligned16(s.h_state) || !aligned16(s.c_state) || !aligned16(s.spikes_f32) ||
-        !aligned16(s.spikes_i8) || !aligned16(s.membrane) || !aligned16(scratch))
-        return SFSN_EINVAL;
+    if (check_segment(s, out, SEG_NEED_ZIN | SEG_MEMBRANE) != SFSN_OK || !aligned16(scratch)) return SFSN_EINVAL;
     if (scratch_bytes < sfsn_scan_split_scratch_bytes(s.R, H)) return SFSN_EINVAL;
     if (T == 0) return SFSN_OK;
     constexpr int G = 2;
@@ -2582,15 +2517,11 @@ extern "C" int sfsn_gsn_layer_scan_split(const sfsn_scan_segment* segs, int n_se
     ScanParams p;
     p.wg_times = nullptr; p.w16 = 0; p.lsplit = 0; p.rpw = 16;
     ScanSegDev& d = p.seg[0];
-    d.zin = s.zin; d.w_hh = s.w_hh; d.w_dq = s.w_dq; d.bias = s.bias; d.bn_alpha = s.bn_alpha; d.bn_beta = s.bn_beta;
-    d.h_state = s.h_state; d.c_state = s.c_state; d.spikes_f32 = s.spikes_f32; d.spikes_i8 = s.spikes_i8; d.count = s.spike_count;
-    d.membrane = s.membrane; d.R = s.R; d.tile0 = 0;
+    copy_segment(d, s, 0);
+    d.membrane = s.membrane; d.tile0 = 0;
     p.nseg = 1; p.T = T; p.H = H; p.NT = NT;
-    auto kern = gsn_scan_split_kernel<G>;
-    static int lds_seen[SFSN_MAX_DEVICES] = {0};
-    if (raise_lds(reinterpret_cast<const void*>(kern), (int)lds, lds_seen) != SFSN_OK) return SFSN_EHIP;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(TPS * 64), lds, static_cast<hipStream_t>(stream), p, static_cast<unsigned*>(scratch), TPS, NSPL);
-    return hip_ok(hipGetLastError());
+    return launch_lds<gsn_scan_split_kernel<G>>(dim3(blocks), dim3(TPS * 64), lds, static_cast<hipStream_t>(stream), p,
+                                                static_cast<unsigned*>(scratch), TPS, NSPL);
 }
 
 extern "C" int sfsn_gsn_layer_scan_fused(const sfsn_scan_segment* segs, const sfsn_fused_input* fin, int n_segs, int T, int H,
@@ -2601,22 +2532,16 @@ extern "C" int sfsn_gsn_layer_scan_fused(const sfsn_scan_segment* segs, const sf
     p.wg_times = nullptr;
     p.rpw = 16;
     p.w16 = 0;
-    p.lsplit = sfsn_s3_lsplit_host();
+    p.lsplit = s3_lsplit_knob();
     int tiles = 0;
     const int out = 2 | (segs[0].spikes_f32 ? 1 : 0);
     for (int i = 0; i < n_segs; ++i) {
         const sfsn_scan_segment& s = segs[i];
-        if (!s.spikes_i8 || (s.spikes_f32 != nullptr) != ((out & 1) != 0) || s.membrane) return SFSN_EINVAL;
-        if (s.R <= 0 || !fin[i].spikes_in || !fin[i].w_ih || !fin[i].w_ih_dq || !s.w_hh || !s.w_dq || !s.bias || !s.bn_alpha ||
-            !s.bn_beta || !s.h_state || !s.c_state)
-            return SFSN_EINVAL;
-        if (!aligned16(fin[i].spikes_in) || !aligned16(fin[i].w_ih) || !aligned16(s.w_hh) || !aligned16(s.h_state) ||
-            !aligned16(s.c_state) || !aligned16(s.spikes_f32) || !aligned16(s.spikes_i8))
-            return SFSN_EINVAL;
+        if (check_segment(s, out, SEG_NO_ZIN) != SFSN_OK) return SFSN_EINVAL;
+        if (!fin[i].spikes_in || !fin[i].w_ih || !fin[i].w_ih_dq || !aligned16(fin[i].spikes_in) || !aligned16(fin[i].w_ih)) return SFSN_EINVAL;
         ScanSegDev& d = p.seg[i];
-        d.zin = nullptr; d.w_hh = s.w_hh; d.w_dq = s.w_dq; d.bias = s.bias; d.bn_alpha = s.bn_alpha; d.bn_beta = s.bn_beta;
-        d.h_state = s.h_state; d.c_state = s.c_state; d.spikes_f32 = s.spikes_f32; d.spikes_i8 = s.spikes_i8; d.count = s.spike_count;
-        d.membrane = nullptr; d.R = s.R; d.tile0 = tiles;
+        copy_segment(d, s, SEG_NO_ZIN);
+        d.membrane = nullptr; d.tile0 = tiles;
         d.spikes_in = fin[i].spikes_in; d.w_ih = fin[i].w_ih; d.w_ih_dq = fin[i].w_ih_dq;
         tiles += (s.R + 15) / 16;
     }
@@ -2627,19 +2552,11 @@ extern "C" int sfsn_gsn_layer_scan_fused(const sfsn_scan_segment* segs, const sf
     if (p.NT <= 14 && !getenv("SFSN_FUSED_V2") && !getenv("SFSN_SCAN_V2")) {
         const bool tl = (H & 63) != 0 && (H & 63) <= 32;
         const int lds3 = KS == 3 ? Scan3jCfg<3>::lds_bytes(p.NT) : Scan3jCfg<4>::lds_bytes(p.NT);
-        {
-            const char* e = getenv("SFSN_S3J_LSPLIT");  // fp32 store instructions per frame the loader wave takes (A/B runs)
-            const int x = e ? atoi(e) : SFSN_S3J_LSPLIT;
-            p.lsplit = x < 0 ? 0 : (x > 14 ? 14 : x);
-        }
+        p.lsplit = sfsn_knob("SFSN_S3J_LSPLIT", SFSN_S3J_LSPLIT, 0, 14);  // fp32 store instructions per frame the loader wave takes (A/B runs)
 #define FUSED3_CASE(KS_, TL_, OUT_)                                                                                        \
     if (KS == KS_ && (int)tl == TL_ && out == OUT_ && lds3 <= 160 * 1024 - 64) {                                           \
-        auto kern = gsn_scan_fused3_kernel<KS_, TL_, OUT_>;                                                                \
-        static int seen[SFSN_MAX_DEVICES] = {0};                                                                           \
-        if (raise_lds(reinterpret_cast<const void*>(kern), lds3, seen) != SFSN_OK) return SFSN_EHIP;                       \
         p.wg_times = sfsn_wgprobe_take(2, tiles);                                                                          \
-        hipLaunchKernelGGL(kern, dim3(tiles), dim3(1024), lds3, st, p);                                                    \
-        return hip_ok(hipGetLastError());                                                                                  \
+        return launch_lds<gsn_scan_fused3_kernel<KS_, TL_, OUT_>>(dim3(tiles), dim3(1024), lds3, st, p);                   \
     }
         // 14 tiles (H = 224) and no fp32 spike tensor: the IO waves compute the input terms of tiles 12 / 13 (scan3j_role, OFF form).
         // Measured (B = 64, T = 1000, 52 workgroups, ms per launch, scripts/exp_s3joff_r06.py): without fp32 spikes 1.320 -> 1.238; WITH
@@ -2651,12 +2568,8 @@ extern "C" int sfsn_gsn_layer_scan_fused(const sfsn_scan_segment* segs, const sf
             const int ldso = Scan3jCfg<4>::lds_bytes_off(14);
 #define FUSED3O_CASE(OUT_)                                                                                                 \
     if (out == OUT_) {                                                                                                     \
-        auto kern = gsn_scan_fused3_kernel<4, 1, OUT_, 1>;                                                                 \
-        static int seen[SFSN_MAX_DEVICES] = {0};                                                                           \
-        if (raise_lds(reinterpret_cast<const void*>(kern), ldso, seen) != SFSN_OK) return SFSN_EHIP;                       \
         p.wg_times = sfsn_wgprobe_take(2, tiles);                                                                          \
-        hipLaunchKernelGGL(kern, dim3(tiles), dim3(1024), ldso, st, p);                                                    \
-        return hip_ok(hipGetLastError());                                                                                  \
+        return launch_lds<gsn_scan_fused3_kernel<4, 1, OUT_, 1>>(dim3(tiles), dim3(1024), ldso, st, p);                    \
     }
             FUSED3O_CASE(2) FUSED3O_CASE(3)
 #undef FUSED3O_CASE
@@ -2668,12 +2581,8 @@ extern "C" int sfsn_gsn_layer_scan_fused(const sfsn_scan_segment* segs, const sf
     if (lds > 160 * 1024) return SFSN_EUNSUPPORTED;
 #define FUSED_CASE(KS_, OUT_)                                                                                              \
     if (KS == KS_ && out == OUT_) {                                                                                        \
-        auto kern = gsn_scan_fused_kernel<KS_, OUT_>;                                                                      \
-        static int seen[SFSN_MAX_DEVICES] = {0}; /* per device, raised to the largest size seen (not a stream operation) */ \
-        if (raise_lds(reinterpret_cast<const void*>(kern), lds, seen) != SFSN_OK) return SFSN_EHIP;                        \
         p.wg_times = sfsn_wgprobe_take(2, tiles);                                                                          \
-        hipLaunchKernelGGL(kern, dim3(tiles), dim3(512), lds, st, p);                                                      \
-        return hip_ok(hipGetLastError());                                                                                  \
+        return launch_lds<gsn_scan_fused_kernel<KS_, OUT_>>(dim3(tiles), dim3(512), lds, st, p);                           \
     }
     FUSED_CASE(3, 2) FUSED_CASE(3, 3) FUSED_CASE(4, 2) FUSED_CASE(4, 3)
 #undef FUSED_CASE
@@ -2688,23 +2597,17 @@ extern "C" int sfsn_gsn_layer_scan_fused_x(const sfsn_scan_segment* segs, const 
     p.wg_times = nullptr;
     p.rpw = 16;
     p.w16 = 0;
-    p.lsplit = sfsn_s3_lsplit_host();
+    p.lsplit = s3_lsplit_knob();
     int tiles = 0, imax = 0;
     const int out = 2 | (segs[0].spikes_f32 ? 1 : 0);
     for (int i = 0; i < n_segs; ++i) {
         const sfsn_scan_segment& s = segs[i];
-        if (!s.spikes_i8 || (s.spikes_f32 != nullptr) != ((out & 1) != 0) || s.membrane) return SFSN_EINVAL;
-        if (s.R <= 0 || !fin[i].x || !fin[i].w_ih || !s.w_hh || !s.w_dq || !s.bias || !s.bn_alpha || !s.bn_beta || !s.h_state ||
-            !s.c_state)
-            return SFSN_EINVAL;
-        if (fin[i].I <= 0 || fin[i].I > 64 || fin[i].I % 2 != 0 || s.R % 16 != 0) return SFSN_EUNSUPPORTED;
-        if (!aligned16(fin[i].x) || !aligned16(s.w_hh) || !aligned16(s.h_state) || !aligned16(s.c_state) || !aligned16(s.spikes_f32) ||
-            !aligned16(s.spikes_i8))
-            return SFSN_EINVAL;
+        if (check_segment(s, out, SEG_NO_ZIN | SEG_DEFER_ALIGN) != SFSN_OK || !fin[i].x || !fin[i].w_ih) return SFSN_EINVAL;
+        if (fin[i].I <= 0 || fin[i].I > 64 || fin[i].I % 2 != 0 || s.R % 16 != 0) return SFSN_EUNSUPPORTED;  // (answers before alignment)
+        if (!aligned16(fin[i].x) || !segment_aligned(s, SEG_NO_ZIN)) return SFSN_EINVAL;
         ScanSegDev& d = p.seg[i];
-        d.zin = nullptr; d.w_hh = s.w_hh; d.w_dq = s.w_dq; d.bias = s.bias; d.bn_alpha = s.bn_alpha; d.bn_beta = s.bn_beta;
-        d.h_state = s.h_state; d.c_state = s.c_state; d.spikes_f32 = s.spikes_f32; d.spikes_i8 = s.spikes_i8; d.count = s.spike_count;
-        d.membrane = nullptr; d.R = s.R; d.tile0 = tiles;
+        copy_segment(d, s, SEG_NO_ZIN);
+        d.membrane = nullptr; d.tile0 = tiles;
         d.spikes_in = nullptr; d.w_ih = nullptr; d.w_ih_dq = nullptr;
         d.x_in = fin[i].x; d.w_ih_f32 = fin[i].w_ih; d.I = fin[i].I;
         if (fin[i].I > imax) imax = fin[i].I;
@@ -2717,19 +2620,11 @@ extern "C" int sfsn_gsn_layer_scan_fused_x(const sfsn_scan_segment* segs, const 
     if (p.NT <= 14 && !getenv("SFSN_FUSED_V2") && !getenv("SFSN_SCAN_V2")) {
         const bool tl = (H & 63) != 0 && (H & 63) <= 32;
         const int lds3 = KS == 3 ? Scan3yCfg<3, 2>::lds_bytes(p.NT) : Scan3yCfg<4, 2>::lds_bytes(p.NT);
-        {
-            const char* e = getenv("SFSN_S3Y_LSPLIT");
-            const int x = e ? atoi(e) : SFSN_S3Y_LSPLIT;
-            p.lsplit = x < 0 ? 0 : (x > 14 ? 14 : x);
-        }
+        p.lsplit = sfsn_knob("SFSN_S3Y_LSPLIT", SFSN_S3Y_LSPLIT, 0, 14);
 #define FUSEDX3_CASE(KS_, TL_, OUT_)                                                                                       \
     if (KS == KS_ && (int)tl == TL_ && out == OUT_ && lds3 <= 160 * 1024 - 64) {                                           \
-        auto kern = gsn_scan_fusedx3_kernel<KS_, TL_, OUT_>;                                                               \
-        static int seen[SFSN_MAX_DEVICES] = {0};                                                                           \
-        if (raise_lds(reinterpret_cast<const void*>(kern), lds3, seen) != SFSN_OK) return SFSN_EHIP;                       \
         p.wg_times = sfsn_wgprobe_take(3, tiles);                                                                          \
-        hipLaunchKernelGGL(kern, dim3(tiles), dim3(1024), lds3, st, p);                                                    \
-        return hip_ok(hipGetLastError());                                                                                  \
+        return launch_lds<gsn_scan_fusedx3_kernel<KS_, TL_, OUT_>>(dim3(tiles), dim3(1024), lds3, st, p);                  \
     }
         FUSEDX3_CASE(3, 0, 2) FUSEDX3_CASE(3, 0, 3) FUSEDX3_CASE(3, 1, 2) FUSEDX3_CASE(3, 1, 3) FUSEDX3_CASE(4, 1, 2) FUSEDX3_CASE(4, 1, 3)
 #undef FUSEDX3_CASE
@@ -2739,12 +2634,8 @@ extern "C" int sfsn_gsn_layer_scan_fused_x(const sfsn_scan_segment* segs, const 
     if (lds > 160 * 1024) return SFSN_EUNSUPPORTED;
 #define FUSEDX_CASE(KS_, OUT_)                                                                                             \
     if (KS == KS_ && out == OUT_) {                                                                                        \
-        auto kern = gsn_scan_fusedx_kernel<KS_, OUT_>;                                                                     \
-        static int seen[SFSN_MAX_DEVICES] = {0}; /* per device, raised to the largest size seen (not a stream operation) */ \
-        if (raise_lds(reinterpret_cast<const void*>(kern), lds, seen) != SFSN_OK) return SFSN_EHIP;                        \
         p.wg_times = sfsn_wgprobe_take(3, tiles);                                                                          \
-        hipLaunchKernelGGL(kern, dim3(tiles), dim3(512), lds, st, p);                                                      \
-        return hip_ok(hipGetLastError());                                                                                  \
+        return launch_lds<gsn_scan_fusedx_kernel<KS_, OUT_>>(dim3(tiles), dim3(512), lds, st, p);                          \
     }
     FUSEDX_CASE(3, 2) FUSEDX_CASE(3, 3) FUSEDX_CASE(4, 2) FUSEDX_CASE(4, 3)
 #undef FUSEDX_CASE
@@ -2774,26 +2665,17 @@ extern "C" int sfsn_spike_proj(const int8_t* s, const int8_t* w_packed, const fl
     if (fast) {
         int fgrid = (M + 63) / 64;
         { const int cap = cu_count() * (TPW == 1 ? 2 : 1); if (fgrid > cap) fgrid = cap; }  // resident workgroups only: the W tiles are loaded once per workgroup
-#define SPF_CASE(TPW_, KS_)                                                                                              \
-    if (TPW == TPW_ && KS == KS_) {                                                                                      \
-        auto kern = spike_proj_fast_kernel<TPW_, KS_>;                                                                   \
-        if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                                  \
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) \
-            return SFSN_EHIP;                                                                                            \
-        hipLaunchKernelGGL(kern, dim3(fgrid), dim3(512), lds, st, s, w_packed, w_dq, bias, y, M, N, ldy, NT, NWN);       \
-        return hip_ok(hipGetLastError());                                                                                \
-    }
+#define SPF_CASE(TPW_, KS_)      \
+    if (TPW == TPW_ && KS == KS_) \
+        return launch_lds<spike_proj_fast_kernel<TPW_, KS_>>(dim3(fgrid), dim3(512), lds, st, s, w_packed, w_dq, bias, y, M, N, ldy, NT, NWN);
         SPF_CASE(1, 1) SPF_CASE(1, 2) SPF_CASE(1, 3) SPF_CASE(1, 4) SPF_CASE(1, 5)
         SPF_CASE(2, 1) SPF_CASE(2, 2) SPF_CASE(2, 3) SPF_CASE(2, 4) SPF_CASE(2, 5)
         SPF_CASE(3, 1) SPF_CASE(3, 2) SPF_CASE(3, 3) SPF_CASE(3, 4) SPF_CASE(3, 5)
 #undef SPF_CASE
     }
-#define SP_CASE(TPW_, KS_)                                                                                          \
-    if (TPW == TPW_ && KS == KS_) {                                                                                 \
-        hipLaunchKernelGGL((spike_proj_kernel<TPW_, KS_>), dim3(grid), dim3(512), 0, st, s, w_packed, w_dq, bias, y, M, N, \
-                           ldy, NT, NWN);                                                                                \
-        return hip_ok(hipGetLastError());                                                                           \
-    }
+#define SP_CASE(TPW_, KS_)       \
+    if (TPW == TPW_ && KS == KS_) \
+        return launch_lds<spike_proj_kernel<TPW_, KS_>>(dim3(grid), dim3(512), 0, st, s, w_packed, w_dq, bias, y, M, N, ldy, NT, NWN);
     SP_CASE(1, 1) SP_CASE(1, 2) SP_CASE(1, 3) SP_CASE(1, 4) SP_CASE(1, 5)
     SP_CASE(2, 1) SP_CASE(2, 2) SP_CASE(2, 3) SP_CASE(2, 4) SP_CASE(2, 5)
     SP_CASE(3, 1) SP_CASE(3, 2) SP_CASE(3, 3) SP_CASE(3, 4) SP_CASE(3, 5)
@@ -2841,15 +2723,8 @@ extern "C" int sfsn_spike_proj_multi(const sfsn_proj_job* jobs, int n, void* str
     int blocks = 0;
     for (int i = 0; i < n; ++i) { p.job[i].block0 = blocks; p.job[i].nblocks = nb[i]; blocks += nb[i]; }
     hipStream_t st = static_cast<hipStream_t>(stream);
-#define SPM_CASE(KS_)                                                                                                    \
-    if (KS0 == KS_) {                                                                                                    \
-        auto kern = spike_proj_multi_kernel<KS_>;                                                                        \
-        if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                                  \
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) \
-            return SFSN_EHIP;                                                                                            \
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(512), lds, st, p);                                                   \
-        return hip_ok(hipGetLastError());                                                                                \
-    }
+#define SPM_CASE(KS_) \
+    if (KS0 == KS_) return launch_lds<spike_proj_multi_kernel<KS_>>(dim3(blocks), dim3(512), lds, st, p);
     SPM_CASE(1) SPM_CASE(2) SPM_CASE(3) SPM_CASE(4) SPM_CASE(5)
 #undef SPM_CASE
     return SFSN_EUNSUPPORTED;
@@ -2857,8 +2732,7 @@ extern "C" int sfsn_spike_proj_multi(const sfsn_proj_job* jobs, int n, void* str
 
 extern "C" int sfsn_input_proj_f32_multi(const sfsn_inproj_job* jobs, int n, void* stream) {
     if (!jobs || n <= 0 || n > SFSN_MAX_SEGMENTS) return SFSN_EINVAL;
-    static const bool no_bf3 = getenv("SFSN_INPROJ_F32") != nullptr;
-    if (no_bf3) return SFSN_EUNSUPPORTED;
+    if (sfsn_knob_set("SFSN_INPROJ_F32")) return SFSN_EUNSUPPORTED;
     InProjMultiParams p;
     p.n = n;
     int ns[SFSN_MAX_SEGMENTS], nb[SFSN_MAX_SEGMENTS];
@@ -2887,11 +2761,7 @@ extern "C" int sfsn_input_proj_f32_multi(const sfsn_inproj_job* jobs, int n, voi
     deal_blocks(wt, ns, n, cu_count(), nb);
     int blocks = 0;
     for (int i = 0; i < n; ++i) { p.job[i].block0 = blocks; p.job[i].nblocks = nb[i]; blocks += nb[i]; }
-    auto kern = input_proj_multi_kernel;
-    if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess)
-        return SFSN_EHIP;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(512), lds, static_cast<hipStream_t>(stream), p);
-    return hip_ok(hipGetLastError());
+    return launch_lds<input_proj_multi_kernel>(dim3(blocks), dim3(512), lds, static_cast<hipStream_t>(stream), p);
 }
 
 extern "C" int sfsn_input_proj_f32(const float* x, const float* w, const float* bias, float* z, int M, int K, int N, int ldz,
@@ -2908,20 +2778,14 @@ extern "C" int sfsn_input_proj_f32(const float* x, const float* w, const float* 
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int KSB = K <= 64 ? 2 : (K <= 96 ? 3 : (K <= 160 ? 5 : 6));
     const size_t blds = ((size_t)3 * 64 * (KSB * 32 + 8) * 2) + (size_t)64 * (N + 4) * sizeof(float);
-    static const bool no_bf3 = getenv("SFSN_INPROJ_F32") != nullptr;  // diagnostic: force the fp32-MFMA kernels
+    const bool no_bf3 = sfsn_knob_set("SFSN_INPROJ_F32");  // diagnostic: force the fp32-MFMA kernels
     if (!no_bf3 && (K % 2 == 0) && K <= 192 && (N % 4 == 0) && (ldz % 4 == 0) && M >= 64 && TPW * KSB <= 12 && blds <= 150 * 1024 &&
         (reinterpret_cast<uintptr_t>(x) & 7) == 0) {
         int fgrid = (M + 63) / 64;
         if (fgrid > cu_count()) fgrid = cu_count();  // one resident workgroup per CU: the W split is paid once per CU
-#define IPB_CASE(TPW_, KS_)                                                                                               \
-    if (TPW == TPW_ && KSB == KS_) {                                                                                      \
-        auto kern = input_proj_bf3_kernel<TPW_, KS_>;                                                                     \
-        if (blds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                                  \
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) \
-            return SFSN_EHIP;                                                                                             \
-        hipLaunchKernelGGL(kern, dim3(fgrid), dim3(512), blds, st, x, w, bias, z, M, K, N, ldz, NT, NWN);                 \
-        return hip_ok(hipGetLastError());                                                                                 \
-    }
+#define IPB_CASE(TPW_, KS_)       \
+    if (TPW == TPW_ && KSB == KS_) \
+        return launch_lds<input_proj_bf3_kernel<TPW_, KS_>>(dim3(fgrid), dim3(512), blds, st, x, w, bias, z, M, K, N, ldz, NT, NWN);
         IPB_CASE(1, 2) IPB_CASE(1, 3) IPB_CASE(1, 5) IPB_CASE(1, 6) IPB_CASE(2, 2) IPB_CASE(2, 3) IPB_CASE(2, 5)
         IPB_CASE(3, 2) IPB_CASE(3, 3)
 #undef IPB_CASE
@@ -2931,25 +2795,16 @@ extern "C" int sfsn_input_proj_f32(const float* x, const float* w, const float* 
     if ((N % 4 == 0) && (ldz % 4 == 0) && M >= 64 && flds <= 150 * 1024) {
         int fgrid = (M + 63) / 64;
         if (fgrid > 512) fgrid = 512;
-#define IPF_CASE(TPW_, KC_)                                                                                               \
-    if (TPW == TPW_ && KCB == KC_) {                                                                                      \
-        auto kern = input_proj_fast_kernel<TPW_, KC_>;                                                                    \
-        if (flds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                                  \
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) \
-            return SFSN_EHIP;                                                                                             \
-        hipLaunchKernelGGL(kern, dim3(fgrid), dim3(512), flds, st, x, w, bias, z, M, K, N, ldz, NT, NWN);                 \
-        return hip_ok(hipGetLastError());                                                                                 \
-    }
+#define IPF_CASE(TPW_, KC_)       \
+    if (TPW == TPW_ && KCB == KC_) \
+        return launch_lds<input_proj_fast_kernel<TPW_, KC_>>(dim3(fgrid), dim3(512), flds, st, x, w, bias, z, M, K, N, ldz, NT, NWN);
         IPF_CASE(1, 3) IPF_CASE(1, 6) IPF_CASE(1, 10) IPF_CASE(1, 12) IPF_CASE(2, 3) IPF_CASE(2, 6) IPF_CASE(2, 10) IPF_CASE(2, 12)
         IPF_CASE(3, 3) IPF_CASE(3, 6) IPF_CASE(3, 10) IPF_CASE(3, 12)
 #undef IPF_CASE
     }
-#define IP_CASE(TPW_, KC_)                                                                                           \
-    if (TPW == TPW_ && KCB == KC_) {                                                                                 \
-        hipLaunchKernelGGL((input_proj_kernel<TPW_, KC_>), dim3(grid), dim3(512), 0, st, x, w, bias, z, M, K, N, ldz, NT, \
-                           NWN);                                                                                     \
-        return hip_ok(hipGetLastError());                                                                            \
-    }
+#define IP_CASE(TPW_, KC_)        \
+    if (TPW == TPW_ && KCB == KC_) \
+        return launch_lds<input_proj_kernel<TPW_, KC_>>(dim3(grid), dim3(512), 0, st, x, w, bias, z, M, K, N, ldz, NT, NWN);
     IP_CASE(1, 3) IP_CASE(1, 6) IP_CASE(1, 10) IP_CASE(1, 12) IP_CASE(2, 3) IP_CASE(2, 6) IP_CASE(2, 10) IP_CASE(2, 12)
     IP_CASE(3, 3) IP_CASE(3, 6) IP_CASE(3, 10) IP_CASE(3, 12)
 #undef IP_CASE
@@ -3017,19 +2872,13 @@ extern "C" int sfsn_features_z(const float* stft_ri, const float* fb_tbf, int B,
     const size_t lds = (tab_off + FEAT_TAB + (wave_rows ? 4 * FEAT_CHUNK : FEAT_STATS)) * sizeof(float);
     if (lds > 150 * 1024) return SFSN_EUNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const void* kern = wave_rows ? reinterpret_cast<const void*>(features_kernel<true>) : reinterpret_cast<const void*>(features_kernel<false>);
-    if (lds > 64 * 1024) {
-        if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return SFSN_EHIP;
-    }
     const unsigned gx = (unsigned)((nt + FEAT_TT - 1) / FEAT_TT);
     const size_t n16 = zero_bytes / 16, zblocks = (n16 + 8 * 256 - 1) / (8 * 256);
     const size_t zrows = (zblocks + gx - 1) / gx;
     if ((size_t)B + zrows > 65535) return SFSN_EUNSUPPORTED;
-    if (wave_rows)
-        hipLaunchKernelGGL(features_kernel<true>, dim3(gx, (unsigned)(B + zrows)), dim3(256), lds, st, stft_ri, fb_tbf, p, zero_ptr, n16);
-    else
-        hipLaunchKernelGGL(features_kernel<false>, dim3(gx, (unsigned)(B + zrows)), dim3(256), lds, st, stft_ri, fb_tbf, p, zero_ptr, n16);
-    return hip_ok(hipGetLastError());
+    const dim3 grid(gx, (unsigned)(B + zrows));
+    if (wave_rows) return launch_lds<features_kernel<true>>(grid, dim3(256), lds, st, stft_ri, fb_tbf, p, zero_ptr, n16);
+    return launch_lds<features_kernel<false>>(grid, dim3(256), lds, st, stft_ri, fb_tbf, p, zero_ptr, n16);
 }
 
 extern "C" int sfsn_laplace_means(const float* stft_ri, const float* fb_tbf, int B, int F, int T, int FB, float fdrc,
@@ -3162,9 +3011,9 @@ extern "C" int sfsn_deepfilter(const float* stft_ri, int B, int F, int T, int S,
     hipStream_t st = static_cast<hipStream_t>(stream);
     {   // pass-structured kernel: every P a multiple of 4 (16-byte coefficient loads), tiles within 48 KB of LDS
         // (tests/frontback.py df_dispatch() restates this block's arithmetic to label which kernel a test case ran: keep the two together)
-        // diagnostic: force the unit-by-unit kernel.  Read ONCE per process (static), so tests must not depend on it: the shapes of
-        // tests/frontback.py reach that kernel on their own (P % 4 != 0, an unaligned proj, > DF_MAX_PASSES passes, a tile > 48 KB).
-        static const bool no_pass = getenv("SFSN_DF_GENERIC") != nullptr;
+        // diagnostic (experiment builds): force the unit-by-unit kernel.  The shapes of tests/frontback.py reach that kernel on their
+        // own (P % 4 != 0, an unaligned proj, > DF_MAX_PASSES passes, a tile > 48 KB).
+        const bool no_pass = sfsn_knob_set("SFSN_DF_GENERIC");
         DfPassParams pp;
         pp.base = p;
         pp.npass = 0;
@@ -3199,13 +3048,7 @@ extern "C" int sfsn_deepfilter(const float* stft_ri, int B, int F, int T, int S,
     }
     const size_t lds = (size_t)32 * (maxP + 1) * sizeof(float);
     if (lds > 150 * 1024) return SFSN_EUNSUPPORTED;
-    if (lds > 64 * 1024) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(deepfilter_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds) != hipSuccess)
-            return SFSN_EHIP;
-    }
-    hipLaunchKernelGGL(deepfilter_kernel, dim3((nt + 31) / 32, B), dim3(256), lds, st, stft_ri, p, enh_ri, enh_mag);
-    return hip_ok(hipGetLastError());
+    return launch_lds<deepfilter_kernel>(dim3((nt + 31) / 32, B), dim3(256), lds, st, stft_ri, p, enh_ri, enh_mag);
 }
 
 #ifdef IP_STAMPS

@@ -21,6 +21,7 @@
 
 #include "sfsn_feat_dev.h"
 #include "sfsn_scan_dev.h"
+#include "sfsn_host.h"
 
 #define PDF_MAX_JOBS 16
 #define PDF_THREADS 512
@@ -317,13 +318,6 @@ __global__ __launch_bounds__(PDF_THREADS) void projdf_kernel(const PdfParams p) 
 // =====================================================================================================
 // host side
 // =====================================================================================================
-static inline bool pdf_aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; }
-static int pdf_cu_count() {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    return n;
-}
-
 static size_t pdf_lds_bytes(int KS, int FT, int U, int P, int fc, int df) {
     const int KP = KS * 64, SROW = KP + 16, MRT = (FT * U + 15) / 16;
     const size_t slot = (size_t)MRT * 16 * SROW + (((size_t)U * fc * (FT + df - 1) * 8 + 15) & ~(size_t)15);
@@ -339,9 +333,8 @@ extern "C" int sfsn_proj_deepfilter(const float* stft_ri, int B, int F, int T, i
     if (t0 < 0 || nt <= 0 || t0 + nt > T) return SFSN_EINVAL;
     const int KS = (H + 63) / 64;
     if (KS > 4) return SFSN_EUNSUPPORTED;
-    static const int ft_env = getenv("SFSN_PDF_FT") ? atoi(getenv("SFSN_PDF_FT")) : 0;        // A/B runs: frames per tile
-    static const int wgs_env = getenv("SFSN_PDF_WGS") ? atoi(getenv("SFSN_PDF_WGS")) : 0;     // A/B runs: workgroups of the launch
-    static const size_t lds_cap_env = getenv("SFSN_PDF_LDS_KB") ? (size_t)atoi(getenv("SFSN_PDF_LDS_KB")) * 1024 : (size_t)150 * 1024;
+    const int wgs_env = sfsn_knob("SFSN_PDF_WGS", 0);  // A/B runs: workgroups of the launch
+    const size_t lds_cap_env = (size_t)sfsn_knob("SFSN_PDF_LDS_KB", 150) * 1024;
     PdfParams p;
     p.n = 0; p.B = B; p.F = F; p.T = T; p.S = S; p.t0 = t0; p.t1 = t0 + nt; p.stft = stft_ri; p.enh = enh_ri; p.mag = enh_mag;
     double wt[PDF_MAX_JOBS];
@@ -351,7 +344,7 @@ extern "C" int sfsn_proj_deepfilter(const float* stft_ri, int B, int F, int T, i
     for (int i = 0; i < n_groups; ++i) {
         const sfsn_projdf_group& g = groups[i];
         if (!g.spikes_i8 || !g.w_packed || !g.w_dq || g.n_units <= 0 || g.fc <= 0 || g.df <= 0) return SFSN_EINVAL;
-        if (!pdf_aligned16(g.spikes_i8) || !pdf_aligned16(g.w_packed) || !pdf_aligned16(g.w_dq) || !pdf_aligned16(g.proj)) return SFSN_EINVAL;
+        if (!aligned16(g.spikes_i8) || !aligned16(g.w_packed) || !aligned16(g.w_dq) || !aligned16(g.proj)) return SFSN_EINVAL;
         const int P = 2 * g.fc * g.df * S, NT = (P + 15) / 16;
         if (P % 4) return SFSN_EUNSUPPORTED;
         int TPW = (NT + PDF_CW - 1) / PDF_CW;
@@ -359,7 +352,6 @@ extern "C" int sfsn_proj_deepfilter(const float* stft_ri, int B, int F, int T, i
         const int NWN = (NT + TPW - 1) / TPW;
         // units per job and frames per tile: the largest that fit the per-thread prefetch slots and the LDS budget
         int FT = 16, U = g.n_units;
-        (void)ft_env;
         auto fits = [&](int ft, int u) {
             return ft * u * (KS * 4) <= PDF_NV * 128 && u * g.fc * (ft + g.df - 1) <= PDF_NX * 128 && g.df <= 200 &&
                    pdf_lds_bytes(KS, ft, u, P, g.fc, g.df) <= lds_cap_env;
@@ -386,7 +378,7 @@ extern "C" int sfsn_proj_deepfilter(const float* stft_ri, int B, int F, int T, i
     }
     if (lo > F) return SFSN_EINVAL;
     p.fcov = lo;
-    const int n_cu = pdf_cu_count();
+    const int n_cu = cu_count();
     // one persistent workgroup per compute unit (the ring and the coefficient tile take most of a unit's LDS).  Measured with the loader
     // waves, B = 64, T = 1000: 256 / 512 / 1024 workgroups 238 / 246 / 296 us per forward (every workgroup reloads its W_p tiles)
     int total = wgs_env > 0 ? wgs_env : n_cu;
@@ -416,15 +408,8 @@ extern "C" int sfsn_proj_deepfilter(const float* stft_ri, int B, int F, int T, i
         total = blocks;
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
-#define PDF_CASE(KS_)                                                                                                      \
-    if (KS == KS_) {                                                                                                       \
-        auto kern = projdf_kernel<KS_>;                                                                                    \
-        if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                                    \
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)    \
-            return SFSN_EHIP;                                                                                              \
-        hipLaunchKernelGGL(kern, dim3(total), dim3(PDF_THREADS), lds, st, p);                                              \
-        return hipGetLastError() == hipSuccess ? SFSN_OK : SFSN_EHIP;                                                      \
-    }
+#define PDF_CASE(KS_) \
+    if (KS == KS_) return launch_lds<projdf_kernel<KS_>>(dim3(total), dim3(PDF_THREADS), lds, st, p);
     PDF_CASE(1) PDF_CASE(2) PDF_CASE(3) PDF_CASE(4)
 #undef PDF_CASE
     return SFSN_EUNSUPPORTED;

@@ -30,6 +30,7 @@
 #include "sfsn_scan3i_dev.h"
 #include "sfsn_scan3x_dev.h"
 #include "sfsn_scan3w_dev.h"
+#include "sfsn_host.h"
 
 #define STACK_MAX_ROLES 24
 #define STACK_ZIN 0
@@ -926,8 +927,6 @@ __global__ __launch_bounds__(768) void gsn_stack_fb_kernel(const StackParams p) 
 // =====================================================================================================
 // host side
 // =====================================================================================================
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 extern "C" size_t sfsn_stack_scratch_bytes(int n_layers, int n_segs, int rows_total) {
     // progress counters: one per workgroup (at most one per 4 rows per layer, plus role padding and PROJ roles) + error word
     if (n_layers <= 0 || n_segs <= 0 || rows_total <= 0) return 0;
@@ -937,8 +936,7 @@ extern "C" size_t sfsn_stack_scratch_bytes(int n_layers, int n_segs, int rows_to
 
 // column parts per 16-row block of a narrow PROJ role: the largest of 1 / 2 / 4 that fits the padding (SFSN_PROJ_SPLIT caps it: A/B runs)
 static int proj_split_host(int room) {
-    int cap = 4;
-    if (const char* e = getenv("SFSN_PROJ_SPLIT")) cap = atoi(e);
+    const int cap = sfsn_knob("SFSN_PROJ_SPLIT", 4);
     int sp = 1;
     while (sp * 2 <= room && sp * 2 <= cap) sp *= 2;
     return sp;
@@ -946,26 +944,16 @@ static int proj_split_host(int room) {
 
 template <int OUT>
 static int launch_stack_fb(const StackParams& p, int blocks, int lds, hipStream_t st) {
-    auto kern = gsn_stack_fb_kernel<OUT>;
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-        return SFSN_EHIP;
     StackParams q = p;
     q.wg_times = sfsn_wgprobe_take(5, 25 * blocks);  // 2 stamps + 12 waves x 4 stall counters per workgroup (S3_PB_*)
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(768), lds, st, q);
-    return hipGetLastError() == hipSuccess ? SFSN_OK : SFSN_EHIP;
+    return launch_lds<gsn_stack_fb_kernel<OUT>>(dim3(blocks), dim3(768), lds, st, q);
 }
 
 template <int KS, int OUT>
 static int launch_stack(const StackParams& p, int blocks, int lds, hipStream_t st) {
-    auto kern = gsn_stack_kernel<KS, OUT>;
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-        return SFSN_EHIP;  // (per device, cheap: set on every launch -- a process may drive several GPUs)
     StackParams q = p;
     q.wg_times = sfsn_wgprobe_take(4, blocks);
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(512), lds, st, q);
-    return hipGetLastError() == hipSuccess ? SFSN_OK : SFSN_EHIP;
+    return launch_lds<gsn_stack_kernel<KS, OUT>>(dim3(blocks), dim3(512), lds, st, q);
 }
 
 extern "C" int sfsn_gsn_stack_scan(const sfsn_scan_segment* segs, const sfsn_fused_input* fin, int n_layers, int n_segs, int T, int H,
@@ -1005,7 +993,7 @@ static int stack_scan_impl(const sfsn_scan_segment* segs, const sfsn_fused_input
         for (int i = 0; i < n_segs; ++i)
             if (!segs[l * n_segs + i].zin) wide = false;
     if (n_layers == 1 && fused) wide = true;
-    if (getenv("SFSN_STACK_NARROW")) wide = false;
+    if (sfsn_knob_set("SFSN_STACK_NARROW")) wide = false;
     // round 4: no input-term buffers, H <= 224, 8 rows per workgroup in the layers >= 1: the wide kernel with FUSED3 roles (the input
     // product inside the IO-wave scan) instead of the 8-wave FUSED roles (SFSN_STACK_FUSED8=1 keeps those: A/B runs)
     bool inscan = fused && !wide && NT <= 14 && n_layers >= 2 && !getenv("SFSN_STACK_FUSED8") && !getenv("SFSN_SCAN_V2");
@@ -1024,7 +1012,7 @@ static int stack_scan_impl(const sfsn_scan_segment* segs, const sfsn_fused_input
     // columns the IO-wave kernel wins or ties there too (B = 4 / 16 / 32 / 64: 1.86 / 1.99 / 2.22 / 2.58-2.63 against 1.95 / 2.08 / 2.30 /
     // 2.61-2.64; no fp32 spike tensors 2.42-2.45 against 2.52-2.53; T = 2000 +1.4 %).  Only very short launches keep round 2's bodies (the
     // new kernel's hand-off chain costs ~24 us more to fill).  SFSN_STACK_FB3=1 / 0 forces it on / off (A/B runs, tests).
-    bool fb3 = !fused && !wide && KS == 5 && !getenv("SFSN_SCAN_V2") && !getenv("SFSN_STACK_FB_V2");
+    bool fb3 = !fused && !wide && KS == 5 && !getenv("SFSN_SCAN_V2") && !sfsn_knob_set("SFSN_STACK_FB_V2");
     bool any4 = false;
     for (int l = 0; l < n_layers && fb3; ++l) {
         const int rp = rows_per_wg ? rows_per_wg[l] : 8;
@@ -1047,12 +1035,9 @@ static int stack_scan_impl(const sfsn_scan_segment* segs, const sfsn_fused_input
         for (int i = 0; i < n_segs; ++i) {
             const sfsn_scan_segment& s = segs[l * n_segs + i];
             const sfsn_fused_input& f = fin[l * n_segs + i];
-            if (!s.spikes_i8 || (s.spikes_f32 != nullptr) != ((out & 1) != 0) || s.membrane) return SFSN_EINVAL;
-            if (s.R <= 0 || !s.w_hh || !s.w_dq || !s.bias || !s.bn_alpha || !s.bn_beta || !s.h_state || !s.c_state) return SFSN_EINVAL;
+            // (the input term: optional here, asked for below where the layout needs it)
+            if (check_segment(s, out, 0) != SFSN_OK) return SFSN_EINVAL;
             if (s.R != segs[i].R) return SFSN_EINVAL;  // a segment has the same rows in every layer
-            if (!aligned16(s.w_hh) || !aligned16(s.h_state) || !aligned16(s.c_state) || !aligned16(s.spikes_f32) || !aligned16(s.spikes_i8) ||
-                !aligned16(s.zin))
-                return SFSN_EINVAL;
             if (l == 0) rows_total += s.R;
             const bool last = l == n_layers - 1;
             if (l > 0) {
@@ -1096,10 +1081,8 @@ static int stack_scan_impl(const sfsn_scan_segment* segs, const sfsn_fused_input
             }
             StackRoleDev& r = p.role[nroles];
             r = StackRoleDev{};
-            r.w_hh = s.w_hh; r.w_dq = s.w_dq; r.bias = s.bias; r.bn_alpha = s.bn_alpha; r.bn_beta = s.bn_beta;
-            r.h_state = s.h_state; r.c_state = s.c_state; r.spikes_f32 = s.spikes_f32; r.spikes_i8 = s.spikes_i8; r.count = s.spike_count;
-            r.zin = const_cast<float*>(s.zin);
-            r.R = s.R; r.rpw = rpw; r.block0 = blocks; r.nblocks = (s.R + rpw - 1) / rpw; r.split = 1;
+            copy_segment(r, s, 0);
+            r.rpw = rpw; r.block0 = blocks; r.nblocks = (s.R + rpw - 1) / rpw; r.split = 1;
             r.pub = last ? 0 : 1;
             if (xrole) {
                 r.kind = STACK_FUSEDX3; r.src = -1; r.src_rpw = rpw; r.x = fx[i].x; r.w_ih_f32 = fx[i].w_ih; r.I = fx[i].I; r.zin = nullptr;
@@ -1160,11 +1143,11 @@ static int stack_scan_impl(const sfsn_scan_segment* segs, const sfsn_fused_input
     if ((size_t)(blocks + 2) * sizeof(unsigned) > scratch_bytes) return SFSN_EINVAL;
     p.prog = static_cast<unsigned*>(scratch);
     p.dbg = nullptr;
-    if (getenv("SFSN_STACK_DEBUG") && (size_t)(blocks + 2) * 5 * sizeof(unsigned) <= scratch_bytes) p.dbg = p.prog + blocks + 2;
+    if (sfsn_knob_set("SFSN_STACK_DEBUG") && (size_t)(blocks + 2) * 5 * sizeof(unsigned) <= scratch_bytes) p.dbg = p.prog + blocks + 2;
     p.nroles = nroles; p.T = T; p.H = H; p.NT = NT; p.lag = lag; p.nblocks = blocks;
     p.v2 = getenv("SFSN_SCAN_V2") ? 1 : 0;
-    p.lsplit = sfsn_s3_lsplit_host();
-    p.lsplit_x = sfsn_s3x_lsplit_host();
+    p.lsplit = s3_lsplit_knob();
+    p.lsplit_x = s3x_lsplit_knob();
     // timing switches of the hand-off roles (wrong results by design: stores dropped, waits skipped): compiled in only with
     // -DSFSN_EXPERIMENTS (make EXTRA=-DSFSN_EXPERIMENTS, scripts/exp_stack_r03.sh) -- a stray environment variable must not be
     // able to corrupt a production launch
@@ -1183,24 +1166,12 @@ static int stack_scan_impl(const sfsn_scan_segment* segs, const sfsn_fused_input
     if (p.dbg && hipMemsetAsync(p.dbg, 0, (size_t)(blocks + 1) * 4 * sizeof(unsigned), st) != hipSuccess) return SFSN_EHIP;
 #define WIDE_CASE(KS_, OUT_)                                                                                                  \
     if (wide && KS == KS_ && out == OUT_) {                                                                                   \
-        auto kern = gsn_stack_wide_kernel<KS_, OUT_>;                                                                         \
-        if (lds > 64 * 1024 &&                                                                                                \
-            hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) \
-            return SFSN_EHIP;                                                                                                 \
         StackParams q = p;                                                                                                    \
         q.wg_times = sfsn_wgprobe_take(6, 33 * blocks); /* 2 stamps + 16 waves x 4 stall counters per workgroup (S3_PB_*) */  \
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(1024), lds, st, q);                                                       \
-        return hipGetLastError() == hipSuccess ? SFSN_OK : SFSN_EHIP;                                                         \
+        return launch_lds<gsn_stack_wide_kernel<KS_, OUT_>>(dim3(blocks), dim3(1024), lds, st, q);                            \
     }
-#define WIDE16_CASE(KS_, OUT_)                                                                                                \
-    if (w16 && wide && !p.v2 && KS == KS_ && out == OUT_) {                                                                   \
-        auto kern = gsn_stack_wide_kernel<KS_, OUT_, 1>;                                                                      \
-        if (lds > 64 * 1024 &&                                                                                                \
-            hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) \
-            return SFSN_EHIP;                                                                                                 \
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(1024), lds, st, p);                                                       \
-        return hipGetLastError() == hipSuccess ? SFSN_OK : SFSN_EHIP;                                                         \
-    }
+#define WIDE16_CASE(KS_, OUT_) \
+    if (w16 && wide && !p.v2 && KS == KS_ && out == OUT_) return launch_lds<gsn_stack_wide_kernel<KS_, OUT_, 1>>(dim3(blocks), dim3(1024), lds, st, p);
     WIDE16_CASE(3, 2) WIDE16_CASE(3, 3) WIDE16_CASE(4, 2) WIDE16_CASE(4, 3)
 #undef WIDE16_CASE
     if (w16) return SFSN_EUNSUPPORTED;

@@ -25,6 +25,7 @@
 #include <cstdlib>
 
 #include "sfsn.h"
+#include "sfsn_host.h"
 
 #define TR_THREADS 256
 #define TR_TILE 16
@@ -33,7 +34,6 @@ __device__ __forceinline__ float tr_pick(const float (&a)[TR_PF], int i) {  // a
     return i == 0 ? a[0] : i == 1 ? a[1] : i == 2 ? a[2] : a[3];
 }
 
-static inline int hip_ok_tr(hipError_t e) { return e == hipSuccess ? SFSN_OK : SFSN_EHIP; }
 
 // block reduction of 16 per-neuron partial sums held by threads (rsub = tid / 16 in [0, 16), j = tid % 16): red[rsub][j] -> total in
 // every thread of column j.  Fixed order.
@@ -399,11 +399,7 @@ extern "C" int sfsn_gsn_train_step_fwd(const float* z, const float* w_hh, const 
     p.invstd = invstd; p.momentum = momentum; p.eps = eps; p.R = R; p.H = H; p.shared = shared; p.use_bn = use_bn;
     p.epoch = epoch; p.scratch = static_cast<float*>(scratch);
     p.counters = scratch ? reinterpret_cast<unsigned*>(static_cast<float*>(scratch) + (size_t)tiles * 16 * TR_PARTG * 2) : nullptr;
-    auto kern = gsn_train_step_fwd_kernel;
-    if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return SFSN_EHIP;
-    hipLaunchKernelGGL(kern, dim3(tiles, p.RB), dim3(TR_THREADS), lds, static_cast<hipStream_t>(stream), p);
-    return hip_ok_tr(hipGetLastError());
+    return launch_lds<gsn_train_step_fwd_kernel>(dim3(tiles, p.RB), dim3(TR_THREADS), lds, static_cast<hipStream_t>(stream), p);
 }
 
 extern "C" int sfsn_gsn_train_step_bwd(const float* dz_next, const float* w_hh, const float* dh_up, const float* dh_rec, const float* dc_next,
@@ -429,11 +425,7 @@ extern "C" int sfsn_gsn_train_step_bwd(const float* dz_next, const float* w_hh, 
     p.R = R; p.H = H; p.shared = shared; p.use_bn = use_bn;
     p.epoch = epoch; p.scratch = static_cast<float*>(scratch);
     p.counters = scratch ? reinterpret_cast<unsigned*>(static_cast<float*>(scratch) + (size_t)tiles * 16 * TR_PARTG * 2) : nullptr;
-    auto kern = gsn_train_step_bwd_kernel;
-    if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return SFSN_EHIP;
-    hipLaunchKernelGGL(kern, dim3(tiles, p.RB), dim3(TR_THREADS), lds, static_cast<hipStream_t>(stream), p);
-    return hip_ok_tr(hipGetLastError());
+    return launch_lds<gsn_train_step_bwd_kernel>(dim3(tiles, p.RB), dim3(TR_THREADS), lds, static_cast<hipStream_t>(stream), p);
 }
 
 // ---- a whole layer call in ONE launch (round 4) ---------------------------------------------------------------------------
@@ -1003,15 +995,17 @@ static size_t seq_lds_bwd(int G, int H, int RB, int rpb) {
 }
 
 // all workgroups of a launch must be resident together: blocks per compute unit at this LDS size x compute units
-static int seq_slots(const void* kern, size_t lds) {
+template <auto Kern>
+static int seq_slots(size_t lds) {
     // (asked before every launch: the last few answers are remembered per (device, kernel, LDS size) -- the occupancy query costs tens of
     //  microseconds, a training step makes sixteen launches)
     struct Memo { int dev; const void* kern; size_t lds; int slots; };
     static thread_local Memo memo[48];
     static thread_local int n_memo = 0;
+    const void* kern = reinterpret_cast<const void*>(Kern);
     int dev = 0, cus = 0, per = 0;
     if (hipGetDevice(&dev) != hipSuccess) return -1;
-    if (lds > 64 * 1024 && hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
+    if (allow_lds<Kern>(lds) != SFSN_OK) return -1;
     for (int i = 0; i < n_memo; ++i)
         if (memo[i].dev == dev && memo[i].kern == kern && memo[i].lds == lds) return memo[i].slots;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return -1;
@@ -1032,7 +1026,6 @@ static int seq_dir_geometry(const int* R, int n, int H, int shared, int dir, int
     const int G = shared ? 1 : 2, tiles = H / TR_TILE;
     for (int i = 0; i < n; ++i)
         if (R[i] <= 0) return SFSN_EINVAL;
-    const void* kern = dir ? reinterpret_cast<const void*>(gsn_train_seq_bwd_kernel) : reinterpret_cast<const void*>(gsn_train_seq_fwd_kernel);
     static const int targets[] = {0, 128, 96, 80, 64, 48, 40, 32, 24, 16};
     for (int target : targets) {
         int total = 0;
@@ -1047,7 +1040,7 @@ static int seq_dir_geometry(const int* R, int n, int H, int shared, int dir, int
             total += tiles * RBs[i];
         }
         if (!fits_lds) return SFSN_EUNSUPPORTED;  // (train_geometry already took as many row blocks as the LDS needs: fewer cannot fit either)
-        const int slots = seq_slots(kern, l);
+        const int slots = dir ? seq_slots<gsn_train_seq_bwd_kernel>(l) : seq_slots<gsn_train_seq_fwd_kernel>(l);
         if (slots < 0) return SFSN_EHIP;
         *wgs = total; *lds = l;
         if (total <= slots) return SFSN_OK;
@@ -1070,7 +1063,7 @@ extern "C" int sfsn_gsn_train_step_check(int R, int H, int shared) {
     const size_t lds_b = ((size_t)rpb * TR_TILE + (size_t)RB * TR_PART + (size_t)G * H * (TR_TILE + rpb)) * sizeof(float);
     if (lds_f > 150 * 1024 || lds_b > 150 * 1024) return SFSN_EUNSUPPORTED;
     if (RB > 1) {
-        const int sf = seq_slots(reinterpret_cast<const void*>(gsn_train_step_fwd_kernel), lds_f), sb = seq_slots(reinterpret_cast<const void*>(gsn_train_step_bwd_kernel), lds_b);
+        const int sf = seq_slots<gsn_train_step_fwd_kernel>(lds_f), sb = seq_slots<gsn_train_step_bwd_kernel>(lds_b);
         if (sf < 0 || sb < 0) return SFSN_EHIP;
         if (tiles * RB > sf || tiles * RB > sb) return SFSN_EUNSUPPORTED;
     }
@@ -1103,7 +1096,6 @@ extern "C" int sfsn_gsn_train_seq_fwd_multi(const SfsnTrainSeqFwd* c, int n, int
     size_t lds;
     int rc = seq_dir_geometry(Rs, n, H, shared, 0, RBs, rpbs, &wgs, &lds);
     if (rc != SFSN_OK) return rc;
-    auto kern = gsn_train_seq_fwd_kernel;
     const int tiles = H / TR_TILE;
     TrainSeqFwdMulti m;
     m.n = n;
@@ -1128,9 +1120,9 @@ extern "C" int sfsn_gsn_train_seq_fwd_multi(const SfsnTrainSeqFwd* c, int n, int
         end += tiles * p.RB;
         m.wg_end[i] = end;
     }
-    hipLaunchKernelGGL(kern, dim3(end), dim3(TR_THREADS), lds, static_cast<hipStream_t>(stream), m);
+    rc = launch_lds<gsn_train_seq_fwd_kernel>(dim3(end), dim3(TR_THREADS), lds, static_cast<hipStream_t>(stream), m);
     if (n == 1) seq_prof_end(m.x[0].prof, "fwd", T, c[0].R, H, m.p[0].RB, static_cast<hipStream_t>(stream));
-    return hip_ok_tr(hipGetLastError());
+    return rc;
 }
 
 extern "C" int sfsn_gsn_train_seq_bwd_multi(const SfsnTrainSeqBwd* c, int n, int T, int H, int shared, void* stream) {
@@ -1146,7 +1138,6 @@ extern "C" int sfsn_gsn_train_seq_bwd_multi(const SfsnTrainSeqBwd* c, int n, int
     size_t lds;
     int rc = seq_dir_geometry(Rs, n, H, shared, 1, RBs, rpbs, &wgs, &lds);
     if (rc != SFSN_OK) return rc;
-    auto kern = gsn_train_seq_bwd_kernel;
     const int tiles = H / TR_TILE;
     TrainSeqBwdMulti m;
     m.n = n;
@@ -1171,9 +1162,9 @@ extern "C" int sfsn_gsn_train_seq_bwd_multi(const SfsnTrainSeqBwd* c, int n, int
         end += tiles * p.RB;
         m.wg_end[i] = end;
     }
-    hipLaunchKernelGGL(kern, dim3(end), dim3(TR_THREADS), lds, static_cast<hipStream_t>(stream), m);
+    rc = launch_lds<gsn_train_seq_bwd_kernel>(dim3(end), dim3(TR_THREADS), lds, static_cast<hipStream_t>(stream), m);
     if (n == 1) seq_prof_end(m.x[0].prof, "bwd", T, c[0].R, H, m.p[0].RB, static_cast<hipStream_t>(stream));
-    return hip_ok_tr(hipGetLastError());
+    return rc;
 }
 
 // one layer call (= the multi entries with n = 1, ABI-13 call shape)

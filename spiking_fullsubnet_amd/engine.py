@@ -217,6 +217,83 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
+def fill_segment(sg: ScanSegment, cell, R: int, H: int, t0: int, zin, state, spikes_i8, spikes_f32=None, membrane=None, count=None) -> None:
+    """One sfsn_scan_segment of a launch over the frames from `t0` on.  `cell`: anything with w_hh_q, w_hh_dq, bias, alpha, beta
+    (_Cell, fullband_engine._Layer).  zin is chunk-local (or None: the launch forms the input term itself), state = (h, c); the output
+    tensors are whole-sequence [T, R, .] buffers and start at frame t0: fp32 spikes / membranes at t0 * R * H * 4 bytes, the int8
+    spikes (rows padded to 64 bytes) at t0 * R * ceil64(H)."""
+    f32_at, i8_at = t0 * R * H * 4, t0 * R * ((H + 63) // 64 * 64)
+    sg.zin, sg.w_hh, sg.w_dq, sg.bias = _ptr(zin), _ptr(cell.w_hh_q), _ptr(cell.w_hh_dq), _ptr(cell.bias)
+    sg.bn_alpha, sg.bn_beta, sg.h_state, sg.c_state = _ptr(cell.alpha), _ptr(cell.beta), _ptr(state[0]), _ptr(state[1])
+    sg.spikes_f32 = None if spikes_f32 is None else ctypes.c_void_p(spikes_f32.data_ptr() + f32_at)
+    sg.membrane = None if membrane is None else ctypes.c_void_p(membrane.data_ptr() + f32_at)
+    sg.spikes_i8 = ctypes.c_void_p(spikes_i8.data_ptr() + i8_at)
+    sg.R = R
+    sg.spike_count = _ptr(count)
+
+
+class ErrorWords:
+    """The error words of launches with bounded in-launch waits (first word of a launch's scratch buffer, sticky: non-zero = a
+    hand-off wait expired, the results are invalid).  A word travels to pinned host memory behind its launch and is looked at
+    without blocking at the next forward (and by check()): a failed launch cannot go unnoticed for long."""
+
+    def __init__(self, engine):
+        self.engine = engine  # its `device`, and its `_err_stream` for words collected off the launch's chain
+        self.pending: List[tuple] = []  # (event, pinned copy, what, scratch buffers)
+
+    def watch(self, stream, scratch, what: str) -> None:
+        """Copy the word of `scratch` (a list: the maximum of their words) behind what `stream` holds so far.  stream None: on the
+        engine's `_err_stream`, behind what the current stream holds so far -- nothing on the current stream waits for the copy."""
+        eng = self.engine
+        scratch = list(scratch) if isinstance(scratch, (list, tuple)) else [scratch]
+        if stream is None:
+            if eng._err_stream is None:
+                eng._err_stream = torch.cuda.Stream(device=eng.device)
+            stream = eng._err_stream
+            ev0 = torch.cuda.Event()
+            ev0.record(torch.cuda.current_stream(eng.device))
+            stream.wait_event(ev0)
+            for sc in scratch:
+                sc.record_stream(stream)
+        with torch.cuda.stream(stream):
+            word = scratch[0][:1] if len(scratch) == 1 else torch.stack([sc[0] for sc in scratch]).max().reshape(1)
+            pin = torch.empty((1,), dtype=torch.int32, pin_memory=True)
+            pin.copy_(word, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(stream)
+        self.pending.append((ev, pin, what, scratch))
+
+    def poll(self, block: bool = False) -> None:
+        keep = []
+        for item in self.pending:
+            ev, pin, what, scratch = item
+            if block:
+                ev.synchronize()
+            if not ev.query():
+                keep.append(item)
+            elif int(pin[0]) != 0:
+                self.pending = []
+                self.clear(scratch)
+                raise RuntimeError("sfsn_gsn_stack_scan: a layer-to-layer hand-off wait expired in an earlier launch "
+                                   f"(that forward's results are invalid): {what}")
+        self.pending = keep
+
+    def clear(self, scratch) -> None:
+        """After a failed launch: the error word is sticky by design (nobody clears it on the device) and the progress counters
+        of a launch that gave up are not all zeroed by its last workgroup -- reset both, or every later launch on this scratch
+        buffer would report the old failure.  Synchronised on both sides: no launch may still poll the counters, and none may
+        start before they are zero."""
+        torch.cuda.synchronize(self.engine.device)
+        for sc in scratch:
+            sc.zero_()
+        torch.cuda.synchronize(self.engine.device)
+
+    def check(self) -> None:
+        """Raise if a watched launch failed (synchronises the device)."""
+        torch.cuda.synchronize(self.engine.device)
+        self.poll(block=True)
+
+
 class Engine:
     """Packed weights + launch sequence for one model on one device."""
 
@@ -303,35 +380,20 @@ class Engine:
         # hand-off wait expired raises HERE instead of at the next forward); False: non-blocking, see check_stack_errors()
         self.strict_errors = os.environ.get("SFSN_STRICT_ERRORS", "0") == "1"
         self._ov_streams = None
-        # overlapped schedule, EXPERIMENT (off): the full-band model's features and layer-0 input products of ALL chunks go out at once
-        # on a stream of their own (nothing gates them), so its stack launches follow one another without the time-parallel kernels
-        # between them.  Bit-identical, but 2.97 instead of 2.80 ms per forward at B = 64, T = 1000: an input term produced a
-        # millisecond before it is read has left the 256 MB Infinity Cache (the sub-band kernels move > 1 GB in between), and the
-        # full-band scan -- two ring slots deep at H = 320 -- runs 1.9 instead of 1.6 us per frame from HBM (profiles/EXPERIMENTS.md)
-        self.overlap_prep_ahead = os.environ.get("SFSN_PREP_AHEAD", "0") != "0"
-        # overlapped schedule, round 6 (profiles/r06_strict_timeline.txt: the full-band chain gates, ~100 us of small kernels between its
-        # stack launches, and they run beside the sub-band stream's feature / input-product launches that the same event releases):
-        #   prep_next   -- the full-band model's features + layer-0 input product of chunk c + 1 go out BEFORE chunk c's projection (which
-        #                  is what releases the sub-band stream): they run alone (27 instead of 82 us) and the next stack launch follows
-        #   post_stream -- the sub-band epilogue (sfsn_proj_deepfilter) of chunk c on a third stream: the sub-band stream goes on with
-        #                  chunk c + 1's features as soon as the pair launch is done
-        # Both bit-identical and both OFF: measured (scripts/exp_ovsched_r06.sh, three interleaved rounds, strict forward API / lean)
-        # default 2.41-2.45 / 2.36-2.38 ms; prep_next 2.42-2.46 / 2.34-2.36 (the small kernels leave the chain, the earlier stack launch
-        # meets the sub-band stream's feature launches instead); post_stream 2.54 / 2.46-2.48 (the epilogue's 0.84 GB beside the next
-        # pair launch costs that launch more than the 100-136 us it takes off the stream); both 2.60-2.64 / 2.53-2.56.
-        self.overlap_prep_next = os.environ.get("SFSN_OV_PREP_NEXT", "0") != "0"
-        self.overlap_post_stream = os.environ.get("SFSN_OV_POST_STREAM", "0") != "0"
         self.stack_wide = True
         self._stack_scratch: List[torch.Tensor] = []
-        self._stack_err_pending: List[tuple] = []  # (event, pinned copy of a launch's error word): polled at the next forward
+        self._errors = ErrorWords(self)  # the launches' error words: polled at the next forward
         self._defer_err = None  # overlapped schedule: [(what, scratch)] of the running forward's stack launches (one copy per forward)
-        self._err_stream = None
+        self._err_stream = None  # ErrorWords' stream for the once-per-forward collection
         self.hw_queues = _check_hw_queues()
         self._last_forward: Dict[int, torch.cuda.Event] = {}  # per calling stream: recorded behind its most recent forward
 
     # ---------------------------------------------------------------------------------------------
     def _stream(self):
         return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _count(self, what: str) -> None:
+        self.launches[what] = self.launches.get(what, 0) + 1
 
     class _Timed:
         """HIP events on the launch stream around a group of launches; no-op unless ``engine.timers`` is a dict."""
@@ -431,7 +493,7 @@ class Engine:
                         a.s, a.w_packed, a.w_dq, a.bias, a.y, a.M, a.K, a.N, a.ldy = s_, w_, dq_, b_, z_, M, K, N, ld
                     rc = L.sfsn_spike_proj_multi(arr, len(jobs), st)
                 if rc == 0:
-                    self.launches["merged_products"] = self.launches.get("merged_products", 0) + 1
+                    self._count("merged_products")
                     return
                 if rc != _lib.SFSN_EUNSUPPORTED:
                     check(rc, "sfsn_input_proj_f32_multi" if l == 0 else "sfsn_spike_proj_multi")
@@ -467,23 +529,16 @@ class Engine:
         if rc == _lib.SFSN_EUNSUPPORTED:
             return False
         check(rc, "sfsn_features_proj")
-        self.launches["featproj"] = self.launches.get("featproj", 0) + 1
+        self._count("featproj")
         return True
 
     def _stage_scan(self, seqs, l, zins, states, spks, s8s, mems, t0, nt, st, tag, rpw, cnts=None):
         L, spec = self.lib, self.spec
         H = seqs[0].H
-        HP = (H + 63) // 64 * 64
         segs = (ScanSegment * len(seqs))()
         for i, seq in enumerate(seqs):
-            cell, sg, R = seq.cells[l], segs[i], s8s[i].shape[1]
-            sg.zin, sg.w_hh, sg.w_dq, sg.bias = _ptr(zins[i]), _ptr(cell.w_hh_q), _ptr(cell.w_hh_dq), _ptr(cell.bias)
-            sg.bn_alpha, sg.bn_beta, sg.h_state, sg.c_state = _ptr(cell.alpha), _ptr(cell.beta), _ptr(states[i][0]), _ptr(states[i][1])
-            sg.spikes_f32 = None if spks[i] is None else ctypes.c_void_p(spks[i].data_ptr() + t0 * R * H * 4)
-            sg.membrane = None if mems[i] is None else ctypes.c_void_p(mems[i].data_ptr() + t0 * R * H * 4)
-            sg.spikes_i8 = ctypes.c_void_p(s8s[i].data_ptr() + t0 * R * HP)
-            sg.R = R
-            sg.spike_count = None if cnts is None else _ptr(cnts[i])
+            fill_segment(segs[i], seq.cells[l], s8s[i].shape[1], H, t0, zins[i], states[i], s8s[i], spks[i], mems[i],
+                         None if cnts is None else cnts[i])
         with self.timed("scan:" + tag, st):
             rc = _lib.SFSN_EUNSUPPORTED
             if (self.split_scan and not spec.shared and H > 256 and len(seqs) == 1 and nt >= 16
@@ -502,13 +557,8 @@ class Engine:
                     scr = torch.zeros((L.sfsn_scan_split_scratch_bytes(R0, H) // 4,), dtype=torch.int32, device=self.device)
                 rc = L.sfsn_gsn_layer_scan_split(segs, 1, nt, H, 0, _ptr(scr), scr.numel() * 4, st)
                 if rc == 0:
-                    with torch.cuda.stream(stream):
-                        pin = torch.empty((1,), dtype=torch.int32, pin_memory=True)
-                        pin.copy_(scr[:1], non_blocking=True)
-                        ev = torch.cuda.Event()
-                        ev.record(stream)
-                    self._stack_err_pending.append((ev, pin, f"split scan {tag} H={H}", scr))
-                    self.launches["split_scan"] = self.launches.get("split_scan", 0) + 1
+                    self._errors.watch(stream, scr, f"split scan {tag} H={H}")
+                    self._count("split_scan")
                     return
                 if rc != _lib.SFSN_EUNSUPPORTED:
                     check(rc, "sfsn_gsn_layer_scan_split")
@@ -536,21 +586,14 @@ class Engine:
         """Layer 0 of the given sequence models, input product inside the scan."""
         L = self.lib
         H = seqs[0].H
-        HP = (H + 63) // 64 * 64
         segs = (ScanSegment * len(seqs))()
         fin = (FusedX * len(seqs))()
         for i, (seq, x) in enumerate(zip(seqs, xs_)):
-            cell, sg, R = seq.cells[0], segs[i], x.shape[1]
-            sg.zin, sg.w_hh, sg.w_dq, sg.bias = None, _ptr(cell.w_hh_q), _ptr(cell.w_hh_dq), _ptr(cell.bias)
-            sg.bn_alpha, sg.bn_beta, sg.h_state, sg.c_state = _ptr(cell.alpha), _ptr(cell.beta), _ptr(states[i][0]), _ptr(states[i][1])
-            sg.spikes_f32 = None if spks[i] is None else ctypes.c_void_p(spks[i].data_ptr() + t0 * R * H * 4)
-            sg.membrane = None
-            sg.spikes_i8 = ctypes.c_void_p(s8s[i].data_ptr() + t0 * R * HP)
-            sg.R = R
-            sg.spike_count = None if cnts is None else _ptr(cnts[i])
+            cell, R = seq.cells[0], x.shape[1]
+            fill_segment(segs[i], cell, R, H, t0, None, states[i], s8s[i], spks[i], count=None if cnts is None else cnts[i])
             fin[i].x = x.data_ptr() + t0 * R * seq.I * 4
             fin[i].w_ih, fin[i].I = cell.w_ih_f32.data_ptr(), seq.I
-        self.launches["fused_x"] = self.launches.get("fused_x", 0) + 1
+        self._count("fused_x")
         with self.timed("scanx:" + tag, st):
             check(L.sfsn_gsn_layer_scan_fused_x(segs, fin, len(seqs), nt, H, st), "sfsn_gsn_layer_scan_fused_x")
 
@@ -561,18 +604,12 @@ class Engine:
         segs = (ScanSegment * len(seqs))()
         fin = (FusedInput * len(seqs))()
         for i, seq in enumerate(seqs):
-            cell, sg, R = seq.cells[l], segs[i], s8s[l][i].shape[1]
+            cell, R = seq.cells[l], s8s[l][i].shape[1]
             pk, dq = cell.w_ih_q[0]
-            sg.zin, sg.w_hh, sg.w_dq, sg.bias = None, _ptr(cell.w_hh_q), _ptr(cell.w_hh_dq), _ptr(cell.bias)
-            sg.bn_alpha, sg.bn_beta, sg.h_state, sg.c_state = _ptr(cell.alpha), _ptr(cell.beta), _ptr(states[i][0]), _ptr(states[i][1])
-            sg.spikes_f32 = None if spks[i] is None else ctypes.c_void_p(spks[i].data_ptr() + t0 * R * H * 4)
-            sg.membrane = None
-            sg.spikes_i8 = ctypes.c_void_p(s8s[l][i].data_ptr() + t0 * R * HP)
-            sg.R = R
-            sg.spike_count = None if cnts is None else _ptr(cnts[i])
+            fill_segment(segs[i], cell, R, H, t0, None, states[i], s8s[l][i], spks[i], count=None if cnts is None else cnts[i])
             fin[i].spikes_in = s8s[l - 1][i].data_ptr() + t0 * R * HP
             fin[i].w_ih, fin[i].w_ih_dq = pk.data_ptr(), dq.data_ptr()
-        self.launches["fused"] = self.launches.get("fused", 0) + 1
+        self._count("fused")
         with self.timed("scanf:" + tag, st):
             check(L.sfsn_gsn_layer_scan_fused(segs, fin, len(seqs), nt, H, st), "sfsn_gsn_layer_scan_fused")
 
@@ -646,20 +683,13 @@ class Engine:
         rows = 0
         for l in range(nl):
             for i, seq in enumerate(seqs):
-                cell, sg, R = seq.cells[l], segs[l * ns + i], d["s8"][l][i].shape[1]
+                cell, R = seq.cells[l], d["s8"][l][i].shape[1]
                 rows += R if l == 0 else 0
                 # layers >= 1: an input-term buffer selects the wide flavour for H <= 256 (16-wave scans fed by PROJ workgroups
                 # of the same launch); without it the 8-wave fused-input roles run
-                sg.zin = _ptr(d["zin"][l][i]) if ((l == 0 and i not in xg) or (l > 0 and (H > 256 or wide))) else None
-                sg.w_hh, sg.w_dq, sg.bias = _ptr(cell.w_hh_q), _ptr(cell.w_hh_dq), _ptr(cell.bias)
-                sg.bn_alpha, sg.bn_beta = _ptr(cell.alpha), _ptr(cell.beta)
-                sg.h_state, sg.c_state = _ptr(d["states"][l][i][0]), _ptr(d["states"][l][i][1])
-                spk = d["spk"][l][i]
-                sg.spikes_f32 = None if spk is None else ctypes.c_void_p(spk.data_ptr() + t0 * R * H * 4)
-                sg.membrane = None
-                sg.spikes_i8 = ctypes.c_void_p(d["s8"][l][i].data_ptr() + t0 * R * HP)
-                sg.R = R
-                sg.spike_count = _ptr(d["cnt"][l][i]) if d.get("cnt") is not None else None
+                zin = d["zin"][l][i] if ((l == 0 and i not in xg) or (l > 0 and (H > 256 or wide))) else None
+                fill_segment(segs[l * ns + i], cell, R, H, t0, zin, d["states"][l][i], d["s8"][l][i], d["spk"][l][i],
+                             count=d["cnt"][l][i] if d.get("cnt") is not None else None)
                 if l > 0:
                     pk, dq = cell.w_ih_q[0]
                     fin[l * ns + i].spikes_in = d["s8"][l - 1][i].data_ptr() + t0 * R * HP
@@ -680,72 +710,40 @@ class Engine:
             self._stack_scratch.append(scratch)
         rp = rpw_stack if rpw_stack else self.stack_rows_per_wg[tag]
         rpw = (ctypes.c_int * nl)(*([rp] * nl))
-        self.launches["stack"] = self.launches.get("stack", 0) + 1
+        lag = self.stack_lag if lag is None else lag
+        self._count("stack")
         with self.timed("stack:" + tag, st):
             rc16 = _lib.SFSN_EUNSUPPORTED
             if self.weight_bits == 16 and self.w16_fast:  # the two-plane roles where the library has them (the pair layout): same results
-                rc16 = L.sfsn_gsn_stack_scan_x_w16(segs, fin, fx, nl, ns, nt, H, rpw, self.stack_lag if lag is None else lag, _ptr(scratch), nbytes, st)
+                rc16 = L.sfsn_gsn_stack_scan_x_w16(segs, fin, fx, nl, ns, nt, H, rpw, lag, _ptr(scratch), nbytes, st)
                 if rc16 not in (0, _lib.SFSN_EUNSUPPORTED):
                     check(rc16, "sfsn_gsn_stack_scan_x_w16")
                 if rc16 == 0:
-                    self.launches["stack_w16"] = self.launches.get("stack_w16", 0) + 1
+                    self._count("stack_w16")
             if rc16 == 0:
                 pass
             elif xg:
-                check(L.sfsn_gsn_stack_scan_x(segs, fin, fx, nl, ns, nt, H, rpw, self.stack_lag if lag is None else lag, _ptr(scratch), nbytes, st),
+                check(L.sfsn_gsn_stack_scan_x(segs, fin, fx, nl, ns, nt, H, rpw, lag, _ptr(scratch), nbytes, st),
                       "sfsn_gsn_stack_scan_x")
             else:
-                check(L.sfsn_gsn_stack_scan(segs, fin, nl, ns, nt, H, rpw, self.stack_lag if lag is None else lag, _ptr(scratch), nbytes, st),
+                check(L.sfsn_gsn_stack_scan(segs, fin, nl, ns, nt, H, rpw, lag, _ptr(scratch), nbytes, st),
                       "sfsn_gsn_stack_scan")
-        # the launch's error word (a bounded hand-off wait expired) travels to pinned host memory behind the launch; it is looked
-        # at without blocking at the next forward (and by check_stack_errors): a failed launch cannot go unnoticed for long
-        if not torch.cuda.is_current_stream_capturing():
-            stream = self._tstream(st)
-            what = f"{tag} rows={rows} frames={nt} wide={wide} rows_per_wg={rp} lag={self.stack_lag if lag is None else lag}"
+        if not torch.cuda.is_current_stream_capturing():  # the launch's error word (ErrorWords)
+            what = f"{tag} rows={rows} frames={nt} wide={wide} rows_per_wg={rp} lag={lag}"
             if self._defer_err is not None and own_scratch:
                 # the overlapped schedule of a forward alone: the copy (a 4-byte blit + its completion) would sit between this launch
                 # and the projection that follows it on the same stream, ~10 us on the forward's chain per launch -- the forward
                 # collects its launches' words once, off the chain, when its streams have joined (_forward_stft)
                 self._defer_err.append((what, scratch))
                 return
-            with torch.cuda.stream(stream):
-                pin = torch.empty((1,), dtype=torch.int32, pin_memory=True)
-                pin.copy_(scratch[:1], non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record(stream)
-            self._stack_err_pending.append((ev, pin, what, scratch))
-
-    def _poll_stack_errors(self, block: bool = False) -> None:
-        keep = []
-        for ev, pin, what, scratch in self._stack_err_pending:
-            if block:
-                ev.synchronize()
-            if ev.query():
-                if int(pin[0]) != 0:
-                    self._stack_err_pending = []
-                    self._clear_stack_scratch(scratch)
-                    raise RuntimeError("sfsn_gsn_stack_scan: a layer-to-layer hand-off wait expired in an earlier launch "
-                                       f"(that forward's results are invalid): {what}")
-            else:
-                keep.append((ev, pin, what, scratch))
-        self._stack_err_pending = keep
-
-    def _clear_stack_scratch(self, scratch) -> None:
-        """After a failed launch: the error word is sticky by design (nobody clears it on the device) and the progress counters
-        of a launch that gave up are not all zeroed by its last workgroup -- reset both, or every later launch on this scratch
-        buffer would report the old failure (round-2 advisor finding)."""
-        torch.cuda.synchronize(self.device)
-        for sc in (scratch if isinstance(scratch, (list, tuple)) else [scratch]):
-            sc.zero_()
-        torch.cuda.synchronize(self.device)
+            self._errors.watch(self._tstream(st), scratch, what)
 
     def check_stack_errors(self) -> None:
         """Raise if a hand-off wait of a stack launch expired (synchronises; tests and bench call it after a forward)."""
-        torch.cuda.synchronize(self.device)
-        self._poll_stack_errors(block=True)
+        self._errors.check()
         for t in self._stack_scratch:
             if int(t[0].item()) != 0:
-                self._clear_stack_scratch(t)
+                self._errors.clear([t])
                 raise RuntimeError("sfsn_gsn_stack_scan: a layer-to-layer hand-off wait expired (results invalid)")
 
     def _stage_proj(self, seqs, s8s, projs, t0, nt, st, tag):
@@ -759,7 +757,7 @@ class Engine:
                     a.y, a.M, a.K, a.N, a.ldy = y.data_ptr() + t0 * R * seq.P * 4, nt * R, seq.H, seq.P, seq.P
                 rc = L.sfsn_spike_proj_multi(arr, len(seqs), st)
                 if rc == 0:
-                    self.launches["merged_products"] = self.launches.get("merged_products", 0) + 1
+                    self._count("merged_products")
                     return
                 if rc != _lib.SFSN_EUNSUPPORTED:
                     check(rc, "sfsn_spike_proj_multi(proj)")
@@ -786,7 +784,7 @@ class Engine:
         if rc == _lib.SFSN_EUNSUPPORTED:
             return False
         check(rc, "sfsn_proj_deepfilter")
-        self.launches["projdf"] = self.launches.get("projdf", 0) + 1
+        self._count("projdf")
         return True
 
     def _zero_states(self, Rs, H, nl, flat=None):
@@ -905,11 +903,6 @@ class Engine:
             if col > 24:
                 raise NotImplementedError("pipelined schedule: the scans would leave fewer than a quarter of the CUs to the other kernels")
             g_pool = columns(col, 32)
-            if os.environ.get("SFSN_PLAIN_STREAMS"):  # diagnostic: no CU partitioning
-                self._pipe_scan = [torch.cuda.Stream(device=self.device) for _ in pools]
-                self._pipe_g = [torch.cuda.Stream(device=self.device) for _ in pools]
-                self._pipe_key = key
-                return self._pipe_scan, self._pipe_g
             self._pipe_scan = [self._masked_stream(p) for p in pools]
             self._pipe_g = [self._masked_stream(g_pool) for _ in pools]  # same CU pool, one queue per stage (a stage's
             # time-parallel kernels wait for its own scan; a shared queue would serialise all four stages)
@@ -937,8 +930,7 @@ class Engine:
                      want_counts: bool = False) -> dict:
         """See ``_forward_stft``; runs with this engine's device current (the C ABI launches on the calling thread's device)."""
         with torch.cuda.device(self.device):
-            if self._stack_err_pending:
-                self._poll_stack_errors()
+            self._errors.poll()
             out = self._forward_stft(stft, want_layers, want_membrane, pipeline, want_counts)
             if not torch.cuda.is_current_stream_capturing():
                 cur = torch.cuda.current_stream(self.device)
@@ -946,11 +938,11 @@ class Engine:
                 if ev is None:
                     ev = self._last_forward[cur.cuda_stream] = torch.cuda.Event()
                 ev.record(cur)  # (what _stack_choice asks: is another stream's forward still running?)
-            if self.strict_errors and self._stack_err_pending:
+            if self.strict_errors:
                 # results are only handed out once every stack launch of THIS forward is known to have completed its hand-offs
                 # (one stream synchronisation per forward: for callers that keep several forwards in flight leave it off and
                 # call check_stack_errors() at their own synchronisation points)
-                self._poll_stack_errors(block=True)
+                self._errors.poll(block=True)
             return out
 
     def _forward_stft(self, stft: torch.Tensor, want_layers: bool = True, want_membrane: bool = False, pipeline: Optional[bool] = None,
@@ -1047,7 +1039,6 @@ class Engine:
         # ---------------- tensors
         x_fb = torch.empty((T, B, spec.fb_in), **f32)
         xs = [torch.empty((T, B * spec.units(g), spec.sb_input_size(g)), **f32) for g in range(ng)]
-        prep_ahead = bool(overlap and self.overlap_prep_ahead)
         # the zero initial state of every scan of the forward: ONE buffer, zeroed by the forward's first feature launch (every scan
         # depends on that launch through its input) -- no fill launch on the forward's chain
         n_fb = 2 * nl_fb * B * self.fb.H
@@ -1061,7 +1052,7 @@ class Engine:
         state_flat = torch.empty((n_fb + n_sb + n_cnt_f,), **f32) if fold else torch.zeros((n_fb + n_sb + n_cnt_f,), **f32)
         zero_job = [state_flat] if fold else []
         cnt_all = state_flat[n_fb + n_sb:n_fb + n_sb + 2 * n_cnt].view(torch.int64) if in_scan else None
-        fb = self._alloc_stack([self.fb], [B], T, T if prep_ahead else nt_max, want_layers, want_membrane, "fb", state_flat[:n_fb],
+        fb = self._alloc_stack([self.fb], [B], T, nt_max, want_layers, want_membrane, "fb", state_flat[:n_fb],
                                None if cnt_all is None else cnt_all[:nl_fb])
         sb = self._alloc_stack(self.sb, [x.shape[1] for x in xs], T, nt_max, want_layers, want_membrane, "sb", state_flat[n_fb:n_fb + n_sb],
                                None if cnt_all is None else cnt_all[nl_fb:])
@@ -1084,7 +1075,6 @@ class Engine:
         # ---------------- streams: sequential = the current stream; pipelined = per stage one scan stream (own CUs) and one
         #                  stream for its time-parallel kernels (shared CU pool), chained by events
         n_stage = nl_fb + nl_sb
-        post_stream = None
         if pipeline:
             rpw_fb, rpw_sb = 16, 16
             fb_tiles = (B + rpw_fb - 1) // rpw_fb
@@ -1098,19 +1088,8 @@ class Engine:
             if self._ov_streams is None:
                 self._ov_streams = {}
             if main.cuda_stream not in self._ov_streams:  # a pair per calling stream: forwards in flight stay independent
-                nx = int(os.environ.get("SFSN_OV_XCD_SPLIT", "0"))
-                if nx > 0:
-                    # experiment (round 5): the full-band stream on the first `nx` XCDs only, the sub-band stream on the others (a mask
-                    # word = one XCD, scripts/exp_cumask.py): the full-band stack's hand-offs then stay inside nx L2s
-                    n_cu = torch.cuda.get_device_properties(dev).multi_processor_count
-                    self._ov_streams[main.cuda_stream] = (self._masked_stream(list(range(0, 32 * nx))), self._masked_stream(list(range(32 * nx, n_cu))))
-                else:
-                    self._ov_streams[main.cuda_stream] = (torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev))
+                self._ov_streams[main.cuda_stream] = (torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev))
             sa, sb_ = self._ov_streams[main.cuda_stream]
-            if self.overlap_post_stream:
-                if ("post", main.cuda_stream) not in self._ov_streams:
-                    self._ov_streams[("post", main.cuda_stream)] = torch.cuda.Stream(device=dev)
-                post_stream = self._ov_streams[("post", main.cuda_stream)]
             self._defer_err = []
             sstreams = gstreams = [sa] * nl_fb + [sb_] * nl_sb
             rpw_fb, rpw_sb = self.rows_per_wg
@@ -1118,13 +1097,6 @@ class Engine:
             fork.record(main)
             sa.wait_event(fork)
             sb_.wait_event(fork)
-            if post_stream is not None:
-                post_stream.wait_event(fork)
-            if prep_ahead:
-                if ("aux", main.cuda_stream) not in self._ov_streams:
-                    self._ov_streams[("aux", main.cuda_stream)] = torch.cuda.Stream(device=dev)
-                aux_stream = self._ov_streams[("aux", main.cuda_stream)]
-                aux_stream.wait_event(fork)
         else:
             sstreams = gstreams = [main] * n_stage
             rpw_fb, rpw_sb = self.rows_per_wg
@@ -1158,51 +1130,22 @@ class Engine:
             use_stack, wide, rpw_stack = self._stack_choice(seqs, [x.shape[1] for x in xs_], want_membrane)
             if not pipeline and use_stack:
                 # all layers in one launch: features, layer 0's input term, the stack scan, the projection
-                ahead = prep_ahead and gate_events is None and d["zin"][0][0].shape[0] >= T
-                def prep(t0, nt, dz, st):
+                g, hg = gstreams[first], hG[first]
+                for c, (t0, nt) in enumerate(bounds):
+                    if staged and gate_events is not None:
+                        g.wait_event(gate_events[c])
                     xg = self._stack_x_groups(seqs, xs_, nt, wide, rpw_stack or self.stack_rows_per_wg[tag], want_membrane)
                     zr = [i for i in range(len(seqs)) if i not in xg]
-                    if not feat_fn(t0, nt, st, (zr, pick(dz["zin"][0], zr))) and zr:  # (True: one launch made the rows and the input terms)
-                        self._stage_input(pick(seqs, zr), 0, pick(xs_, zr), pick(dz["zin"][0], zr), t0, nt, st, tag)
-                    return xg
-                if ahead:  # layer 0's input term has a buffer for the whole sequence: chunk c's rows are [t0, t0 + nt)
-                    views = [dict(d, zin=[[z[t0:t0 + nt] if l_ == 0 else z[:nt] for z in zl] for l_, zl in enumerate(d["zin"])]) for t0, nt in bounds]
-                    h_aux, ready = self._handle(aux_stream), []
-                    for (t0, nt), dv in zip(bounds, views):
-                        xg = prep(t0, nt, dv, h_aux)
-                        ev = torch.cuda.Event()
-                        ev.record(aux_stream)
-                        ready.append((ev, xg))
-                # prep_next (ungated model of the overlapped schedule = the full-band one; needs the chunk-local input term buffer free:
-                # the stack launch of chunk c is behind us on the same stream when chunk c + 1's product is enqueued)
-                nxt = bool(overlap and self.overlap_prep_next and gate_events is None and not ahead and sstreams[first] is gstreams[first])
-                post_h = hG[first]
-                on_post = bool(overlap and fused_post is not None and post_stream is not None and gate_events is not None)
-                xg_next = prep(bounds[0][0], bounds[0][1], d, hG[first]) if nxt else None
-                for c, (t0, nt) in enumerate(bounds):
-                    if ahead:
-                        dv, (ev, xg) = views[c], ready[c]
-                        sstreams[first].wait_event(ev)
-                    elif nxt:
-                        dv, xg = d, xg_next
-                    else:
-                        dv = d
-                        if staged and gate_events is not None:
-                            gstreams[first].wait_event(gate_events[c])
-                        xg = prep(t0, nt, dv, hG[first])
-                    self._stage_stack(seqs, dv, t0, nt, hS[first], tag, wide, rpw_stack, xs_=xs_, xg=xg)
-                    if nxt and c + 1 < len(bounds):
-                        xg_next = prep(bounds[c + 1][0], bounds[c + 1][1], d, hG[first])
-                    if on_post:
-                        link(sstreams[first], post_stream)
-                        post_h = self._handle(post_stream)
-                    if fused_post is None or not fused_post(t0, nt, post_h):  # (the two-launch epilogue reads the same tensors)
-                        self._stage_proj(seqs, d["s8"][nl - 1], d["proj"], t0, nt, post_h, tag)
+                    if not feat_fn(t0, nt, hg, (zr, pick(d["zin"][0], zr))) and zr:  # (True: one launch made the rows and the input terms)
+                        self._stage_input(pick(seqs, zr), 0, pick(xs_, zr), pick(d["zin"][0], zr), t0, nt, hg, tag)
+                    self._stage_stack(seqs, d, t0, nt, hS[first], tag, wide, rpw_stack, xs_=xs_, xg=xg)
+                    if fused_post is None or not fused_post(t0, nt, hg):  # (the two-launch epilogue reads the same tensors)
+                        self._stage_proj(seqs, d["s8"][nl - 1], d["proj"], t0, nt, hg, tag)
                         if post_fn is not None:
-                            post_fn(t0, nt, post_h)
+                            post_fn(t0, nt, hg)
                     if staged:
                         ev = torch.cuda.Event()
-                        ev.record(post_stream if on_post else gstreams[first])
+                        ev.record(g)
                         done.append(ev)
                 return done
             # layer 0: groups whose real-valued input product can run inside the scan / the rest (input product first)
@@ -1333,29 +1276,13 @@ class Engine:
         else:
             sb_done = run_model(self.sb, sb, xs, nl_fb, feat_sb, "sb", rpw_sb, post_sb, fb_done if staged else None, fused_post_sb)
         if staged:
-            extra = ([aux_stream] if prep_ahead else []) + ([post_stream] if (overlap and post_stream is not None) else [])
-            for s_ in {id(x): x for x in sstreams + gstreams + extra}.values():
+            for s_ in {id(x): x for x in sstreams + gstreams}.values():
                 link(s_, main)
         if self._defer_err:
             # the error words of this forward's stack launches: one maximum, one copy to pinned memory, on a stream of its own behind
             # the joined forward (nothing of the forward waits for it)
             items, self._defer_err = self._defer_err, None
-            if self._err_stream is None:
-                self._err_stream = torch.cuda.Stream(device=dev)
-            es = self._err_stream
-            ev0 = torch.cuda.Event()
-            ev0.record(main)
-            es.wait_event(ev0)
-            with torch.cuda.stream(es):
-                uniq = list({id(sc): sc for _, sc in items}.values())
-                word = torch.stack([sc[0] for sc in uniq]).max().reshape(1)
-                pin = torch.empty((1,), dtype=torch.int32, pin_memory=True)
-                pin.copy_(word, non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record(es)
-            for sc in uniq:
-                sc.record_stream(es)
-            self._stack_err_pending.append((ev, pin, "; ".join(sorted({w for w, _ in items})), uniq))
+            self._errors.watch(None, list({id(sc): sc for _, sc in items}.values()), "; ".join(sorted({w for w, _ in items})))
         self._defer_err = None
 
         if want_counts and not want_layers:

@@ -23,7 +23,7 @@ import torch
 
 from . import _lib
 from ._lib import FusedInput, ScanSegment, check
-from .engine import _dev, _ptr, fold_batchnorm, pack_w3
+from .engine import ErrorWords, _dev, _ptr, fill_segment, fold_batchnorm, pack_w3
 
 ACTIVATIONS = {"tanh": _lib.ACT_TANH, "sigmoid": _lib.ACT_SIGMOID, "relu": _lib.ACT_RELU}
 
@@ -172,7 +172,7 @@ class FullbandEngine:
         self.stack_scan = True  # all layers in one sfsn_gsn_stack_scan launch where it applies (False: one scan launch per layer)
         self.stack_lag = 4
         self._ws: Dict[tuple, dict] = {}
-        self._err_pending = []
+        self._errors = ErrorWords(self)  # the stack launches' error words: polled at the next forward
 
     def _count(self, what: str) -> None:
         self.launches[what] = self.launches.get(what, 0) + 1
@@ -212,38 +212,7 @@ class FullbandEngine:
 
     def check_stack_errors(self) -> None:
         """Raise if a hand-off wait of an earlier stack launch expired (synchronises)."""
-        torch.cuda.synchronize(self.device)
-        pending, self._err_pending = self._err_pending, []
-        for _, pin, scratch in pending:
-            if int(pin[0]) != 0:
-                scratch.zero_()
-                torch.cuda.synchronize(self.device)
-                raise RuntimeError("sfsn_gsn_stack_scan: a layer-to-layer hand-off wait expired (that forward's results are invalid)")
-
-    def _poll_errors(self) -> None:
-        keep = []
-        for ev, pin, scratch in self._err_pending:
-            if ev.query():
-                if int(pin[0]) != 0:
-                    self._err_pending = []
-                    torch.cuda.synchronize(self.device)
-                    scratch.zero_()
-                    raise RuntimeError("sfsn_gsn_stack_scan: a layer-to-layer hand-off wait expired in an earlier forward "
-                                       "(its results are invalid)")
-            else:
-                keep.append((ev, pin, scratch))
-        self._err_pending = keep
-
-    def _segment(self, l: int, zin, ws, spk, states, B: int) -> ScanSegment:
-        layer, sg = self.layers[l], ScanSegment()
-        sg.zin, sg.w_hh, sg.w_dq, sg.bias = _ptr(zin), _ptr(layer.w_hh_q), _ptr(layer.w_hh_dq), _ptr(layer.bias)
-        sg.bn_alpha, sg.bn_beta, sg.h_state, sg.c_state = _ptr(layer.alpha), _ptr(layer.beta), _ptr(states[l][0]), _ptr(states[l][1])
-        sg.spikes_f32 = _ptr(spk[l])
-        sg.membrane = None
-        sg.spikes_i8 = _ptr(ws["s8"][l])
-        sg.R = B
-        sg.spike_count = None
-        return sg
+        self._errors.check()
 
     @torch.no_grad()
     def forward_stft(self, noisy_cmp: torch.Tensor, want_layers: bool = False) -> dict:
@@ -253,7 +222,7 @@ class FullbandEngine:
         if noisy_cmp.device != self.device or noisy_cmp.dtype != torch.complex64 or noisy_cmp.ndim != 3 or noisy_cmp.shape[1] != F:
             raise ValueError(f"expected complex64 [B, {F}, T] on {self.device}, got {noisy_cmp.dtype} {tuple(noisy_cmp.shape)} "
                              f"on {noisy_cmp.device}")
-        self._poll_errors()
+        self._errors.poll()
         B, _, T = noisy_cmp.shape
         ri = torch.view_as_real(noisy_cmp.contiguous())
         st, dev, nl, S = self._stream(), self.device, spec.layers, spec.num_spks
@@ -285,7 +254,7 @@ class FullbandEngine:
             for l in range(nl):
                 # layers >= 1 with Hp > 256: the launch's input-term workgroups write their [T][B][Hp] buffer; Hp <= 256: in-scan
                 zin = ws["zin"][0] if l == 0 else (ws["zin"][l] if Hp > 256 else None)
-                segs[l] = self._segment(l, zin, ws, spk, states, B)
+                fill_segment(segs[l], self.layers[l], B, Hp, 0, zin, states[l], ws["s8"][l], spk[l])
                 if l > 0:
                     pk, dq = self.layers[l].w_ih_q[0]
                     fin[l].spikes_in, fin[l].w_ih, fin[l].w_ih_dq = ws["s8"][l - 1].data_ptr(), pk.data_ptr(), dq.data_ptr()
@@ -296,11 +265,7 @@ class FullbandEngine:
                   "sfsn_gsn_stack_scan")
             self._count("stack")
             if not torch.cuda.is_current_stream_capturing():  # the launch's error word, looked at without blocking next time
-                pin = torch.empty((1,), dtype=torch.int32, pin_memory=True)
-                pin.copy_(scratch[:1], non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record(torch.cuda.current_stream(dev))
-                self._err_pending.append((ev, pin, scratch))
+                self._errors.watch(torch.cuda.current_stream(dev), scratch, f"full-band stack rows={B} frames={T} rows_per_wg={rp}")
         else:
             for l in range(nl):
                 zin = ws["zin"][l]
@@ -312,7 +277,7 @@ class FullbandEngine:
                                                 ctypes.c_void_p(zin.data_ptr() + g * Hp * 4), T * B, Hp, Hp, G * Hp, st), "sfsn_spike_proj")
                         self._count("spike_proj")
                 seg = (ScanSegment * 1)()
-                seg[0] = self._segment(l, zin, ws, spk, states, B)
+                fill_segment(seg[0], self.layers[l], B, Hp, 0, zin, states[l], ws["s8"][l], spk[l])
                 check(L.sfsn_gsn_layer_scan(seg, 1, T, Hp, int(spec.shared), 0, st), "sfsn_gsn_layer_scan")
                 self._count("layer_scan")
         enh = torch.empty((B, S, F, T, 2), **f32)

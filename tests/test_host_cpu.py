@@ -461,3 +461,169 @@ def test_training_istft_without_the_host_check_equals_torch_istft(n_fft, hop, wl
         ga, = torch.autograd.grad(a.pow(2).sum(), x)
         gb, = torch.autograd.grad(b.pow(2).sum(), x)
         assert float((ga - gb).abs().max()) <= 1e-6 * float(ga.abs().max())
+
+
+# ---- the five scan / stack entry points: what each asks of a sfsn_scan_segment, pinned as (entry point, defect, code) ----------------
+# The expected codes are the answers of the library as it was before the entry points shared their checks (csrc/sfsn_host.h):
+# SFSN_EHIP = every check passed and the launch found no device.  Pointers are made-up addresses: nothing dereferences them here.
+_SEG_PTRS = ("zin", "w_hh", "w_dq", "bias", "bn_alpha", "bn_beta", "h_state", "c_state", "spikes_i8")
+
+
+def _scan_abi_rc(L, entry, H=None, n_segs=2, T=200, shared=None, rows_per_wg=0, seg=None, every_seg=None, upper=None, fin=None, fx=None,
+                 n_layers=2, rpws=(8, 8), lag=4, scratch=0x7000000, scratch_bytes=1 << 24):
+    """Return code of `entry` for a valid argument set with the given changes: `seg` / `every_seg` = field overrides of the last /
+    of every segment, `upper` = of the last segment of the stack's layer 1, `fin` / `fx` = of the last fused-input descriptor."""
+    import ctypes
+    from spiking_fullsubnet_amd import _lib
+    stack = entry.startswith("sfsn_gsn_stack")
+    split = entry == "sfsn_gsn_layer_scan_split"
+    no_zin = entry in ("sfsn_gsn_layer_scan_fused", "sfsn_gsn_layer_scan_fused_x")
+    H = H if H is not None else (320 if split else 224)
+    n = 1 if split else 2
+    nl = n_layers if stack else 1
+    segs, fins, fxs = (_lib.ScanSegment * (nl * n))(), (_lib.FusedInput * (nl * n))(), (_lib.FusedX * n)()
+    for l in range(nl):
+        for i in range(n):
+            sg, base = segs[l * n + i], 0x100000 * (l * n + i + 1)
+            for k, name in enumerate(_SEG_PTRS):
+                setattr(sg, name, base + 0x1000 * k)
+            sg.R = 16
+            if no_zin or l > 0 or (fx is not None and stack):
+                sg.zin = None
+            fi = fins[l * n + i]
+            fi.spikes_in = segs[(l - 1) * n + i].spikes_i8 if (stack and l > 0) else 0x9000000 + 0x1000 * i
+            fi.w_ih, fi.w_ih_dq = 0xA000000 + 0x1000 * (l * n + i), 0xB000000 + 0x1000 * (l * n + i)
+    for i in range(n):
+        fxs[i].x, fxs[i].w_ih, fxs[i].I = 0xC000000 + 0x1000 * i, 0xD000000 + 0x1000 * i, 38
+    for target, changes in ((segs[n - 1], seg), (segs[nl * n - 1], upper), (fins[nl * n - 1], fin), (fxs[n - 1], fx)):
+        for k, v in (changes or {}).items():
+            setattr(target, k, v)
+    for sg in segs:
+        for k, v in (every_seg or {}).items():
+            setattr(sg, k, v)
+    S, FI, FX, I, P = ctypes.POINTER(_lib.ScanSegment), ctypes.POINTER(_lib.FusedInput), ctypes.POINTER(_lib.FusedX), ctypes.c_int, ctypes.c_void_p
+    fn = getattr(L, entry)
+    if entry in ("sfsn_gsn_layer_scan", "sfsn_gsn_layer_scan_w16"):
+        fn.argtypes = [S, I, I, I, I, I, P]
+        return fn(segs, n_segs, T, H, 1 if shared is None else shared, rows_per_wg, None)
+    if split:
+        fn.argtypes = [S, I, I, I, I, P, ctypes.c_size_t, P]
+        return fn(segs, 1 if n_segs == 2 else n_segs, T, H, 0 if shared is None else shared, scratch, scratch_bytes, None)
+    if entry == "sfsn_gsn_layer_scan_fused":
+        fn.argtypes = [S, FI, I, I, I, P]
+        return fn(segs, fins, n_segs, T, H, None)
+    if entry == "sfsn_gsn_layer_scan_fused_x":
+        fn.argtypes = [S, FX, I, I, I, P]
+        return fn(segs, fxs, n_segs, T, H, None)
+    rp = (I * nl)(*rpws[:nl])
+    if entry == "sfsn_gsn_stack_scan":
+        fn.argtypes = [S, FI, I, I, I, I, ctypes.POINTER(I), I, P, ctypes.c_size_t, P]
+        return fn(segs, fins, nl, n_segs, T, H, rp, lag, scratch, scratch_bytes, None)
+    fn.argtypes = [S, FI, FX, I, I, I, I, ctypes.POINTER(I), I, P, ctypes.c_size_t, P]
+    return fn(segs, fins, fxs if fx is not None else None, nl, n_segs, T, H, rp, lag, scratch, scratch_bytes, None)
+
+
+_EINVAL, _EUNSUP, _EHIP = -1, -2, -3
+_MEM, _F32, _ODD = 0x6000000, 0x6100000, 0x5000004  # a membrane buffer, an fp32 spike buffer, an address that is not 16-byte aligned
+SCAN_ABI_CASES = [
+    # sfsn_gsn_layer_scan: input term required, membrane allowed (with the fp32 spikes)
+    ("sfsn_gsn_layer_scan", "valid", {}, _EHIP),
+    ("sfsn_gsn_layer_scan", "no input term", dict(seg=dict(zin=None)), _EINVAL),
+    ("sfsn_gsn_layer_scan", "input term off by 4 bytes", dict(seg=dict(zin=_ODD)), _EINVAL),
+    ("sfsn_gsn_layer_scan", "no int8 spikes", dict(seg=dict(spikes_i8=None)), _EINVAL),
+    ("sfsn_gsn_layer_scan", "membranes with fp32 spikes", dict(every_seg=dict(membrane=_MEM, spikes_f32=_F32)), _EHIP),
+    ("sfsn_gsn_layer_scan", "membranes without fp32 spikes", dict(every_seg=dict(membrane=_MEM)), _EUNSUP),
+    ("sfsn_gsn_layer_scan", "membrane in one segment only", dict(every_seg=dict(spikes_f32=_F32), seg=dict(membrane=_MEM)), _EINVAL),
+    ("sfsn_gsn_layer_scan", "membrane off by 4 bytes", dict(every_seg=dict(membrane=_ODD, spikes_f32=_F32)), _EINVAL),
+    ("sfsn_gsn_layer_scan", "fp32 spikes in one segment only", dict(seg=dict(spikes_f32=_F32)), _EINVAL),
+    ("sfsn_gsn_layer_scan", "R = 0", dict(seg=dict(R=0)), _EINVAL),
+    ("sfsn_gsn_layer_scan", "R = 17", dict(seg=dict(R=17)), _EHIP),
+    ("sfsn_gsn_layer_scan", "no segments", dict(n_segs=0), _EINVAL),
+    ("sfsn_gsn_layer_scan", "too many segments", dict(n_segs=9), _EINVAL),
+    ("sfsn_gsn_layer_scan", "H = 0", dict(H=0), _EINVAL),
+    ("sfsn_gsn_layer_scan", "H = 8", dict(H=8), _EUNSUP),
+    ("sfsn_gsn_layer_scan", "H = 336", dict(H=336), _EUNSUP),
+    ("sfsn_gsn_layer_scan", "5 rows per workgroup", dict(rows_per_wg=5), _EINVAL),
+    ("sfsn_gsn_layer_scan_w16", "valid", {}, _EHIP),
+    ("sfsn_gsn_layer_scan_w16", "H = 320: no two-plane form", dict(H=320), _EUNSUP),
+    # sfsn_gsn_layer_scan_split: one segment, the same flags, plus its scratch
+    ("sfsn_gsn_layer_scan_split", "valid", {}, _EHIP),
+    ("sfsn_gsn_layer_scan_split", "no input term", dict(seg=dict(zin=None)), _EINVAL),
+    ("sfsn_gsn_layer_scan_split", "membranes without fp32 spikes", dict(seg=dict(membrane=_MEM)), _EUNSUP),
+    ("sfsn_gsn_layer_scan_split", "membrane off by 4 bytes", dict(seg=dict(membrane=_ODD, spikes_f32=_F32)), _EINVAL),
+    ("sfsn_gsn_layer_scan_split", "scratch off by 4 bytes", dict(scratch=0x7000004), _EINVAL),
+    ("sfsn_gsn_layer_scan_split", "scratch too small", dict(scratch_bytes=64), _EINVAL),
+    ("sfsn_gsn_layer_scan_split", "H = 224: one compute unit serves it", dict(H=224), _EUNSUP),
+    # sfsn_gsn_layer_scan_fused: the input term is ignored, no membrane
+    ("sfsn_gsn_layer_scan_fused", "valid", {}, _EHIP),
+    ("sfsn_gsn_layer_scan_fused", "a stray misaligned input term is ignored", dict(seg=dict(zin=_ODD)), _EHIP),
+    ("sfsn_gsn_layer_scan_fused", "membrane", dict(every_seg=dict(membrane=_MEM, spikes_f32=_F32)), _EINVAL),
+    ("sfsn_gsn_layer_scan_fused", "c_state off by 4 bytes", dict(seg=dict(c_state=_ODD)), _EINVAL),
+    ("sfsn_gsn_layer_scan_fused", "no input spikes", dict(fin=dict(spikes_in=None)), _EINVAL),
+    ("sfsn_gsn_layer_scan_fused", "input weights off by 4 bytes", dict(fin=dict(w_ih=_ODD)), _EINVAL),
+    ("sfsn_gsn_layer_scan_fused", "H = 64", dict(H=64), _EUNSUP),
+    # sfsn_gsn_layer_scan_fused_x: the shape answers (I, R) come between the presence and the alignment checks
+    ("sfsn_gsn_layer_scan_fused_x", "valid", {}, _EHIP),
+    ("sfsn_gsn_layer_scan_fused_x", "I = 0", dict(fx=dict(I=0)), _EUNSUP),
+    ("sfsn_gsn_layer_scan_fused_x", "I = 39", dict(fx=dict(I=39)), _EUNSUP),
+    ("sfsn_gsn_layer_scan_fused_x", "I = 66", dict(fx=dict(I=66)), _EUNSUP),
+    ("sfsn_gsn_layer_scan_fused_x", "R = 8", dict(seg=dict(R=8)), _EUNSUP),
+    ("sfsn_gsn_layer_scan_fused_x", "h_state off by 4 bytes", dict(seg=dict(h_state=_ODD)), _EINVAL),
+    ("sfsn_gsn_layer_scan_fused_x", "I = 66 and h_state off by 4 bytes", dict(fx=dict(I=66), seg=dict(h_state=_ODD)), _EUNSUP),
+    ("sfsn_gsn_layer_scan_fused_x", "I = 66 and no w_hh", dict(fx=dict(I=66), seg=dict(w_hh=None)), _EINVAL),
+    ("sfsn_gsn_layer_scan_fused_x", "rows off by 4 bytes", dict(fx=dict(x=_ODD)), _EINVAL),
+    ("sfsn_gsn_layer_scan_fused_x", "membrane", dict(every_seg=dict(membrane=_MEM, spikes_f32=_F32)), _EINVAL),
+    # sfsn_gsn_stack_scan: the input term is optional per layer (asked for where the layout needs it), aligned when given
+    ("sfsn_gsn_stack_scan", "valid", {}, _EHIP),
+    ("sfsn_gsn_stack_scan", "layer 0 without an input term", dict(seg=dict(zin=None)), _EINVAL),
+    ("sfsn_gsn_stack_scan", "layer 1's input term off by 4 bytes", dict(upper=dict(zin=_ODD)), _EINVAL),
+    ("sfsn_gsn_stack_scan", "membrane", dict(every_seg=dict(membrane=_MEM, spikes_f32=_F32)), _EINVAL),
+    ("sfsn_gsn_stack_scan", "fp32 spikes in one layer only", dict(upper=dict(spikes_f32=_F32)), _EINVAL),
+    ("sfsn_gsn_stack_scan", "rows differ between the layers", dict(upper=dict(R=8)), _EINVAL),
+    ("sfsn_gsn_stack_scan", "layer 1 does not read layer 0's spikes", dict(fin=dict(spikes_in=0x9000000)), _EINVAL),
+    ("sfsn_gsn_stack_scan", "negative lag", dict(lag=-1), _EINVAL),
+    ("sfsn_gsn_stack_scan", "5 rows per workgroup", dict(rpws=(5, 5)), _EINVAL),
+    ("sfsn_gsn_stack_scan", "no scratch", dict(scratch=None), _EINVAL),
+    ("sfsn_gsn_stack_scan", "scratch too small", dict(scratch_bytes=64), _EINVAL),
+    ("sfsn_gsn_stack_scan", "H = 336", dict(H=336), _EUNSUP),
+    ("sfsn_gsn_stack_scan_x", "layer 0 from the feature rows", dict(fx={}), _EHIP),
+    ("sfsn_gsn_stack_scan_x", "I = 66", dict(fx=dict(I=66)), _EUNSUP),
+    ("sfsn_gsn_stack_scan_x", "I = 66 and no bias", dict(fx=dict(I=66), every_seg=dict(bias=None)), _EINVAL),
+    ("sfsn_gsn_stack_scan_x_w16", "the pair layout", dict(fx={}), _EHIP),
+    ("sfsn_gsn_stack_scan_x_w16", "H = 320: no two-plane form", dict(H=320, rpws=(4, 4)), _EUNSUP),
+]
+
+
+@pytest.mark.skipif(torch.cuda.is_available(), reason="on a box with a device the valid rows would launch on made-up addresses")
+def test_scan_entry_points_answer_every_segment_defect_with_the_same_code():
+    from spiking_fullsubnet_amd import _lib
+    L = _lib.lib()
+    got = [(e, what, _scan_abi_rc(L, e, **kw)) for e, what, kw, _ in SCAN_ABI_CASES]
+    assert got == [(e, what, rc) for e, what, _, rc in SCAN_ABI_CASES]
+
+
+@pytest.mark.parametrize("H,t0", [(16, 0), (16, 2), (80, 0), (80, 2)])
+@pytest.mark.parametrize("extras", [False, True])
+def test_fill_segment_points_every_field_at_its_documented_offset(H, t0, extras):
+    """engine.fill_segment on CPU tensors (only data_ptr() is read): weights, input term and state as they are; the whole-sequence
+    outputs at frame t0 -- fp32 spikes / membranes t0 * R * H * 4 bytes in, int8 spikes t0 * R * ceil64(H) (H = 16: 64-byte rows,
+    H = 80: 128); fp32 spikes, membrane and counter None when absent."""
+    from types import SimpleNamespace
+    from spiking_fullsubnet_amd import _lib
+    from spiking_fullsubnet_amd.engine import fill_segment
+    T, R, HP = 3, 2, (H + 63) // 64 * 64
+    assert HP == {16: 64, 80: 128}[H]
+    f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32)
+    cell = SimpleNamespace(w_hh_q=torch.zeros(3 * H * HP, dtype=torch.int8), w_hh_dq=f32(H), bias=f32(2 * H), alpha=f32(H), beta=f32(H))
+    zin, h, c, s8 = f32(T - t0, R, H), f32(R, H), f32(R, H), torch.zeros((T, R, HP), dtype=torch.int8)
+    spk, mem, cnt = (f32(T, R, H), f32(T, R, H), torch.zeros((), dtype=torch.int64)) if extras else (None, None, None)
+    sg = _lib.ScanSegment()
+    fill_segment(sg, cell, R, H, t0, zin, (h, c), s8, spk, mem, cnt)
+    want = dict(zin=zin.data_ptr(), w_hh=cell.w_hh_q.data_ptr(), w_dq=cell.w_hh_dq.data_ptr(), bias=cell.bias.data_ptr(),
+                bn_alpha=cell.alpha.data_ptr(), bn_beta=cell.beta.data_ptr(), h_state=h.data_ptr(), c_state=c.data_ptr(),
+                spikes_i8=s8.data_ptr() + t0 * R * HP, R=R,
+                spikes_f32=spk.data_ptr() + t0 * R * H * 4 if extras else None, membrane=mem.data_ptr() + t0 * R * H * 4 if extras else None,
+                spike_count=cnt.data_ptr() if extras else None)
+    assert {name: getattr(sg, name) for name, _ in _lib.ScanSegment._fields_} == want
+    fill_segment(sg, cell, R, H, t0, None, (h, c), s8)  # (a launch that forms the input term itself; a reused struct is overwritten)
+    assert (sg.zin, sg.spikes_f32, sg.membrane, sg.spike_count) == (None, None, None, None) and sg.spikes_i8 == s8.data_ptr() + t0 * R * HP
