@@ -714,6 +714,66 @@ int sfsn_fullband_deepfilter_fwd(const float* spec_ri /* [B][F][T][2] */, const 
 int sfsn_fullband_deepfilter_bwd(const float* spec_ri /* [B][F][T][2] */, const float* g_ri /* [B][S][F][T][2] */, int B, int F, int T,
                                  int S, int df, float* d_coef /* [T][B][2 df S F] */, void* stream);
 
+/* ----------------------------------------------------------------------------------------------------
+ * The cIRM-GSN model frame by frame: `hop` new frames of every clip through features, GSN stack, projection and deep filter in ONE
+ * launch (csrc/sfsn_fullband_hop.hip; the plan of sfsn_stream_hop: one wave per 16-neuron tile with its digits in registers, frames
+ * handed from stage to stage through L2 as data-tagged granules, recurrent product before the input arrives, bounded spins with an
+ * error word in scratch word 0, refused unless every workgroup can be resident).  Bit-identical to sfsn_fullband_features ->
+ * sfsn_fullband_input_proj -> the GSN scans -> sfsn_fullband_proj_deepfilter on the concatenated input.
+ *
+ * Coverage (sfsn_fullband_hop_check, host only, no device needed; SFSN_EUNSUPPORTED outside it, SFSN_EINVAL for non-positive
+ * sizes or D != df - 1):
+ *     shared gate weights (unshared = 0);  Hp % 16 == 0, Hp <= 320 (hidden size padded as fullband_engine.pad_cell does);
+ *     1 .. SFSN_FULLBAND_HOP_MAX_LAYERS layers;  193 <= F <= 320 (F <= 192 is sfsn_input_proj_f32's fp32-MFMA product offline);
+ *     S <= 2;  df <= 5;  D + hop <= 32;  B <= 16.  BatchNorm folded into bn_alpha / bn_beta, LayerNorm optional, any SFSN_ACT_*.
+ *
+ * State (caller-owned, zeroed at the start of a session, touched by nothing else): per layer the last spikes h[2] [B][pad64(Hp)]
+ * (double-buffered by launch parity) and the membranes c [B][Hp]; hist_ri[2] [B][F][D][2] (double-buffered likewise).  Work buffers
+ * rewritten by every launch: spikes [hop][B][pad64(Hp)] per layer (tagged), z0 [hop][B][Hp][2] ({value, tag} granules of layer 0's
+ * input term).  launch_index: launches made on this state so far, counted by the caller (tag and parity).  clip_start (nullable,
+ * [B]): the launch index at which clip b's utterance began -- in that launch the clip's state and history read as zero.
+ * Weights: w_ih0 fp32 [Hp][F] row-major; w_ih / w_hh / w_p as sfsn_w3_pack images ([Hp][Hp]; w_p bin-major as for
+ * sfsn_fullband_proj_deepfilter), bias [2 Hp].  Outputs enh_ri [B][S][F][hop][2], enh_mag [B][S][F][hop] (nullable).
+ * (Added without an ABI bump: no existing struct or signature changed.)
+ * ---------------------------------------------------------------------------------------------------- */
+#define SFSN_FULLBAND_HOP_MAX_LAYERS 4
+typedef struct {
+    const int8_t* w_ih;    /* layers >= 1 */
+    const float* w_ih_dq;
+    const int8_t* w_hh;
+    const float* w_hh_dq;
+    const float* bias;
+    const float* bn_alpha;
+    const float* bn_beta;
+    int8_t* h[2];
+    float* c;
+    int8_t* spikes;
+} sfsn_fullband_hop_layer;
+typedef struct {
+    sfsn_fullband_hop_layer layer[SFSN_FULLBAND_HOP_MAX_LAYERS];
+    int n_layers, Hp, B, F, S, df, hop, D, act, unshared;
+    float fdrc, ln_eps;
+    const float* w_ih0;
+    const float* ln_w; /* nullable (both): no LayerNorm */
+    const float* ln_b;
+    const int8_t* w_p;
+    const float* w_p_dq;
+    const float* b_p; /* nullable */
+    const float* inp_ri; /* [B][F][hop][2] */
+    float* hist_ri[2];
+    float* enh_ri;
+    float* enh_mag;
+    float* z0;
+    const unsigned* clip_start;
+    void* scratch;
+    size_t scratch_bytes; /* >= sfsn_fullband_hop_scratch_bytes */
+    unsigned launch_index;
+} sfsn_fullband_hop_desc;
+
+int sfsn_fullband_hop_check(int Hp, int n_layers, int F, int S, int df, int B, int hop, int D, int unshared);
+size_t sfsn_fullband_hop_scratch_bytes(const sfsn_fullband_hop_desc* desc); /* 0: not covered (host only) */
+int sfsn_fullband_stream_hop(const sfsn_fullband_hop_desc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -106,11 +106,27 @@ class HopDesc(ctypes.Structure):
                 ("clip_start", _P), ("spike_slots", _P)]
 
 
+FULLBAND_HOP_MAX_LAYERS = 4
+
+
+class FullbandHopLayer(ctypes.Structure):  # sfsn_fullband_hop_layer
+    _fields_ = [("w_ih", _P), ("w_ih_dq", _P), ("w_hh", _P), ("w_hh_dq", _P), ("bias", _P), ("bn_alpha", _P), ("bn_beta", _P),
+                ("h", _P * 2), ("c", _P), ("spikes", _P)]
+
+
+class FullbandHopDesc(ctypes.Structure):  # sfsn_fullband_hop_desc
+    _fields_ = [("layer", FullbandHopLayer * FULLBAND_HOP_MAX_LAYERS), ("n_layers", _I), ("Hp", _I), ("B", _I), ("F", _I), ("S", _I),
+                ("df", _I), ("hop", _I), ("D", _I), ("act", _I), ("unshared", _I), ("fdrc", _F), ("ln_eps", _F), ("w_ih0", _P),
+                ("ln_w", _P), ("ln_b", _P), ("w_p", _P), ("w_p_dq", _P), ("b_p", _P), ("inp_ri", _P), ("hist_ri", _P * 2),
+                ("enh_ri", _P), ("enh_mag", _P), ("z0", _P), ("clip_start", _P), ("scratch", _P), ("scratch_bytes", ctypes.c_size_t),
+                ("launch_index", ctypes.c_uint)]
+
+
 def _sources():
     """The files the library is made of, in the order the Makefile hashes them (SRCS)."""
     return [os.path.join(_HERE, "..", "include", "sfsn.h")] + [
-        os.path.join(CSRC, f) for f in ("sfsn_scan_dev.h", "sfsn_scan3_dev.h", "sfsn_scan3i_dev.h", "sfsn_scan3x_dev.h", "sfsn_scan3w_dev.h", "sfsn_scan3j_dev.h", "sfsn_scan3g_dev.h", "sfsn_feat_dev.h", "sfsn_fft_dev.h", "sfsn_host.h", "sfsn_kernels.hip", "sfsn_stack.hip", "sfsn_hop.hip", "sfsn_fft.hip", "sfsn_train.hip",
-                                  "sfsn_featproj.hip", "sfsn_projdf.hip", "sfsn_fullband.hip", "sfsn_fullband_train.hip", "sfsn_pack.cpp")]
+        os.path.join(CSRC, f) for f in ("sfsn_scan_dev.h", "sfsn_scan3_dev.h", "sfsn_scan3i_dev.h", "sfsn_scan3x_dev.h", "sfsn_scan3w_dev.h", "sfsn_scan3j_dev.h", "sfsn_scan3g_dev.h", "sfsn_feat_dev.h", "sfsn_fft_dev.h", "sfsn_hop_dev.h", "sfsn_fullband_dev.h", "sfsn_host.h", "sfsn_kernels.hip", "sfsn_stack.hip", "sfsn_hop.hip", "sfsn_fft.hip", "sfsn_train.hip",
+                                  "sfsn_featproj.hip", "sfsn_projdf.hip", "sfsn_fullband.hip", "sfsn_fullband_train.hip", "sfsn_fullband_hop.hip", "sfsn_pack.cpp")]
 
 
 def source_hash() -> str:
@@ -268,6 +284,12 @@ def lib() -> ctypes.CDLL:
     L.sfsn_fullband_deepfilter_fwd.argtypes = [_P, _P, _I, _I, _I, _I, _I, _P, _P]
     L.sfsn_fullband_deepfilter_bwd.restype = _I  # spec_ri, g_ri | B, F, T, S, df | d_coef, stream
     L.sfsn_fullband_deepfilter_bwd.argtypes = [_P, _P, _I, _I, _I, _I, _I, _P, _P]
+    L.sfsn_fullband_hop_check.restype = _I  # Hp, n_layers, F, S, df, B, hop, D, unshared (host only)
+    L.sfsn_fullband_hop_check.argtypes = [_I] * 9
+    L.sfsn_fullband_hop_scratch_bytes.restype = ctypes.c_size_t
+    L.sfsn_fullband_hop_scratch_bytes.argtypes = [ctypes.POINTER(FullbandHopDesc)]
+    L.sfsn_fullband_stream_hop.restype = _I
+    L.sfsn_fullband_stream_hop.argtypes = [ctypes.POINTER(FullbandHopDesc), _P]
     if L.sfsn_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH}: ABI version {L.sfsn_abi_version()} != {ABI_VERSION}; rebuild (make -C {CSRC})")
     _lib = L
@@ -283,7 +305,8 @@ EXPORTS = ("sfsn_abi_version", "sfsn_source_hash", "sfsn_strerror", "sfsn_device
            "sfsn_spike_proj_multi", "sfsn_input_proj_f32_multi", "sfsn_features_proj",
            "sfsn_scan_split_scratch_bytes", "sfsn_gsn_layer_scan_split", "sfsn_proj_deepfilter", "sfsn_gsn_stack_scan_x_w16",
            "sfsn_hop_spike_slots", "sfsn_spike_count_rows", "sfsn_fullband_features", "sfsn_fullband_input_proj",
-           "sfsn_fullband_proj_deepfilter", "sfsn_fullband_deepfilter_fwd", "sfsn_fullband_deepfilter_bwd")
+           "sfsn_fullband_proj_deepfilter", "sfsn_fullband_deepfilter_fwd", "sfsn_fullband_deepfilter_bwd",
+           "sfsn_fullband_hop_check", "sfsn_fullband_hop_scratch_bytes", "sfsn_fullband_stream_hop")
 
 
 def check(rc: int, what: str = "") -> None:

@@ -19,6 +19,7 @@
 
 #include "sfsn_feat_dev.h"
 #include "sfsn_scan_dev.h"
+#include "sfsn_fullband_dev.h"
 
 static inline bool fbd_aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; }
 
@@ -64,40 +65,20 @@ __global__ __launch_bounds__(256) void fullband_features_kernel(const float* __r
         lw[u] = in ? ln_w[j] : 0.0f;
         lb[u] = in ? ln_b[j] : 0.0f;
     }
-    const float inv_I = 1.0f / (float)F;
     for (int tt = wave; tt < FBF_TT; tt += 4) {
         const int t = tb + tt;
         if (t >= t1) break;  // wave-uniform
-        float v[NU];
-        bool have[NU];
-        float sum = 0.0f;
+        float v[NU], y[NU];
 #pragma unroll
         for (int u = 0; u < NU; ++u) {
             const int j = lane + 64 * u;
-            have[u] = j < F;
-            v[u] = have[u] ? magT[j * 33 + tt] : 0.0f;
-            sum += v[u];
+            v[u] = j < F ? magT[j * 33 + tt] : 0.0f;
         }
-        float y[NU];
-        if (ln_w) {  // feat_chunk_rows' LayerNorm, expression for expression
-            const float mean = wave_sum(sum) * inv_I;
-            float ss = 0.0f;
-#pragma unroll
-            for (int u = 0; u < NU; ++u) {
-                const float d = v[u] - mean;
-                if (have[u]) ss += d * d;
-            }
-            const float rstd = __builtin_amdgcn_rsqf(wave_sum(ss) * inv_I + eps);
-#pragma unroll
-            for (int u = 0; u < NU; ++u) y[u] = ((v[u] - mean) * rstd) * lw[u] + lb[u];
-        } else {
-#pragma unroll
-            for (int u = 0; u < NU; ++u) y[u] = v[u];
-        }
+        fullband_norm_row<NU>(v, lane, F, ln_w != nullptr, lw, lb, eps, y);
         float* out = x + ((size_t)t * B + b) * F;
 #pragma unroll
         for (int u = 0; u < NU; ++u)
-            if (have[u]) out[lane + 64 * u] = y[u];
+            if (lane + 64 * u < F) out[lane + 64 * u] = y[u];
     }
 }
 
@@ -209,13 +190,6 @@ struct FbdfParams {
     int t0, t1, ntile, items;
 };
 
-__device__ __forceinline__ float fbd_act(float v, int act) {
-    if (act == SFSN_ACT_TANH) return tanhf(v);
-    if (act == SFSN_ACT_SIGMOID) return 1.0f / (1.0f + expf(-v));
-    if (act == SFSN_ACT_RELU) return v < 0.0f ? 0.0f : v;
-    return v;
-}
-
 template <int KS>
 __global__ __launch_bounds__(256) void fullband_projdf_kernel(const FbdfParams p) {
     constexpr int KP = KS * 64;
@@ -267,7 +241,7 @@ __global__ __launch_bounds__(256) void fullband_projdf_kernel(const FbdfParams p
                 const v4f bv = p.bias ? *reinterpret_cast<const v4f*>(p.bias + ct * 16 + q * 4) : v4f{0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const float v = recombine3(a0[r], a1[r], a2[r]) * dqv[r] + bv[r];  // = sfsn_spike_proj's output
+                    const float v = fbd_coef(a0[r], a1[r], a2[r], dqv[r], bv[r]);  // = sfsn_spike_proj's output
                     if (p.proj && tv && fbase + r < F) p.proj[prow + (size_t)j * F + fbase + r] = v;
                     cf[c][r] = fbd_act(v, p.act);
                 }
@@ -278,9 +252,7 @@ __global__ __launch_bounds__(256) void fullband_projdf_kernel(const FbdfParams p
             for (int r = 0; r < 4; ++r) {
                 float2 xv = *reinterpret_cast<const float2*>(xrow[r] + (size_t)tsc * 2);
                 if (ts < 0) xv = make_float2(0.0f, 0.0f);
-                // the oracle's deepfilter_group: d ascending, no contraction (-ffp-contract=off)
-                yr[r] += xv.x * cf[0][r] - xv.y * cf[1][r];
-                yi[r] += xv.x * cf[1][r] + xv.y * cf[0][r];
+                fbd_tap(yr[r], yi[r], xv, cf[0][r], cf[1][r]);
             }
         }
         if (tv) {
@@ -290,8 +262,7 @@ __global__ __launch_bounds__(256) void fullband_projdf_kernel(const FbdfParams p
                 if (f >= F) continue;
                 const size_t o = (((size_t)b * S + s_) * F + f) * T + t;
                 *reinterpret_cast<float2*>(p.enh + 2 * o) = make_float2(yr[r], yi[r]);
-                // |.| as glibc's hypotf rounds it (the oracle's finish_spectrum): the double sum of squares, one correctly rounded sqrt
-                if (p.mag) p.mag[o] = (float)__builtin_sqrt((double)yr[r] * (double)yr[r] + (double)yi[r] * (double)yi[r]);
+                if (p.mag) p.mag[o] = fbd_mag(yr[r], yi[r]);
             }
         }
     }

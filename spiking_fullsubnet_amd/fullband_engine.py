@@ -199,20 +199,86 @@ class FullbandEngine:
         if ws is None:
             if len(self._ws) >= 4:
                 self._ws.clear()
-            dev, nl, Hp, G = self.device, self.spec.layers, self.Hp, self.G
-            f32 = dict(dtype=torch.float32, device=dev)
-            n_zin = nl if (not stack or Hp > 256) else 1
-            ws = dict(zin=[torch.empty((T, B, G * Hp), **f32) for _ in range(n_zin)],
-                      s8=[torch.zeros((T, B, self.HP8), dtype=torch.int8, device=dev) for _ in range(nl)])
-            if stack:
-                nbytes = self.lib.sfsn_stack_scratch_bytes(nl, 1, B)
-                ws["scratch"] = torch.zeros(((nbytes + 3) // 4,), dtype=torch.int32, device=dev)
-            self._ws[key] = ws
+            ws = self._ws[key] = self._make_workspace(B, T, T, stack)
+        return ws
+
+    def _make_workspace(self, B: int, nt: int, T: int, stack: bool) -> dict:
+        """Scratch of launches over `nt` frames of a [B, F, T] spectrum: input terms of the nt frames, int8 spikes of all T."""
+        dev, nl, Hp, G = self.device, self.spec.layers, self.Hp, self.G
+        f32 = dict(dtype=torch.float32, device=dev)
+        n_zin = nl if (not stack or Hp > 256) else 1
+        ws = dict(zin=[torch.empty((nt, B, G * Hp), **f32) for _ in range(n_zin)],
+                  s8=[torch.zeros((T, B, self.HP8), dtype=torch.int8, device=dev) for _ in range(nl)])
+        if stack:
+            nbytes = self.lib.sfsn_stack_scratch_bytes(nl, 1, B)
+            ws["scratch"] = torch.zeros(((nbytes + 3) // 4,), dtype=torch.int32, device=dev)
         return ws
 
     def check_stack_errors(self) -> None:
         """Raise if a hand-off wait of an earlier stack launch expired (synchronises)."""
         self._errors.check()
+
+    def _launch_frames(self, ri, B: int, T: int, t0: int, nt: int, stack: bool, ws: dict, x, states, spk, proj, enh, mag) -> None:
+        """The launch sequence of the model on frames [t0, t0 + nt) of the spectrum ri [B, F, T, 2], on torch's current stream:
+        features -> layer 0's input term -> the GSN layers from `states` (updated in place) -> projection + deep filter.
+        forward_stft runs it on (0, T) from zero states; a streaming session (fullband_streaming.py) on the `hop` new frames behind
+        its history, with the states carried.  x [T, B, F], spk[l] [T, B, Hp] or None, proj [T, B, P] or None, enh [B, S, F, T, 2],
+        mag [B, S, F, T] or None are whole-spectrum buffers; ws = _make_workspace(B, nt, T, stack)."""
+        spec, L, Hp, G, F = self.spec, self.lib, self.Hp, self.G, self.F
+        st, dev, nl, S = self._stream(), self.device, spec.layers, spec.num_spks
+        check(L.sfsn_fullband_features(_ptr(ri), B, F, T, spec.fdrc, _ptr(self.ln_w), _ptr(self.ln_b), 1e-5, _ptr(x), t0, nt, st),
+              "sfsn_fullband_features")
+        self._count("features")
+        # layer 0's input term
+        z0, l0 = ws["zin"][0], self.layers[0]
+        x_at = ctypes.c_void_p(x.data_ptr() + t0 * B * F * 4)
+        for g in range(G):
+            args = (x_at, ctypes.c_void_p(l0.w_ih_f32.data_ptr() + g * Hp * F * 4), ctypes.c_void_p(l0.bias.data_ptr() + g * Hp * 4),
+                    ctypes.c_void_p(z0.data_ptr() + g * Hp * 4), nt * B, F, Hp, G * Hp, st)
+            rc = L.sfsn_input_proj_f32(*args)
+            if rc == _lib.SFSN_EUNSUPPORTED:  # K = F > 192 (every n_fft = 512 model): the full-band library's own product
+                check(L.sfsn_fullband_input_proj(*args), "sfsn_fullband_input_proj")
+                self._count("inproj_wide")
+            else:
+                check(rc, "sfsn_input_proj_f32")
+                self._count("inproj")
+        s8_at = t0 * B * self.HP8  # frame t0 of an int8 spike buffer
+        if stack:
+            segs = (ScanSegment * nl)()
+            fin = (FusedInput * nl)()
+            for l in range(nl):
+                # layers >= 1 with Hp > 256: the launch's input-term workgroups write their [nt][B][Hp] buffer; Hp <= 256: in-scan
+                zin = ws["zin"][0] if l == 0 else (ws["zin"][l] if Hp > 256 else None)
+                fill_segment(segs[l], self.layers[l], B, Hp, t0, zin, states[l], ws["s8"][l], spk[l])
+                if l > 0:
+                    pk, dq = self.layers[l].w_ih_q[0]
+                    fin[l].spikes_in, fin[l].w_ih, fin[l].w_ih_dq = ws["s8"][l - 1].data_ptr() + s8_at, pk.data_ptr(), dq.data_ptr()
+            rp = 4 if Hp > 256 else 8
+            rpw = (ctypes.c_int * nl)(*([rp] * nl))
+            scratch = ws["scratch"]
+            check(L.sfsn_gsn_stack_scan(segs, fin, nl, 1, nt, Hp, rpw, self.stack_lag, _ptr(scratch), scratch.numel() * 4, st),
+                  "sfsn_gsn_stack_scan")
+            self._count("stack")
+            if not torch.cuda.is_current_stream_capturing():  # the launch's error word, looked at without blocking next time
+                self._errors.watch(torch.cuda.current_stream(dev), scratch, f"full-band stack rows={B} frames={nt} rows_per_wg={rp}")
+        else:
+            for l in range(nl):
+                zin = ws["zin"][l]
+                if l > 0:
+                    for g in range(G):
+                        pk, dq = self.layers[l].w_ih_q[g]
+                        check(L.sfsn_spike_proj(ctypes.c_void_p(ws["s8"][l - 1].data_ptr() + s8_at), _ptr(pk), _ptr(dq),
+                                                ctypes.c_void_p(self.layers[l].bias.data_ptr() + g * Hp * 4),
+                                                ctypes.c_void_p(zin.data_ptr() + g * Hp * 4), nt * B, Hp, Hp, G * Hp, st), "sfsn_spike_proj")
+                        self._count("spike_proj")
+                seg = (ScanSegment * 1)()
+                fill_segment(seg[0], self.layers[l], B, Hp, t0, zin, states[l], ws["s8"][l], spk[l])
+                check(L.sfsn_gsn_layer_scan(seg, 1, nt, Hp, int(spec.shared), 0, st), "sfsn_gsn_layer_scan")
+                self._count("layer_scan")
+        check(L.sfsn_fullband_proj_deepfilter(_ptr(ri), _ptr(ws["s8"][-1]), Hp, _ptr(self.proj_q), _ptr(self.proj_dq), _ptr(self.proj_b),
+                                              spec.act, B, F, T, S, spec.df, _ptr(proj), _ptr(enh), _ptr(mag), t0, nt, st),
+              "sfsn_fullband_proj_deepfilter")
+        self._count("projdf")
 
     @torch.no_grad()
     def forward_stft(self, noisy_cmp: torch.Tensor, want_layers: bool = False) -> dict:
@@ -230,63 +296,13 @@ class FullbandEngine:
         stack = self._use_stack(B)
         ws = self._workspace(B, T, stack)
         x = torch.empty((T, B, F), **f32)
-        check(L.sfsn_fullband_features(_ptr(ri), B, F, T, spec.fdrc, _ptr(self.ln_w), _ptr(self.ln_b), 1e-5, _ptr(x), 0, T, st),
-              "sfsn_fullband_features")
-        self._count("features")
-        # layer 0's input term
-        z0, l0 = ws["zin"][0], self.layers[0]
-        for g in range(G):
-            args = (_ptr(x), ctypes.c_void_p(l0.w_ih_f32.data_ptr() + g * Hp * F * 4), ctypes.c_void_p(l0.bias.data_ptr() + g * Hp * 4),
-                    ctypes.c_void_p(z0.data_ptr() + g * Hp * 4), T * B, F, Hp, G * Hp, st)
-            rc = L.sfsn_input_proj_f32(*args)
-            if rc == _lib.SFSN_EUNSUPPORTED:  # K = F > 192 (every n_fft = 512 model): the full-band library's own product
-                check(L.sfsn_fullband_input_proj(*args), "sfsn_fullband_input_proj")
-                self._count("inproj_wide")
-            else:
-                check(rc, "sfsn_input_proj_f32")
-                self._count("inproj")
         flat = torch.zeros((nl, 2, B, Hp), **f32)  # zero initial state (modeling_cirm_gsn.py:95-101)
         states = [(flat[l, 0], flat[l, 1]) for l in range(nl)]
         spk = [torch.empty((T, B, Hp), **f32) if want_layers else None for _ in range(nl)]
-        if stack:
-            segs = (ScanSegment * nl)()
-            fin = (FusedInput * nl)()
-            for l in range(nl):
-                # layers >= 1 with Hp > 256: the launch's input-term workgroups write their [T][B][Hp] buffer; Hp <= 256: in-scan
-                zin = ws["zin"][0] if l == 0 else (ws["zin"][l] if Hp > 256 else None)
-                fill_segment(segs[l], self.layers[l], B, Hp, 0, zin, states[l], ws["s8"][l], spk[l])
-                if l > 0:
-                    pk, dq = self.layers[l].w_ih_q[0]
-                    fin[l].spikes_in, fin[l].w_ih, fin[l].w_ih_dq = ws["s8"][l - 1].data_ptr(), pk.data_ptr(), dq.data_ptr()
-            rp = 4 if Hp > 256 else 8
-            rpw = (ctypes.c_int * nl)(*([rp] * nl))
-            scratch = ws["scratch"]
-            check(L.sfsn_gsn_stack_scan(segs, fin, nl, 1, T, Hp, rpw, self.stack_lag, _ptr(scratch), scratch.numel() * 4, st),
-                  "sfsn_gsn_stack_scan")
-            self._count("stack")
-            if not torch.cuda.is_current_stream_capturing():  # the launch's error word, looked at without blocking next time
-                self._errors.watch(torch.cuda.current_stream(dev), scratch, f"full-band stack rows={B} frames={T} rows_per_wg={rp}")
-        else:
-            for l in range(nl):
-                zin = ws["zin"][l]
-                if l > 0:
-                    for g in range(G):
-                        pk, dq = self.layers[l].w_ih_q[g]
-                        check(L.sfsn_spike_proj(_ptr(ws["s8"][l - 1]), _ptr(pk), _ptr(dq),
-                                                ctypes.c_void_p(self.layers[l].bias.data_ptr() + g * Hp * 4),
-                                                ctypes.c_void_p(zin.data_ptr() + g * Hp * 4), T * B, Hp, Hp, G * Hp, st), "sfsn_spike_proj")
-                        self._count("spike_proj")
-                seg = (ScanSegment * 1)()
-                fill_segment(seg[0], self.layers[l], B, Hp, 0, zin, states[l], ws["s8"][l], spk[l])
-                check(L.sfsn_gsn_layer_scan(seg, 1, T, Hp, int(spec.shared), 0, st), "sfsn_gsn_layer_scan")
-                self._count("layer_scan")
         enh = torch.empty((B, S, F, T, 2), **f32)
         mag = torch.empty((B, S, F, T), **f32) if S == 1 else None
         proj = torch.empty((T, B, spec.P), **f32) if want_layers else None
-        check(L.sfsn_fullband_proj_deepfilter(_ptr(ri), _ptr(ws["s8"][-1]), Hp, _ptr(self.proj_q), _ptr(self.proj_dq), _ptr(self.proj_b),
-                                              spec.act, B, F, T, S, spec.df, _ptr(proj), _ptr(enh), _ptr(mag), 0, T, st),
-              "sfsn_fullband_proj_deepfilter")
-        self._count("projdf")
+        self._launch_frames(ri, B, T, 0, T, stack, ws, x, states, spk, proj, enh, mag)
         out = dict(enh_stft=torch.view_as_complex(enh), enh_mag=mag, all_layers=None)
         if want_layers:
             out["all_layers"] = [x] + [s[:, :, :self.H] for s in spk] + [proj]

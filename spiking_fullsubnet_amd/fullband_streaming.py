@@ -1,0 +1,302 @@
+"""Frame-by-frame (streaming) execution of the cIRM-GSN model (``modeling_cirm_gsn.Model``).
+
+The model is causal after the STFT: the features of a frame (``|X|^fdrc``, a LayerNorm over the bins of that frame) need the frame
+only, the GSN cells carry ``(h, c)``, and the deep filter reaches back ``df - 1`` frames of the noisy spectrum with zeros before
+frame 0.  A session keeps, on the device, the ``(h, c)`` of every layer at the padded size ``Hp = ceil16(H)`` and ``df - 1`` frames
+of input history; every ``step`` computes ``hop`` new frames.  Outputs are bit-identical to ``FullbandEngine.forward_stft`` on the
+concatenated input (tests/test_cirm_streaming.py).
+
+Two ways to run a hop:
+
+* the per-kernel sequence (``one_launch=False``): exactly the launches of ``FullbandEngine.forward_stft``
+  (``FullbandEngine._launch_frames``) restricted to the ``hop`` new frames behind the history, behind one history-shift launch;
+  captured once into a HIP graph when ``graph=True``.  Covers every GSN configuration the engine covers.
+* ``sfsn_fullband_stream_hop`` (``one_launch=True``; csrc/sfsn_fullband_hop.hip): the whole hop in ONE launch.  Covers shared gate
+  weights, ``Hp <= 320``, up to 4 layers, ``193 <= F <= 320``, ``S <= 2``, ``df <= 5``, ``df - 1 + hop <= 32``, ``B <= 16``
+  (include/sfsn.h); outside that ``one_launch=True`` raises ``NotImplementedError`` and ``"auto"`` takes the per-kernel sequence.
+
+``one_launch="auto"`` picks the tier ``AUTO_ONE_LAUNCH`` names where the hop kernel covers the session (profiles/cirm_streaming.md
+has the measurement behind the setting).
+
+Per-clip utterances: ``reset(clips=[...])`` restarts some clips of a batched session while the others go on bit for bit.  The
+one-launch hop gives every clip its own origin (the launch at which its utterance began) and reads a restarted clip's state and
+history as zero in that launch; the per-kernel sequence zeroes the clips' rows with stream-ordered fills.  Neither synchronises.
+
+Not covered here (follow-ups): ``waveform``, ``host_io``, ``resident`` and ``count_spikes`` sessions, and LSTM models.
+"""
+from __future__ import annotations
+
+import ctypes
+import weakref
+from typing import Dict, Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import FullbandHopDesc, check
+from .engine import _ptr
+from .fullband_engine import FullbandEngine
+
+# what one_launch="auto" takes where sfsn_fullband_stream_hop covers the session: the tier that measured faster at the recipe
+# geometry, B = 1, hop = 1 (profiles/cirm_streaming.md)
+AUTO_ONE_LAUNCH = True
+
+
+def hop_covers(engine: FullbandEngine, batch: int, hop: int) -> bool:
+    """sfsn_fullband_stream_hop's coverage of a session of this engine (the library's host-only check; 16-bit weights are the
+    engine's own mode and use the same digit images)."""
+    spec = engine.spec
+    rc = engine.lib.sfsn_fullband_hop_check(engine.Hp, spec.layers, engine.F, spec.num_spks, spec.df, batch, hop, spec.df - 1,
+                                            0 if spec.shared else 1)
+    if rc == _lib.SFSN_EUNSUPPORTED:
+        return False
+    check(rc, "sfsn_fullband_hop_check")
+    return True
+
+
+class FullbandStreamingSession:
+    """``step(frames [B, F, hop] complex64) -> (enh_stft [B, S, F, hop], enh_mag [B, S, F, hop] or None when S > 1)``."""
+
+    def __init__(self, engine: FullbandEngine, batch: int = 1, hop: int = 1, graph: bool = True, one_launch="auto", owner=None):
+        if batch < 1 or hop < 1:
+            raise ValueError("batch and hop must be positive")
+        if one_launch not in ("auto", True, False):
+            raise ValueError("one_launch must be 'auto', True or False")
+        spec = engine.spec
+        self.eng, self.B, self.hop = engine, batch, hop
+        self._owner = weakref.ref(owner) if owner is not None else None
+        dev = self.dev = engine.device
+        self.F, self.S = engine.F, spec.num_spks
+        self.D = D = spec.df - 1  # frames of input history the deep filter reaches back
+        self.Th = D + hop
+        self.launches: Dict[str, int] = {}
+        self.frames_done = 0
+        self._clip_f0 = np.zeros(batch, dtype=np.int64)
+        self._graph: Optional[torch.cuda.CUDAGraph] = None
+        self._hop = None
+        covered = hop_covers(engine, batch, hop)
+        if one_launch is True and not covered:
+            raise NotImplementedError(
+                f"sfsn_fullband_stream_hop does not cover this session (shared={spec.shared}, Hp={engine.Hp}, layers={spec.layers}, "
+                f"F={engine.F}, S={spec.num_spks}, df={spec.df}, B={batch}, hop={hop}; coverage: include/sfsn.h) -- use "
+                "one_launch='auto' or False for the per-kernel sequence")
+        self.one_launch = covered and (AUTO_ONE_LAUNCH if one_launch == "auto" else bool(one_launch))
+        self.inp = torch.zeros((batch, self.F, hop), dtype=torch.complex64, device=dev)
+        with torch.cuda.device(dev):
+            if self.one_launch:
+                self._build_hop()
+            else:
+                self._build_sequence()
+                if graph:
+                    self._capture()
+
+    def _count(self, what: str) -> None:
+        self.launches[what] = self.launches.get(what, 0) + 1
+
+    # ---- the one-launch hop ---------------------------------------------------------------------------------------------------------
+    def _build_hop(self) -> None:
+        eng, spec, dev = self.eng, self.eng.spec, self.dev
+        B, F, S, hop, D, Hp, HP8, nl = self.B, self.F, self.S, self.hop, self.D, eng.Hp, eng.HP8, spec.layers
+        f32 = dict(dtype=torch.float32, device=dev)
+        i8 = dict(dtype=torch.int8, device=dev)
+        # carried state (zero = the start of an utterance) and the launch's tagged work buffers
+        st = dict(h=[torch.zeros((2, B, HP8), **i8) for _ in range(nl)], c=[torch.zeros((B, Hp), **f32) for _ in range(nl)],
+                  hist=torch.zeros((2, B, F, max(D, 1), 2), **f32))
+        work = dict(spikes=[torch.zeros((hop, B, HP8), **i8) for _ in range(nl)], z0=torch.zeros((hop, B, Hp, 2), **f32))
+        enh = torch.zeros((B, S, F, hop, 2), **f32)
+        mag = torch.zeros((B, S, F, hop), **f32) if S == 1 else None
+        origin = torch.zeros((B,), dtype=torch.int32, device=dev)  # the launch index of every clip's frame 0
+        d = FullbandHopDesc()
+        for l, layer in enumerate(eng.layers):
+            o = d.layer[l]
+            if l > 0:
+                o.w_ih, o.w_ih_dq = layer.w_ih_q[0][0].data_ptr(), layer.w_ih_q[0][1].data_ptr()
+            o.w_hh, o.w_hh_dq, o.bias = layer.w_hh_q.data_ptr(), layer.w_hh_dq.data_ptr(), layer.bias.data_ptr()
+            o.bn_alpha, o.bn_beta = layer.alpha.data_ptr(), layer.beta.data_ptr()
+            o.h[0], o.h[1], o.c, o.spikes = st["h"][l][0].data_ptr(), st["h"][l][1].data_ptr(), st["c"][l].data_ptr(), work["spikes"][l].data_ptr()
+        d.n_layers, d.Hp, d.B, d.F, d.S, d.df, d.hop, d.D, d.act, d.unshared = nl, Hp, B, F, S, spec.df, hop, D, spec.act, 0
+        d.fdrc, d.ln_eps = spec.fdrc, 1e-5
+        d.w_ih0 = eng.layers[0].w_ih_f32.data_ptr()
+        if eng.ln_w is not None:
+            d.ln_w, d.ln_b = eng.ln_w.data_ptr(), eng.ln_b.data_ptr()
+        d.w_p, d.w_p_dq, d.b_p = eng.proj_q.data_ptr(), eng.proj_dq.data_ptr(), eng.proj_b.data_ptr()
+        d.inp_ri = self.inp.data_ptr()
+        d.hist_ri[0], d.hist_ri[1] = st["hist"][0].data_ptr(), st["hist"][1].data_ptr()
+        d.enh_ri, d.enh_mag, d.z0 = enh.data_ptr(), (mag.data_ptr() if mag is not None else None), work["z0"].data_ptr()
+        d.clip_start = origin.data_ptr()
+        nbytes = eng.lib.sfsn_fullband_hop_scratch_bytes(ctypes.byref(d))
+        assert nbytes, "sfsn_fullband_hop_check accepted this geometry"
+        scratch = torch.zeros((nbytes // 4,), dtype=torch.int32, device=dev)  # word 0: the error word
+        d.scratch, d.scratch_bytes, d.launch_index = scratch.data_ptr(), nbytes, 0
+        self._hop = dict(desc=d, ref=ctypes.byref(d), st=st, work=work, enh=torch.view_as_complex(enh), mag=mag, origin=origin,
+                         scratch=scratch, err=torch.zeros((1,), dtype=torch.int32).pin_memory(), err_pending=False)
+
+    def _launch_hop(self, frames: torch.Tensor) -> None:
+        h = self._hop
+        if h["err_pending"] and int(h["err"][0]) != 0:  # written behind an earlier launch; no blocking here
+            self.check_errors()
+        d = h["desc"]
+        d.inp_ri = frames.data_ptr()
+        with torch.cuda.device(self.dev):  # the C ABI launches on the calling thread's current device
+            rc = self.eng.lib.sfsn_fullband_stream_hop(h["ref"], ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream))
+        if rc:
+            check(rc, "sfsn_fullband_stream_hop")
+        d.launch_index = (d.launch_index + 1) & 0xFFFFFFFF
+        self._count("hop")
+        if (self.frames_done + self.hop) % 256 < self.hop:  # every ~256 frames the error word follows the launches into pinned memory
+            h["err"].copy_(h["scratch"][:1], non_blocking=True)
+            h["err_pending"] = True
+
+    # ---- the per-kernel sequence ----------------------------------------------------------------------------------------------------
+    def _build_sequence(self) -> None:
+        eng, spec, dev = self.eng, self.eng.spec, self.dev
+        B, F, S, Th, Hp, nl = self.B, self.F, self.S, self.Th, eng.Hp, spec.layers
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.hist = torch.zeros((B, F, Th), dtype=torch.complex64, device=dev)
+        self._tmp = torch.zeros((B, F, max(self.D, 1)), dtype=torch.complex64, device=dev)
+        self._stack = eng._use_stack(B)
+        self._ws = eng._make_workspace(B, self.hop, Th, self._stack)
+        self._x = torch.empty((Th, B, F), **f32)
+        self._flat = torch.zeros((nl, 2, B, Hp), **f32)
+        self._states = [(self._flat[l, 0], self._flat[l, 1]) for l in range(nl)]
+        self.enh = torch.zeros((B, S, F, Th), dtype=torch.complex64, device=dev)
+        self.enh_mag = torch.zeros((B, S, F, Th), **f32) if S == 1 else None
+
+    def _enqueue(self) -> None:
+        """One hop on torch's current stream: the history shift, then the offline forward's launches on frames [D, D + hop)."""
+        eng, B, F, D, hop = self.eng, self.B, self.F, self.D, self.hop
+        with torch.cuda.device(self.dev):
+            ri = torch.view_as_real(self.hist)
+            if D + hop <= 16:  # history shift + append in one launch
+                st = ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+                check(eng.lib.sfsn_hist_shift(_ptr(ri), _ptr(torch.view_as_real(self.inp)), B * F, D, hop, st), "sfsn_hist_shift")
+            else:
+                if D > 0:
+                    self._tmp[:, :, :D].copy_(self.hist[:, :, hop:hop + D])
+                    self.hist[:, :, :D].copy_(self._tmp[:, :, :D])
+                self.hist[:, :, D:].copy_(self.inp)
+            before = dict(eng.launches)
+            eng._launch_frames(ri, B, self.Th, D, hop, self._stack, self._ws, self._x, self._states, [None] * len(self._states), None,
+                               torch.view_as_real(self.enh), self.enh_mag)
+            self._last = {k: v - before.get(k, 0) for k, v in eng.launches.items() if v != before.get(k, 0)}
+
+    def _capture(self) -> None:
+        side = torch.cuda.Stream(device=self.dev)
+        side.wait_stream(torch.cuda.current_stream(self.dev))
+        with torch.cuda.stream(side):
+            for _ in range(2):  # module loading, function attributes and allocator warm-up happen outside the capture
+                self._enqueue()
+        torch.cuda.current_stream(self.dev).wait_stream(side)
+        torch.cuda.synchronize(self.dev)
+        self.eng._errors.poll(block=True)  # (the warm-up launches' error words)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self._enqueue()
+        self._graph = g
+        self.reset()
+
+    # ---- the session ----------------------------------------------------------------------------------------------------------------
+    def step(self, frames: torch.Tensor, copy: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """``frames``: complex64 [B, F, hop] on the device.  Returns the enhanced frames and (one speaker) their magnitudes; with
+        ``copy=False`` the returned tensors are views of the session's buffers, valid until the next ``step``.  The one-launch hop
+        reads ``frames`` in place, in stream order: do not overwrite it before the stream has passed this step."""
+        if frames.device != self.dev or frames.dtype != torch.complex64 or tuple(frames.shape) != (self.B, self.F, self.hop):
+            raise RuntimeError(f"expected complex64 {(self.B, self.F, self.hop)} on {self.dev}, got {frames.dtype} {tuple(frames.shape)} "
+                               f"on {frames.device}")
+        if self._hop is not None:
+            if not (frames.is_contiguous() and frames.data_ptr() % 8 == 0):
+                self.inp.copy_(frames)
+                frames = self.inp
+            self._launch_hop(frames)  # read in place: no staging copy in front
+            e, m = self._hop["enh"], self._hop["mag"]
+        else:
+            self.inp.copy_(frames)
+            if self._graph is not None:
+                self._graph.replay()
+            else:
+                self.eng._errors.poll()  # the eager launches' error words, looked at without blocking
+                self._enqueue()
+            for k, v in self._last.items():
+                self.launches[k] = self.launches.get(k, 0) + v
+            e, m = self.enh[..., self.D:], (self.enh_mag[..., self.D:] if self.enh_mag is not None else None)
+        self.frames_done += self.hop
+        if copy:
+            return e.clone(), (m.clone() if m is not None else None)
+        return e, m
+
+    def reset(self, clips=None) -> None:
+        """Back to the start of an utterance: zero (h, c) and zero history.  ``clips`` (a sequence or 1-D tensor of clip indices): only
+        these clips restart, at their next step; the others go on as if nothing happened.  Ordered with the steps on torch's current
+        stream, no synchronisation.  ``clips=None``: the whole session (also checks the error word and that the module's parameters
+        have not changed since the session packed them)."""
+        if clips is not None:
+            self._reset_clips(clips)
+            return
+        owner = self._owner() if self._owner is not None else None
+        if owner is not None and owner.engine() is not self.eng:
+            raise RuntimeError("the module's parameters (or device) changed after this streaming session was created: its packed "
+                               "weights are stale -- create a new session with module.streaming(...)")
+        if self._hop is not None:
+            self.check_errors()
+            h = self._hop
+            for t in h["st"]["h"] + h["st"]["c"] + [h["st"]["hist"]]:
+                t.zero_()
+            h["origin"].fill_(self._as_i32(h["desc"].launch_index))  # every clip's frame 0 is the next launch
+        else:
+            self._flat.zero_()
+            self.hist.zero_()
+        self.frames_done = 0
+        self._clip_f0[:] = 0
+
+    @staticmethod
+    def _as_i32(v: int) -> int:  # a launch index (uint32) as the int32 a fill writes
+        v &= 0xFFFFFFFF
+        return v - (1 << 32) if v >= 1 << 31 else v
+
+    def _reset_clips(self, clips) -> None:
+        if isinstance(clips, (torch.Tensor, np.ndarray)) and clips.ndim != 1:
+            raise TypeError("clips: a 1-D tensor or a sequence of clip indices")
+        items = clips.tolist() if isinstance(clips, (torch.Tensor, np.ndarray)) else list(clips)
+        if any(isinstance(i, bool) or not isinstance(i, (int, np.integer)) for i in items):
+            raise TypeError("clips: integer clip indices")
+        idx = sorted(set(int(i) for i in items))
+        bad = [i for i in idx if not 0 <= i < self.B]
+        if bad:
+            raise IndexError(f"clip index {bad[0]} out of range for a session of {self.B} clips")
+        if not idx:
+            return
+        self._clip_f0[idx] = self.frames_done
+        if self._hop is not None:  # (a fill behind the queued launches: none of them sees the new origin)
+            org = self._as_i32(self._hop["desc"].launch_index)
+            for b in idx:
+                self._hop["origin"][b:b + 1].fill_(org)
+            return
+        for b in idx:  # the per-kernel sequence: the clips' rows of the states and their history, in stream order
+            self._flat[:, :, b].zero_()
+            self.hist[b].zero_()
+
+    def clip_frames(self) -> np.ndarray:
+        """int64 [B]: the frames each clip has seen since its own utterance began."""
+        return self.frames_done - self._clip_f0
+
+    def check_errors(self) -> None:
+        """Raise if a bounded hand-off wait expired inside an earlier launch (blocks until the steps enqueued so far have finished)."""
+        torch.cuda.current_stream(self.dev).synchronize()
+        if self._hop is not None:
+            h = self._hop
+            if int(h["scratch"][0].item()) != 0:
+                h["scratch"][:1].zero_()  # sticky on the device: cleared when reported
+                h["err"].zero_()
+                h["err_pending"] = False
+                torch.cuda.current_stream(self.dev).synchronize()
+                raise RuntimeError("sfsn_fullband_stream_hop: a bounded hand-off wait expired inside a launch (results invalid)")
+            return
+        self.eng._errors.poll(block=True)
+        sc = self._ws.get("scratch")
+        if sc is not None and int(sc[0].item()) != 0:  # (graph replays are not watched launch by launch)
+            self.eng._errors.clear([sc])
+            raise RuntimeError("sfsn_gsn_stack_scan: a layer-to-layer hand-off wait expired inside a streaming step (results invalid)")
+
+    def close(self) -> None:
+        """Nothing keeps running between steps; kept for the shape of StreamingSession."""

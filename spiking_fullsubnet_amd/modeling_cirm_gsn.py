@@ -9,7 +9,8 @@ return values (:206-245).  A recipe switches over by changing only
     path = "spiking_fullsubnet_amd.modeling_cirm_gsn.Model"
 
 In ``eval()`` mode a GSN model runs everything between ``stft`` and ``istft`` on the gfx950 kernels through ``FullbandEngine``; an
-LSTM model runs its sequence model on ATen (``training.sequence_model``) and the deep filter as torch operations.
+LSTM model runs its sequence model on ATen (``training.sequence_model``) and the deep filter as torch operations.  ``streaming()``
+opens a frame-by-frame session of a GSN model (``fullband_streaming.py``).
 
 In ``train()`` mode -- or in ``eval()`` mode with grad enabled and an input that requires grad (or ``autograd_in_eval = True``) --
 ``forward()`` takes the differentiable path ``training.forward_cirm``: the GSN stack on the one-launch training layer calls of
@@ -62,8 +63,26 @@ class Model(_EngineMixin, nn.Module):
     def _kernel_path(self) -> bool:
         return True  # (eval mode without gradients: the engine for GSN, _forward_lstm for LSTM -- both below)
 
-    def streaming(self, *args, **kwargs):
-        raise NotImplementedError("cIRM-GSN has no streaming session: the one-launch hop covers the Spiking-FullSubNet models only")
+    def streaming(self, batch: int = 1, hop: int = 1, graph: bool = True, one_launch="auto", waveform: bool = False,
+                  host_io: bool = False, resident: bool = False, count_spikes: bool = False):
+        """Frame-by-frame session (``fullband_streaming.FullbandStreamingSession``): ``step(frames [B, F, hop])`` with the GSN states
+        and ``df_order - 1`` frames of history kept on the device, bit-identical to the offline forward on the concatenated input.
+        ``one_launch``: True = the whole hop in one ``sfsn_fullband_stream_hop`` launch (``NotImplementedError`` where it does not cover
+        the model), False = the offline kernels on the new frames (from a HIP graph when ``graph``), "auto" = the faster one that
+        applies.  GSN models on a HIP device, spectra in and out."""
+        if self.fb_model.sequence_model_name == "LSTM":
+            raise NotImplementedError("cIRM-GSN streaming covers the GSN sequence model: an LSTM model runs on ATen and has no session")
+        for name, on in (("waveform", waveform), ("host_io", host_io), ("resident", resident), ("count_spikes", count_spikes)):
+            if on:
+                raise NotImplementedError(f"cIRM-GSN streaming: {name}=True is not built yet (a follow-up; the Spiking-FullSubNet "
+                                          "sessions have it) -- sessions take and return spectra")
+        self._check_mode()
+        if batch < 1 or hop < 1:
+            raise ValueError("batch and hop must be positive")
+        if next(self.parameters()).device.type != "cuda":
+            raise NotImplementedError("cIRM-GSN streaming has no CPU path: move the module to a HIP device (`.to('cuda')`) first")
+        from .fullband_streaming import FullbandStreamingSession
+        return FullbandStreamingSession(self.engine(), batch=batch, hop=hop, graph=graph, one_launch=one_launch, owner=self)
 
     def forward(self, input):
         assert input.ndim == 2, f"Input tensor must be 2D, but got {input.ndim}D."
