@@ -774,6 +774,49 @@ int sfsn_fullband_hop_check(int Hp, int n_layers, int F, int S, int df, int B, i
 size_t sfsn_fullband_hop_scratch_bytes(const sfsn_fullband_hop_desc* desc); /* 0: not covered (host only) */
 int sfsn_fullband_stream_hop(const sfsn_fullband_hop_desc* desc, void* stream);
 
+/* ----------------------------------------------------------------------------------------------------
+ * Waveform mode of the cIRM-GSN hop: 128 new samples per clip in, 128 enhanced samples per clip and speaker out, in ONE launch -- the
+ * new frame's STFT (one workgroup in front of the input stage, a wave per clip), the hop above, and the inverse STFT with its
+ * overlap-add state (ceil(B S / 8) workgroups behind the projection stage, a wave per (clip, speaker)).  The transforms are those of
+ * sfsn_stft / sfsn_istft and of sfsn_hop_desc's waveform mode (csrc/sfsn_hop_wave_dev.h: one body): torch.stft(center=True,
+ * pad_mode="constant") framing, torch.istft's overlap-add and envelope, bit-identical to the offline kernels.
+ *
+ * Coverage (sfsn_fullband_wave_hop_check, host only, no device needed): what sfsn_fullband_hop_check returns at hop = 1, D = df - 1,
+ * and SFSN_EUNSUPPORTED unless F == 257 (512-point frames with hop 128 are what csrc/sfsn_fft_dev.h implements).
+ *
+ * The descriptor embeds the hop's: hop.hop == 1, hop.D == hop.df - 1 (SFSN_EINVAL otherwise); hop.inp_ri is ignored; hop.enh_ri and
+ * hop.enh_mag are nullable (written when set); hop.clip_start is REQUIRED -- the frame index of every clip comes from it.  With
+ * k = (int)(hop.launch_index - hop.clip_start[b]) (unsigned difference, wrap-safe):
+ *     k == -1   the clip's first call, no frame yet: its old wave_state reads as zero and the launch leaves [0 x 384 | the new samples]
+ *               in it; whatever the model stages write for the clip is discarded by the next launch
+ *     k ==  0   the clip's frame 0: h, c, the history and ola_state read as zero; wave_state is loaded
+ *     k  <  2   wave_out of clip b is zero
+ *     k >=  2   wave_out holds the padded positions [128 k, 128 k + 128): call c of an utterance returns the samples that entered
+ *               with call c - 3
+ * So a session starts with clip_start[b] = launch_index + 1, and restarts a clip by writing (stream-ordered) the index of the launch
+ * after the next one.  Every granule of spec_g and enh_g is written by every launch for every clip, whatever its k.
+ * NULL or misaligned (8 bytes; done: 4) required pointers: SFSN_EINVAL.  Scratch and the error word: as for sfsn_fullband_stream_hop
+ * (sfsn_fullband_hop_scratch_bytes(&desc->hop)).  The launch is refused (SFSN_EUNSUPPORTED) unless all its workgroups -- at most
+ * 1 + 4 more than the spectrum hop's -- can be resident.
+ * (Added without an ABI bump: no existing struct or signature changed.)
+ * ---------------------------------------------------------------------------------------------------- */
+typedef struct {
+    sfsn_fullband_hop_desc hop;
+    const float* wave_in; /* [B][128] the new samples                                                         */
+    float* wave_state;    /* [B][512] the last 512 input samples, in/out                                       */
+    float* ola_state;     /* [B][S][512] overlap-add accumulator of the output, in/out                         */
+    float* wave_out;      /* [B][S][128] out                                                                   */
+    const float* window;  /* [512] analysis / synthesis window (the reference: hann)                           */
+    float* spec_g;        /* [B][F][4] scratch ({re, tag, im, tag} granules of the noisy frame), zeroed once     */
+    float* enh_g;         /* [B][S][F][4] scratch (granules of the enhanced frame), zeroed once                 */
+    unsigned* done;       /* nullable, [B][S]: word (b, s) is set to launch_index + 1 (system-scope release) once wave_out (b, s)
+                             has been written.  wave_in, wave_out and done may be pinned host memory the device can reach: the
+                             caller spins on the words instead of synchronising the stream                       */
+} sfsn_fullband_wave_desc;
+
+int sfsn_fullband_wave_hop_check(int Hp, int n_layers, int F, int S, int df, int B, int unshared);
+int sfsn_fullband_stream_hop_wave(const sfsn_fullband_wave_desc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
 """cIRM-GSN streaming latency per hop (modeling_cirm_gsn.Model.streaming at the recipe's geometry: H = 268, 4 layers, F = 257, df 3,
-BatchNorm, LayerNorm, shared gates), B clips, `hop` frames per step.  Three legs, alternated block by block in one process:
+BatchNorm, LayerNorm, shared gates), B clips, `hop` frames per step.  The legs, alternated block by block in one process:
 
     one_launch   sfsn_fullband_stream_hop, one launch per hop
     graph        the per-kernel sequence replayed from its HIP graph
     eager        the per-kernel sequence launched kernel by kernel
+    wave         (hop 1) samples in, samples out on the device: sfsn_fullband_stream_hop_wave, step_wave(copy=False) + synchronise
+    wave_host    (hop 1) samples in, samples out on the host: step_wave_host (pinned buffers, completion words, no synchronise)
 
 Timed with a host clock around `step(copy=False)` plus a stream synchronise: what a caller that needs the frame back waits for.
 
@@ -27,7 +29,9 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from test_cirm_gsn import recipe_model  # noqa: E402
 
-LEGS = {"one_launch": dict(one_launch=True), "graph": dict(one_launch=False, graph=True), "eager": dict(one_launch=False, graph=False)}
+LEGS = {"one_launch": dict(one_launch=True), "graph": dict(one_launch=False, graph=True), "eager": dict(one_launch=False, graph=False),
+        "wave": dict(waveform=True), "wave_host": dict(waveform=True, host_io=True)}
+WAVE_LEGS = ("wave", "wave_host")
 
 
 def run(sess, frames, n, stream):
@@ -35,6 +39,23 @@ def run(sess, frames, n, stream):
     for i in range(n):
         t0 = time.perf_counter()
         sess.step(frames[i % len(frames)], copy=False)
+        stream.synchronize()
+        us[i] = (time.perf_counter() - t0) * 1e6
+    return us
+
+
+def run_wave(sess, chunks, n, stream):
+    us = np.empty(n)
+    if sess.host_io:
+        for i in range(n):
+            x = chunks[i % len(chunks)]
+            t0 = time.perf_counter()
+            sess.step_wave_host(x)
+            us[i] = (time.perf_counter() - t0) * 1e6
+        return us
+    for i in range(n):
+        t0 = time.perf_counter()
+        sess.step_wave(chunks[i % len(chunks)], copy=False)
         stream.synchronize()
         us[i] = (time.perf_counter() - t0) * 1e6
     return us
@@ -53,22 +74,26 @@ def main():
     m = m.cuda()
     g = torch.Generator("cuda").manual_seed(0)
     frames = [torch.view_as_complex(torch.randn(a.batch, 257, a.hop, 2, device="cuda", generator=g) * 0.5) for _ in range(64)]
+    chunks = [torch.randn(a.batch, 128, device="cuda", generator=g) * 0.05 for _ in range(64)]
+    data = {k: frames for k in LEGS}
+    data.update(wave=chunks, wave_host=[c.cpu() for c in chunks])
+    legs = {k: kw for k, kw in LEGS.items() if a.hop == 1 or k not in WAVE_LEGS}  # (a waveform session computes one frame per call)
     stream = torch.cuda.current_stream()
     if a.trace:
         sess = m.streaming(batch=a.batch, hop=a.hop, **LEGS[a.trace])
-        run(sess, frames, 200, stream)
+        (run_wave if a.trace in WAVE_LEGS else run)(sess, data[a.trace], 200, stream)
         sess.check_errors()
         print(json.dumps(dict(leg=a.trace, launches=sess.launches)))
         return
-    sessions = {k: m.streaming(batch=a.batch, hop=a.hop, **kw) for k, kw in LEGS.items()}
-    samples = {k: [] for k in LEGS}
+    sessions = {k: m.streaming(batch=a.batch, hop=a.hop, **kw) for k, kw in legs.items()}
+    samples = {k: [] for k in legs}
     for k, s in sessions.items():
-        run(s, frames, a.warmup, stream)
+        (run_wave if k in WAVE_LEGS else run)(s, data[k], a.warmup, stream)
     done = 0
-    while done < a.hops:  # the legs take turns, a block of hops each, so that drift of the machine falls on all three alike
+    while done < a.hops:  # the legs take turns, a block of hops each, so that drift of the machine falls on all alike
         n = min(a.block, a.hops - done)
         for k, s in sessions.items():
-            samples[k].append(run(s, frames, n, stream))
+            samples[k].append((run_wave if k in WAVE_LEGS else run)(s, data[k], n, stream))
         done += n
     out = dict(batch=a.batch, hop=a.hop, hops=a.hops, device=torch.cuda.get_device_name())
     for k, s in sessions.items():

@@ -122,10 +122,15 @@ class FullbandHopDesc(ctypes.Structure):  # sfsn_fullband_hop_desc
                 ("launch_index", ctypes.c_uint)]
 
 
+class FullbandWaveDesc(ctypes.Structure):  # sfsn_fullband_wave_desc
+    _fields_ = [("hop", FullbandHopDesc), ("wave_in", _P), ("wave_state", _P), ("ola_state", _P), ("wave_out", _P), ("window", _P),
+                ("spec_g", _P), ("enh_g", _P), ("done", _P)]
+
+
 def _sources():
     """The files the library is made of, in the order the Makefile hashes them (SRCS)."""
     return [os.path.join(_HERE, "..", "include", "sfsn.h")] + [
-        os.path.join(CSRC, f) for f in ("sfsn_scan_dev.h", "sfsn_scan3_dev.h", "sfsn_scan3i_dev.h", "sfsn_scan3x_dev.h", "sfsn_scan3w_dev.h", "sfsn_scan3j_dev.h", "sfsn_scan3g_dev.h", "sfsn_feat_dev.h", "sfsn_fft_dev.h", "sfsn_hop_dev.h", "sfsn_fullband_dev.h", "sfsn_host.h", "sfsn_kernels.hip", "sfsn_stack.hip", "sfsn_hop.hip", "sfsn_fft.hip", "sfsn_train.hip",
+        os.path.join(CSRC, f) for f in ("sfsn_scan_dev.h", "sfsn_scan3_dev.h", "sfsn_scan3i_dev.h", "sfsn_scan3x_dev.h", "sfsn_scan3w_dev.h", "sfsn_scan3j_dev.h", "sfsn_scan3g_dev.h", "sfsn_feat_dev.h", "sfsn_fft_dev.h", "sfsn_hop_dev.h", "sfsn_hop_wave_dev.h", "sfsn_fullband_dev.h", "sfsn_host.h", "sfsn_kernels.hip", "sfsn_stack.hip", "sfsn_hop.hip", "sfsn_fft.hip", "sfsn_train.hip",
                                   "sfsn_featproj.hip", "sfsn_projdf.hip", "sfsn_fullband.hip", "sfsn_fullband_train.hip", "sfsn_fullband_hop.hip", "sfsn_pack.cpp")]
 
 
@@ -290,6 +295,10 @@ def lib() -> ctypes.CDLL:
     L.sfsn_fullband_hop_scratch_bytes.argtypes = [ctypes.POINTER(FullbandHopDesc)]
     L.sfsn_fullband_stream_hop.restype = _I
     L.sfsn_fullband_stream_hop.argtypes = [ctypes.POINTER(FullbandHopDesc), _P]
+    L.sfsn_fullband_wave_hop_check.restype = _I  # Hp, n_layers, F, S, df, B, unshared (host only)
+    L.sfsn_fullband_wave_hop_check.argtypes = [_I] * 7
+    L.sfsn_fullband_stream_hop_wave.restype = _I
+    L.sfsn_fullband_stream_hop_wave.argtypes = [ctypes.POINTER(FullbandWaveDesc), _P]
     if L.sfsn_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH}: ABI version {L.sfsn_abi_version()} != {ABI_VERSION}; rebuild (make -C {CSRC})")
     _lib = L
@@ -306,7 +315,8 @@ EXPORTS = ("sfsn_abi_version", "sfsn_source_hash", "sfsn_strerror", "sfsn_device
            "sfsn_scan_split_scratch_bytes", "sfsn_gsn_layer_scan_split", "sfsn_proj_deepfilter", "sfsn_gsn_stack_scan_x_w16",
            "sfsn_hop_spike_slots", "sfsn_spike_count_rows", "sfsn_fullband_features", "sfsn_fullband_input_proj",
            "sfsn_fullband_proj_deepfilter", "sfsn_fullband_deepfilter_fwd", "sfsn_fullband_deepfilter_bwd",
-           "sfsn_fullband_hop_check", "sfsn_fullband_hop_scratch_bytes", "sfsn_fullband_stream_hop")
+           "sfsn_fullband_hop_check", "sfsn_fullband_hop_scratch_bytes", "sfsn_fullband_stream_hop",
+           "sfsn_fullband_wave_hop_check", "sfsn_fullband_stream_hop_wave")
 
 
 def check(rc: int, what: str = "") -> None:

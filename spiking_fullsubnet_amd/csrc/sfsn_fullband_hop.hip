@@ -19,6 +19,16 @@
 //   projection  ceil(F / 16) * S workgroups: (bin block, speaker); wave w owns the coefficient tiles (c, d) = w, w + 8 of its 2 df;
 //               activated coefficients to LDS, then thread (clip, bin) adds the taps in ascending d and shifts the bin's history.
 //
+// Waveform mode (sfsn_fullband_stream_hop_wave; hop == 1, F = 257: 512-point frames, 128 new samples per clip): a second instantiation
+// of the kernel with two more roles, sfsn_hop.hip's waveform stages (sfsn_hop_wave_dev.h, one body for both hops):
+//   STFT        one workgroup in front of the input role, a wave per clip (two clips per wave when B > 8): the frame's 257 bins leave
+//               as {re, tag, im, tag} granules (spec_g); the input role forms its feature rows from them, thread (clip, bin) of the
+//               projection role takes its bin once (new-frame tap and the history it writes).
+//   inverse     ceil(B S / 8) workgroups behind the projection role, a wave per (clip, speaker): the enhanced bins arrive as granules
+//   STFT        (enh_g, written by the projection role), overlap-add against the carried accumulator, 128 samples out, done words.
+// Every granule is written in every launch for every clip, whatever the clip's frame index: the consumers wait on all of them.  The
+// spectrum kernel is compiled without any of this (template parameter WAVE): its code is what it was (profiles/cirm_streaming.md).
+//
 // Arithmetic: sfsn_fullband_dev.h's expressions (shared with the offline kernels) and scan_body's cell: bit-identical to
 // FullbandEngine.forward_stft on the concatenated input (tests/test_cirm_streaming.py).
 #include <hip/hip_runtime.h>
@@ -31,6 +41,7 @@
 #include "sfsn_feat_dev.h"
 #include "sfsn_fullband_dev.h"
 #include "sfsn_hop_dev.h"
+#include "sfsn_hop_wave_dev.h"
 #include "sfsn_host.h"
 
 #define FBH_NPW 32      // layer-0 input-term neurons per input workgroup
@@ -70,21 +81,37 @@ struct FbhParams {
     int nwg_in, wpl, nwg_proj, nblocks;
     float fdrc, eps;
     unsigned launch;
+    // waveform mode (appended: the spectrum kernel's argument offsets stay what they were)
+    const float* wave_in;
+    float* wave_state;
+    float* ola_state;
+    float* wave_out;
+    const float* window;
+    float* spec_g;
+    float* enh_g;
+    unsigned* done;
+    int nwg_istft;
 };
 
 // clip b restarts in this launch: its carried state and history read as zero (sfsn_hop.hip's hop_clip_k == 0)
 __device__ __forceinline__ bool fbh_fresh(const FbhParams& p, int b) {
     return p.clip_start && p.launch == __hip_atomic_load(p.clip_start + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
+// waveform mode: clip b's frame index in this launch, k = launch - clip_start[b] (unsigned difference: wrap-safe).  k == -1: the clip's
+// first call, no frame yet; k == 0: its frame 0 (fbh_fresh); its samples come out from k == 2 on.
+__device__ __forceinline__ int fbh_clip_k(const FbhParams& p, int b) {
+    return (int)(p.launch - __hip_atomic_load(p.clip_start + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM));
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // input role.  LDS: [ws: F x 33 floats (my neurons' rows of W_ih, k-major)][xs: F x 16 floats (the frame's feature rows, k-major)]
 // ---------------------------------------------------------------------------------------------------------------------
+template <bool WAVE>
 __device__ __forceinline__ void fbh_input_role(const FbhParams& p, char* smem) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int F = p.F, B = p.B, Hp = p.Hp, hop = p.hop;
-    const int n0 = (int)blockIdx.x * FBH_NPW;
+    const int F = p.F, B = p.B, Hp = p.Hp, hop = WAVE ? 1 : p.hop;
+    const int n0 = ((int)blockIdx.x - (WAVE ? 1 : 0)) * FBH_NPW;  // (waveform mode: block 0 is the STFT)
     const int nn = Hp - n0 < FBH_NPW ? Hp - n0 : FBH_NPW;
     float* ws = reinterpret_cast<float*>(smem);
     float* xs = ws + F * FBH_LDW;
@@ -121,6 +148,7 @@ __device__ __forceinline__ void fbh_input_role(const FbhParams& p, char* smem) {
     const int b = tid & 15, nme = tid >> 4;
     const bool mine = nme < nn && b < B;
     const float bias = mine ? p.layer[0].bias[n0 + nme] : 0.0f;
+    [[maybe_unused]] bool ok = true;
     for (int t = 0; t < hop; ++t) {
         if (t > 0) __syncthreads();  // the previous frame's chains have read xs
         for (int b_ = wave; b_ < B; b_ += HOP_WAVES) {
@@ -130,7 +158,11 @@ __device__ __forceinline__ void fbh_input_role(const FbhParams& p, char* smem) {
                 const int j = lane + 64 * u;
                 v[u] = 0.0f;
                 if (j < F) {
-                    const float2 xc = *reinterpret_cast<const float2*>(p.inp + (((size_t)b_ * F + j) * hop + t) * 2);
+                    float2 xc;
+                    if constexpr (WAVE)  // (hop == 1) the STFT workgroup's granules
+                        xc = hop_take_cplx(p.spec_g + ((size_t)b_ * F + j) * 4, tagw, ok, p.cnt);
+                    else
+                        xc = *reinterpret_cast<const float2*>(p.inp + (((size_t)b_ * F + j) * hop + t) * 2);
                     v[u] = compress_mag(xc.x, xc.y, p.fdrc);
                 }
             }
@@ -289,11 +321,12 @@ __device__ __forceinline__ void fbh_layer_role(const FbhParams& p, int l, int pa
 // ---------------------------------------------------------------------------------------------------------------------
 // projection + activation + deep filter of one (bin block, speaker).  LDS: [64 B][hb: 5 KB][cbuf: 16 rows x 2 df tiles x 16 floats]
 // ---------------------------------------------------------------------------------------------------------------------
+template <bool WAVE>
 __device__ __forceinline__ void fbh_proj_role(const FbhParams& p, int idx, char* smem) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n = lane & 15, q = lane >> 4;
-    const int S = p.S, df = p.df, F = p.F, B = p.B, D = p.D, hop = p.hop, KS = p.KS, HP = KS * 64;
+    const int S = p.S, df = p.df, F = p.F, B = p.B, D = p.D, hop = WAVE ? 1 : p.hop, KS = p.KS, HP = KS * 64;
     const int fb = idx / S, s_ = idx - fb * S;
     const int ntl = 2 * df;
     const unsigned tagw = hop_tag(p.launch) * 0x02020202u;
@@ -325,6 +358,7 @@ __device__ __forceinline__ void fbh_proj_role(const FbhParams& p, int idx, char*
     const bool fresh = fbh_fresh(p, b_);
     const float* hrow = p.hist[p.launch & 1u] + ((size_t)b_ * F + fc) * D * 2;
     const float* irow = p.inp + ((size_t)b_ * F + fc) * hop * 2;
+    bool ok = true;
     // tap i of [history (D) | new frames (hop)]; a restarted clip's history reads as zero
     auto tap = [&](int i) -> float2 {
         if (i >= D) return *reinterpret_cast<const float2*>(irow + 2 * (i - D));
@@ -332,10 +366,15 @@ __device__ __forceinline__ void fbh_proj_role(const FbhParams& p, int idx, char*
     };
     float2 tap0[FBH_DF_MAX];
 #pragma unroll
-    for (int d = 0; d < FBH_DF_MAX; ++d) tap0[d] = (mine && d < df) ? tap(d) : make_float2(0.0f, 0.0f);
+    for (int d = 0; d < FBH_DF_MAX; ++d) tap0[d] = (mine && d < df && !(WAVE && d == D)) ? tap(d) : make_float2(0.0f, 0.0f);
+    if constexpr (WAVE) {  // (hop == 1) my bin of the new frame, taken once from the STFT workgroup's granules: tap D = df - 1
+        const float2 newv = mine ? hop_take_cplx(p.spec_g + ((size_t)b_ * F + fc) * 4, tagw, ok, p.cnt) : make_float2(0.0f, 0.0f);
+#pragma unroll
+        for (int d = 0; d < FBH_DF_MAX; ++d)
+            if (d == D) tap0[d] = newv;
+    }
 
     const int8_t* last = p.layer[p.nl - 1].spikes;
-    bool ok = true;
     for (int t = 0; t < hop; ++t) {
         v4i b[HOP_KS_MAX];
         // (for t > 0 the barrier inside also orders the previous frame's reads of cbuf before the writes below)
@@ -371,22 +410,51 @@ __device__ __forceinline__ void fbh_proj_role(const FbhParams& p, int idx, char*
                 fbd_tap(yr, yi, xv, cbuf[(rl * ntl + d) * 16 + bi], cbuf[(rl * ntl + df + d) * 16 + bi]);
             }
             const size_t o = (((size_t)rl * S + s_) * F + f) * hop + t;
-            *reinterpret_cast<float2*>(p.enh + 2 * o) = make_float2(yr, yi);
+            if constexpr (WAVE) {  // the enhanced bin to the inverse-STFT wave of (clip, speaker); the spectrum only on request
+                hop_put_cplx(p.enh_g + 4 * o, make_float2(yr, yi), tagw);
+                if (p.enh) *reinterpret_cast<float2*>(p.enh + 2 * o) = make_float2(yr, yi);
+            } else {
+                *reinterpret_cast<float2*>(p.enh + 2 * o) = make_float2(yr, yi);
+            }
             if (p.mag) p.mag[o] = fbd_mag(yr, yi);
         }
     }
     // the history the next launch reads (the other half of the double buffer): the last D of [history | new frames]
     if (mine && s_ == 0) {
         float* hnext = p.hist[(p.launch + 1u) & 1u] + ((size_t)rl * F + f) * D * 2;
-        for (int i = 0; i < D; ++i) *reinterpret_cast<float2*>(hnext + 2 * i) = tap(i + hop);
+        if constexpr (WAVE) {  // (the taps are in registers: history 1 .. D - 1, then the granule taken above)
+#pragma unroll
+            for (int i = 0; i < FBH_DF_MAX - 1; ++i)
+                if (i < D) *reinterpret_cast<float2*>(hnext + 2 * i) = tap0[i + 1];
+        } else {
+            for (int i = 0; i < D; ++i) *reinterpret_cast<float2*>(hnext + 2 * i) = tap(i + hop);
+        }
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// waveform mode: the new frame's spectrum (block 0) and the enhanced frame back to samples (the last blocks); sfsn_hop_wave_dev.h
+// ---------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void fbh_stft_role(const FbhParams& p, char* smem) {
+    hop_wave_stft(p.wave_in, p.wave_state, p.window, p.spec_g, p.F, 0, p.B, hop_tag(p.launch) * 0x02020202u, smem,
+                  [&](int ln, int n) { return __ballot(ln < n && fbh_clip_k(p, ln) == -1); });
+}
+__device__ __forceinline__ void fbh_istft_role(const FbhParams& p, int wg, char* smem) {
+    hop_wave_istft(
+        p.ola_state, p.wave_out, p.window, p.enh_g, p.done, p.cnt, p.F, wg, p.B * p.S, hop_tag(p.launch) * 0x02020202u, p.launch + 1u, smem,
+        [&](int pair, int& fi, bool& fresh, bool& mute) {
+            fi = fbh_clip_k(p, pair / p.S);
+            fresh = fi == 0;
+            mute = fi < 2;
+        },
+        [](bool&) {});
 }
 
 __global__ __launch_bounds__(HOP_THREADS) void fullband_stream_hop_kernel(const FbhParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int bi = (int)blockIdx.x;
     if (bi < p.nwg_in) {
-        fbh_input_role(p, smem);
+        fbh_input_role<false>(p, smem);
         return;
     }
     const int li = bi - p.nwg_in;
@@ -398,7 +466,36 @@ __global__ __launch_bounds__(HOP_THREADS) void fullband_stream_hop_kernel(const 
             fbh_layer_role<false>(p, l, part, smem);
         return;
     }
-    fbh_proj_role(p, li - p.nl * p.wpl, smem);
+    fbh_proj_role<false>(p, li - p.nl * p.wpl, smem);
+}
+// Waveform mode, a kernel of its own (the spectrum kernel keeps its code and its register allocation): the STFT in front, the inverse
+// STFT behind -- producers keep lower block indices than their consumers
+__global__ __launch_bounds__(HOP_THREADS) void fullband_stream_hop_wave_kernel(const FbhParams p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int bi = (int)blockIdx.x - 1;
+    if (bi < 0) {
+        fbh_stft_role(p, smem);
+        return;
+    }
+    if (bi < p.nwg_in) {
+        fbh_input_role<true>(p, smem);
+        return;
+    }
+    const int li = bi - p.nwg_in;
+    if (li < p.nl * p.wpl) {
+        const int l = li / p.wpl, part = li - l * p.wpl;
+        if (l == 0)
+            fbh_layer_role<true>(p, 0, part, smem);
+        else
+            fbh_layer_role<false>(p, l, part, smem);
+        return;
+    }
+    const int pi = li - p.nl * p.wpl;
+    if (pi < p.nwg_proj) {
+        fbh_proj_role<true>(p, pi, smem);
+        return;
+    }
+    fbh_istft_role(p, pi - p.nwg_proj, smem);
 }
 
 #ifdef SFSN_FBH_ROLE_KERNELS
@@ -407,7 +504,7 @@ __global__ __launch_bounds__(HOP_THREADS) void fullband_stream_hop_kernel(const 
 // -Rpass-analysis=kernel-resource-usage"` prints them.
 __global__ __launch_bounds__(HOP_THREADS) void fbh_role_input_kernel(const FbhParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    fbh_input_role(p, smem);
+    fbh_input_role<false>(p, smem);
 }
 __global__ __launch_bounds__(HOP_THREADS) void fbh_role_layer0_kernel(const FbhParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -419,7 +516,24 @@ __global__ __launch_bounds__(HOP_THREADS) void fbh_role_layer_kernel(const FbhPa
 }
 __global__ __launch_bounds__(HOP_THREADS) void fbh_role_proj_kernel(const FbhParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    fbh_proj_role(p, (int)blockIdx.x, smem);
+    fbh_proj_role<false>(p, (int)blockIdx.x, smem);
+}
+// waveform mode's roles
+__global__ __launch_bounds__(HOP_THREADS) void fbh_role_wave_input_kernel(const FbhParams p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    fbh_input_role<true>(p, smem);
+}
+__global__ __launch_bounds__(HOP_THREADS) void fbh_role_wave_proj_kernel(const FbhParams p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    fbh_proj_role<true>(p, (int)blockIdx.x, smem);
+}
+__global__ __launch_bounds__(HOP_THREADS) void fbh_role_stft_kernel(const FbhParams p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    fbh_stft_role(p, smem);
+}
+__global__ __launch_bounds__(HOP_THREADS) void fbh_role_istft_kernel(const FbhParams p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    fbh_istft_role(p, (int)blockIdx.x, smem);
 }
 #endif
 
@@ -435,9 +549,17 @@ extern "C" int sfsn_fullband_hop_check(int Hp, int n_layers, int F, int S, int d
     return SFSN_OK;
 }
 
-static int fbh_plan(FbhParams& p, size_t& lds, const sfsn_fullband_hop_desc* d) {
+extern "C" int sfsn_fullband_wave_hop_check(int Hp, int n_layers, int F, int S, int df, int B, int unshared) {
+    const int rc = sfsn_fullband_hop_check(Hp, n_layers, F, S, df, B, 1, df - 1, unshared);
+    if (rc != SFSN_OK) return rc;
+    return F == FFT_F ? SFSN_OK : SFSN_EUNSUPPORTED;  // sfsn_fft_dev.h: 512-point frames, hop 128
+}
+
+static int fbh_plan(FbhParams& p, size_t& lds, const sfsn_fullband_hop_desc* d, bool wave = false) {
     if (!d) return SFSN_EINVAL;
-    const int rc = sfsn_fullband_hop_check(d->Hp, d->n_layers, d->F, d->S, d->df, d->B, d->hop, d->D, d->unshared);
+    if (wave && (d->hop != 1 || d->D != d->df - 1)) return SFSN_EINVAL;
+    const int rc = wave ? sfsn_fullband_wave_hop_check(d->Hp, d->n_layers, d->F, d->S, d->df, d->B, d->unshared)
+                        : sfsn_fullband_hop_check(d->Hp, d->n_layers, d->F, d->S, d->df, d->B, d->hop, d->D, d->unshared);
     if (rc != SFSN_OK) return rc;
     if (d->act < SFSN_ACT_NONE || d->act > SFSN_ACT_RELU || (d->ln_w == nullptr) != (d->ln_b == nullptr)) return SFSN_EINVAL;
     memset(&p, 0, sizeof(p));
@@ -448,12 +570,14 @@ static int fbh_plan(FbhParams& p, size_t& lds, const sfsn_fullband_hop_desc* d) 
     p.nwg_in = (d->Hp + FBH_NPW - 1) / FBH_NPW;
     p.wpl = (p.NT + HOP_WAVES - 1) / HOP_WAVES;
     p.nwg_proj = (d->F + 15) / 16 * d->S;
-    p.nblocks = p.nwg_in + p.nl * p.wpl + p.nwg_proj;
+    p.nwg_istft = wave ? (d->B * d->S + HOP_WAVES - 1) / HOP_WAVES : 0;
+    p.nblocks = p.nwg_in + p.nl * p.wpl + p.nwg_proj + (wave ? 1 + p.nwg_istft : 0);
     const size_t lds_in = (size_t)d->F * (FBH_LDW + 16) * sizeof(float);
     const size_t lds_layer = 64 + (size_t)2 * HOP_KS_MAX * 1024;
     const size_t lds_proj = 64 + (size_t)HOP_KS_MAX * 1024 + (size_t)16 * 2 * d->df * 16 * sizeof(float);
     lds = lds_in > lds_layer ? lds_in : lds_layer;
     if (lds_proj > lds) lds = lds_proj;
+    if (wave && HOP_WAVE_LDS_ISTFT > lds) lds = HOP_WAVE_LDS_ISTFT;  // (37 KB: below the input role's 50 KB at F = 257)
     return SFSN_OK;
 }
 
@@ -463,16 +587,25 @@ extern "C" size_t sfsn_fullband_hop_scratch_bytes(const sfsn_fullband_hop_desc* 
     return fbh_plan(p, lds, desc) == SFSN_OK ? 64 : 0;  // word 0: the error word
 }
 
-extern "C" int sfsn_fullband_stream_hop(const sfsn_fullband_hop_desc* d, void* stream) {
+static bool aligned8(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 7u) == 0; }
+
+// the launch of both modes; w != nullptr: waveform mode (d = &w->hop)
+static int fbh_launch(const sfsn_fullband_hop_desc* d, const sfsn_fullband_wave_desc* w, void* stream) {
     FbhParams p;
     size_t lds;
-    const int rc = fbh_plan(p, lds, d);
+    const int rc = fbh_plan(p, lds, d, w != nullptr);
     if (rc != SFSN_OK) return rc;
-    if (!d->w_ih0 || !d->w_p || !d->w_p_dq || !d->inp_ri || !d->enh_ri || !d->z0 || !d->scratch || d->scratch_bytes < 64) return SFSN_EINVAL;
+    if (!d->w_ih0 || !d->w_p || !d->w_p_dq || !d->z0 || !d->scratch || d->scratch_bytes < 64) return SFSN_EINVAL;
+    if (!w && (!d->inp_ri || !d->enh_ri)) return SFSN_EINVAL;
     if (d->D > 0 && (!d->hist_ri[0] || !d->hist_ri[1])) return SFSN_EINVAL;
-    bool al = aligned16(d->w_p) && aligned16(d->w_p_dq) && aligned16(d->b_p) && (reinterpret_cast<uintptr_t>(d->inp_ri) & 7u) == 0 &&
-              (reinterpret_cast<uintptr_t>(d->enh_ri) & 7u) == 0 && (reinterpret_cast<uintptr_t>(d->z0) & 7u) == 0 &&
-              (reinterpret_cast<uintptr_t>(d->hist_ri[0]) & 7u) == 0 && (reinterpret_cast<uintptr_t>(d->hist_ri[1]) & 7u) == 0;
+    bool al = aligned16(d->w_p) && aligned16(d->w_p_dq) && aligned16(d->b_p) && (w || aligned8(d->inp_ri)) && aligned8(d->enh_ri) &&
+              aligned8(d->z0) && aligned8(d->hist_ri[0]) && aligned8(d->hist_ri[1]);
+    if (w) {
+        if (!d->clip_start || !w->wave_in || !w->wave_state || !w->ola_state || !w->wave_out || !w->window || !w->spec_g || !w->enh_g)
+            return SFSN_EINVAL;
+        al = al && aligned8(w->wave_in) && aligned8(w->wave_state) && aligned8(w->ola_state) && aligned8(w->wave_out) &&
+             aligned8(w->window) && aligned8(w->spec_g) && aligned8(w->enh_g) && (reinterpret_cast<uintptr_t>(w->done) & 3u) == 0;
+    }
     for (int l = 0; l < d->n_layers; ++l) {
         const sfsn_fullband_hop_layer& L = d->layer[l];
         if (!L.w_hh || !L.w_hh_dq || !L.bias || !L.bn_alpha || !L.bn_beta || !L.h[0] || !L.h[1] || !L.c || !L.spikes) return SFSN_EINVAL;
@@ -485,12 +618,25 @@ extern "C" int sfsn_fullband_stream_hop(const sfsn_fullband_hop_desc* d, void* s
     }
     if (!al) return SFSN_EINVAL;
     p.w_ih0 = d->w_ih0; p.ln_w = d->ln_w; p.ln_b = d->ln_b; p.w_p = d->w_p; p.w_p_dq = d->w_p_dq; p.b_p = d->b_p;
-    p.inp = d->inp_ri; p.hist[0] = d->hist_ri[0]; p.hist[1] = d->hist_ri[1]; p.enh = d->enh_ri; p.mag = d->enh_mag; p.z0 = d->z0;
+    p.inp = w ? nullptr : d->inp_ri;
+    p.hist[0] = d->hist_ri[0]; p.hist[1] = d->hist_ri[1]; p.enh = d->enh_ri; p.mag = d->enh_mag; p.z0 = d->z0;
     p.cnt = static_cast<unsigned*>(d->scratch);
     p.clip_start = d->clip_start;
     p.launch = d->launch_index;
+    if (w) {
+        p.wave_in = w->wave_in; p.wave_state = w->wave_state; p.ola_state = w->ola_state; p.wave_out = w->wave_out;
+        p.window = w->window; p.spec_g = w->spec_g; p.enh_g = w->enh_g; p.done = w->done;
+    }
     // every workgroup must be resident at once (consumers wait for producers): one per compute unit at most
     if (p.nblocks > cu_count()) return SFSN_EUNSUPPORTED;
     if (lds > 160 * 1024) return SFSN_EUNSUPPORTED;
+    if (w) return launch_lds<fullband_stream_hop_wave_kernel>(dim3(p.nblocks), dim3(HOP_THREADS), lds, static_cast<hipStream_t>(stream), p);
     return launch_lds<fullband_stream_hop_kernel>(dim3(p.nblocks), dim3(HOP_THREADS), lds, static_cast<hipStream_t>(stream), p);
+}
+
+extern "C" int sfsn_fullband_stream_hop(const sfsn_fullband_hop_desc* d, void* stream) { return fbh_launch(d, nullptr, stream); }
+
+extern "C" int sfsn_fullband_stream_hop_wave(const sfsn_fullband_wave_desc* w, void* stream) {
+    if (!w) return SFSN_EINVAL;
+    return fbh_launch(&w->hop, w, stream);
 }

@@ -38,6 +38,7 @@
 #include "sfsn_feat_dev.h"
 #include "sfsn_fft_dev.h"
 #include "sfsn_hop_dev.h"
+#include "sfsn_hop_wave_dev.h"
 #include "sfsn_host.h"
 
 #define HOP_MAX_SEQS (1 + SFSN_HOP_MAX_GROUPS)
@@ -142,24 +143,6 @@ __device__ __forceinline__ int hop_clip_k(const HopParams& p, const HopStep& hs,
     return (int)(hs.launch - __hip_atomic_load(p.clip_start + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM));
 }
 
-// A complex value as two 8-byte {value, tag} granules (waveform mode: the noisy frame comes from the STFT workgroups of this
-// launch, the enhanced frame goes to the inverse-STFT workgroups).  Every lane polls its own granules.
-__device__ __forceinline__ void hop_put_cplx(float* g, float2 v, unsigned tagw) {
-    st64_agent(g, ((unsigned long long)tagw << 32) | __float_as_uint(v.x));
-    st64_agent(g + 2, ((unsigned long long)tagw << 32) | __float_as_uint(v.y));
-}
-__device__ __forceinline__ float2 hop_take_cplx(const float* g, unsigned tagw, bool& ok, unsigned* err) {
-    for (unsigned spins = 0;; ++spins) {
-        const unsigned long long a = ld64_agent(g), c = ld64_agent(g + 2);
-        if (((unsigned)(a >> 32) == tagw && (unsigned)(c >> 32) == tagw) || !ok)
-            return make_float2(__uint_as_float((unsigned)a), __uint_as_float((unsigned)c));
-        if (spins > HOP_SPIN_LIMIT) {
-            st_agent(err, 1u);
-            ok = false;
-        }
-        __builtin_amdgcn_s_sleep(1);
-    }
-}
 // bin f of clip b's new frame t: the caller's spectrum, or (waveform mode) the STFT workgroups' granules
 __device__ __forceinline__ float2 hop_in_bin(const HopParams& p, int b, int f, int t, int hop, unsigned tagw, bool& ok) {
     if (!p.spec_g) return *reinterpret_cast<const float2*>(p.inp + (((size_t)b * p.F + f) * hop + t) * 2);
@@ -741,154 +724,41 @@ __device__ __forceinline__ void hop_proj_role(const HopParams& p, const HopStep&
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// waveform mode (hop == 1), first stage: the new frame's spectrum.  One workgroup per 16 clips, a wave per clip: the frame is
-// the last 384 samples of the state followed by the 128 new ones; sfsn_fft.hip's transform (same code, same bits); the bins
-// leave as granules; then the state moves on by one hop.  LDS: [64 B][unit table 4 KB][8 x 2 KB exchange].
+// waveform mode (hop == 1), first and last stage: the new frame's spectrum (one workgroup per 16 clips, a wave per clip) and the
+// enhanced frame back to samples (a wave per (clip, speaker)).  The bodies are sfsn_hop_wave_dev.h's, shared with the cIRM-GSN hop.
 // ---------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void hop_stft_role(const HopParams& p, const HopStep& hs, const HopStageDev& sd, char* smem) {
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int rt = (int)blockIdx.x - sd.wg0;
     const int nclip = (p.B - 16 * rt) < 16 ? (p.B - 16 * rt) : 16;
-    const unsigned tagw = hop_tag(hs.launch) * 0x02020202u;
-    float2* unit = reinterpret_cast<float2*>(smem + 64);
-    float2(*fbuf)[FFT_N] = reinterpret_cast<float2(*)[FFT_N]>(smem + 64 + FFT_NFFT * 8);
-    fill_unit_table(unit, tid, HOP_THREADS);
-    __syncthreads();
-    const Twiddles tw = make_twiddles<false>(unit, lane);
-    // bit ci: clip 16 rt + ci makes its first call in this launch (its state reads as zero).  Read once, before anything leaves
-    // this workgroup: the resident kernel's host may write the origins of the next hop as soon as this hop's samples are out.
-    const unsigned long long first = p.clip_start ? __ballot(lane < nclip && hop_clip_k(p, hs, 16 * rt + lane) == -1) : 0ull;
-    float2 win[4], wk[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int n = 2 * (lane + 64 * r);
-        win[r] = make_float2(p.window[n], p.window[n + 1]);
-        wk[r] = unit_at<false>(unit, lane + 64 * r);
-    }
-    for (int ci = wave; ci < nclip; ci += HOP_WAVES) {
-        const int b = 16 * rt + ci;
-        const float* ws = p.wave_state + (size_t)b * FFT_NFFT;
-        const float* wn = p.wave_in + (size_t)b * 128;
-        const bool zero = (first >> ci) & 1ull;
-        float2 v[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int j = 2 * (lane + 64 * r);  // sample j of the frame: state[128 + j] for j < 384, then the new samples
-            const float2 x = j < 384 ? (zero ? make_float2(0.0f, 0.0f) : *reinterpret_cast<const float2*>(ws + 128 + j))
-                                     : *reinterpret_cast<const float2*>(wn + j - 384);
-            v[r] = make_float2(x.x * win[r].x, x.y * win[r].y);
-        }
-        fft256<false>(v, fbuf[wave], lane, tw);
-        float2 X[4], nyq = make_float2(0.0f, 0.0f);
-        rfft512_split(v, fbuf[wave], lane, wk, X, nyq);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) hop_put_cplx(p.spec_g + ((size_t)b * p.F + lane + 64 * r) * 4, X[r], tagw);
-        if (lane == 0) hop_put_cplx(p.spec_g + ((size_t)b * p.F + FFT_N) * 4, nyq, tagw);
-    }
-    // the state moves on by one hop (every sample is read before any is written; a clip's first call leaves [0 x 384 | samples])
-    float keep[16];
-#pragma unroll
-    for (int ci = 0; ci < 16; ++ci) {
-        keep[ci] = 0.0f;
-        if (ci < nclip) {
-            const int b = 16 * rt + ci;
-            if (tid >= 384) keep[ci] = p.wave_in[(size_t)b * 128 + tid - 384];
-            else if (!((first >> ci) & 1ull)) keep[ci] = p.wave_state[(size_t)b * FFT_NFFT + 128 + tid];
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int ci = 0; ci < 16; ++ci)
-        if (ci < nclip) p.wave_state[(size_t)(16 * rt + ci) * FFT_NFFT + tid] = keep[ci];
+    // (the origins are read once, before anything leaves this workgroup: the resident kernel's host may write the origins of the
+    //  next hop as soon as this hop's samples are out)
+    hop_wave_stft(p.wave_in, p.wave_state, p.window, p.spec_g, p.F, 16 * rt, nclip, hop_tag(hs.launch) * 0x02020202u, smem,
+                  [&](int ln, int n) { return p.clip_start ? __ballot(ln < n && hop_clip_k(p, hs, 16 * rt + ln) == -1) : 0ull; });
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// waveform mode, last stage: the enhanced frame back to samples.  A wave per (clip, speaker): polls the 257 bins of the
-// enhanced frame (granules written by the deep-filter workgroups), sfsn_fft.hip's inverse transform and window, overlap-add
-// in registers against the carried accumulator (ascending frame order, as istft_kernel adds them), the hop that is now
-// complete divided by the squared-window envelope of the frames that exist (t - q >= 0), accumulator moved on by one hop.
-// LDS: [64 B][unit table 4 KB][8 x 2 KB exchange][8 x 264 float2 spectrum rows].
-// ---------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void hop_istft_role(const HopParams& p, const HopStep& hs, const HopStageDev& sd, char* smem) {
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int pair = ((int)blockIdx.x - sd.wg0) * HOP_WAVES + wave;  // clip * S + speaker
-    const unsigned tagw = hop_tag(hs.launch) * 0x02020202u;
-    float2* unit = reinterpret_cast<float2*>(smem + 64);
-    float2(*fbuf)[FFT_N] = reinterpret_cast<float2(*)[FFT_N]>(smem + 64 + FFT_NFFT * 8);
-    float2(*xs)[264] = reinterpret_cast<float2(*)[264]>(smem + 64 + FFT_NFFT * 8 + HOP_WAVES * FFT_N * 8);
-    fill_unit_table(unit, tid, HOP_THREADS);
-    __syncthreads();
-    if (pair >= p.B * p.S) return;
-    const Twiddles tw = make_twiddles<true>(unit, lane);
-    // the clip's own frame index (per-clip utterances): its accumulator reads as zero in the launch that restarts it, and its
-    // output is zero until its frame 2 (calls 0 .. 2 of the utterance)
-    const int fi = p.clip_start ? hop_clip_k(p, hs, pair / p.S) : hs.frame_index;
-    float2 win[4], wk[4], ola[4];
-    float* os = p.ola_state + (size_t)pair * FFT_NFFT;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int n = 2 * (lane + 64 * r);
-        win[r] = make_float2(p.window[n], p.window[n + 1]);
-        wk[r] = unit_at<true>(unit, lane + 64 * r);
-        ola[r] = make_float2(0.0f, 0.0f);
-        if (!p.clip_start || fi != 0) ola[r] = *reinterpret_cast<const float2*>(os + n);
-    }
-    bool ok = true;
-    const float* eg = p.enh_g + (size_t)pair * p.F * 4;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) xs[wave][lane + 64 * r] = hop_take_cplx(eg + (size_t)(lane + 64 * r) * 4, tagw, ok, p.cnt);
-    if (lane == 0) xs[wave][FFT_N] = hop_take_cplx(eg + (size_t)FFT_N * 4, tagw, ok, p.cnt);
-    __builtin_amdgcn_wave_barrier();
-    float2 v[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int k = lane + 64 * r;
-        v[r] = irfft512_presplit(xs[wave][k], xs[wave][FFT_N - k], k, wk[r]);
-    }
-    fft256<true>(v, fbuf[wave], lane, tw);
-    const float sc = 1.0f / (float)FFT_N;
-    float2 acc[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const float2 res = make_float2(v[r].x * sc * win[r].x, v[r].y * sc * win[r].y);
-        acc[r] = make_float2(ola[r].x + res.x, ola[r].y + res.y);
-    }
-    // the hop that is complete now: padded positions n = 128 t + 2 lane + e; envelope over the frames t - q that exist, oldest first
-    float2 env = make_float2(0.0f, 0.0f);
-#pragma unroll
-    for (int q = 3; q >= 0; --q)
-        if (fi - q >= 0) {
-            env.x += win[q].x * win[q].x;
-            env.y += win[q].y * win[q].y;
-        }
-    float2 out = make_float2(env.x > 1e-11f ? acc[0].x / env.x : 0.0f, env.y > 1e-11f ? acc[0].y / env.y : 0.0f);
-    if (p.clip_start && fi < 2) out = make_float2(0.0f, 0.0f);
-    *reinterpret_cast<float2*>(p.wave_out + (size_t)pair * 128 + 2 * lane) = out;
-    if (hs.wait_fin) {
-        // (resident kernel, spike slots: each other workgroup counts itself finished after s_waitcnt(0) -- once all have, the slots
-        //  of this hop are in memory, and the done words below may tell the host so; the inverse STFT is the last stage)
-        const unsigned need = (hs.launch - p.launch + 1u) * gridDim.x - (unsigned)sd.nwg;
-        for (unsigned spins = 0; ok && (int)(ld_agent(p.cnt + 2) - need) < 0; ++spins) {
-            if (spins > HOP_SPIN_LIMIT) {
-                st_agent(p.cnt, 1u);
-                ok = false;
+    hop_wave_istft(
+        p.ola_state, p.wave_out, p.window, p.enh_g, p.done, p.cnt, p.F, (int)blockIdx.x - sd.wg0, p.B * p.S, hop_tag(hs.launch) * 0x02020202u,
+        hs.launch + 1u, smem,
+        [&](int pair, int& fi, bool& fresh, bool& mute) {
+            fi = p.clip_start ? hop_clip_k(p, hs, pair / p.S) : hs.frame_index;
+            fresh = p.clip_start && fi == 0;
+            mute = p.clip_start && fi < 2;
+        },
+        [&](bool& ok) {
+            if (hs.wait_fin) {
+                // (resident kernel, spike slots: each other workgroup counts itself finished after s_waitcnt(0) -- once all have, the
+                //  slots of this hop are in memory, and the done words may tell the host so; the inverse STFT is the last stage)
+                const unsigned need = (hs.launch - p.launch + 1u) * gridDim.x - (unsigned)sd.nwg;
+                for (unsigned spins = 0; ok && (int)(ld_agent(p.cnt + 2) - need) < 0; ++spins) {
+                    if (spins > HOP_SPIN_LIMIT) {
+                        st_agent(p.cnt, 1u);
+                        ok = false;
+                    }
+                    __builtin_amdgcn_s_sleep(1);
+                }
             }
-            __builtin_amdgcn_s_sleep(1);
-        }
-    }
-    if (p.done) {
-        // wave_out (and this word) may be host memory the device can reach: a caller that keeps its samples on the host spins on
-        // the word instead of synchronising the stream -- the samples are there when it changes (system-scope release)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (lane == 0) __hip_atomic_store(p.done + pair, hs.launch + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int n = 2 * (lane + 64 * r);
-        *reinterpret_cast<float2*>(os + n) = r < 3 ? acc[r + 1] : make_float2(0.0f, 0.0f);
-    }
+        });
 }
 
 // one hop of one workgroup: the role its block index selects
@@ -1121,7 +991,7 @@ static int hop_plan(HopParams& p, size_t& lds, const sfsn_hop_desc* d) {
                              (size_t)3 * p.seq[0].PT * p.seq[0].KS * 1024;
     const size_t lds_proj = 64 + (size_t)HOP_KS_MAX * 1024 + (size_t)16 * (pmax + 4) * sizeof(float);
     lds = lds_layer > lds_proj ? lds_layer : lds_proj;
-    const size_t lds_wave = 64 + (size_t)FFT_NFFT * 8 + (size_t)HOP_WAVES * FFT_N * 8 + (size_t)HOP_WAVES * 264 * 8;
+    const size_t lds_wave = HOP_WAVE_LDS_ISTFT;
     if (wave && lds_wave > lds) lds = lds_wave;
     return SFSN_OK;
 }

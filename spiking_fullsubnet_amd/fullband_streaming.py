@@ -22,11 +22,23 @@ Per-clip utterances: ``reset(clips=[...])`` restarts some clips of a batched ses
 one-launch hop gives every clip its own origin (the launch at which its utterance began) and reads a restarted clip's state and
 history as zero in that launch; the per-kernel sequence zeroes the clips' rows with stream-ordered fills.  Neither synchronises.
 
-Not covered here (follow-ups): ``waveform``, ``host_io``, ``resident`` and ``count_spikes`` sessions, and LSTM models.
+Waveform sessions (``waveform=True``): ``step_wave(samples [B, 128])`` returns ``[B, S, 128]`` enhanced samples, the frame's STFT, the
+hop and the inverse STFT with its overlap-add state in ONE ``sfsn_fullband_stream_hop_wave`` launch, bit-identical to ``model(wave)``
+(tests/test_cirm_waveform.py).  Call c of an utterance returns the samples that entered with call c - 3 (centred 512-point frames
+need 256 samples of look-ahead, the overlap-add another hop); the first three calls return zeros.  Every call is a launch: a clip's
+first call only moves its samples into the STFT state (the kernel's k == -1), so every clip's origin is the launch after its next one.
+With ``host_io=True``, ``step_wave_host`` takes and returns CPU tensors: the launch reads the samples from pinned host memory and
+writes the enhanced samples and a completion word per (clip, speaker) back into pinned host memory, no copy launch and no stream
+synchronisation.  Waveform sessions exist on the one-launch kernel only (``hop == 1``, 512-point frames with hop 128, ``B <= 16``,
+shared gate weights); anything else has no waveform tier and raises ``NotImplementedError``.
+
+Not covered here: ``resident`` and ``count_spikes`` sessions, waveform sessions beyond 16 clips or with separate gate weights, and
+LSTM models.
 """
 from __future__ import annotations
 
 import ctypes
+import time
 import weakref
 from typing import Dict, Optional, Tuple
 
@@ -34,7 +46,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import FullbandHopDesc, check
+from ._lib import FullbandHopDesc, FullbandWaveDesc, check
 from .engine import _ptr
 from .fullband_engine import FullbandEngine
 
@@ -55,14 +67,48 @@ def hop_covers(engine: FullbandEngine, batch: int, hop: int) -> bool:
     return True
 
 
-class FullbandStreamingSession:
-    """``step(frames [B, F, hop] complex64) -> (enh_stft [B, S, F, hop], enh_mag [B, S, F, hop] or None when S > 1)``."""
+def wave_refusal(engine: FullbandEngine, batch: int, hop: int, frame=None) -> Optional[str]:
+    """The first thing about a waveform session that sfsn_fullband_stream_hop_wave does not cover, or None.  ``frame``: the module's
+    ``(n_fft, hop_length, win_length)`` (None: taken to be the engine's n_fft with hop n_fft / 4)."""
+    spec = engine.spec
+    n_fft, hop_length, win_length = frame if frame is not None else (spec.n_fft, spec.n_fft // 4, spec.n_fft)
+    if hop != 1:
+        return f"hop={hop}: a waveform session computes one frame (128 new samples) per call"
+    if (n_fft, hop_length, win_length) != (512, 128, 512):
+        return (f"n_fft={n_fft}, hop_length={hop_length}, win_length={win_length}: the in-launch transforms are 512-point frames with hop "
+                "128 (other frame sizes have no waveform tier)")
+    rc = engine.lib.sfsn_fullband_wave_hop_check(engine.Hp, spec.layers, engine.F, spec.num_spks, spec.df, batch, 0 if spec.shared else 1)
+    if rc == _lib.SFSN_EUNSUPPORTED:
+        if not spec.shared:
+            return "shared_weights=False: separate gate weights have no waveform tier"
+        if batch > 16:
+            return f"B={batch}: more than 16 clips have no waveform tier"
+        return (f"Hp={engine.Hp}, layers={spec.layers}, F={engine.F}, S={spec.num_spks}, df={spec.df}: outside "
+                "sfsn_fullband_wave_hop_check's coverage (include/sfsn.h)")
+    check(rc, "sfsn_fullband_wave_hop_check")
+    return None
 
-    def __init__(self, engine: FullbandEngine, batch: int = 1, hop: int = 1, graph: bool = True, one_launch="auto", owner=None):
+
+class FullbandStreamingSession:
+    """``step(frames [B, F, hop] complex64) -> (enh_stft [B, S, F, hop], enh_mag [B, S, F, hop] or None when S > 1)``;
+    ``waveform=True``: ``step_wave(samples [B, 128] float32) -> [B, S, 128]`` (``host_io=True``: ``step_wave_host``, CPU tensors)."""
+
+    def __init__(self, engine: FullbandEngine, batch: int = 1, hop: int = 1, graph: bool = True, one_launch="auto", owner=None,
+                 waveform: bool = False, host_io: bool = False, frame=None):
         if batch < 1 or hop < 1:
             raise ValueError("batch and hop must be positive")
         if one_launch not in ("auto", True, False):
             raise ValueError("one_launch must be 'auto', True or False")
+        self.waveform, self.host_io = bool(waveform), bool(host_io)
+        if self.host_io and not self.waveform:
+            raise ValueError("host_io goes with waveform=True")
+        if self.waveform:
+            if one_launch is False:
+                raise ValueError("waveform=True runs on the one-launch kernel only (one_launch='auto' or True)")
+            why = wave_refusal(engine, batch, hop, frame)
+            if why is not None:
+                raise NotImplementedError(f"waveform=True: {why}")
+            one_launch = True
         spec = engine.spec
         self.eng, self.B, self.hop = engine, batch, hop
         self._owner = weakref.ref(owner) if owner is not None else None
@@ -73,6 +119,8 @@ class FullbandStreamingSession:
         self.launches: Dict[str, int] = {}
         self.frames_done = 0
         self._clip_f0 = np.zeros(batch, dtype=np.int64)
+        self._calls = 0  # waveform sessions: step_wave / step_wave_host calls (= launches) since the last whole reset
+        self._clip_c0 = np.zeros(batch, dtype=np.int64)
         self._graph: Optional[torch.cuda.CUDAGraph] = None
         self._hop = None
         covered = hop_covers(engine, batch, hop)
@@ -82,7 +130,7 @@ class FullbandStreamingSession:
                 f"F={engine.F}, S={spec.num_spks}, df={spec.df}, B={batch}, hop={hop}; coverage: include/sfsn.h) -- use "
                 "one_launch='auto' or False for the per-kernel sequence")
         self.one_launch = covered and (AUTO_ONE_LAUNCH if one_launch == "auto" else bool(one_launch))
-        self.inp = torch.zeros((batch, self.F, hop), dtype=torch.complex64, device=dev)
+        self.inp = None if self.waveform else torch.zeros((batch, self.F, hop), dtype=torch.complex64, device=dev)
         with torch.cuda.device(dev):
             if self.one_launch:
                 self._build_hop()
@@ -107,7 +155,8 @@ class FullbandStreamingSession:
         enh = torch.zeros((B, S, F, hop, 2), **f32)
         mag = torch.zeros((B, S, F, hop), **f32) if S == 1 else None
         origin = torch.zeros((B,), dtype=torch.int32, device=dev)  # the launch index of every clip's frame 0
-        d = FullbandHopDesc()
+        wd = FullbandWaveDesc() if self.waveform else None
+        d = wd.hop if wd is not None else FullbandHopDesc()
         for l, layer in enumerate(eng.layers):
             o = d.layer[l]
             if l > 0:
@@ -121,7 +170,7 @@ class FullbandStreamingSession:
         if eng.ln_w is not None:
             d.ln_w, d.ln_b = eng.ln_w.data_ptr(), eng.ln_b.data_ptr()
         d.w_p, d.w_p_dq, d.b_p = eng.proj_q.data_ptr(), eng.proj_dq.data_ptr(), eng.proj_b.data_ptr()
-        d.inp_ri = self.inp.data_ptr()
+        d.inp_ri = self.inp.data_ptr() if self.inp is not None else None
         d.hist_ri[0], d.hist_ri[1] = st["hist"][0].data_ptr(), st["hist"][1].data_ptr()
         d.enh_ri, d.enh_mag, d.z0 = enh.data_ptr(), (mag.data_ptr() if mag is not None else None), work["z0"].data_ptr()
         d.clip_start = origin.data_ptr()
@@ -131,6 +180,86 @@ class FullbandStreamingSession:
         d.scratch, d.scratch_bytes, d.launch_index = scratch.data_ptr(), nbytes, 0
         self._hop = dict(desc=d, ref=ctypes.byref(d), st=st, work=work, enh=torch.view_as_complex(enh), mag=mag, origin=origin,
                          scratch=scratch, err=torch.zeros((1,), dtype=torch.int32).pin_memory(), err_pending=False)
+        if wd is not None:
+            self._build_wave(wd)
+
+    def _build_wave(self, wd: FullbandWaveDesc) -> None:
+        """The waveform state, the granule scratch (zeroed once) and, with host_io, the pinned buffers the launch reads and writes."""
+        B, F, S, dev, h = self.B, self.F, self.S, self.dev, self._hop
+        f32 = dict(dtype=torch.float32, device=dev)
+        wv = dict(state=torch.zeros((B, 512), **f32), ola=torch.zeros((B, S, 512), **f32), out=torch.zeros((B, S, 128), **f32),
+                  window=torch.hann_window(512, **f32), spec_g=torch.zeros((B, F, 4), **f32), enh_g=torch.zeros((B, S, F, 4), **f32))
+        wd.wave_state, wd.ola_state, wd.wave_out, wd.window = (wv[k].data_ptr() for k in ("state", "ola", "out", "window"))
+        wd.spec_g, wd.enh_g = wv["spec_g"].data_ptr(), wv["enh_g"].data_ptr()
+        wd.wave_in = wv["out"].data_ptr()  # (set per call)
+        if self.host_io:  # pinned host memory the kernel reads / writes directly (device-reachable at the same address)
+            host = dict(inp=torch.zeros((B, 128), dtype=torch.float32).pin_memory(), out=torch.zeros((B, S, 128), dtype=torch.float32).pin_memory(),
+                        done=torch.zeros((B * S,), dtype=torch.int32).pin_memory())
+            host["done_np"] = host["done"].numpy()
+            wd.wave_in, wd.wave_out, wd.done = host["inp"].data_ptr(), host["out"].data_ptr(), host["done"].data_ptr()
+            wv["host"] = host
+        h["origin"].fill_(1)  # every clip's first call is launch 0: its frame 0 is launch 1
+        h.update(wave=wv, wdesc=wd, wref=ctypes.byref(wd))
+
+    def _launch_wave(self, wave_in_ptr: int) -> None:
+        h = self._hop
+        if h["err_pending"] and int(h["err"][0]) != 0:  # written behind an earlier launch; no blocking here
+            self.check_errors()
+        d = h["desc"]
+        h["wdesc"].wave_in = wave_in_ptr
+        with torch.cuda.device(self.dev):  # the C ABI launches on the calling thread's current device
+            rc = self.eng.lib.sfsn_fullband_stream_hop_wave(h["wref"], ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream))
+        if rc:
+            check(rc, "sfsn_fullband_stream_hop_wave")
+        d.launch_index = (d.launch_index + 1) & 0xFFFFFFFF
+        self._count("hop")
+        self._calls += 1
+        if self._calls % 256 == 0:  # every 256 launches the error word follows them into pinned memory
+            h["err"].copy_(h["scratch"][:1], non_blocking=True)
+            h["err_pending"] = True
+
+    def step_wave(self, samples: torch.Tensor, copy: bool = True) -> torch.Tensor:
+        """Waveform streaming (``waveform=True``): ``samples`` float32 [B, 128], contiguous, on the device -- the next 8 ms of every
+        clip, read in place in stream order.  Returns enhanced samples [B, S, 128]: call c of a clip's utterance returns the samples
+        that entered with its call c - 3; a clip's first three calls return zeros.  One launch per call.  ``copy=False``: a view of the
+        session's buffer, valid until the next call."""
+        if not self.waveform:
+            raise RuntimeError("open the session with waveform=True")
+        if self.host_io:
+            raise RuntimeError("this session was opened with host_io=True: use step_wave_host(samples)")
+        if (samples.device != self.dev or samples.dtype != torch.float32 or tuple(samples.shape) != (self.B, 128) or not samples.is_contiguous()
+                or samples.data_ptr() % 8 != 0):
+            raise RuntimeError(f"expected contiguous float32 {(self.B, 128)} on {self.dev}, got {samples.dtype} {tuple(samples.shape)} on "
+                               f"{samples.device}")
+        self._launch_wave(samples.data_ptr())
+        out = self._hop["wave"]["out"]
+        return out.clone() if copy else out
+
+    def step_wave_host(self, samples, timeout_s: float = 2.0) -> torch.Tensor:
+        """Waveform streaming with the samples on the HOST (``waveform=True, host_io=True``): ``samples`` = float32 [B, 128] CPU tensor
+        (or anything ``torch.as_tensor`` takes).  The launch reads them from pinned host memory and writes the enhanced samples and a
+        completion word per (clip, speaker) back into pinned host memory; the caller's thread spins on the words -- no copy launch,
+        no stream synchronisation.  Returns a CPU tensor [B, S, 128] (a view of the session's pinned buffer, valid until the next
+        call); same three-call delay as ``step_wave``."""
+        if not self.host_io:
+            raise RuntimeError("open the session with waveform=True, host_io=True")
+        host = self._hop["wave"]["host"]
+        host["inp"].copy_(torch.as_tensor(samples, dtype=torch.float32).reshape(self.B, 128))
+        target = (self._hop["desc"].launch_index + 1) & 0xFFFFFFFF
+        self._launch_wave(host["inp"].data_ptr())
+        done, t_end, t_soft = host["done_np"], None, None
+        while (int(done.min()) & 0xFFFFFFFF) != target or (int(done.max()) & 0xFFFFFFFF) != target:  # (uint32 compare: the index wraps)
+            if t_end is None:
+                t_end = time.perf_counter() + timeout_s
+                t_soft = t_end - timeout_s + 0.02
+            elif t_soft is not None and time.perf_counter() > t_soft:
+                # 20 ms without the words (a hop takes tens of microseconds): a hand-off wait inside the launch has probably expired --
+                # the launch has ended by now, its error word says so, and check_errors() raises it
+                t_soft = None
+                self.check_errors()
+            elif time.perf_counter() > t_end:
+                raise RuntimeError("sfsn_fullband_stream_hop_wave: no completion word from the launch (see check_errors())")
+        return host["out"]
 
     def _launch_hop(self, frames: torch.Tensor) -> None:
         h = self._hop
@@ -201,6 +330,8 @@ class FullbandStreamingSession:
         """``frames``: complex64 [B, F, hop] on the device.  Returns the enhanced frames and (one speaker) their magnitudes; with
         ``copy=False`` the returned tensors are views of the session's buffers, valid until the next ``step``.  The one-launch hop
         reads ``frames`` in place, in stream order: do not overwrite it before the stream has passed this step."""
+        if self.waveform:
+            raise RuntimeError("this session was opened with waveform=True: use step_wave(samples)")
         if frames.device != self.dev or frames.dtype != torch.complex64 or tuple(frames.shape) != (self.B, self.F, self.hop):
             raise RuntimeError(f"expected complex64 {(self.B, self.F, self.hop)} on {self.dev}, got {frames.dtype} {tuple(frames.shape)} "
                                f"on {frames.device}")
@@ -242,12 +373,19 @@ class FullbandStreamingSession:
             h = self._hop
             for t in h["st"]["h"] + h["st"]["c"] + [h["st"]["hist"]]:
                 t.zero_()
-            h["origin"].fill_(self._as_i32(h["desc"].launch_index))  # every clip's frame 0 is the next launch
+            if self.waveform:  # every clip's next call is its first (no frame yet): its frame 0 is the launch after the next
+                h["wave"]["state"].zero_()
+                h["wave"]["ola"].zero_()
+                h["origin"].fill_(self._as_i32(h["desc"].launch_index + 1))
+            else:
+                h["origin"].fill_(self._as_i32(h["desc"].launch_index))  # every clip's frame 0 is the next launch
         else:
             self._flat.zero_()
             self.hist.zero_()
         self.frames_done = 0
         self._clip_f0[:] = 0
+        self._calls = 0
+        self._clip_c0[:] = 0
 
     @staticmethod
     def _as_i32(v: int) -> int:  # a launch index (uint32) as the int32 a fill writes
@@ -267,8 +405,11 @@ class FullbandStreamingSession:
         if not idx:
             return
         self._clip_f0[idx] = self.frames_done
+        self._clip_c0[idx] = self._calls
         if self._hop is not None:  # (a fill behind the queued launches: none of them sees the new origin)
-            org = self._as_i32(self._hop["desc"].launch_index)
+            # the launch that computes the clips' frame 0: the next one -- in waveform mode the one after (the next call is the
+            # clips' first, which has no frame yet)
+            org = self._as_i32(self._hop["desc"].launch_index + (1 if self.waveform else 0))
             for b in idx:
                 self._hop["origin"][b:b + 1].fill_(org)
             return
@@ -277,7 +418,10 @@ class FullbandStreamingSession:
             self.hist[b].zero_()
 
     def clip_frames(self) -> np.ndarray:
-        """int64 [B]: the frames each clip has seen since its own utterance began."""
+        """int64 [B]: the frames each clip has seen since its own utterance began (waveform sessions, as the kernel counts them: the
+        calls since the clip's origin minus one, floored at zero -- a clip's first call has no frame yet)."""
+        if self.waveform:
+            return np.maximum(self._calls - self._clip_c0 - 1, 0)
         return self.frames_done - self._clip_f0
 
     def check_errors(self) -> None:

@@ -69,20 +69,28 @@ class Model(_EngineMixin, nn.Module):
         and ``df_order - 1`` frames of history kept on the device, bit-identical to the offline forward on the concatenated input.
         ``one_launch``: True = the whole hop in one ``sfsn_fullband_stream_hop`` launch (``NotImplementedError`` where it does not cover
         the model), False = the offline kernels on the new frames (from a HIP graph when ``graph``), "auto" = the faster one that
-        applies.  GSN models on a HIP device, spectra in and out."""
+        applies.  ``waveform=True``: samples in, samples out -- ``step_wave(samples [B, 128])`` returns ``[B, S, 128]`` enhanced samples,
+        the frame's STFT, the hop and the inverse STFT in one ``sfsn_fullband_stream_hop_wave`` launch, bit-identical to
+        ``model(wave)`` three calls later (``hop == 1``, 512-point frames with hop 128, ``B <= 16``, shared gate weights; anything else
+        has no waveform tier: ``NotImplementedError``).  ``host_io=True`` (with ``waveform``): ``step_wave_host`` takes and returns CPU
+        tensors through pinned host memory, no copy launch and no stream synchronisation.  ``resident`` and ``count_spikes`` are not
+        built for this model.  GSN models on a HIP device."""
         if self.fb_model.sequence_model_name == "LSTM":
             raise NotImplementedError("cIRM-GSN streaming covers the GSN sequence model: an LSTM model runs on ATen and has no session")
-        for name, on in (("waveform", waveform), ("host_io", host_io), ("resident", resident), ("count_spikes", count_spikes)):
+        for name, on in (("resident", resident), ("count_spikes", count_spikes)):
             if on:
-                raise NotImplementedError(f"cIRM-GSN streaming: {name}=True is not built yet (a follow-up; the Spiking-FullSubNet "
-                                          "sessions have it) -- sessions take and return spectra")
+                raise NotImplementedError(f"cIRM-GSN streaming: {name}=True is not built (the Spiking-FullSubNet sessions have it)")
         self._check_mode()
         if batch < 1 or hop < 1:
             raise ValueError("batch and hop must be positive")
         if next(self.parameters()).device.type != "cuda":
-            raise NotImplementedError("cIRM-GSN streaming has no CPU path: move the module to a HIP device (`.to('cuda')`) first")
+            # (before anything else about these options is judged: host_io without waveform is a ValueError on a HIP module)
+            asked = [f"{name}=True: " for name, on in (("waveform", waveform), ("host_io", host_io)) if on]
+            raise NotImplementedError((asked[0] if asked else "") + "cIRM-GSN streaming has no CPU path: move the module to a HIP "
+                                      "device (`.to('cuda')`) first")
         from .fullband_streaming import FullbandStreamingSession
-        return FullbandStreamingSession(self.engine(), batch=batch, hop=hop, graph=graph, one_launch=one_launch, owner=self)
+        return FullbandStreamingSession(self.engine(), batch=batch, hop=hop, graph=graph, one_launch=one_launch, owner=self,
+                                        waveform=waveform, host_io=host_io, frame=(self.n_fft, self.hop_length, self.win_length))
 
     def forward(self, input):
         assert input.ndim == 2, f"Input tensor must be 2D, but got {input.ndim}D."
