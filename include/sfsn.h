@@ -773,6 +773,16 @@ typedef struct {
 int sfsn_fullband_hop_check(int Hp, int n_layers, int F, int S, int df, int B, int hop, int D, int unshared);
 size_t sfsn_fullband_hop_scratch_bytes(const sfsn_fullband_hop_desc* desc); /* 0: not covered (host only) */
 int sfsn_fullband_stream_hop(const sfsn_fullband_hop_desc* desc, void* stream);
+/* The same launch with running spike counts (SynOPs of a streaming clip).  spike_slots: sfsn_fullband_hop_spike_slots(desc) words on the
+ * device, zeroed by the caller to reset.  Layout: layer by layer; within a layer [B][Hp / 4]: slot (b, j) counts the spikes of neurons
+ * 4j .. 4j + 3 of clip b (the padded neurons Hp - H never spike).  One lane of the launch owns each slot and adds, once per launch, the
+ * spikes of the `hop` frames it computed (plain per-lane load + store: no atomics).  With clip_start: in the launch that restarts
+ * clip b its slots read as zero instead of being loaded, as h and c do.  Everything else -- results, state, scratch, coverage -- is
+ * sfsn_fullband_stream_hop's, which stays the launch of sessions that do not count (a kernel of its own).  NULL or 4-byte-misaligned
+ * spike_slots: SFSN_EINVAL.  The waveform launch has no counted form.
+ * (Added without an ABI bump: no existing struct or signature changed.) */
+size_t sfsn_fullband_hop_spike_slots(const sfsn_fullband_hop_desc* desc); /* n_layers * B * Hp / 4; 0: not covered (host only) */
+int sfsn_fullband_stream_hop_counted(const sfsn_fullband_hop_desc* desc, unsigned* spike_slots, void* stream);
 
 /* ----------------------------------------------------------------------------------------------------
  * Waveform mode of the cIRM-GSN hop: 128 new samples per clip in, 128 enhanced samples per clip and speaker out, in ONE launch -- the

@@ -3,6 +3,7 @@
 BatchNorm, LayerNorm, shared gates), B clips, `hop` frames per step.  The legs, alternated block by block in one process:
 
     one_launch   sfsn_fullband_stream_hop, one launch per hop
+    counted      the same with count_spikes=True: sfsn_fullband_stream_hop_counted, per-lane spike slots inside the launch
     graph        the per-kernel sequence replayed from its HIP graph
     eager        the per-kernel sequence launched kernel by kernel
     wave         (hop 1) samples in, samples out on the device: sfsn_fullband_stream_hop_wave, step_wave(copy=False) + synchronise
@@ -29,7 +30,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from test_cirm_gsn import recipe_model  # noqa: E402
 
-LEGS = {"one_launch": dict(one_launch=True), "graph": dict(one_launch=False, graph=True), "eager": dict(one_launch=False, graph=False),
+LEGS = {"one_launch": dict(one_launch=True), "counted": dict(one_launch=True, count_spikes=True), "graph": dict(one_launch=False, graph=True), "eager": dict(one_launch=False, graph=False),
         "wave": dict(waveform=True), "wave_host": dict(waveform=True, host_io=True)}
 WAVE_LEGS = ("wave", "wave_host")
 

@@ -295,6 +295,10 @@ def lib() -> ctypes.CDLL:
     L.sfsn_fullband_hop_scratch_bytes.argtypes = [ctypes.POINTER(FullbandHopDesc)]
     L.sfsn_fullband_stream_hop.restype = _I
     L.sfsn_fullband_stream_hop.argtypes = [ctypes.POINTER(FullbandHopDesc), _P]
+    L.sfsn_fullband_hop_spike_slots.restype = ctypes.c_size_t  # words of spike_slots; 0: not covered (host only)
+    L.sfsn_fullband_hop_spike_slots.argtypes = [ctypes.POINTER(FullbandHopDesc)]
+    L.sfsn_fullband_stream_hop_counted.restype = _I  # desc, spike_slots, stream
+    L.sfsn_fullband_stream_hop_counted.argtypes = [ctypes.POINTER(FullbandHopDesc), _P, _P]
     L.sfsn_fullband_wave_hop_check.restype = _I  # Hp, n_layers, F, S, df, B, unshared (host only)
     L.sfsn_fullband_wave_hop_check.argtypes = [_I] * 7
     L.sfsn_fullband_stream_hop_wave.restype = _I
@@ -316,7 +320,8 @@ EXPORTS = ("sfsn_abi_version", "sfsn_source_hash", "sfsn_strerror", "sfsn_device
            "sfsn_hop_spike_slots", "sfsn_spike_count_rows", "sfsn_fullband_features", "sfsn_fullband_input_proj",
            "sfsn_fullband_proj_deepfilter", "sfsn_fullband_deepfilter_fwd", "sfsn_fullband_deepfilter_bwd",
            "sfsn_fullband_hop_check", "sfsn_fullband_hop_scratch_bytes", "sfsn_fullband_stream_hop",
-           "sfsn_fullband_wave_hop_check", "sfsn_fullband_stream_hop_wave")
+           "sfsn_fullband_wave_hop_check", "sfsn_fullband_stream_hop_wave", "sfsn_fullband_hop_spike_slots",
+           "sfsn_fullband_stream_hop_counted")
 
 
 def check(rc: int, what: str = "") -> None:

@@ -29,6 +29,10 @@
 // Every granule is written in every launch for every clip, whatever the clip's frame index: the consumers wait on all of them.  The
 // spectrum kernel is compiled without any of this (template parameter WAVE): its code is what it was (profiles/cirm_streaming.md).
 //
+// Spike counts (sfsn_fullband_stream_hop_counted): a third kernel, the spectrum hop with the layer role's COUNT form -- every lane that
+// stores spikes adds the set bytes of its words over the launch's frames into a slot of its own (include/sfsn.h).  The other two
+// kernels are compiled without it.
+//
 // Arithmetic: sfsn_fullband_dev.h's expressions (shared with the offline kernels) and scan_body's cell: bit-identical to
 // FullbandEngine.forward_stft on the concatenated input (tests/test_cirm_streaming.py).
 #include <hip/hip_runtime.h>
@@ -189,8 +193,11 @@ __device__ __forceinline__ void fbh_input_role(const FbhParams& p, char* smem) {
 // barrier), so it alternates hbA / hbB by frame parity instead: frame t + 2's writes come behind frame t + 1's barrier, which every
 // wave passes after it has read frame t's fragments.
 // ---------------------------------------------------------------------------------------------------------------------
-template <bool L0>
-__device__ __forceinline__ void fbh_layer_role(const FbhParams& p, int l, int part, char* smem) {
+// COUNT (sfsn_fullband_stream_hop_counted): the lane also keeps the running spike count of its four neurons of its clip row in the slot
+// it alone owns, slots[(l B + row) Hp / 4 + cc / 4] -- requested with the carried state, read as zero where the clip restarts, written
+// back once per launch (plain load + store).  Without COUNT nothing of this is compiled: the role is the uncounted launches' code.
+template <bool L0, bool COUNT = false>
+__device__ __forceinline__ void fbh_layer_role(const FbhParams& p, int l, int part, char* smem, [[maybe_unused]] unsigned* slots = nullptr) {
     const FbhLayerDev& L = p.layer[l];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -224,6 +231,10 @@ __device__ __forceinline__ void fbh_layer_role(const FbhParams& p, int l, int pa
         }
     v4f c = {0.0f, 0.0f, 0.0f, 0.0f};
     if (!fresh) c = *reinterpret_cast<const v4f*>(L.c + (size_t)rowc * H + cc);
+    [[maybe_unused]] unsigned nspk = 0;  // COUNT: my slot's value so far, then + the spikes of this launch's frames
+    if constexpr (COUNT) {
+        if (active && row < R && !fresh) nspk = slots[((size_t)l * R + row) * (H >> 2) + (cc >> 2)];
+    }
     const v4f dq = *reinterpret_cast<const v4f*>(L.w_hh_dq + cc);
     const v4f bf = *reinterpret_cast<const v4f*>(L.bias + cc);
     const v4f bg = *reinterpret_cast<const v4f*>(L.bias + H + cc);
@@ -311,10 +322,12 @@ __device__ __forceinline__ void fbh_layer_role(const FbhParams& p, int l, int pa
             pk |= (y >= 0.0f) ? (1u << (8 * r)) : 0u;
         }
         if (active && row < R) st_agent(L.spikes + ((size_t)t * R + row) * HP + cc, pk | tagw);  // data + tag: published
+        if constexpr (COUNT) nspk += (unsigned)__builtin_popcount(pk);  // (bytes 0/1: a popcount)
     }
     if (active && row < R) {
         *reinterpret_cast<v4f*>(L.c + (size_t)row * H + cc) = c;
         st_agent(hnext + (size_t)row * HP + cc, pk);
+        if constexpr (COUNT) slots[((size_t)l * R + row) * (H >> 2) + (cc >> 2)] = nspk;
     }
 }
 
@@ -468,6 +481,25 @@ __global__ __launch_bounds__(HOP_THREADS) void fullband_stream_hop_kernel(const 
     }
     fbh_proj_role<false>(p, li - p.nl * p.wpl, smem);
 }
+// The counting launch, a kernel of its own (sessions that do not count keep the kernel above): the same roles, the layer role with COUNT
+__global__ __launch_bounds__(HOP_THREADS) void fullband_stream_hop_counted_kernel(const FbhParams p, unsigned* slots) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int bi = (int)blockIdx.x;
+    if (bi < p.nwg_in) {
+        fbh_input_role<false>(p, smem);
+        return;
+    }
+    const int li = bi - p.nwg_in;
+    if (li < p.nl * p.wpl) {
+        const int l = li / p.wpl, part = li - l * p.wpl;
+        if (l == 0)
+            fbh_layer_role<true, true>(p, 0, part, smem, slots);
+        else
+            fbh_layer_role<false, true>(p, l, part, smem, slots);
+        return;
+    }
+    fbh_proj_role<false>(p, li - p.nl * p.wpl, smem);
+}
 // Waveform mode, a kernel of its own (the spectrum kernel keeps its code and its register allocation): the STFT in front, the inverse
 // STFT behind -- producers keep lower block indices than their consumers
 __global__ __launch_bounds__(HOP_THREADS) void fullband_stream_hop_wave_kernel(const FbhParams p) {
@@ -513,6 +545,14 @@ __global__ __launch_bounds__(HOP_THREADS) void fbh_role_layer0_kernel(const FbhP
 __global__ __launch_bounds__(HOP_THREADS) void fbh_role_layer_kernel(const FbhParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     fbh_layer_role<false>(p, 1, (int)blockIdx.x, smem);
+}
+__global__ __launch_bounds__(HOP_THREADS) void fbh_role_layer0_counted_kernel(const FbhParams p, unsigned* slots) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    fbh_layer_role<true, true>(p, 0, (int)blockIdx.x, smem, slots);
+}
+__global__ __launch_bounds__(HOP_THREADS) void fbh_role_layer_counted_kernel(const FbhParams p, unsigned* slots) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    fbh_layer_role<false, true>(p, 1, (int)blockIdx.x, smem, slots);
 }
 __global__ __launch_bounds__(HOP_THREADS) void fbh_role_proj_kernel(const FbhParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -589,8 +629,13 @@ extern "C" size_t sfsn_fullband_hop_scratch_bytes(const sfsn_fullband_hop_desc* 
 
 static bool aligned8(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 7u) == 0; }
 
-// the launch of both modes; w != nullptr: waveform mode (d = &w->hop)
-static int fbh_launch(const sfsn_fullband_hop_desc* d, const sfsn_fullband_wave_desc* w, void* stream) {
+extern "C" size_t sfsn_fullband_hop_spike_slots(const sfsn_fullband_hop_desc* d) {
+    if (!d || sfsn_fullband_hop_check(d->Hp, d->n_layers, d->F, d->S, d->df, d->B, d->hop, d->D, d->unshared) != SFSN_OK) return 0;
+    return (size_t)d->n_layers * d->B * (d->Hp / 4);
+}
+
+// the launch of every mode; w != nullptr: waveform mode (d = &w->hop); slots != nullptr: the counting spectrum launch
+static int fbh_launch(const sfsn_fullband_hop_desc* d, const sfsn_fullband_wave_desc* w, void* stream, unsigned* slots = nullptr) {
     FbhParams p;
     size_t lds;
     const int rc = fbh_plan(p, lds, d, w != nullptr);
@@ -631,10 +676,16 @@ static int fbh_launch(const sfsn_fullband_hop_desc* d, const sfsn_fullband_wave_
     if (p.nblocks > cu_count()) return SFSN_EUNSUPPORTED;
     if (lds > 160 * 1024) return SFSN_EUNSUPPORTED;
     if (w) return launch_lds<fullband_stream_hop_wave_kernel>(dim3(p.nblocks), dim3(HOP_THREADS), lds, static_cast<hipStream_t>(stream), p);
+    if (slots) return launch_lds<fullband_stream_hop_counted_kernel>(dim3(p.nblocks), dim3(HOP_THREADS), lds, static_cast<hipStream_t>(stream), p, slots);
     return launch_lds<fullband_stream_hop_kernel>(dim3(p.nblocks), dim3(HOP_THREADS), lds, static_cast<hipStream_t>(stream), p);
 }
 
 extern "C" int sfsn_fullband_stream_hop(const sfsn_fullband_hop_desc* d, void* stream) { return fbh_launch(d, nullptr, stream); }
+
+extern "C" int sfsn_fullband_stream_hop_counted(const sfsn_fullband_hop_desc* d, unsigned* spike_slots, void* stream) {
+    if (!spike_slots || (reinterpret_cast<uintptr_t>(spike_slots) & 3u) != 0) return SFSN_EINVAL;
+    return fbh_launch(d, nullptr, stream, spike_slots);
+}
 
 extern "C" int sfsn_fullband_stream_hop_wave(const sfsn_fullband_wave_desc* w, void* stream) {
     if (!w) return SFSN_EINVAL;

@@ -22,8 +22,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import FusedInput, ScanSegment, check
-from .engine import ErrorWords, _dev, _ptr, fill_segment, fold_batchnorm, pack_w3
+from ._lib import MAX_COUNT_TENSORS, FusedInput, RowCount, ScanSegment, check
+from .engine import ErrorWords, SpikeSummary, _dev, _ptr, fill_segment, fold_batchnorm, pack_w3
 
 ACTIVATIONS = {"tanh": _lib.ACT_TANH, "sigmoid": _lib.ACT_SIGMOID, "relu": _lib.ACT_RELU}
 
@@ -281,9 +281,13 @@ class FullbandEngine:
         self._count("projdf")
 
     @torch.no_grad()
-    def forward_stft(self, noisy_cmp: torch.Tensor, want_layers: bool = False) -> dict:
+    def forward_stft(self, noisy_cmp: torch.Tensor, want_layers: bool = False, want_counts: bool = False) -> dict:
         """complex64 [B, F, T] on the device -> dict(enh_stft complex [B, S, F, T], enh_mag [B, S, F, T] (num_spks == 1) or None,
-        all_layers = [x [T, B, F], spikes [T, B, H] per layer, proj [T, B, P]] when want_layers, else None)."""
+        all_layers = [x [T, B, F], spikes [T, B, H] per layer, proj [T, B, P]] when want_layers, else None).  want_counts: also
+        clip_counts, int64 [layers, B] -- every layer's spikes per clip, counted on the device from the int8 spikes the scans write
+        (one sfsn_spike_count_rows launch); without want_layers no fp32 spike or projection tensor is allocated and all_layers is
+        [x] + [SpikeSummary(count over the clips, (T, B, H)) per layer] + [proj (T, B, P), shape only (a meta tensor)]: all that
+        metric.compute_synops / compute_neuronops read."""
         spec, L, Hp, G, F = self.spec, self.lib, self.Hp, self.G, self.F
         if noisy_cmp.device != self.device or noisy_cmp.dtype != torch.complex64 or noisy_cmp.ndim != 3 or noisy_cmp.shape[1] != F:
             raise ValueError(f"expected complex64 [B, {F}, T] on {self.device}, got {noisy_cmp.dtype} {tuple(noisy_cmp.shape)} "
@@ -304,6 +308,18 @@ class FullbandEngine:
         proj = torch.empty((T, B, spec.P), **f32) if want_layers else None
         self._launch_frames(ri, B, T, 0, T, stack, ws, x, states, spk, proj, enh, mag)
         out = dict(enh_stft=torch.view_as_complex(enh), enh_mag=mag, all_layers=None)
+        if want_counts:  # SynOPs without the fp32 spike tensors: the workspace's int8 spikes [T][B][HP8] (pad columns zero), a row per clip
+            counts = out["clip_counts"] = torch.zeros((nl, B), dtype=torch.int64, device=dev)
+            for l0 in range(0, nl, MAX_COUNT_TENSORS):
+                arr = (RowCount * min(MAX_COUNT_TENSORS, nl - l0))()
+                for j in range(len(arr)):
+                    arr[j].spikes_i8, arr[j].T, arr[j].R, arr[j].HP, arr[j].rows_per_clip = _ptr(ws["s8"][l0 + j]), T, B, self.HP8, 1
+                    arr[j].counts = _ptr(counts[l0 + j])
+                check(L.sfsn_spike_count_rows(arr, len(arr), 0, T, st), "sfsn_spike_count_rows")
+                self._count("spike_count")
         if want_layers:
             out["all_layers"] = [x] + [s[:, :, :self.H] for s in spk] + [proj]
+        elif want_counts:
+            out["all_layers"] = [x] + [SpikeSummary(c, (T, B, self.H)) for c in counts.sum(1)] + \
+                                [torch.empty((T, B, spec.P), dtype=torch.float32, device="meta")]
         return out

@@ -32,8 +32,14 @@ writes the enhanced samples and a completion word per (clip, speaker) back into 
 synchronisation.  Waveform sessions exist on the one-launch kernel only (``hop == 1``, 512-point frames with hop 128, ``B <= 16``,
 shared gate weights); anything else has no waveform tier and raises ``NotImplementedError``.
 
-Not covered here: ``resident`` and ``count_spikes`` sessions, waveform sessions beyond 16 clips or with separate gate weights, and
-LSTM models.
+Spike counts (``count_spikes=True``, spectrum sessions): the session counts every layer's spikes per clip as it runs, and
+``spike_summary(clips)`` returns them in the form of the offline forward's ``want_counts`` list, so that
+``metric.compute_synops(session.spike_summary([b]), [], shared_weights=...)`` is clip b's SynOPs.  The one-launch hop adds each
+launch's spikes into per-lane slots (``sfsn_fullband_stream_hop_counted``, still one launch per hop; a restarted clip's slots read as
+zero); the per-kernel sequence ends with one per-clip count launch (``sfsn_spike_count_rows``), captured with the rest.
+
+Not covered here: ``resident`` sessions, ``count_spikes`` together with ``waveform``, waveform sessions beyond 16 clips or with
+separate gate weights, and LSTM models.
 """
 from __future__ import annotations
 
@@ -46,8 +52,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import FullbandHopDesc, FullbandWaveDesc, check
-from .engine import _ptr
+from ._lib import MAX_COUNT_TENSORS, FullbandHopDesc, FullbandWaveDesc, RowCount, check
+from .engine import SpikeSummary, _ptr
 from .fullband_engine import FullbandEngine
 
 # what one_launch="auto" takes where sfsn_fullband_stream_hop covers the session: the tier that measured faster at the recipe
@@ -91,10 +97,11 @@ def wave_refusal(engine: FullbandEngine, batch: int, hop: int, frame=None) -> Op
 
 class FullbandStreamingSession:
     """``step(frames [B, F, hop] complex64) -> (enh_stft [B, S, F, hop], enh_mag [B, S, F, hop] or None when S > 1)``;
-    ``waveform=True``: ``step_wave(samples [B, 128] float32) -> [B, S, 128]`` (``host_io=True``: ``step_wave_host``, CPU tensors)."""
+    ``waveform=True``: ``step_wave(samples [B, 128] float32) -> [B, S, 128]`` (``host_io=True``: ``step_wave_host``, CPU tensors);
+    ``count_spikes=True``: ``spike_summary(clips)`` (spectrum sessions)."""
 
     def __init__(self, engine: FullbandEngine, batch: int = 1, hop: int = 1, graph: bool = True, one_launch="auto", owner=None,
-                 waveform: bool = False, host_io: bool = False, frame=None):
+                 waveform: bool = False, host_io: bool = False, frame=None, count_spikes: bool = False):
         if batch < 1 or hop < 1:
             raise ValueError("batch and hop must be positive")
         if one_launch not in ("auto", True, False):
@@ -102,6 +109,13 @@ class FullbandStreamingSession:
         self.waveform, self.host_io = bool(waveform), bool(host_io)
         if self.host_io and not self.waveform:
             raise ValueError("host_io goes with waveform=True")
+        # count_spikes: per-clip spike counts of every layer (spike_summary) -- the one-launch hop keeps them in its slots (`_hop["slots"]`),
+        # the per-kernel sequence in `_rows` [layers, B] int64, filled by one sfsn_spike_count_rows launch per step
+        self.count_spikes = bool(count_spikes)
+        self._rows = None
+        if self.count_spikes and self.waveform:
+            raise NotImplementedError("count_spikes=True with waveform=True: sfsn_fullband_stream_hop_wave has no counted form (count on a "
+                                      "spectrum session)")
         if self.waveform:
             if one_launch is False:
                 raise ValueError("waveform=True runs on the one-launch kernel only (one_launch='auto' or True)")
@@ -178,8 +192,13 @@ class FullbandStreamingSession:
         assert nbytes, "sfsn_fullband_hop_check accepted this geometry"
         scratch = torch.zeros((nbytes // 4,), dtype=torch.int32, device=dev)  # word 0: the error word
         d.scratch, d.scratch_bytes, d.launch_index = scratch.data_ptr(), nbytes, 0
+        slots = None
+        if self.count_spikes:  # running spike counts, one word per lane that writes 4 neurons of a clip row (include/sfsn.h)
+            n = eng.lib.sfsn_fullband_hop_spike_slots(ctypes.byref(d))
+            assert n == nl * B * (Hp // 4), (n, nl, B, Hp)
+            slots = torch.zeros((n,), dtype=torch.int32, device=dev)
         self._hop = dict(desc=d, ref=ctypes.byref(d), st=st, work=work, enh=torch.view_as_complex(enh), mag=mag, origin=origin,
-                         scratch=scratch, err=torch.zeros((1,), dtype=torch.int32).pin_memory(), err_pending=False)
+                         scratch=scratch, slots=slots, err=torch.zeros((1,), dtype=torch.int32).pin_memory(), err_pending=False)
         if wd is not None:
             self._build_wave(wd)
 
@@ -268,9 +287,13 @@ class FullbandStreamingSession:
         d = h["desc"]
         d.inp_ri = frames.data_ptr()
         with torch.cuda.device(self.dev):  # the C ABI launches on the calling thread's current device
-            rc = self.eng.lib.sfsn_fullband_stream_hop(h["ref"], ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream))
+            st = ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+            if h["slots"] is not None:
+                rc = self.eng.lib.sfsn_fullband_stream_hop_counted(h["ref"], ctypes.c_void_p(h["slots"].data_ptr()), st)
+            else:
+                rc = self.eng.lib.sfsn_fullband_stream_hop(h["ref"], st)
         if rc:
-            check(rc, "sfsn_fullband_stream_hop")
+            check(rc, "sfsn_fullband_stream_hop_counted" if h["slots"] is not None else "sfsn_fullband_stream_hop")
         d.launch_index = (d.launch_index + 1) & 0xFFFFFFFF
         self._count("hop")
         if (self.frames_done + self.hop) % 256 < self.hop:  # every ~256 frames the error word follows the launches into pinned memory
@@ -291,6 +314,16 @@ class FullbandStreamingSession:
         self._states = [(self._flat[l, 0], self._flat[l, 1]) for l in range(nl)]
         self.enh = torch.zeros((B, S, F, Th), dtype=torch.complex64, device=dev)
         self.enh_mag = torch.zeros((B, S, F, Th), **f32) if S == 1 else None
+        self._row_jobs = []
+        if self.count_spikes:  # the workspace's int8 spikes [Th][B][HP8], one row per clip; frames [D, D + hop) are this step's
+            self._rows = torch.zeros((nl, B), dtype=torch.int64, device=dev)
+            for l0 in range(0, nl, MAX_COUNT_TENSORS):
+                arr = (RowCount * min(MAX_COUNT_TENSORS, nl - l0))()
+                for j in range(len(arr)):
+                    t = self._ws["s8"][l0 + j]
+                    arr[j].spikes_i8, arr[j].T, arr[j].R, arr[j].HP, arr[j].rows_per_clip = _ptr(t), t.shape[0], t.shape[1], t.shape[2], 1
+                    arr[j].counts = _ptr(self._rows[l0 + j])
+                self._row_jobs.append(arr)
 
     def _enqueue(self) -> None:
         """One hop on torch's current stream: the history shift, then the offline forward's launches on frames [D, D + hop)."""
@@ -308,6 +341,10 @@ class FullbandStreamingSession:
             before = dict(eng.launches)
             eng._launch_frames(ri, B, self.Th, D, hop, self._stack, self._ws, self._x, self._states, [None] * len(self._states), None,
                                torch.view_as_real(self.enh), self.enh_mag)
+            for arr in self._row_jobs:  # count_spikes: the new frames' spikes per clip (one launch up to 16 layers; capturable)
+                check(eng.lib.sfsn_spike_count_rows(arr, len(arr), D, hop, ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)),
+                      "sfsn_spike_count_rows")
+                eng._count("spike_count")
             self._last = {k: v - before.get(k, 0) for k, v in eng.launches.items() if v != before.get(k, 0)}
 
     def _capture(self) -> None:
@@ -357,10 +394,10 @@ class FullbandStreamingSession:
         return e, m
 
     def reset(self, clips=None) -> None:
-        """Back to the start of an utterance: zero (h, c) and zero history.  ``clips`` (a sequence or 1-D tensor of clip indices): only
-        these clips restart, at their next step; the others go on as if nothing happened.  Ordered with the steps on torch's current
-        stream, no synchronisation.  ``clips=None``: the whole session (also checks the error word and that the module's parameters
-        have not changed since the session packed them)."""
+        """Back to the start of an utterance: zero (h, c), zero history and zero spike counts.  ``clips`` (a sequence or 1-D tensor of
+        clip indices): only these clips restart, at their next step; the others go on as if nothing happened.  Ordered with the steps
+        on torch's current stream, no synchronisation.  ``clips=None``: the whole session (also checks the error word and that the
+        module's parameters have not changed since the session packed them)."""
         if clips is not None:
             self._reset_clips(clips)
             return
@@ -379,9 +416,13 @@ class FullbandStreamingSession:
                 h["origin"].fill_(self._as_i32(h["desc"].launch_index + 1))
             else:
                 h["origin"].fill_(self._as_i32(h["desc"].launch_index))  # every clip's frame 0 is the next launch
+            if h["slots"] is not None:
+                h["slots"].zero_()
         else:
             self._flat.zero_()
             self.hist.zero_()
+            if self._rows is not None:
+                self._rows.zero_()
         self.frames_done = 0
         self._clip_f0[:] = 0
         self._calls = 0
@@ -392,7 +433,7 @@ class FullbandStreamingSession:
         v &= 0xFFFFFFFF
         return v - (1 << 32) if v >= 1 << 31 else v
 
-    def _reset_clips(self, clips) -> None:
+    def _clip_indices(self, clips) -> list:
         if isinstance(clips, (torch.Tensor, np.ndarray)) and clips.ndim != 1:
             raise TypeError("clips: a 1-D tensor or a sequence of clip indices")
         items = clips.tolist() if isinstance(clips, (torch.Tensor, np.ndarray)) else list(clips)
@@ -402,13 +443,17 @@ class FullbandStreamingSession:
         bad = [i for i in idx if not 0 <= i < self.B]
         if bad:
             raise IndexError(f"clip index {bad[0]} out of range for a session of {self.B} clips")
+        return idx
+
+    def _reset_clips(self, clips) -> None:
+        idx = self._clip_indices(clips)
         if not idx:
             return
         self._clip_f0[idx] = self.frames_done
         self._clip_c0[idx] = self._calls
         if self._hop is not None:  # (a fill behind the queued launches: none of them sees the new origin)
             # the launch that computes the clips' frame 0: the next one -- in waveform mode the one after (the next call is the
-            # clips' first, which has no frame yet)
+            # clips' first, which has no frame yet).  Spike slots: read as zero in that launch, as h and c are
             org = self._as_i32(self._hop["desc"].launch_index + (1 if self.waveform else 0))
             for b in idx:
                 self._hop["origin"][b:b + 1].fill_(org)
@@ -416,6 +461,8 @@ class FullbandStreamingSession:
         for b in idx:  # the per-kernel sequence: the clips' rows of the states and their history, in stream order
             self._flat[:, :, b].zero_()
             self.hist[b].zero_()
+            if self._rows is not None:
+                self._rows[:, b].zero_()
 
     def clip_frames(self) -> np.ndarray:
         """int64 [B]: the frames each clip has seen since its own utterance began (waveform sessions, as the kernel counts them: the
@@ -423,6 +470,39 @@ class FullbandStreamingSession:
         if self.waveform:
             return np.maximum(self._calls - self._clip_c0 - 1, 0)
         return self.frames_done - self._clip_f0
+
+    def spike_summary(self, clips=None) -> list:
+        """The model's layer list of the selected clips' current utterances (``clips=None``: every clip), shaped like the offline
+        forward's ``want_counts`` list over ``clip_frames()`` frames: ``[x (T, nb, F)] + [SpikeSummary (T, nb, H) per layer] +
+        [proj (T, nb, P)]``, input and projection entries shape-only (meta tensors), spike entries with the exact spike count of the
+        selected clips.  ``H`` is the model's hidden size: the padded neurons never spike and do not enter the rate's denominator.
+        Counts are summed on the device (nothing synchronises until they are read).  So
+        ``metric.compute_synops(session.spike_summary([b]), [], shared_weights=...)`` is clip b's SynOPs.  The selected clips must
+        have seen the same number of frames (``ValueError`` otherwise); the session must have been opened with ``count_spikes=True``
+        (``RuntimeError``)."""
+        if not self.count_spikes:
+            raise RuntimeError("open the session with count_spikes=True to count spikes")
+        if clips is None:
+            idx = list(range(self.B))
+        else:
+            idx = self._clip_indices(clips)
+            if not idx:
+                raise ValueError("clips: no clip selected")
+        frames = self.clip_frames()[idx]
+        if (frames != frames[0]).any():
+            raise ValueError(f"spike_summary: the selected clips have seen different numbers of frames {frames.tolist()}; select "
+                             "clips whose utterances are equally long")
+        T, nb = int(frames[0]), len(idx)
+        eng, nl = self.eng, self.eng.spec.layers
+        if self._hop is not None:  # (include/sfsn.h: layer by layer, [B][Hp / 4])
+            counts = self._hop["slots"].view(nl, self.B, -1)[:, idx].sum((1, 2), dtype=torch.int64)
+        else:
+            counts = self._rows[:, idx].sum(1)
+
+        def meta(*shape):
+            return torch.empty(shape, dtype=torch.float32, device="meta")
+
+        return [meta(T, nb, self.F)] + [SpikeSummary(counts[l], (T, nb, eng.H)) for l in range(nl)] + [meta(T, nb, eng.spec.P)]
 
     def check_errors(self) -> None:
         """Raise if a bounded hand-off wait expired inside an earlier launch (blocks until the steps enqueued so far have finished)."""

@@ -10,7 +10,8 @@ return values (:206-245).  A recipe switches over by changing only
 
 In ``eval()`` mode a GSN model runs everything between ``stft`` and ``istft`` on the gfx950 kernels through ``FullbandEngine``; an
 LSTM model runs its sequence model on ATen (``training.sequence_model``) and the deep filter as torch operations.  ``streaming()``
-opens a frame-by-frame session of a GSN model (``fullband_streaming.py``).
+opens a frame-by-frame session of a GSN model (``fullband_streaming.py``).  Spike counts for SynOPs: ``layer_outputs = "counts"``
+(the two-speaker ``forward``), ``forward_stft(want_counts=True)`` and ``streaming(count_spikes=True)`` + ``session.spike_summary``.
 
 In ``train()`` mode -- or in ``eval()`` mode with grad enabled and an input that requires grad (or ``autograd_in_eval = True``) --
 ``forward()`` takes the differentiable path ``training.forward_cirm``: the GSN stack on the one-launch training layer calls of
@@ -73,24 +74,35 @@ class Model(_EngineMixin, nn.Module):
         the frame's STFT, the hop and the inverse STFT in one ``sfsn_fullband_stream_hop_wave`` launch, bit-identical to
         ``model(wave)`` three calls later (``hop == 1``, 512-point frames with hop 128, ``B <= 16``, shared gate weights; anything else
         has no waveform tier: ``NotImplementedError``).  ``host_io=True`` (with ``waveform``): ``step_wave_host`` takes and returns CPU
-        tensors through pinned host memory, no copy launch and no stream synchronisation.  ``resident`` and ``count_spikes`` are not
-        built for this model.  GSN models on a HIP device."""
+        tensors through pinned host memory, no copy launch and no stream synchronisation.  ``count_spikes=True`` (spectrum sessions, both
+        tiers): per-clip spike counts of every layer, kept on the device as the session runs, for ``session.spike_summary(clips)`` --
+        ``metric.compute_synops(session.spike_summary([b]), [], shared_weights=...)`` is clip b's SynOPs; together with ``waveform``
+        it raises ``NotImplementedError`` (the waveform launch does not count).  ``resident`` is not built for this model.  GSN models
+        on a HIP device."""
         if self.fb_model.sequence_model_name == "LSTM":
             raise NotImplementedError("cIRM-GSN streaming covers the GSN sequence model: an LSTM model runs on ATen and has no session")
-        for name, on in (("resident", resident), ("count_spikes", count_spikes)):
-            if on:
-                raise NotImplementedError(f"cIRM-GSN streaming: {name}=True is not built (the Spiking-FullSubNet sessions have it)")
+        if resident:
+            raise NotImplementedError("cIRM-GSN streaming: resident=True is not built (the Spiking-FullSubNet sessions have it)")
         self._check_mode()
         if batch < 1 or hop < 1:
             raise ValueError("batch and hop must be positive")
         if next(self.parameters()).device.type != "cuda":
             # (before anything else about these options is judged: host_io without waveform is a ValueError on a HIP module)
-            asked = [f"{name}=True: " for name, on in (("waveform", waveform), ("host_io", host_io)) if on]
+            asked = [f"{name}=True: " for name, on in (("waveform", waveform), ("host_io", host_io), ("count_spikes", count_spikes)) if on]
             raise NotImplementedError((asked[0] if asked else "") + "cIRM-GSN streaming has no CPU path: move the module to a HIP "
                                       "device (`.to('cuda')`) first")
         from .fullband_streaming import FullbandStreamingSession
         return FullbandStreamingSession(self.engine(), batch=batch, hop=hop, graph=graph, one_launch=one_launch, owner=self,
-                                        waveform=waveform, host_io=host_io, frame=(self.n_fft, self.hop_length, self.win_length))
+                                        waveform=waveform, host_io=host_io, frame=(self.n_fft, self.hop_length, self.win_length),
+                                        count_spikes=count_spikes)
+
+    @torch.no_grad()
+    def forward_stft(self, noisy_cmp, want_layers=False, want_counts=False):
+        """The hot path alone (GSN models): complex64 [B, F, T] -> ``FullbandEngine.forward_stft``'s result dict."""
+        if self.fb_model.sequence_model_name == "LSTM":
+            raise NotImplementedError("forward_stft runs the GSN kernels: an LSTM model runs on ATen (call the module itself)")
+        self._check_mode(noisy_cmp)
+        return self.engine().forward_stft(noisy_cmp, want_layers=want_layers, want_counts=want_counts)
 
     def forward(self, input):
         assert input.ndim == 2, f"Input tensor must be 2D, but got {input.ndim}D."
@@ -112,9 +124,16 @@ class Model(_EngineMixin, nn.Module):
 
     def _forward_gsn(self, input):
         batch_size, sequence_length = input.shape
-        res = self.engine().forward_stft(self._stft(input), want_layers=self.num_spks > 1)
+        # (one speaker returns no layer list; two speakers: layer_outputs says what stands in for the fp32 spike tensors)
+        kw = self._layer_kwargs() if self.num_spks > 1 else dict(want_layers=False, want_counts=False)
+        res = self.engine().forward_stft(self._stft(input), **kw)
         mag = res["enh_mag"][:, 0] if res["enh_mag"] is not None else None
-        return self._finish(res["enh_stft"], mag, res["all_layers"], batch_size, sequence_length)
+        layers = res["all_layers"]
+        if layers is None and self.num_spks > 1:  # "none": the list keeps its length and the shapes of its two ends
+            T, F, P = res["enh_stft"].shape[-1], self.fb_input_size, self._fb_spec.P
+            layers = [torch.empty((T, batch_size, F), device="meta")] + [None] * self._fb_spec.layers + \
+                     [torch.empty((T, batch_size, P), device="meta")]
+        return self._finish(res["enh_stft"], mag, layers, batch_size, sequence_length)
 
     def _forward_lstm(self, input):
         from . import training
