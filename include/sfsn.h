@@ -827,6 +827,36 @@ typedef struct {
 int sfsn_fullband_wave_hop_check(int Hp, int n_layers, int F, int S, int df, int B, int unshared);
 int sfsn_fullband_stream_hop_wave(const sfsn_fullband_wave_desc* desc, void* stream);
 
+/* ----------------------------------------------------------------------------------------------------
+ * The intel_ndns recipe's training loss (recipes/intel_ndns/spiking_fullsubnet/trainer.py:24-48 on audiozen/loss.py) and its
+ * gradient with respect to the estimate, in one call of two launches:
+ *     freq  = mean |Re E - Re T| + mean |Im E - Im T|          (freq_MAE, loss.py:138-155)
+ *     mag   = mean | |E| - |T| |                               (mag_MAE, loss.py:167-183)
+ *     sisnr = mean over rows of 10 log10(ratio + eps)          (SISNRLoss, loss.py:25-40; eps = 2^-23)
+ *     total = c_freq freq + c_mag mag + c_sdr sisnr
+ * E, T = torch.stft(x, 2048, 512, window=hann_window(2048), center=True, pad_mode="reflect", return_complex=True) of est, tgt
+ * [rows][n_samples]: T' = 1 + n_samples / 512 frames per row, bins 0..1024, means over rows * 1025 * T' elements.  SI-SNR per row:
+ * both signals minus their means, proj = <s_t, s_e> s_t / |s_t|^2, ratio = |proj|^2 / (|s_e - proj|^2 + eps); an all-zero target
+ * row gives what IEEE arithmetic gives.
+ *   flags     SFSN_LOSS_* bits: the terms that are computed; the others are reported as 0 and take no part in total or gradient
+ *             (SDR alone runs no transform)
+ *   terms     [4] device, 16-byte aligned: freq, mag, sisnr, total
+ *   grad_est  [rows][n_samples] device, d total / d est (sgn(0) = 0 and E / |E| = 0 at E = 0, ATen's conventions); NULL: forward only
+ *   scratch   the scratch-bytes function's size, 16-byte aligned; needs no initialisation and carries nothing between calls
+ * Deterministic: no atomics, every sum in a fixed order; repeated calls and graph replays return the same bits.  Capturable: no host
+ * synchronisation, no waits between workgroups.
+ * Checked before any launch: NULL or misaligned pointer, rows < 1, flags outside 1..7, n_samples <= 1024 (the reflect padding of
+ * 1024 samples is undefined there; torch.stft raises) -> SFSN_EINVAL; rows * n_samples or rows * T' * 2048 >= 2^31 ->
+ * SFSN_EUNSUPPORTED.  The scratch-bytes function returns 0 for a shape the call refuses.
+ * ---------------------------------------------------------------------------------------------------- */
+#define SFSN_LOSS_FREQ 1
+#define SFSN_LOSS_MAG 2
+#define SFSN_LOSS_SDR 4
+size_t sfsn_recipe_loss_scratch_bytes(int rows, int n_samples);
+int sfsn_recipe_loss(const float* est /* [rows][n_samples] */, const float* tgt /* [rows][n_samples] */, int rows, int n_samples,
+                     float c_freq, float c_mag, float c_sdr, int flags, float* terms /* [4] */, float* grad_est /* nullable */,
+                     void* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,6 +6,9 @@ Drop-in modules (same constructor keywords, state-dict names and forward() tuple
 * ``spiking_fullsubnet_amd.model_low_freq.Separator``                        (frozen recipe / model_zoo checkpoints)
 * ``spiking_fullsubnet_amd.modeling_cirm_gsn.Model``                         (the cIRM-GSN baseline recipe)
 
+The intel_ndns recipe's training loss (``freq_MAE``, ``mag_MAE``, ``SISNRLoss`` and the fused ``RecipeLoss``) is in
+``spiking_fullsubnet_amd.loss``.
+
 All compute between ``stft`` and ``istft`` runs in hand-written gfx950 kernels behind the C ABI of
 ``include/sfsn.h`` (``csrc/libsfsn_hip.so``).  There is no CPU fallback.
 """
@@ -16,5 +19,7 @@ from .model_low_freq import Separator  # noqa: F401
 from .modeling_spiking_fullsubnet import SpikingFullSubNet  # noqa: F401
 from .modeling_cirm_gsn import Model  # noqa: F401
 from .streaming import StreamingSession  # noqa: F401
+from . import loss  # noqa: F401
+from .loss import RecipeLoss  # noqa: F401
 
-__all__ = ["SpikingFullSubNet", "Separator", "Engine", "PathSpec", "StreamingSession", "Model"]
+__all__ = ["SpikingFullSubNet", "Separator", "Engine", "PathSpec", "StreamingSession", "Model", "RecipeLoss", "loss"]
