@@ -857,6 +857,43 @@ int sfsn_recipe_loss(const float* est /* [rows][n_samples] */, const float* tgt 
                      float c_freq, float c_mag, float c_sdr, int flags, float* terms /* [4] */, float* grad_est /* nullable */,
                      void* scratch, void* stream);
 
+/* ----------------------------------------------------------------------------------------------------
+ * The wsj0-mix recipes' training loss, PITWrapper(PairwiseNegSDR()) of audiozen/pit.py (recipes/wsj0-mix/spiking_fullsubnet/
+ * trainer.py:24-33), and its gradient with respect to the estimates, in one call of two launches.  est, ref [clips][sources][n_samples].
+ * For clip b, estimate i and reference j (pit.py:11-56), with a = est[b][i] and r = ref[b][j], each minus its own mean when zero_mean:
+ *     dot = <a, r>,  tn = |r|^2,  alpha = dot / (tn + eps),  proj = alpha r,  noise = a - proj
+ *     pair[b][i][j] = -10 log10(|proj|^2 / (|noise|^2 + eps) + eps)
+ * Permutations p of 0..S-1 in the order of itertools.permutations (pit.py:63-94):
+ *     loss_p[b] = (1 / S) sum_j pair[b][p[j]][j];  perm[b] = the p with the smallest loss_p[b], on an exact tie the earliest in that order
+ *     loss = mean_b min_p loss_p[b];  reordered[b][j] = est[b][perm[b][j]] (the input's own bits)
+ * The sums behind pair are accumulated in fp64 and |noise|^2 = |a|^2 - 2 alpha dot + alpha^2 tn is formed from them in fp64; pair is
+ * rounded to fp32 once, and the search adds those fp32 values (in fp64, j ascending), so perm is the first minimum of the pair the
+ * caller reads.
+ *   pair_cot  NULL: PIT mode.  pair, perm [clips][sources] and loss [1] are written; grad_est = d loss / d est, i.e. 1 / (clips S)
+ *             times d pair[b][perm[b][j]][j] / d est on row perm[b][j], through the mean subtraction when zero_mean; reordered
+ *             (nullable) as above.
+ *             [clips][S][S]: pairwise mode.  perm, loss and reordered must be NULL; pair is written;
+ *             grad_est[b][i] = sum_j pair_cot[b][i][j] d pair[b][i][j] / d est[b][i].
+ *   grad_est  [clips][sources][n_samples] or NULL: forward only, with the same values.  It is written as A est + sum_j R_j ref_j + C per
+ *             row with fp32 coefficients A, R_j, C (d pair / d a = ca a + cr r with
+ *             ca = (20 / ln 10) P / (arg den^2), cr = -(20 / ln 10) alpha / arg (tn / (tn' den) + P (1 + eps / tn') / den^2),
+ *             P = alpha^2 tn, den = |noise|^2 + eps, arg = P / den + eps, tn' = tn + eps; the means leave the constant C)
+ *   scratch   the scratch-bytes function's size, 16-byte aligned; needs no initialisation and carries nothing between calls
+ * Every pointer is device memory; est, ref, pair_cot, pair, perm, loss, grad_est, reordered and scratch are 16-byte aligned at their
+ * base (rows inside need not be: n_samples % 4 != 0 is covered).
+ * Deterministic: no atomics, every sum in a fixed order; repeated calls and graph replays return the same bits.  Capturable: two plain
+ * launches on the caller's stream, no host synchronisation, no waits between workgroups.
+ * Checked before any launch: a NULL est, ref, pair, scratch, or (PIT mode) perm or loss; a base pointer that is not 16-byte aligned;
+ * clips < 1, sources < 1 or n_samples < 2; eps negative or not finite; perm, loss or reordered given together with pair_cot
+ * -> SFSN_EINVAL.  sources > 4, or clips * sources * n_samples >= 2^31 -> SFSN_EUNSUPPORTED.  The scratch-bytes function returns 0
+ * exactly for the shapes the call refuses.
+ * ---------------------------------------------------------------------------------------------------- */
+size_t sfsn_pit_sdr_scratch_bytes(int clips, int sources, int n_samples);
+int sfsn_pit_sdr(const float* est, const float* ref /* [clips][sources][n_samples] */, int clips, int sources, int n_samples, int zero_mean,
+                 float eps, const float* pair_cot /* nullable [clips][S][S] */, float* pair /* [clips][S][S] */,
+                 int32_t* perm /* [clips][S] */, float* loss /* [1] */, float* grad_est /* nullable */, float* reordered /* nullable */,
+                 void* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

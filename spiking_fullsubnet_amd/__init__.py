@@ -7,7 +7,8 @@ Drop-in modules (same constructor keywords, state-dict names and forward() tuple
 * ``spiking_fullsubnet_amd.modeling_cirm_gsn.Model``                         (the cIRM-GSN baseline recipe)
 
 The intel_ndns recipe's training loss (``freq_MAE``, ``mag_MAE``, ``SISNRLoss`` and the fused ``RecipeLoss``) is in
-``spiking_fullsubnet_amd.loss``.
+``spiking_fullsubnet_amd.loss``; the wsj0-mix recipes' permutation-invariant SI-SDR loss (``PITWrapper(PairwiseNegSDR())``) is in
+``spiking_fullsubnet_amd.pit``.
 
 All compute between ``stft`` and ``istft`` runs in hand-written gfx950 kernels behind the C ABI of
 ``include/sfsn.h`` (``csrc/libsfsn_hip.so``).  There is no CPU fallback.
@@ -21,5 +22,8 @@ from .modeling_cirm_gsn import Model  # noqa: F401
 from .streaming import StreamingSession  # noqa: F401
 from . import loss  # noqa: F401
 from .loss import RecipeLoss  # noqa: F401
+from . import pit  # noqa: F401
+from .pit import PITWrapper, PairwiseNegSDR  # noqa: F401
 
-__all__ = ["SpikingFullSubNet", "Separator", "Engine", "PathSpec", "StreamingSession", "Model", "RecipeLoss", "loss"]
+__all__ = ["SpikingFullSubNet", "Separator", "Engine", "PathSpec", "StreamingSession", "Model", "RecipeLoss", "loss", "pit", "PITWrapper",
+           "PairwiseNegSDR"]

@@ -132,7 +132,7 @@ def _sources():
     """The files the library is made of, in the order the Makefile hashes them (SRCS)."""
     return [os.path.join(_HERE, "..", "include", "sfsn.h")] + [
         os.path.join(CSRC, f) for f in ("sfsn_scan_dev.h", "sfsn_scan3_dev.h", "sfsn_scan3i_dev.h", "sfsn_scan3x_dev.h", "sfsn_scan3w_dev.h", "sfsn_scan3j_dev.h", "sfsn_scan3g_dev.h", "sfsn_feat_dev.h", "sfsn_fft_dev.h", "sfsn_hop_dev.h", "sfsn_hop_wave_dev.h", "sfsn_fullband_dev.h", "sfsn_host.h", "sfsn_kernels.hip", "sfsn_stack.hip", "sfsn_hop.hip", "sfsn_fft.hip", "sfsn_train.hip",
-                                  "sfsn_featproj.hip", "sfsn_projdf.hip", "sfsn_fullband.hip", "sfsn_fullband_train.hip", "sfsn_fullband_hop.hip", "sfsn_loss.hip", "sfsn_pack.cpp")]
+                                  "sfsn_featproj.hip", "sfsn_projdf.hip", "sfsn_fullband.hip", "sfsn_fullband_train.hip", "sfsn_fullband_hop.hip", "sfsn_loss.hip", "sfsn_pit.hip", "sfsn_pack.cpp")]
 
 
 def source_hash() -> str:
@@ -308,6 +308,10 @@ def lib() -> ctypes.CDLL:
     L.sfsn_recipe_loss_scratch_bytes.argtypes = [_I, _I]
     L.sfsn_recipe_loss.restype = _I  # est, tgt | rows, n_samples | c_freq, c_mag, c_sdr | flags | terms, grad_est, scratch, stream
     L.sfsn_recipe_loss.argtypes = [_P, _P, _I, _I, _F, _F, _F, _I, _P, _P, _P, _P]
+    L.sfsn_pit_sdr_scratch_bytes.restype = ctypes.c_size_t  # clips, sources, n_samples; 0: refused (host only)
+    L.sfsn_pit_sdr_scratch_bytes.argtypes = [_I, _I, _I]
+    L.sfsn_pit_sdr.restype = _I  # est, ref | clips, sources, n_samples, zero_mean | eps | pair_cot, pair, perm, loss, grad_est, reordered, scratch, stream
+    L.sfsn_pit_sdr.argtypes = [_P, _P, _I, _I, _I, _I, _F] + [_P] * 8
     if L.sfsn_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH}: ABI version {L.sfsn_abi_version()} != {ABI_VERSION}; rebuild (make -C {CSRC})")
     _lib = L
@@ -326,7 +330,8 @@ EXPORTS = ("sfsn_abi_version", "sfsn_source_hash", "sfsn_strerror", "sfsn_device
            "sfsn_fullband_proj_deepfilter", "sfsn_fullband_deepfilter_fwd", "sfsn_fullband_deepfilter_bwd",
            "sfsn_fullband_hop_check", "sfsn_fullband_hop_scratch_bytes", "sfsn_fullband_stream_hop",
            "sfsn_fullband_wave_hop_check", "sfsn_fullband_stream_hop_wave", "sfsn_fullband_hop_spike_slots",
-           "sfsn_fullband_stream_hop_counted", "sfsn_recipe_loss_scratch_bytes", "sfsn_recipe_loss")
+           "sfsn_fullband_stream_hop_counted", "sfsn_recipe_loss_scratch_bytes", "sfsn_recipe_loss",
+           "sfsn_pit_sdr_scratch_bytes", "sfsn_pit_sdr")
 
 
 def check(rc: int, what: str = "") -> None:
