@@ -484,7 +484,8 @@ int sfsn_cum_laplace_norm(float* x /* [T][R][I] */, int T, int R, int I, float* 
  * Arithmetic is that of sfsn_features / sfsn_spike_proj / sfsn_gsn_layer_scan / sfsn_deepfilter expression by expression;
  * the real-valued input product is sfsn_input_proj_f32's fp32-MFMA form with four accumulators.
  *
- * Shared or separate gate weights (sfsn_hop_desc.unshared), LayerNorm / cumulative Laplace / no normalisation, H % 16 == 0, H <= 320, I <= 192, P <= 256 (full-band P <= 128), at most
+ * Shared or separate gate weights (sfsn_hop_desc.unshared), LayerNorm / cumulative Laplace / no normalisation, or the offline
+ * Laplace / Gaussian normalisation with the clips' statistics GIVEN (feat.mu, feat.ln_w: see sfsn_hop_seq), H % 16 == 0, H <= 320, I <= 192, P <= 256 (full-band P <= 128), at most
  * SFSN_HOP_MAX_LAYERS layers and SFSN_HOP_MAX_GROUPS groups, D + hop <= 32, and few enough rows that every wave tile gets
  * its own compute unit (SFSN_EUNSUPPORTED otherwise: the caller then runs the per-kernel sequence).
  * ---------------------------------------------------------------------------------------------------- */
@@ -512,8 +513,16 @@ typedef struct sfsn_hop_layer {
 typedef struct sfsn_hop_seq {      /* one sequence model: the full-band model or one sub-band group                  */
     sfsn_hop_layer layer[SFSN_HOP_MAX_LAYERS];
     int n_layers, H, P;
-    sfsn_feature_group feat;       /* geometry + normalisation of this model's input rows (`x` and `mu` unused);
-                                      rows R = B * feat.n_units, row b * n_units + k                                 */
+    sfsn_feature_group feat;       /* geometry + normalisation of this model's input rows (`x` unused); rows R = B * feat.n_units,
+                                      row b * n_units + k.  SFSN_NORM_LAPLACE: `mu` = [B] device floats, the clips' means, GIVEN by
+                                      the caller (a calibration pass, an earlier utterance, sfsn_laplace_means of the clip itself):
+                                      y = v / (mu[b] + 2.220446049250313e-16f), sfsn_features' expression; mu == NULL answers
+                                      SFSN_EUNSUPPORTED (utterance statistics the launch would have to compute are not causal).
+                                      SFSN_NORM_GAUSSIAN: `mu` = [B] means and `ln_w` = [B] standard deviations,
+                                      y = (v - mu[b]) / (ln_w[b] + 2.220446049250313e-16f); either NULL: SFSN_EINVAL.  Both must be
+                                      4-byte aligned (SFSN_EINVAL).  Every launch reads them; nothing of them is carried in the state.
+                                      Given statistics run kernels of their own: in one descriptor they go with each other and
+                                      with SFSN_NORM_NONE, not with LayerNorm / the cumulative norm (SFSN_EUNSUPPORTED)          */
     const int8_t* w_p;             /* sfsn_w3_pack(proj.weight [P][H])                                               */
     const float* w_p_dq;
     const float* b_p;              /* [P]                                                                            */

@@ -69,8 +69,9 @@ struct HopSeqDev {
     const int8_t* w_p;
     const float* w_p_dq;
     const float* b_p;
-    const float* ln_w;
+    const float* ln_w;  // (SFSN_NORM_GAUSSIAN: [B] the clips' given standard deviations)
     const float* ln_b;
+    const float* mu;    // SFSN_NORM_LAPLACE / SFSN_NORM_GAUSSIAN: [B] the clips' given means
     float* cum[2];  // SFSN_NORM_CUMLAPLACE: running sum of every row, double-buffered by launch parity
     int nl, H, P, R, KS, NT, PT, I, I1, KC;
     int slot0;      // desc.spike_slots: this sequence's first slot (layer l, row r, column group j at slot0 + (l R + r) H / 4 + j)
@@ -88,6 +89,7 @@ struct HopParams {
     unsigned stage_of_block[HOP_MAX_BLOCKS / 4];  // one byte per workgroup: a single scalar load finds the role
     int nseq, nstage, nblocks;
     int B, F, S, hop, D, FB, fcov;
+    int given;  // 1: the sequences' norm is SFSN_NORM_LAPLACE / SFSN_NORM_GAUSSIAN with given statistics (or none): the GIVEN kernels
     int G;  // 1: the forget and the cell gate share their weights (one product serves both); 2: separate weights, 2H rows per image
     float fdrc;
     unsigned launch;  // launches made on this state since it was zeroed: tag and state parity
@@ -112,6 +114,8 @@ struct HopParams {
     const unsigned* clip_start;  // optional [B]: the launch index at which clip b's utterance began (frame 0); NULL = the counters above
     unsigned* slots;  // optional: running spike counts, one word per (sequence, layer, row, 4-neuron column group) -- desc.spike_slots
 };
+
+static_assert(sizeof(HopParams) <= 4096, "HopParams travels as a kernel argument");
 
 // what changes from hop to hop (a launch takes them from its kernel arguments; the resident kernel counts them up itself)
 struct HopStep {
@@ -160,7 +164,10 @@ __device__ __forceinline__ float2 hop_in_bin(const HopParams& p, int b, int f, i
 // recurrent weights are requested when the first gate's matrix instructions have been issued, its input weights when the
 // recurrent half is done: both arrive while the wave waits for the stage upstream.  Same products, same two roundings per gate and
 // the same cell as scan_body's G = 2 epilogue: bit-identical to the offline kernels.
-template <bool L0, bool ONE, int G>
+// GIVEN (layer 0 only): the offline Laplace / Gaussian norm with the clips' statistics given (sfsn_hop_seq.feat) -- a kernel of its
+// own, so that the kernels of the other norms keep their register allocation (these kernels have no register to spare; the two
+// branches compiled into them cost the multi-frame and the resident kernels 4 to 48 bytes of scratch per lane).
+template <bool L0, bool ONE, int G, bool GIVEN>
 __device__ __forceinline__ void hop_layer_role(const HopParams& p, const HopStep& hs, const HopStageDev& sd, const HopSeqDev& sq, char* smem) {
     const int l = sd.layer;
     const HopLayerDev& L = sq.layer[l];
@@ -270,7 +277,7 @@ __device__ __forceinline__ void hop_layer_role(const HopParams& p, const HopStep
 #pragma unroll
     for (int u = 0; u < HOP_NU_MAX; ++u) {
         const int j = lane + 64 * u;
-        const bool in = L0 && j < I && sq.norm == SFSN_NORM_LAYERNORM;
+        const bool in = L0 && !GIVEN && j < I && sq.norm == SFSN_NORM_LAYERNORM;
         lw[u] = in ? sq.ln_w[j] : 0.0f;
         lb[u] = in ? sq.ln_b[j] : 0.0f;
     }
@@ -282,6 +289,9 @@ __device__ __forceinline__ void hop_layer_role(const HopParams& p, const HopStep
     // cumulative_laplace_norm: the running sums of my rows (every workgroup of the row tile computes the same sequence; the first
     // one stores it for the next launch, into the other half of the double buffer)
     // (per-clip utterances: the row's own frame count, and a zero sum in the launch that restarts its clip)
+    // GIVEN statistics (features_kernel's expressions): the same two registers per row hold the divisor (mu[b] or sd[b], + eps),
+    // formed here once per row, and the bits of the Gaussian mean.  Every launch reads them from the descriptor's arrays; nothing of
+    // them is state.
     float cumr[HOP_ROWS_PER_WAVE];
     int fbr[HOP_ROWS_PER_WAVE];
 #pragma unroll
@@ -289,7 +299,16 @@ __device__ __forceinline__ void hop_layer_role(const HopParams& p, const HopStep
         const int frow = 16 * rt + wave + HOP_WAVES * ri;
         cumr[ri] = 0.0f;
         fbr[ri] = hs.frames_before;
-        if (L0 && sq.norm == SFSN_NORM_CUMLAPLACE && frow < R) {
+        if constexpr (GIVEN) {
+            cumr[ri] = 1.0f;
+            fbr[ri] = 0;
+            if (L0 && sq.norm == SFSN_NORM_LAPLACE && frow < R) {
+                cumr[ri] = sq.mu[frow / sq.N] + 2.220446049250313e-16f;
+            } else if (L0 && sq.norm == SFSN_NORM_GAUSSIAN && frow < R) {
+                cumr[ri] = sq.ln_w[frow / sq.N] + 2.220446049250313e-16f;
+                fbr[ri] = __float_as_int(sq.mu[frow / sq.N]);
+            }
+        } else if (L0 && sq.norm == SFSN_NORM_CUMLAPLACE && frow < R) {
             if (p.clip_start) fbr[ri] = hop_clip_k(p, hs, frow / sq.N) * hop;
             // (agent-scope load: in the resident form the previous hop's sum was written by ANOTHER workgroup of the same launch --
             //  no launch boundary has made it visible to this CU's L1 / this XCD's L2)
@@ -416,7 +435,13 @@ __device__ __forceinline__ void hop_layer_role(const HopParams& p, const HopStep
 #pragma unroll
                 for (int u = 0; u < HOP_NU_MAX; ++u) sum += v[ri][u];
                 float y[HOP_NU_MAX];
-                if (sq.norm == SFSN_NORM_LAYERNORM) {
+                if constexpr (GIVEN) {
+                    // one expression, no branch: features_kernel's (v - mu) / den for the Gaussian norm; its v / den for the Laplace
+                    // norm, whose "mean" is +0.0f (v - 0.0f is v, bit for bit); v itself (over 1.0f) where a sequence has no norm
+                    const float sub = __int_as_float(fbr[ri]);
+#pragma unroll
+                    for (int u = 0; u < HOP_NU_MAX; ++u) y[u] = (v[ri][u] - sub) / cumr[ri];
+                } else if (sq.norm == SFSN_NORM_LAYERNORM) {
                     const float inv_I = 1.0f / (float)I;
                     const float mean = wave_sum(sum) * inv_I;
                     float ss = 0.0f;
@@ -535,7 +560,7 @@ __device__ __forceinline__ void hop_layer_role(const HopParams& p, const HopStep
             __hip_atomic_store(slot, first ? 0u : prev + nspk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
-    if (L0 && sq.norm == SFSN_NORM_CUMLAPLACE && wgl - rt * wpr == 0 && lane == 0) {
+    if (L0 && !GIVEN && sq.norm == SFSN_NORM_CUMLAPLACE && wgl - rt * wpr == 0 && lane == 0) {
 #pragma unroll
         for (int ri = 0; ri < HOP_ROWS_PER_WAVE; ++ri) {
             const int frow = 16 * rt + wave + HOP_WAVES * ri;
@@ -762,12 +787,12 @@ __device__ __forceinline__ void hop_istft_role(const HopParams& p, const HopStep
 }
 
 // one hop of one workgroup: the role its block index selects
-template <bool ONE, int G>
+template <bool ONE, int G, bool GIVEN>
 __device__ __forceinline__ void hop_dispatch(const HopParams& p, const HopStep& hs, char* smem) {
     if ((int)blockIdx.x < p.st[0].nwg) {
         // layer 0 of the full-band model is the head of the frame's critical path: its descriptors sit at fixed kernarg
         // offsets, so every scalar load is issued at once instead of table -> stage -> sequence
-        hop_layer_role<true, ONE, G>(p, hs, p.st[0], p.seq[0], smem);
+        hop_layer_role<true, ONE, G, GIVEN>(p, hs, p.st[0], p.seq[0], smem);
         return;
     }
     const int si = (int)((p.stage_of_block[blockIdx.x >> 2] >> (8 * (blockIdx.x & 3))) & 0xffu);
@@ -775,9 +800,9 @@ __device__ __forceinline__ void hop_dispatch(const HopParams& p, const HopStep& 
     const HopSeqDev& sq = p.seq[sd.seq];
     if (sd.layer >= 0) {
         if (sd.layer == 0)
-            hop_layer_role<true, ONE, G>(p, hs, sd, sq, smem);
+            hop_layer_role<true, ONE, G, GIVEN>(p, hs, sd, sq, smem);
         else
-            hop_layer_role<false, ONE, G>(p, hs, sd, sq, smem);
+            hop_layer_role<false, ONE, G, false>(p, hs, sd, sq, smem);
     } else if (sd.layer == -1) {
         hop_proj_role<ONE>(p, hs, sd, sq, smem);
     } else if (ONE && sd.layer == -2) {
@@ -789,7 +814,8 @@ __device__ __forceinline__ void hop_dispatch(const HopParams& p, const HopStep& 
 
 // (G = 2, separate gate weights, is a kernel of its own: the shared-weights kernels keep their register allocation -- 252 registers,
 //  no spills for the one-frame hop)
-template <bool ONE, int G>
+// (GIVEN, the offline norms with given statistics, likewise: see hop_layer_role)
+template <bool ONE, int G, bool GIVEN>
 __global__ __launch_bounds__(HOP_THREADS) void stream_hop_kernel(const HopParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -797,7 +823,7 @@ __global__ __launch_bounds__(HOP_THREADS) void stream_hop_kernel(const HopParams
     HopStep hs;
     hs.launch = p.launch; hs.frame_index = p.frame_index; hs.frames_before = p.frames_before;
     hs.wait_fin = 0;
-    hop_dispatch<ONE, G>(p, hs, smem);
+    hop_dispatch<ONE, G, GIVEN>(p, hs, smem);
     HOP_STAMP(7);
 }
 
@@ -809,7 +835,7 @@ __global__ __launch_bounds__(HOP_THREADS) void stream_hop_kernel(const HopParams
 // its memory, and only then may it ring the next hop (every consumer of hop k has read its inputs by then: the last stage
 // depends on all of them).  Bounded: a doorbell that stays silent for `idle_polls` polls ends the kernel (it must never outlive
 // its host thread), as does a hand-off wait that expires inside a hop.  Waveform mode, one-frame hops.
-template <int G>
+template <int G, bool GIVEN>
 __global__ __launch_bounds__(HOP_THREADS) void stream_hop_resident_kernel(const HopParams p, unsigned* doorbell, unsigned idle_ticks) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     unsigned* fin = p.cnt + 2;  // workgroups that have finished (and released) a hop, counted up over the hops
@@ -850,7 +876,7 @@ __global__ __launch_bounds__(HOP_THREADS) void stream_hop_resident_kernel(const 
         HopStep hs;
         hs.launch = p.launch + k; hs.frame_index = p.frame_index + (int)k; hs.frames_before = p.frames_before + (int)k * p.hop;
         hs.wait_fin = p.slots != nullptr;
-        hop_dispatch<true, G>(p, hs, smem);
+        hop_dispatch<true, G, GIVEN>(p, hs, smem);
 #ifdef SFSN_HOP_STAMPS
         HOP_STAMP(7);
 #endif
@@ -878,7 +904,12 @@ static int hop_fill_seq(HopSeqDev& d, const sfsn_hop_seq& s, int B, int F, int S
     const int I1 = g.ctr + 2 * g.nbr, I2 = g.ctr_fb > 0 ? g.ctr_fb + 2 * g.nbr_fb : 0, I = I1 + I2;
     if (I > 16 * HOP_KC_MAX || I > 64 * HOP_NU_MAX) return SFSN_EUNSUPPORTED;
     if (g.lo + g.n_units * g.ctr > nf || g.nbr >= nf || (I2 && (FB <= 0 || g.nbr_fb >= nf))) return SFSN_EINVAL;
-    if (g.norm == SFSN_NORM_LAPLACE) return SFSN_EUNSUPPORTED;  // utterance-level statistics: not causal
+    // utterance-level statistics are not causal: the launch computes none, it takes the clips' statistics as given
+    if (g.norm == SFSN_NORM_LAPLACE && !g.mu) return SFSN_EUNSUPPORTED;
+    if (g.norm == SFSN_NORM_GAUSSIAN && (!g.mu || !g.ln_w)) return SFSN_EINVAL;
+    if ((g.norm == SFSN_NORM_LAPLACE || g.norm == SFSN_NORM_GAUSSIAN) &&
+        ((reinterpret_cast<uintptr_t>(g.mu) & 3u) || (g.norm == SFSN_NORM_GAUSSIAN && (reinterpret_cast<uintptr_t>(g.ln_w) & 3u))))
+        return SFSN_EINVAL;
     if (g.norm == SFSN_NORM_CUMLAPLACE && (!s.cum[0] || !s.cum[1])) return SFSN_EINVAL;
     if (g.norm == SFSN_NORM_LAYERNORM && (!g.ln_w || !g.ln_b)) return SFSN_EINVAL;
     if (!s.w_p || !s.w_p_dq || !s.b_p) return SFSN_EINVAL;
@@ -886,7 +917,7 @@ static int hop_fill_seq(HopSeqDev& d, const sfsn_hop_seq& s, int B, int F, int S
     d.nl = s.n_layers; d.H = s.H; d.P = s.P; d.R = B * g.n_units; d.KS = (s.H + 63) / 64; d.NT = s.H / 16; d.PT = (s.P + 15) / 16;
     d.I = I; d.I1 = I1; d.KC = (I + 15) / 16;
     d.lo = g.lo; d.N = g.n_units; d.ctr = g.ctr; d.nbr = g.nbr; d.ctr_fb = g.ctr_fb; d.nbr_fb = g.nbr_fb; d.norm = g.norm; d.eps = g.ln_eps;
-    d.ln_w = g.ln_w; d.ln_b = g.ln_b; d.cum[0] = s.cum[0]; d.cum[1] = s.cum[1];
+    d.ln_w = g.ln_w; d.ln_b = g.ln_b; d.mu = g.mu; d.cum[0] = s.cum[0]; d.cum[1] = s.cum[1];
     d.w_p = s.w_p; d.w_p_dq = s.w_p_dq; d.b_p = s.b_p;
     d.df = is_fb ? 0 : s.df; d.fc = s.fc;
     if (!is_fb) {
@@ -937,6 +968,15 @@ static int hop_plan(HopParams& p, size_t& lds, const sfsn_hop_desc* d) {
     }
     if (dmax - 1 > d->D || fcov > d->F) return SFSN_EINVAL;
     p.fcov = fcov;
+    // given statistics are a kernel of their own, which has no LayerNorm and no running means: all sequences or none
+    int n_given = 0, n_other = 0;
+    for (int i = 0; i < p.nseq; ++i) {
+        const int nm = p.seq[i].norm;
+        n_given += nm == SFSN_NORM_LAPLACE || nm == SFSN_NORM_GAUSSIAN;
+        n_other += nm == SFSN_NORM_LAYERNORM || nm == SFSN_NORM_CUMLAPLACE;
+    }
+    if (n_given && n_other) return SFSN_EUNSUPPORTED;
+    p.given = n_given ? 1 : 0;
     for (int i = 0, o = 0; i < p.nseq; ++i) {  // (spike slots: sequences in descriptor order, layers, rows, column groups)
         p.seq[i].slot0 = o;
         o += p.seq[i].nl * p.seq[i].R * (p.seq[i].H / 4);
@@ -1051,8 +1091,12 @@ extern "C" int sfsn_stream_hop(const sfsn_hop_desc* desc, void* stream) {
     const bool one = local.hop == 1, g2 = local.G == 2;
     const dim3 grid(local.nblocks), block(HOP_THREADS);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (one) return g2 ? launch_lds<stream_hop_kernel<true, 2>>(grid, block, lds, st, local) : launch_lds<stream_hop_kernel<true, 1>>(grid, block, lds, st, local);
-    return g2 ? launch_lds<stream_hop_kernel<false, 2>>(grid, block, lds, st, local) : launch_lds<stream_hop_kernel<false, 1>>(grid, block, lds, st, local);
+    if (local.given) {
+        if (one) return g2 ? launch_lds<stream_hop_kernel<true, 2, true>>(grid, block, lds, st, local) : launch_lds<stream_hop_kernel<true, 1, true>>(grid, block, lds, st, local);
+        return g2 ? launch_lds<stream_hop_kernel<false, 2, true>>(grid, block, lds, st, local) : launch_lds<stream_hop_kernel<false, 1, true>>(grid, block, lds, st, local);
+    }
+    if (one) return g2 ? launch_lds<stream_hop_kernel<true, 2, false>>(grid, block, lds, st, local) : launch_lds<stream_hop_kernel<true, 1, false>>(grid, block, lds, st, local);
+    return g2 ? launch_lds<stream_hop_kernel<false, 2, false>>(grid, block, lds, st, local) : launch_lds<stream_hop_kernel<false, 1, false>>(grid, block, lds, st, local);
 }
 
 extern "C" int sfsn_stream_hop_resident(const sfsn_hop_desc* desc, void* doorbell, unsigned idle_ms, void* stream) {
@@ -1075,6 +1119,9 @@ extern "C" int sfsn_stream_hop_resident(const sfsn_hop_desc* desc, void* doorbel
     const unsigned polls = (idle_ms > 30000u ? 30000u : idle_ms) * 100000u;  // ticks of the 100 MHz wall clock
     const dim3 grid(local.nblocks), block(HOP_THREADS);
     unsigned* bell = static_cast<unsigned*>(doorbell);
-    return g2 ? launch_lds<stream_hop_resident_kernel<2>>(grid, block, lds, st, local, bell, polls)
-              : launch_lds<stream_hop_resident_kernel<1>>(grid, block, lds, st, local, bell, polls);
+    if (local.given)
+        return g2 ? launch_lds<stream_hop_resident_kernel<2, true>>(grid, block, lds, st, local, bell, polls)
+                  : launch_lds<stream_hop_resident_kernel<1, true>>(grid, block, lds, st, local, bell, polls);
+    return g2 ? launch_lds<stream_hop_resident_kernel<2, false>>(grid, block, lds, st, local, bell, polls)
+              : launch_lds<stream_hop_resident_kernel<1, false>>(grid, block, lds, st, local, bell, polls);
 }

@@ -190,6 +190,57 @@ SOAKED_HW_QUEUES = (4, 24)  # GPU_MAX_HW_QUEUES values the two-stream schedule h
 _hw_queues_warned = False
 
 
+@dataclass
+class NormStats:
+    """The utterance-level statistics of the frozen front-end's offline norms (model_low_freq.py:147-169, 205-218), one set per
+    clip: ``mu_fb`` [B] divides (Gaussian: is subtracted from) the full-band input, ``mu_sb`` [n_groups, B] each sub-band group's;
+    ``sd_fb`` / ``sd_sb`` (same shapes) are the standard deviations of ``offline_gaussian_norm`` and ``None`` otherwise.  float32, on
+    the model's device.  An offline forward computes them from the whole clip (``forward_stft(..., return_norm_stats=True)``,
+    ``Separator.norm_stats``); given to ``forward_stft(..., norm_stats=...)`` or to a streaming session they replace that pass."""
+    mu_fb: torch.Tensor
+    mu_sb: torch.Tensor
+    sd_fb: Optional[torch.Tensor] = None
+    sd_sb: Optional[torch.Tensor] = None
+
+    def _map(self, fn) -> "NormStats":
+        return NormStats(*(None if t is None else fn(t) for t in (self.mu_fb, self.mu_sb, self.sd_fb, self.sd_sb)))
+
+    def select(self, clips) -> "NormStats":
+        """The statistics of the given clips (a sequence or 1-D tensor of clip indices), in that order."""
+        idx = torch.as_tensor(clips, dtype=torch.long, device=self.mu_fb.device).reshape(-1)
+        return self._map(lambda t: t.index_select(-1, idx))
+
+    def to(self, device) -> "NormStats":
+        return self._map(lambda t: t.to(device))
+
+    def clone(self) -> "NormStats":
+        return self._map(lambda t: t.clone())
+
+    def validate(self, spec: PathSpec, batch: int, device) -> None:
+        """``ValueError`` naming what is wrong: a model that takes no statistics, a missing / surplus ``sd``, shape, dtype, device."""
+        if not spec.laplace:
+            kind = "cumulative_laplace_norm computes its running means itself" if spec.cum_laplace else \
+                "the live front-end normalises every frame by LayerNorm"
+            raise ValueError(f"norm_stats: this model takes no utterance statistics ({kind})")
+        want = [("mu_fb", self.mu_fb, (batch,)), ("mu_sb", self.mu_sb, (spec.n_groups, batch))]
+        if spec.gaussian:
+            want += [("sd_fb", self.sd_fb, (batch,)), ("sd_sb", self.sd_sb, (spec.n_groups, batch))]
+        elif self.sd_fb is not None or self.sd_sb is not None:
+            raise ValueError("norm_stats: sd_fb / sd_sb belong to offline_gaussian_norm; this model uses offline_laplace_norm")
+        device = torch.device(device)
+        for name, t, shape in want:
+            if t is None:
+                raise ValueError(f"norm_stats.{name} is missing: offline_gaussian_norm needs the clips' standard deviations")
+            if not torch.is_tensor(t):
+                raise ValueError(f"norm_stats.{name}: expected a tensor, got {type(t).__name__}")
+            if tuple(t.shape) != shape:
+                raise ValueError(f"norm_stats.{name}: expected shape {shape}, got {tuple(t.shape)}")
+            if t.dtype != torch.float32:
+                raise ValueError(f"norm_stats.{name}: expected float32, got {t.dtype}")
+            if t.device != device:
+                raise ValueError(f"norm_stats.{name}: expected a tensor on {device}, got one on {t.device}")
+
+
 def _check_hw_queues() -> int:
     """The overlapped schedule of a forward alone runs two launches of resident workgroups with in-launch waits on two HIP streams
     (the sub-band pair launch and the full-band stack), and bench.py's timed region a dozen forwards on as many streams.  How the
@@ -927,11 +978,22 @@ class Engine:
         return [SpikeSummary(counts[i], shp) for i, shp in enumerate(shapes)]
 
     def forward_stft(self, stft: torch.Tensor, want_layers: bool = True, want_membrane: bool = False, pipeline: Optional[bool] = None,
-                     want_counts: bool = False) -> dict:
-        """See ``_forward_stft``; runs with this engine's device current (the C ABI launches on the calling thread's device)."""
+                     want_counts: bool = False, norm_stats: Optional[NormStats] = None, return_norm_stats: bool = False) -> dict:
+        """See ``_forward_stft``; runs with this engine's device current (the C ABI launches on the calling thread's device).
+
+        Frozen front-end with an offline norm only (``ValueError`` otherwise): ``norm_stats`` -- the clips' statistics are taken as
+        given instead of being computed from ``stft`` (the two statistics launches are skipped, the schedule is otherwise the same);
+        ``return_norm_stats=True`` -- the result also carries ``"norm_stats"``, the statistics this forward used, as clones."""
+        if norm_stats is not None:
+            norm_stats.validate(self.spec, stft.shape[0] if stft.dim() == 3 else -1, self.device)
+        elif return_norm_stats and not self.spec.laplace:
+            raise ValueError("return_norm_stats: this model computes no utterance statistics")
         with torch.cuda.device(self.device):
             self._errors.poll()
-            out = self._forward_stft(stft, want_layers, want_membrane, pipeline, want_counts)
+            out = self._forward_stft(stft, want_layers, want_membrane, pipeline, want_counts, norm_stats)
+            if return_norm_stats:
+                out["norm_stats"] = NormStats(out["mu_fb"][0], out["mu_sb"], None if out["sd_fb"] is None else out["sd_fb"][0],
+                                              out["sd_sb"]).clone()
             if not torch.cuda.is_current_stream_capturing():
                 cur = torch.cuda.current_stream(self.device)
                 ev = self._last_forward.get(cur.cuda_stream)
@@ -946,7 +1008,7 @@ class Engine:
             return out
 
     def _forward_stft(self, stft: torch.Tensor, want_layers: bool = True, want_membrane: bool = False, pipeline: Optional[bool] = None,
-                      want_counts: bool = False) -> dict:
+                      want_counts: bool = False, norm_stats: Optional[NormStats] = None) -> dict:
         """complex64 [B, n_fft/2+1, T] on the device -> dict(enh_stft [B,S,F,T] complex64, enh_mag [B,S,F,T],
         fb_all, sb_all (the reference's all_layer_outputs lists; spike entries are None when want_layers=False)).
 
@@ -1063,7 +1125,11 @@ class Engine:
         for g in range(ng):
             dfg[g].proj, dfg[g].n_units, dfg[g].fc, dfg[g].df = _ptr(sb["proj"][g]), spec.units(g), spec.ctr[g], spec.df[g]
         mu_fb = mu_sb = sd_fb = sd_sb = scratch = None
-        if spec.laplace:
+        if norm_stats is not None:  # (validated by forward_stft) the clips' statistics as given: no statistics launches below
+            mu_fb, mu_sb = norm_stats.mu_fb.contiguous().view(1, B), norm_stats.mu_sb.contiguous()
+            if spec.gaussian:
+                sd_fb, sd_sb = norm_stats.sd_fb.contiguous().view(1, B), norm_stats.sd_sb.contiguous()
+        elif spec.laplace:
             mu_fb, mu_sb = torch.empty((1, B), **f32), torch.empty((ng, B), **f32)
             if spec.gaussian:
                 sd_fb, sd_sb = torch.empty((1, B), **f32), torch.empty((ng, B), **f32)
@@ -1252,7 +1318,9 @@ class Engine:
             proj_skipped[0] = not write_proj
             return True
 
-        if spec.laplace and spec.gaussian:
+        if norm_stats is not None:
+            pass
+        elif spec.laplace and spec.gaussian:
             check(L.sfsn_gaussian_stats(_ptr(ri), None, B, F, T, 0, spec.fdrc, fg_fb, 1, _ptr(mu_fb), _ptr(sd_fb), _ptr(scratch), hG[0]),
                   "sfsn_gaussian_stats(fb)")
         elif spec.laplace:
@@ -1262,7 +1330,9 @@ class Engine:
             # the utterance-level Laplace mean of the sub-band input needs the whole full-band output: no chunk overlap fb -> sb
             if pipeline:
                 gstreams[nl_fb].wait_event(fb_done[-1])
-            if spec.gaussian:
+            if norm_stats is not None:
+                pass
+            elif spec.gaussian:
                 check(L.sfsn_gaussian_stats(_ptr(ri), _ptr(fb_proj), B, F, T, spec.fb_proj, spec.fdrc, fg_sb, ng, _ptr(mu_sb), _ptr(sd_sb),
                                             _ptr(scratch), hG[nl_fb]), "sfsn_gaussian_stats(sb)")
             else:
@@ -1311,4 +1381,4 @@ class Engine:
         return dict(enh_stft=enh, enh_mag=enh_mag, fb_all=outs(x_fb, fb, 0, x_skipped["fb"]),
                     sb_all=[outs(xs[g], sb, g, x_skipped["sb"], proj_skipped[0]) for g in range(ng)],
                     fb_mem=[fb["mem"][l][0] for l in range(nl_fb)], sb_mem=[[sb["mem"][l][g] for l in range(nl_sb)] for g in range(ng)],
-                    mu_fb=mu_fb, mu_sb=mu_sb, pipelined=bool(pipeline), overlapped=overlap, n_chunks=len(bounds))
+                    mu_fb=mu_fb, mu_sb=mu_sb, sd_fb=sd_fb, sd_sb=sd_sb, pipelined=bool(pipeline), overlapped=overlap, n_chunks=len(bounds))

@@ -98,9 +98,22 @@ class Separator(_EngineMixin, nn.Module):
         return self._path_spec
 
     @torch.no_grad()
-    def forward_stft(self, complex_stft, want_layers=True, want_membrane=False, want_counts=False):
+    def forward_stft(self, complex_stft, want_layers=True, want_membrane=False, want_counts=False, norm_stats=None, return_norm_stats=False):
         self._check_mode(complex_stft)
-        return self.engine().forward_stft(complex_stft, want_layers=want_layers, want_membrane=want_membrane, want_counts=want_counts)
+        return self.engine().forward_stft(complex_stft, want_layers=want_layers, want_membrane=want_membrane, want_counts=want_counts,
+                                          norm_stats=norm_stats, return_norm_stats=return_norm_stats)
+
+    @torch.no_grad()
+    def norm_stats(self, wave_or_stft):
+        """The calibration pass: an offline forward of samples ``[B, L]`` (or ``[B, 1, L]``) or of a complex64 spectrum ``[B, F, T]``,
+        returning the ``engine.NormStats`` it computed -- what ``streaming(norm_stats=...)`` and ``forward_stft(norm_stats=...)`` take."""
+        x = wave_or_stft
+        if not self._path_spec.laplace:
+            raise ValueError("norm_stats: this model computes no utterance statistics (cumulative_laplace_norm keeps running means)")
+        self._check_mode(x)
+        if not torch.is_complex(x):
+            x = self._stft(x.squeeze(1) if x.dim() == 3 else x)
+        return self.engine().forward_stft(x, want_layers=False, return_norm_stats=True)["norm_stats"]
 
     def _kernel_path(self) -> bool:
         return True  # (every constructor option that is accepted is served by the kernels)

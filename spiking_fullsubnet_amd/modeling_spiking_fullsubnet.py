@@ -203,15 +203,23 @@ class _EngineMixin:
         return Engine(self._spec(), state_dict, device, weight_bits=self.weight_bits)
 
     def streaming(self, batch: int = 1, hop: int = 1, graph: bool = True, rows_per_wg=None, one_launch="auto", waveform: bool = False,
-                  host_io: bool = False, resident: bool = False, idle_ms: int = 1000, count_spikes: bool = False):
+                  host_io: bool = False, resident: bool = False, idle_ms: int = 1000, count_spikes: bool = False, norm_stats=None):
         """Frame-by-frame session (``streaming.StreamingSession``): state and deep-filter history stay on the device between
         calls; one launch per hop (``sfsn_stream_hop``) where the library covers the model, else the offline kernels replayed
         from a HIP graph.  ``waveform=True``: samples in, samples out (``step_wave``).  ``count_spikes=True``: per-clip spike
-        counts for ``session.spike_summary()`` (SynOPs / NeuronOPs).  Live front-end only."""
-        from .streaming import StreamingSession
+        counts for ``session.spike_summary()`` (SynOPs / NeuronOPs).  The live front-end and the frozen one with
+        ``cumulative_laplace_norm`` stream as they are; the frozen one with an offline norm needs the clips' statistics,
+        ``norm_stats=`` (``engine.NormStats``; ``NotImplementedError`` without, ``ValueError`` where the model takes none)."""
+        from .streaming import OFFLINE_NORM_MESSAGE, StreamingSession
+        spec = self._spec()
+        if norm_stats is not None and not spec.laplace:
+            norm_stats.validate(spec, batch, "cpu")  # (raises: this model takes no statistics)
+        if norm_stats is None and spec.laplace:
+            raise NotImplementedError(OFFLINE_NORM_MESSAGE)
         self._check_mode()
         return StreamingSession(self.engine(), batch=batch, hop=hop, graph=graph, rows_per_wg=rows_per_wg, owner=self, one_launch=one_launch,
-                                waveform=waveform, host_io=host_io, resident=resident, idle_ms=idle_ms, count_spikes=count_spikes)
+                                waveform=waveform, host_io=host_io, resident=resident, idle_ms=idle_ms, count_spikes=count_spikes,
+                                norm_stats=norm_stats)
 
     def _check_mode(self, x=None):
         """The inference kernels have no autograd graph and no training-mode BatchNorm: the entry points that use them

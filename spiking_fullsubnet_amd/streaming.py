@@ -14,9 +14,12 @@ the frame from stage to stage through L2 (csrc/sfsn_hop.hip); its state is its o
 history).  Otherwise the ~15 launches of the offline kernels, captured once into a HIP graph and replayed per hop: at
 hop = 1 that step is launch-bound, not compute-bound.  Both are bit-identical to the offline forward (tested).
 
-The frozen front-end (``model_low_freq.Separator``) with ``offline_laplace_norm`` normalises with utterance-level means
-(model_low_freq.py:147-169), which are not causal: a session on it raises ``NotImplementedError``.  With
-``cumulative_laplace_norm`` (every row by its own running mean) it streams, through the one-launch hop only.
+The frozen front-end (``model_low_freq.Separator``) with ``offline_laplace_norm`` / ``offline_gaussian_norm`` normalises with
+utterance-level statistics (model_low_freq.py:147-169, 205-218), which are not causal -- everything else of it is.  A session on it
+therefore takes the statistics from the caller (``norm_stats=``: an ``engine.NormStats`` from a calibration pass, an earlier utterance
+of the same channel, or the clip itself) and raises ``NotImplementedError`` without them; fed a clip's own statistics it reproduces
+the offline forward bit for bit, in both tiers.  The session owns device copies; ``set_norm_stats`` replaces them in stream order.
+With ``cumulative_laplace_norm`` (every row by its own running mean) the front-end streams through the one-launch hop only.
 
 Per-clip utterances: ``reset(clips=[...])`` starts a new utterance on some clips of a batched session while the others go on,
 bit for bit.  The one-launch hop gives every clip its own origin (``sfsn_hop_desc.clip_start``: the launch at which its utterance
@@ -41,7 +44,12 @@ import numpy as np
 import torch
 
 from ._lib import DfGroup, HopDesc, HOP_MAX_GROUPS, HOP_MAX_LAYERS, MAX_COUNT_TENSORS, NORM_CUMLAPLACE, RowCount, check
-from .engine import Engine, SpikeSummary, _ptr
+from .engine import Engine, NormStats, SpikeSummary, _ptr
+
+
+OFFLINE_NORM_MESSAGE = ("the frozen front-end's offline normalisation (model_low_freq.py:147-169, 205-218) divides by statistics of the "
+                        "whole utterance, which a stream does not have: pass them as norm_stats= (an engine.NormStats, e.g. from "
+                        "Separator.norm_stats(calibration_clip)); cumulative_laplace_norm and the live front-end stream without")
 
 
 def _raw_stream(device_index: int) -> int:
@@ -57,17 +65,21 @@ class StreamingSession:
 
     def __init__(self, engine: Engine, batch: int = 1, hop: int = 1, graph: bool = True, rows_per_wg=None, owner=None,
                  one_launch="auto", waveform: bool = False, host_io: bool = False, resident: bool = False, idle_ms: int = 1000,
-                 count_spikes: bool = False):
+                 count_spikes: bool = False, norm_stats: Optional[NormStats] = None):
         spec = engine.spec
         # the module the engine was packed from: reset() checks that its parameters have not changed since (the session's
         # captured graph holds pointers to THIS engine's packed weights)
         import weakref
         self._owner = weakref.ref(owner) if owner is not None else None
-        if spec.laplace:
-            raise NotImplementedError("the frozen front-end's offline Laplace normalisation (model_low_freq.py:147-169) needs the whole "
-                                      "utterance; streaming is defined for the live (LayerNorm) front-end only")
         if batch < 1 or hop < 1:
             raise ValueError("batch and hop must be positive")
+        if norm_stats is not None:
+            norm_stats.validate(spec, batch, engine.device)
+        elif spec.laplace:
+            raise NotImplementedError(OFFLINE_NORM_MESSAGE)
+        # the session's own copies of the clips' statistics: the descriptors and the captured graph point at THESE
+        self._stats = None if norm_stats is None else NormStats(*(None if t is None else t.clone().contiguous() for t in
+                                                                  (norm_stats.mu_fb, norm_stats.mu_sb, norm_stats.sd_fb, norm_stats.sd_sb)))
         self.eng, self.B, self.hop = engine, batch, hop
         self.rows_per_wg = rows_per_wg  # (full-band, sub-band) rows per scan workgroup; None = the engine's setting
         self.use_stack = True           # layer-pipelined stack launches where the engine's rule picks them (few rows: always)
@@ -104,8 +116,9 @@ class StreamingSession:
         # [fb layers + groups x sb layers, B] int64, filled by one sfsn_spike_count_rows launch per step (captured with the rest)
         self.count_spikes = bool(count_spikes)
         self._rows = None
-        self.fg_fb = engine._feature_groups("fb", [self.x_fb], None)
-        self.fg_sb = engine._feature_groups("sb", self.xs, None)
+        ns = self._stats
+        self.fg_fb = engine._feature_groups("fb", [self.x_fb], None if ns is None else ns.mu_fb, None if ns is None else ns.sd_fb)
+        self.fg_sb = engine._feature_groups("sb", self.xs, None if ns is None else ns.mu_sb, None if ns is None else ns.sd_sb)
         self.frames_done = 0
         # per-clip utterances: the session's frame / call count at which each clip's utterance began (clip_frames = the difference)
         self._clip_f0 = np.zeros(batch, dtype=np.int64)
@@ -232,8 +245,8 @@ class StreamingSession:
         weights, window = put_weights()
 
         # ---- one part = the clips [b0, b0 + nb) of the batch: descriptor + state
-        def make_desc(nb, spool, a=None):
-            """a: placeholder address for the sizing call (the plan never dereferences device pointers)."""
+        def make_desc(nb, spool, a=None, b0=0):
+            """a: placeholder address for the sizing call (the plan never dereferences device pointers); b0: the part's first clip."""
             desc = HopDesc()
             fgs = [self.fg_fb[0]] + [self.fg_sb[g] for g in range(ng)]
             dsts = [desc.fb] + [desc.sb[g] for g in range(ng)]
@@ -245,6 +258,11 @@ class StreamingSession:
                 dst.feat = fg
                 if w["ln"] is not None:
                     dst.feat.ln_w, dst.feat.ln_b = w["ln"]
+                if self._stats is not None:  # given statistics: the part's clips of the session's copies ([B] / row i - 1 of [ng, B])
+                    off = ((i - 1) * B if i else 0) + b0
+                    dst.feat.mu = (self._stats.mu_fb if i == 0 else self._stats.mu_sb).data_ptr() + 4 * off
+                    if spec.gaussian:
+                        dst.feat.ln_w = (self._stats.sd_fb if i == 0 else self._stats.sd_sb).data_ptr() + 4 * off
                 if spec.cum_laplace:  # the rows' running sums travel with the session
                     dst.feat.norm = NORM_CUMLAPLACE
                     c0, c1 = spool.zeros((R,), torch.float32), spool.zeros((R,), torch.float32)
@@ -309,7 +327,7 @@ class StreamingSession:
             spool = Pool()
             make_desc(nb, spool, probe.data_ptr())
             spool.allocate()
-            desc, st = make_desc(nb, spool)
+            desc, st = make_desc(nb, spool, b0=b0)
             desc.inp_ri = _ptr(self.inp)
             desc.enh_ri, desc.enh_mag = ptr(enh[b0:]), ptr(mag[b0:])
             if self.waveform:
@@ -405,6 +423,43 @@ class StreamingSession:
         self.frames_done = 0
         self._clip_f0[:] = 0
         self._clip_c0[:] = 0
+
+    def set_norm_stats(self, stats: NormStats, clips=None) -> None:
+        """Replace the statistics of every clip (``stats`` of the session's batch) or of ``clips`` (``stats`` of ``len(clips)`` clips,
+        in that order; distinct indices).  Ordered with the steps on torch's current stream: hops already queued still read the old
+        values.  A resident launch is ended first, as by ``reset()``.  Nothing of the statistics is state, so with
+        ``reset(clips=[b])`` this starts a new utterance with its own statistics on clip b while the others go on."""
+        if self._stats is None:
+            raise ValueError("set_norm_stats: this session's model takes no utterance statistics")
+        if clips is None:
+            idx = None
+            n = self.B
+        else:
+            if isinstance(clips, (torch.Tensor, np.ndarray)) and clips.ndim != 1:
+                raise TypeError("clips: a 1-D tensor or a sequence of clip indices")
+            items = clips.tolist() if isinstance(clips, (torch.Tensor, np.ndarray)) else list(clips)
+            if any(isinstance(i, bool) or not isinstance(i, (int, np.integer)) for i in items):
+                raise TypeError("clips: integer clip indices")
+            idx = [int(i) for i in items]
+            bad = [i for i in idx if not 0 <= i < self.B]
+            if bad:
+                raise IndexError(f"clip index {bad[0]} out of range for a session of {self.B} clips")
+            if len(set(idx)) != len(idx):
+                raise ValueError("set_norm_stats: clip indices must be distinct")
+            if not idx:
+                return
+            n = len(idx)
+        stats.validate(self.eng.spec, n, self.dev)
+        self._stop_resident()
+        sel = None if idx is None else torch.tensor(idx, dtype=torch.long).to(self.dev, non_blocking=True)
+        for mine, new in ((self._stats.mu_fb, stats.mu_fb), (self._stats.mu_sb, stats.mu_sb), (self._stats.sd_fb, stats.sd_fb),
+                          (self._stats.sd_sb, stats.sd_sb)):
+            if mine is None:
+                continue
+            if sel is None:
+                mine.copy_(new)
+            else:
+                mine.index_copy_(-1, sel, new)
 
     @staticmethod
     def _as_i32(v: int) -> int:  # a launch index (uint32) as the int32 a fill writes
