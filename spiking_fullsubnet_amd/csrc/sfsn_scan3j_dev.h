@@ -11,7 +11,11 @@
 //       the wave's four values per lane (no re-deal: all 16 MFMA columns are live), new spikes to LDS; then -- off the step's
 //       dependency chain -- the input product of frame t + 1 (12 matrix instructions, W_ih planes 0 / 1 from LDS, plane 2 in registers,
 //       spike fragments from the loader's ring), finished to fma(exact sum, dq_ih, b_f) in four registers for the next step.
-//       No global memory instruction, no address arithmetic in the loop.
+//       For H mod 64 in (0, 32] the last k-step of BOTH products is one 16x16x32 instruction per plane (9 + 3 instead of 12).
+//       No global memory instruction in the loop.  What the loop holds at H = 224 (cross-compiled, per step; profiles/scan_step_trim.md):
+//       24 matrix instructions, 58 VALU + 8 transcendental, of which 12 are packed fp32 (hipcc's SLP pairing of the cell), 16 the two
+//       v_lshl_add_u32 per value that recombine the digit planes, and 4 address adds: the ring slot (wave-uniform, carried in a scalar) onto
+//       the four spike-fragment offsets.  The loop runs two steps per trip so that the state double buffer's parity is an immediate offset.
 //   loader wave: the previous layer's int8 rows -> an LDS ring by LDS-DMA (4 KiB per frame, chunk (c + r) mod 16 of row r).
 //   storer wave: the spikes of frame t - 1, LDS -> global as whole contiguous blocks (fp32 + int8), counting them when no fp32 tensor is
 //       written.  (The loader wave can take a share of the fp32 store instructions: Scan3jRole::lsplit.)
@@ -21,6 +25,7 @@
 #ifndef SFSN_SCAN3J_DEV_H
 #define SFSN_SCAN3J_DEV_H
 #include "sfsn_scan3_dev.h"
+#include <type_traits>
 
 #ifndef SFSN_S3J_LSPLIT
 // fp32 store instructions per frame issued by the loader wave (of 14 at H = 224; the storer also carries the four int8 stores); the
@@ -47,30 +52,53 @@ struct Scan3jCfg {
     __host__ __device__ static constexpr int lds_bytes_off(int NT) { return lds_bytes(NT) + 4096; }
 };
 
-// The input term of frame f (ring slot f % D) for output tile `ct`, as the wave's four values per lane: 12 matrix instructions (full
-// 16x16x64 steps, zero padded k), planes 0 / 1 of W_ih from LDS two k-steps at a time, plane 2 from the caller's registers;
-// z = fma(exact sum, dq_ih, b_f) (= sfsn_spike_proj).  Used by the compute waves for their own tile and, in the OFF form, by the IO waves
-// for tiles 12 / 13.
-template <int KS>
-__device__ __forceinline__ v4f s3j_in_product(const char* smem, int f, const unsigned (&soff)[KS], unsigned woff, int PLANE, const v4i (&Wi2)[KS],
-                                              const char* cq) {
+// (a2 << 16) + (a1 << 8) + a0 of the three digit planes' exact sums as ((a2 << 8) + a1) << 8) + a0: the same int32, wrap-around included,
+// in two v_lshl_add_u32 instead of two shifts and an add3 (hipcc re-associates the plain Horner form back to those; the empty asm
+// statement keeps the inner sum opaque.  The instructions themselves are the compiler's, so it pads the matrix-result hazards)
+__device__ __forceinline__ int s3j_recombine(int a2, int a1, int a0) {
+    int t = (a2 << 8) + a1;
+    asm("" : "+v"(t));
+    return (t << 8) + a0;
+}
+
+// The input term of the frame in ring slot `slot` (a wave-uniform byte offset, frame % D * SLOT) for output tile `ct`, as the wave's four
+// values per lane: planes 0 / 1 of W_ih from LDS two k-steps at a time, plane 2 from the caller's registers; z = fma(exact sum, dq_ih, b_f)
+// (= sfsn_spike_proj).  TL = 0: KS full 16x16x64 steps.  TL = 1 (H mod 64 in (0, 32]): the last k-step is one 16x16x32 instruction per
+// plane on the low half of the fragment (soff[KS - 1] / wtoff: each lane's 8 bytes, Wi2t its plane-2 digits), issued FIRST from zero
+// accumulators with the wait states of the recurrent tail (scan3i_role); columns HP - 32 .. HP - 1 of the input spikes are not read.
+// Used by the compute waves for their own tile and, in the OFF form, by the IO waves for tiles 12 / 13.
+template <int KS, int TL>
+__device__ __forceinline__ v4f s3j_in_product(const char* smem, unsigned slot, const unsigned (&soff)[KS], unsigned woff, unsigned wtoff, int PLANE,
+                                              const v4i (&Wi2)[KS - TL], long Wi2t, const char* cq) {
     using C = Scan3jCfg<KS>;
-    constexpr int HP = C::HP;
-    const char* ring = smem + (f % C::D) * C::SLOT;
+    constexpr int HP = C::HP, KSF = KS - TL;
+    const char* ring = smem + slot;
     v4i e[3] = {v4i{0, 0, 0, 0}, v4i{0, 0, 0, 0}, v4i{0, 0, 0, 0}};
+    if constexpr (TL) {
+        const long sbt = *reinterpret_cast<const long*>(ring + soff[KS - 1]);
+        const long w0t = *reinterpret_cast<const long*>(smem + wtoff);
+        const long w1t = *reinterpret_cast<const long*>(smem + wtoff + PLANE);
+        asm volatile(
+            "v_mfma_i32_16x16x32_i8 %0, %3, %6, 0\n\t"
+            "v_mfma_i32_16x16x32_i8 %1, %4, %6, 0\n\t"
+            "v_mfma_i32_16x16x32_i8 %2, %5, %6, 0\n\t"
+            "s_nop 5"
+            : "=&v"(e[0]), "=&v"(e[2]), "=&v"(e[1])
+            : "v"(w0t), "v"(Wi2t), "v"(w1t), "v"(sbt));
+    }
 #pragma unroll
-    for (int k0 = 0; k0 < KS; k0 += 2) {
+    for (int k0 = 0; k0 < KSF; k0 += 2) {
         v4i sb[2], w0[2], w1[2];
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            if (k0 + i >= KS) continue;
+            if (k0 + i >= KSF) continue;
             sb[i] = *reinterpret_cast<const v4i*>(ring + soff[k0 + i]);
             w0[i] = *reinterpret_cast<const v4i*>(smem + woff + (k0 + i) * 1024);
             w1[i] = *reinterpret_cast<const v4i*>(smem + woff + PLANE + (k0 + i) * 1024);
         }
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            if (k0 + i >= KS) continue;
+            if (k0 + i >= KSF) continue;
             e[0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(w0[i], sb[i], e[0], 0, 0, 0);
             e[2] = __builtin_amdgcn_mfma_i32_16x16x64_i8(Wi2[k0 + i], sb[i], e[2], 0, 0, 0);
             e[1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(w1[i], sb[i], e[1], 0, 0, 0);
@@ -80,21 +108,54 @@ __device__ __forceinline__ v4f s3j_in_product(const char* smem, int f, const uns
     const v4f bf = *reinterpret_cast<const v4f*>(cq + 5 * HP * 4);
     v4f z;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) z[r] = __builtin_fmaf((float)((e[2][r] << 16) + (e[1][r] << 8) + e[0][r]), dqi[r], bf[r]);
+    for (int r = 0; r < 4; ++r) z[r] = __builtin_fmaf((float)s3j_recombine(e[2][r], e[1][r], e[0][r]), dqi[r], bf[r]);
     return z;
 }
 
-struct Scan3jRole;
-// What an IO wave of the OFF form needs to compute tile `ct`'s input terms: plane 2 of its W_ih rows in registers, its fragment offsets
-template <int KS>
+// A lane's operands of s3j_in_product for output tile `ct`: plane 2 of its W_ih rows in registers and its LDS fragment offsets
+template <int KS, int TL>
+struct S3jIn {
+    static constexpr int KSF = KS - TL;
+    v4i Wi2[KSF];
+    long Wi2t;
+    unsigned soff[KS], woff, wtoff;
+    __device__ __forceinline__ void init(const int8_t* w_ih, int NT, int ct, int lane) {
+        using C = Scan3jCfg<KS>;
+        const int n = lane & 15, q = lane >> 4;
+        const unsigned toff = (unsigned)((((q >> 1) * 16 + n) * 16) + (q & 1) * 8);  // my 8 bytes of a k-tail fragment
+#pragma unroll
+        for (int ks = 0; ks < KSF; ++ks) {
+            Wi2[ks] = *reinterpret_cast<const v4i*>(w_ih + ((((size_t)2 * NT + ct) * KS + ks) * 64 + lane) * 16);
+            soff[ks] = (unsigned)(n * 256 + ((ks * 4 + q + n) & 15) * 16);  // row n, k chunk c = 4 ks + q at position (c + n) & 15
+        }
+        Wi2t = 0;
+        if constexpr (TL) {
+            Wi2t = *reinterpret_cast<const long*>(w_ih + (((size_t)2 * NT + ct) * KS + KS - 1) * 1024 + toff);
+            soff[KS - 1] = (unsigned)(n * 256 + (((KS - 1) * 4 + (q >> 1) + n) & 15) * 16 + (q & 1) * 8);  // k = 64 (KS - 1) + 8 q .. + 7
+        }
+        woff = (unsigned)(C::WIH_OFF + (ct * KS) * 1024 + lane * 16);
+        wtoff = (unsigned)(C::WIH_OFF + (ct * KS + KS - 1) * 1024) + toff;
+    }
+    __device__ __forceinline__ v4f run(const char* smem, unsigned slot, int PLANE, const char* cq) const {
+        return s3j_in_product<KS, TL>(smem, slot, soff, woff, wtoff, PLANE, Wi2, Wi2t, cq);
+    }
+};
+
+// What an IO wave of the OFF form needs to compute tile `ct`'s input terms
+template <int KS, int TL>
 struct S3jHelper {
-    v4i Wi2[KS];
-    unsigned soff[KS], woff;
+    S3jIn<KS, TL> in;
     const char* cq;
     char* mbox;  // my lane's 16 bytes of parity 0; parity 1 at + 2048
-    __device__ __forceinline__ void init(const Scan3jRole& rl, char* smem, int NT, int ct, int lane);
+    __device__ __forceinline__ void init(const int8_t* w_ih, char* smem, int NT, int ct, int lane) {
+        using C = Scan3jCfg<KS>;
+        in.init(w_ih, NT, ct, lane);
+        cq = smem + C::CST_OFF + (ct * 16 + (lane >> 4) * 4) * 4;
+        mbox = smem + C::mbox_off(NT) + (ct - 12) * 1024 + lane * 16;
+    }
     __device__ __forceinline__ void run(const char* smem, int f, int PLANE) const {
-        const v4f z = s3j_in_product<KS>(smem, f, soff, woff, PLANE, Wi2, cq);
+        using C = Scan3jCfg<KS>;
+        const v4f z = in.run(smem, (unsigned)((f % C::D) * C::SLOT), PLANE, cq);
         *reinterpret_cast<v4f*>(mbox + (f & 1) * 2048) = z;
     }
 };
@@ -116,20 +177,6 @@ struct Scan3jRole {
     unsigned long long* count;  // nullable: a launch without fp32 spikes adds the number of spikes it wrote
     int lsplit;                 // fp32 store instructions per frame issued by the loader wave (the storer takes the rest)
 };
-
-template <int KS>
-__device__ __forceinline__ void S3jHelper<KS>::init(const Scan3jRole& rl, char* smem, int NT, int ct, int lane) {
-    using C = Scan3jCfg<KS>;
-    const int n = lane & 15, q = lane >> 4;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-        Wi2[ks] = *reinterpret_cast<const v4i*>(rl.w_ih + ((((size_t)2 * NT + ct) * KS + ks) * 64 + lane) * 16);
-        soff[ks] = (unsigned)(n * 256 + ((ks * 4 + q + n) & 15) * 16);
-    }
-    woff = (unsigned)(C::WIH_OFF + (ct * KS) * 1024 + lane * 16);
-    cq = smem + C::CST_OFF + (ct * 16 + q * 4) * 4;
-    mbox = smem + C::mbox_off(NT) + (ct - 12) * 1024 + lane * 16;
-}
 
 // TL = 1: H mod 64 in (0, 32]: the last k-step of the RECURRENT product is one 16x16x32 instruction (scan3i_role's form).
 // OUT bit 0: fp32 spikes, bit 1: int8 spikes (always).
@@ -183,15 +230,15 @@ __device__ __forceinline__ void scan3j_role(const Scan3jRole& rl, char* smem, in
         const bool live = row0 + n < R;
         const int grow = live ? row0 + n : R - 1;
         const unsigned toff = (unsigned)((((q >> 1) * 16 + n) * 16) + (q & 1) * 8);  // my 8 bytes of a k-tail fragment
-        v4i Whh[KSF > 0 ? KSF : 1][3], Wi2[KS];
+        v4i Whh[KSF > 0 ? KSF : 1][3];
         long Wht[3] = {0, 0, 0};
 #pragma unroll
         for (int ks = 0; ks < KSF; ++ks)
 #pragma unroll
             for (int d = 0; d < 3; ++d)
                 Whh[ks][d] = *reinterpret_cast<const v4i*>(rl.w_hh + ((((size_t)d * NT + ct) * KS + ks) * 64 + lane) * 16);
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) Wi2[ks] = *reinterpret_cast<const v4i*>(rl.w_ih + ((((size_t)2 * NT + ct) * KS + ks) * 64 + lane) * 16);
+        S3jIn<KS, TL> in;  // plane 2 of my W_ih rows, my B fragments of the input product
+        in.init(rl.w_ih, NT, ct, lane);
         if constexpr (TL) {
 #pragma unroll
             for (int d = 0; d < 3; ++d) Wht[d] = *reinterpret_cast<const long*>(rl.w_hh + (((size_t)d * NT + ct) * KS + KS - 1) * 1024 + toff);
@@ -200,29 +247,22 @@ __device__ __forceinline__ void scan3j_role(const Scan3jRole& rl, char* smem, in
         const unsigned boff = (unsigned)(n * LDH + q * 16);
         const unsigned boft = (unsigned)(n * LDH + (KS - 1) * 64 + q * 8);
         const unsigned hoff = (unsigned)(n * LDH + cj);
-        unsigned soff[KS];  // my B fragments of the input product: row n, k chunk c = 4 ks + q at position (c + n) & 15
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) soff[ks] = (unsigned)(n * 256 + ((ks * 4 + q + n) & 15) * 16);
-        const unsigned woff = (unsigned)(C::WIH_OFF + (ct * KS) * 1024 + lane * 16);
         const char* cq = smem + C::CST_OFF + cj * 4;  // my four neurons' constants: vector k at cq + k * HP * 4
         v4f z = {0.f, 0.f, 0.f, 0.f};                 // the input term of my four values at the NEXT frame to be finished
 
         const bool served = OFF && ct >= 12;  // (wave-uniform) my input terms come from an IO wave's mailbox
         const char* mbox = smem + C::mbox_off(NT) + (ct >= 12 ? ct - 12 : 0) * 1024 + lane * 16;
-        auto in_product = [&](int f) __attribute__((always_inline)) { z = s3j_in_product<KS>(smem, f, soff, woff, PLANE, Wi2, cq); };
-
-        __syncthreads();                       // initial state in hbuf[0], W_ih planes and constants in LDS
-        __builtin_amdgcn_s_barrier();          // the loader's prologue frames (0 .. A - 1) have landed
-        if (!served) in_product(0);
-        if constexpr (OFF) {
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-            __builtin_amdgcn_s_barrier();      // the IO waves' input terms of frame 0 are in the mailbox
-        }
-#pragma unroll 1
-        for (int t = 0; t < T; ++t) {
-            if constexpr (OFF) if (served) z = *reinterpret_cast<const v4f*>(mbox + (t & 1) * 2048);
-            const int8_t* hc = hbuf + (t & 1) * 16 * LDH;
-            int8_t* hn = hbuf + ((t & 1) ^ 1) * 16 * LDH;
+        unsigned slot = 0;                    // (wave-uniform) the ring slot of the next frame to be finished, as a byte offset
+        auto in_product = [&]() __attribute__((always_inline)) {
+            z = in.run(smem, slot, PLANE, cq);
+            slot = slot + SLOT == D * SLOT ? 0u : slot + SLOT;
+        };
+        // one step on the state buffer of parity PAR (a compile-time value: both buffers' addresses are immediate offsets)
+        auto step = [&](auto par, unsigned boff, unsigned boft, unsigned hoff, const char* cq) __attribute__((always_inline)) {
+            constexpr int PAR = decltype(par)::value;
+            if constexpr (OFF) if (served) z = *reinterpret_cast<const v4f*>(mbox + PAR * 2048);
+            const int8_t* hc = hbuf + PAR * 16 * LDH;
+            int8_t* hn = hbuf + (PAR ^ 1) * 16 * LDH;
             v4i b[KSF > 0 ? KSF : 1];
 #pragma unroll
             for (int ks = 0; ks < KSF; ++ks) b[ks] = *reinterpret_cast<const v4i*>(hc + boff + ks * 64);
@@ -253,7 +293,7 @@ __device__ __forceinline__ void scan3j_role(const Scan3jRole& rl, char* smem, in
             unsigned pk = 0;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float rec = (float)((a[2][r] << 16) + (a[1][r] << 8) + a[0][r]);  // exact sum, rounded once (= recombine3)
+                const float rec = (float)s3j_recombine(a[2][r], a[1][r], a[0][r]);  // exact sum, rounded once (= recombine3)
                 const float pre_f = __builtin_fmaf(rec, dq[r], z[r]);
                 const float pre_g = pre_f + db[r];
                 const float f = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(pre_f * -1.44269504088896341f));
@@ -264,18 +304,41 @@ __device__ __forceinline__ void scan3j_role(const Scan3jRole& rl, char* smem, in
             }
             *reinterpret_cast<unsigned*>(hn + hoff) = pk;
             __builtin_amdgcn_sched_barrier(0);
-            // off the chain: the input term of frame t + 1 (the loader clamps frames past the end to the last one: harmless work)
-            if (!served) in_product(t + 1);
+            // off the chain: the input term of the next frame (the loader clamps frames past the end to the last one: harmless work)
+            if (!served) in_product();
             __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
             __builtin_amdgcn_s_barrier();
+        };
+
+        __syncthreads();                       // initial state in hbuf[0], W_ih planes and constants in LDS
+        __builtin_amdgcn_s_barrier();          // the loader's prologue frames (0 .. A - 1) have landed
+        if (!served) in_product();
+        if constexpr (OFF) {
+            __builtin_amdgcn_s_waitcnt(0xc07f);
+            __builtin_amdgcn_s_barrier();      // the IO waves' input terms of frame 0 are in the mailbox
         }
-        // final state
+        // two steps per trip: step t reads the state buffer t & 1 and writes the other one; an odd T ends with one more step on buffer 0,
+        // its state-buffer and constant addresses worked out again from the lane number read afresh (mbcnt): what that copy of the step
+        // would otherwise carry through the loop are the registers the loop is short of (128 per lane, no scratch)
+        int t = 0;
+#pragma unroll 1
+        for (; t + 1 < T; t += 2) {
+            step(std::integral_constant<int, 0>{}, boff, boft, hoff, cq);
+            step(std::integral_constant<int, 1>{}, boff, boft, hoff, cq);
+        }
+        const int le = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+        const int ne = le & 15, qe = le >> 4, cje = ct * 16 + qe * 4;
+        if (t < T)
+            step(std::integral_constant<int, 0>{}, (unsigned)(ne * LDH + qe * 16), (unsigned)(ne * LDH + (KS - 1) * 64 + qe * 8), (unsigned)(ne * LDH + cje),
+                 smem + C::CST_OFF + cje * 4);
+        // final state (addresses from the fresh lane number too)
         const int8_t* hl = hbuf + (T & 1) * 16 * LDH;
-        if (live) {
-            *reinterpret_cast<v4f*>(rl.c_state + (size_t)grow * H + cj) = c;
-            const unsigned pk = *reinterpret_cast<const unsigned*>(hl + hoff);
+        if (row0 + ne < R) {
+            const size_t ge = (size_t)(row0 + ne) * H + cje;
+            *reinterpret_cast<v4f*>(rl.c_state + ge) = c;
+            const unsigned pk = *reinterpret_cast<const unsigned*>(hl + ne * LDH + cje);
             const v4f h = {(float)(pk & 1u), (float)((pk >> 8) & 1u), (float)((pk >> 16) & 1u), (float)((pk >> 24) & 1u)};
-            *reinterpret_cast<v4f*>(rl.h_state + (size_t)grow * H + cj) = h;
+            *reinterpret_cast<v4f*>(rl.h_state + ge) = h;
         }
         return;
     }
@@ -305,8 +368,8 @@ __device__ __forceinline__ void scan3j_role(const Scan3jRole& rl, char* smem, in
 #pragma unroll
             for (int p = 0; p < NP; ++p) dma16_to_lds<false>(__builtin_amdgcn_readfirstlane((unsigned)(slot * SLOT + p * 1024)), st, goff[p]);
         };
-        S3jHelper<KS> hp;
-        if constexpr (OFF) hp.init(rl, smem, NT, 12, lane);
+        S3jHelper<KS, TL> hp;
+        if constexpr (OFF) hp.init(rl.w_ih, smem, NT, 12, lane);
         __syncthreads();
         for (int s0 = 0; s0 < A; ++s0) issue(s0, s0 < T ? s0 : (T > 0 ? T - 1 : 0));
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -360,8 +423,8 @@ __device__ __forceinline__ void scan3j_role(const Scan3jRole& rl, char* smem, in
             }
             if constexpr (F32) ff.run(hsrc, rl.spikes_f32 + ((size_t)ts * R + row0) * H, lane);
         };
-        S3jHelper<KS> hp;
-        if constexpr (OFF) hp.init(rl, smem, NT, 13, lane);
+        S3jHelper<KS, TL> hp;
+        if constexpr (OFF) hp.init(rl.w_ih, smem, NT, 13, lane);
         __syncthreads();
         __builtin_amdgcn_s_barrier();
         if constexpr (OFF) {
@@ -521,9 +584,12 @@ __device__ __forceinline__ void scan3y_role(const Scan3yRole& rl, char* smem, in
         const unsigned xoff = (unsigned)(C::PL_OFF + (n * LDX + q * 8) * 2);  // my B fragment: row n, k = 32 ks + 8 q .. + 7 of a plane
         const char* cq = smem + C::CST_OFF + cj * 4;
         v4f z = {0.f, 0.f, 0.f, 0.f};
-        // the input term of frame f (plane slot f % DP) -> z: the product sequence of input_proj_bf3_kernel, instruction for instruction
-        auto in_product = [&](int f) __attribute__((always_inline)) {
-            const char* pl = smem + xoff + (f % DP) * 3 * PLANE;
+        // the input term of the next frame to be finished (plane slot frame % DP, carried as a wave-uniform byte offset) -> z: the product
+        // sequence of input_proj_bf3_kernel, instruction for instruction
+        unsigned pslot = 0;
+        auto in_product = [&]() __attribute__((always_inline)) {
+            const char* pl = smem + xoff + pslot;
+            pslot = pslot + 3 * PLANE == DP * 3 * PLANE ? 0u : pslot + 3 * PLANE;
             v4f hi = {0.f, 0.f, 0.f, 0.f}, lo = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int ks = 0; ks < KSB; ++ks) {
@@ -543,14 +609,11 @@ __device__ __forceinline__ void scan3y_role(const Scan3yRole& rl, char* smem, in
 #pragma unroll
             for (int r = 0; r < 4; ++r) z[r] = (hi[r] + lo[r]) + bf[r];  // = input_proj_bf3_kernel's epilogue
         };
-
-        __syncthreads();                       // initial state, W_ih pieces 2 / 3 and constants in LDS
-        __builtin_amdgcn_s_barrier();          // the loader's planes of frames 0 .. 2
-        in_product(0);
-#pragma unroll 1
-        for (int t = 0; t < T; ++t) {
-            const int8_t* hc = hbuf + (t & 1) * 16 * LDH;
-            int8_t* hn = hbuf + ((t & 1) ^ 1) * 16 * LDH;
+        // one step on the state buffer of parity PAR (a compile-time value: see scan3j_role)
+        auto step = [&](auto par) __attribute__((always_inline)) {
+            constexpr int PAR = decltype(par)::value;
+            const int8_t* hc = hbuf + PAR * 16 * LDH;
+            int8_t* hn = hbuf + (PAR ^ 1) * 16 * LDH;
             v4i b[KSF > 0 ? KSF : 1];
 #pragma unroll
             for (int ks = 0; ks < KSF; ++ks) b[ks] = *reinterpret_cast<const v4i*>(hc + boff + ks * 64);
@@ -578,7 +641,7 @@ __device__ __forceinline__ void scan3y_role(const Scan3yRole& rl, char* smem, in
             unsigned pk = 0;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float rec = (float)((a[2][r] << 16) + (a[1][r] << 8) + a[0][r]);
+                const float rec = (float)s3j_recombine(a[2][r], a[1][r], a[0][r]);
                 const float pre_f = __builtin_fmaf(rec, dq[r], z[r]);
                 const float pre_g = pre_f + db[r];
                 const float f = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(pre_f * -1.44269504088896341f));
@@ -589,10 +652,22 @@ __device__ __forceinline__ void scan3y_role(const Scan3yRole& rl, char* smem, in
             }
             *reinterpret_cast<unsigned*>(hn + hoff) = pk;
             __builtin_amdgcn_sched_barrier(0);
-            in_product(t + 1);                   // off the chain (frames past the end: the loader converts clamped copies of the last one)
+            in_product();                        // off the chain (frames past the end: the loader converts clamped copies of the last one)
             __builtin_amdgcn_s_waitcnt(0xc07f);
             __builtin_amdgcn_s_barrier();
+        };
+
+        __syncthreads();                       // initial state, W_ih pieces 2 / 3 and constants in LDS
+        __builtin_amdgcn_s_barrier();          // the loader's planes of frames 0 .. 2
+        in_product();
+        // two steps per trip; an odd T ends with one more step on buffer 0
+        int t = 0;
+#pragma unroll 1
+        for (; t + 1 < T; t += 2) {
+            step(std::integral_constant<int, 0>{});
+            step(std::integral_constant<int, 1>{});
         }
+        if (t < T) step(std::integral_constant<int, 0>{});
         const int8_t* hl = hbuf + (T & 1) * 16 * LDH;
         if (live) {
             *reinterpret_cast<v4f*>(rl.c_state + (size_t)grow * H + cj) = c;
