@@ -903,6 +903,50 @@ int sfsn_pit_sdr(const float* est, const float* ref /* [clips][sources][n_sample
                  int32_t* perm /* [clips][S] */, float* loss /* [1] */, float* grad_est /* nullable */, float* reordered /* nullable */,
                  void* scratch, void* stream);
 
+/* ----------------------------------------------------------------------------------------------------
+ * Ragged batches: clips of different lengths, zero-padded into one batch (csrc/sfsn_ragged.hip).  Everything of a forward that
+ * depends on where a clip ends sits at the edges of the path -- STFT, inverse STFT, the utterance statistics of the frozen
+ * front-end, spike counts -- and each of those calls has a sibling here that takes the clips' own lengths: device int32 arrays
+ * with one entry per clip, `clip_len` [B] in samples and `clip_frames` [B] in frames (T_b = 1 + L_b / hop).  The scans need none:
+ * the model is causal, frames t < T_b of a padded clip are those of the clip alone.
+ *
+ * Contract: clip b of a ragged call has, over its valid range, the BITS of the equal-length call on that clip alone (B = 1,
+ * T = T_b, L = length = L_b): the same expressions on the same values in the same order; what the padding would contribute is
+ * skipped, never added as +0 and never reordered.  The lengths are read on the device (no host synchronisation) and clamped
+ * to the buffer's extent before any address is formed; what the host can check it checks before any launch: NULL pointers (the
+ * length arrays included), B <= 0 (B > 65535 where B is a grid dimension) and the sibling's own conditions -> SFSN_EINVAL,
+ * n_fft != 512 -> SFSN_EUNSUPPORTED.  All are capturable in a HIP graph.
+ *
+ *   sfsn_stft_ragged            sfsn_stft; samples at index >= clip_len[b] read as zero whatever the buffer holds.  All T frames are
+ *                               written (frames t >= T_b: the transform of what remains of the clip, then of zeros).
+ *   sfsn_istft_ragged           sfsn_istft; frames t >= clip_frames[b] do not exist for clip b (they add nothing to the overlap-add
+ *                               sum and nothing to the window envelope, whatever stft_ri holds there); samples m >= clip_len[b] are
+ *                               written as 0.  Tile origin, ascending-frame accumulation and the env > 1e-11f rule are sfsn_istft's.
+ *   sfsn_laplace_means_ragged   sfsn_laplace_means / sfsn_gaussian_stats; the row sums run over t < clip_frames[b], the divisor
+ *   sfsn_gaussian_stats_ragged  (Gaussian: n and n - 1) uses the clip's own T_b.  Same scratch sizes.  Gaussian: clip_frames[b] >= 2
+ *                               is the caller's to ensure (T < 2 -> SFSN_EINVAL).
+ *   sfsn_spike_count_rows_ragged  sfsn_spike_count_rows for B clips per tensor (R == B * rows_per_clip, else SFSN_EINVAL):
+ *                               counts[b] += #{ spikes : t0 <= t < min(t0 + nt, clip_frames[b]), r in clip b }.  One workgroup
+ *                               owns each counter, no atomics.
+ *   sfsn_zero_tail_frames       x [B][rows][T][width] float: frames t >= clip_frames[b] := 0 (each element stored once; the rest
+ *                               of x is not touched).  T * width < 2^31.
+ * ---------------------------------------------------------------------------------------------------- */
+int sfsn_stft_ragged(const float* wave /* [B][L] */, int B, int L, int n_fft, int hop, const float* window,
+                     float* stft_ri /* [B][n_fft/2+1][T][2] */, int T, const int32_t* clip_len /* device [B] */, void* stream);
+int sfsn_istft_ragged(const float* stft_ri /* [B][n_fft/2+1][T][2] */, int B, int T, int n_fft, int hop, const float* window,
+                      float* wave /* [B][length] */, int length, const int32_t* clip_frames /* device [B] */,
+                      const int32_t* clip_len /* device [B] */, void* stream);
+int sfsn_laplace_means_ragged(const float* stft_ri, const float* fb_tbf, int B, int F, int T, int FB, float fdrc,
+                              const sfsn_feature_group* groups /* host, only geometry fields are read */, int n_groups,
+                              const int32_t* clip_frames /* device [B] */, float* mu_out, float* scratch, void* stream);
+int sfsn_gaussian_stats_ragged(const float* stft_ri, const float* fb_tbf, int B, int F, int T, int FB, float fdrc,
+                               const sfsn_feature_group* groups /* host, only geometry fields are read */, int n_groups,
+                               const int32_t* clip_frames /* device [B] */, float* mu_out, float* sd_out, float* scratch, void* stream);
+int sfsn_spike_count_rows_ragged(const sfsn_row_count* tensors /* host */, int n_tensors, int t0, int nt,
+                                 const int32_t* clip_frames /* device [B] */, int B, void* stream);
+int sfsn_zero_tail_frames(float* x /* [B][rows][T][width] */, int B, int rows, int T, int width,
+                          const int32_t* clip_frames /* device [B] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

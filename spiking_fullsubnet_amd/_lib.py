@@ -132,7 +132,7 @@ def _sources():
     """The files the library is made of, in the order the Makefile hashes them (SRCS)."""
     return [os.path.join(_HERE, "..", "include", "sfsn.h")] + [
         os.path.join(CSRC, f) for f in ("sfsn_scan_dev.h", "sfsn_scan3_dev.h", "sfsn_scan3i_dev.h", "sfsn_scan3x_dev.h", "sfsn_scan3w_dev.h", "sfsn_scan3j_dev.h", "sfsn_scan3g_dev.h", "sfsn_feat_dev.h", "sfsn_fft_dev.h", "sfsn_hop_dev.h", "sfsn_hop_wave_dev.h", "sfsn_fullband_dev.h", "sfsn_host.h", "sfsn_kernels.hip", "sfsn_stack.hip", "sfsn_hop.hip", "sfsn_fft.hip", "sfsn_train.hip",
-                                  "sfsn_featproj.hip", "sfsn_projdf.hip", "sfsn_fullband.hip", "sfsn_fullband_train.hip", "sfsn_fullband_hop.hip", "sfsn_loss.hip", "sfsn_pit.hip", "sfsn_pack.cpp")]
+                                  "sfsn_featproj.hip", "sfsn_projdf.hip", "sfsn_fullband.hip", "sfsn_fullband_train.hip", "sfsn_fullband_hop.hip", "sfsn_loss.hip", "sfsn_pit.hip", "sfsn_ragged.hip", "sfsn_pack.cpp")]
 
 
 def source_hash() -> str:
@@ -312,6 +312,19 @@ def lib() -> ctypes.CDLL:
     L.sfsn_pit_sdr_scratch_bytes.argtypes = [_I, _I, _I]
     L.sfsn_pit_sdr.restype = _I  # est, ref | clips, sources, n_samples, zero_mean | eps | pair_cot, pair, perm, loss, grad_est, reordered, scratch, stream
     L.sfsn_pit_sdr.argtypes = [_P, _P, _I, _I, _I, _I, _F] + [_P] * 8
+    # ragged batches (per-clip lengths as device int32 arrays): each sibling's arguments plus clip_len / clip_frames
+    L.sfsn_stft_ragged.restype = _I  # wave | B, L, n_fft, hop | window, stft_ri | T | clip_len, stream
+    L.sfsn_stft_ragged.argtypes = [_P, _I, _I, _I, _I, _P, _P, _I, _P, _P]
+    L.sfsn_istft_ragged.restype = _I  # stft_ri | B, T, n_fft, hop | window, wave | length | clip_frames, clip_len, stream
+    L.sfsn_istft_ragged.argtypes = [_P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P]
+    L.sfsn_laplace_means_ragged.restype = _I  # ... groups, n_groups | clip_frames, mu_out, scratch, stream
+    L.sfsn_laplace_means_ragged.argtypes = [_P, _P, _I, _I, _I, _I, _F, ctypes.POINTER(FeatureGroup), _I, _P, _P, _P, _P]
+    L.sfsn_gaussian_stats_ragged.restype = _I  # ... groups, n_groups | clip_frames, mu_out, sd_out, scratch, stream
+    L.sfsn_gaussian_stats_ragged.argtypes = [_P, _P, _I, _I, _I, _I, _F, ctypes.POINTER(FeatureGroup), _I, _P, _P, _P, _P, _P]
+    L.sfsn_spike_count_rows_ragged.restype = _I  # tensors, n_tensors, t0, nt | clip_frames, B, stream
+    L.sfsn_spike_count_rows_ragged.argtypes = [ctypes.POINTER(RowCount), _I, _I, _I, _P, _I, _P]
+    L.sfsn_zero_tail_frames.restype = _I  # x | B, rows, T, width | clip_frames, stream
+    L.sfsn_zero_tail_frames.argtypes = [_P, _I, _I, _I, _I, _P, _P]
     if L.sfsn_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH}: ABI version {L.sfsn_abi_version()} != {ABI_VERSION}; rebuild (make -C {CSRC})")
     _lib = L
@@ -331,7 +344,8 @@ EXPORTS = ("sfsn_abi_version", "sfsn_source_hash", "sfsn_strerror", "sfsn_device
            "sfsn_fullband_hop_check", "sfsn_fullband_hop_scratch_bytes", "sfsn_fullband_stream_hop",
            "sfsn_fullband_wave_hop_check", "sfsn_fullband_stream_hop_wave", "sfsn_fullband_hop_spike_slots",
            "sfsn_fullband_stream_hop_counted", "sfsn_recipe_loss_scratch_bytes", "sfsn_recipe_loss",
-           "sfsn_pit_sdr_scratch_bytes", "sfsn_pit_sdr")
+           "sfsn_pit_sdr_scratch_bytes", "sfsn_pit_sdr", "sfsn_stft_ragged", "sfsn_istft_ragged", "sfsn_laplace_means_ragged",
+           "sfsn_gaussian_stats_ragged", "sfsn_spike_count_rows_ragged", "sfsn_zero_tail_frames")
 
 
 def check(rc: int, what: str = "") -> None:

@@ -19,7 +19,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import CountTensor, DfGroup, FeatProjJob, FeatureGroup, FusedInput, FusedX, InProjJob, ProjDfGroup, ProjJob, ScanSegment, check
+from ._lib import (CountTensor, DfGroup, FeatProjJob, FeatureGroup, FusedInput, FusedX, InProjJob, ProjDfGroup, ProjJob, RowCount, ScanSegment,
+                   check)
 
 
 @dataclass
@@ -977,9 +978,33 @@ class Engine:
             check(self.lib.sfsn_spike_count(arr, n, st), "sfsn_spike_count")
         return [SpikeSummary(counts[i], shp) for i, shp in enumerate(shapes)]
 
+    def _count_spikes_ragged(self, s8_lists, shapes, rpcs, frames, frames_dev, st):
+        """One launch of sfsn_spike_count_rows_ragged over every layer's int8 spike tensor -> list of ragged.ClipSpikeSummary
+        (per-clip counts over each clip's own frames)."""
+        from .ragged import ClipSpikeSummary
+        n, B = len(s8_lists), len(frames)
+        if n > _lib.MAX_COUNT_TENSORS:
+            raise NotImplementedError(f"more than {_lib.MAX_COUNT_TENSORS} spike tensors to count")
+        counts = torch.zeros((n, B), dtype=torch.int64, device=self.device)
+        arr = (RowCount * n)()
+        T = s8_lists[0].shape[0]
+        for i, t in enumerate(s8_lists):
+            arr[i].spikes_i8, arr[i].T, arr[i].R, arr[i].HP, arr[i].rows_per_clip = t.data_ptr(), t.shape[0], t.shape[1], t.shape[2], rpcs[i]
+            arr[i].counts = counts.data_ptr() + 8 * i * B
+        with self.timed("spike_count", st):
+            check(self.lib.sfsn_spike_count_rows_ragged(arr, n, 0, T, _ptr(frames_dev), B, st), "sfsn_spike_count_rows_ragged")
+        return [ClipSpikeSummary(counts[i], shp, frames) for i, shp in enumerate(shapes)]
+
     def forward_stft(self, stft: torch.Tensor, want_layers: bool = True, want_membrane: bool = False, pipeline: Optional[bool] = None,
-                     want_counts: bool = False, norm_stats: Optional[NormStats] = None, return_norm_stats: bool = False) -> dict:
+                     want_counts: bool = False, norm_stats: Optional[NormStats] = None, return_norm_stats: bool = False,
+                     frames=None, frames_dev: Optional[torch.Tensor] = None) -> dict:
         """See ``_forward_stft``; runs with this engine's device current (the C ABI launches on the calling thread's device).
+
+        ``frames`` -- a ragged batch (``ragged.py``): a length-B sequence of ints, clip b has ``frames[b]`` frames
+        (``1 <= frames[b] <= T``; ``ValueError`` otherwise) and the rest of its row is padding.  The launches of the model are the
+        same; the offline norms' statistics run over each clip's own frames, ``want_counts`` gives per-clip counts over each clip's
+        own frames (``ragged.ClipSpikeSummary``) and ``enh_stft`` / ``enh_mag`` are zero at frames ``>= frames[b]``.  The lengths go to
+        the device once, without a host synchronisation (``frames_dev``: they are there already, as int32 [B]).
 
         Frozen front-end with an offline norm only (``ValueError`` otherwise): ``norm_stats`` -- the clips' statistics are taken as
         given instead of being computed from ``stft`` (the two statistics launches are skipped, the schedule is otherwise the same);
@@ -988,9 +1013,15 @@ class Engine:
             norm_stats.validate(self.spec, stft.shape[0] if stft.dim() == 3 else -1, self.device)
         elif return_norm_stats and not self.spec.laplace:
             raise ValueError("return_norm_stats: this model computes no utterance statistics")
+        if frames is not None:
+            from . import ragged
+            frames = ragged.check_frames(frames, stft.shape[0] if stft.dim() == 3 else -1, stft.shape[-1],
+                                         gaussian=self.spec.gaussian and norm_stats is None)
         with torch.cuda.device(self.device):
             self._errors.poll()
-            out = self._forward_stft(stft, want_layers, want_membrane, pipeline, want_counts, norm_stats)
+            if frames is not None and frames_dev is None:
+                frames_dev = ragged.upload(frames, self.device)
+            out = self._forward_stft(stft, want_layers, want_membrane, pipeline, want_counts, norm_stats, frames, frames_dev)
             if return_norm_stats:
                 out["norm_stats"] = NormStats(out["mu_fb"][0], out["mu_sb"], None if out["sd_fb"] is None else out["sd_fb"][0],
                                               out["sd_sb"]).clone()
@@ -1008,7 +1039,7 @@ class Engine:
             return out
 
     def _forward_stft(self, stft: torch.Tensor, want_layers: bool = True, want_membrane: bool = False, pipeline: Optional[bool] = None,
-                      want_counts: bool = False, norm_stats: Optional[NormStats] = None) -> dict:
+                      want_counts: bool = False, norm_stats: Optional[NormStats] = None, frames=None, frames_dev=None) -> dict:
         """complex64 [B, n_fft/2+1, T] on the device -> dict(enh_stft [B,S,F,T] complex64, enh_mag [B,S,F,T],
         fb_all, sb_all (the reference's all_layer_outputs lists; spike entries are None when want_layers=False)).
 
@@ -1108,7 +1139,8 @@ class Engine:
         fold = os.environ.get("SFSN_ZERO_FOLD", "1") != "0"  # (0: a fill launch of its own, for comparison)
         # layer_outputs="counts": the scans count the spikes they write (sfsn_scan_segment.spike_count) -- the int64 counters sit behind
         # the states in the same zeroed buffer (two floats each; the buffer's length stays a multiple of 16 bytes)
-        in_scan = bool(want_counts and not want_layers and self.count_in_scan)
+        # (a ragged batch counts each clip's own frames after the forward: the in-scan counter is per tensor, not per clip)
+        in_scan = bool(want_counts and not want_layers and self.count_in_scan and frames is None)
         n_cnt = (nl_fb + ng * nl_sb) if in_scan else 0
         n_cnt_f = (2 * n_cnt + 3) // 4 * 4
         state_flat = torch.empty((n_fb + n_sb + n_cnt_f,), **f32) if fold else torch.zeros((n_fb + n_sb + n_cnt_f,), **f32)
@@ -1318,26 +1350,31 @@ class Engine:
             proj_skipped[0] = not write_proj
             return True
 
-        if norm_stats is not None:
-            pass
-        elif spec.laplace and spec.gaussian:
-            check(L.sfsn_gaussian_stats(_ptr(ri), None, B, F, T, 0, spec.fdrc, fg_fb, 1, _ptr(mu_fb), _ptr(sd_fb), _ptr(scratch), hG[0]),
-                  "sfsn_gaussian_stats(fb)")
-        elif spec.laplace:
-            check(L.sfsn_laplace_means(_ptr(ri), None, B, F, T, 0, spec.fdrc, fg_fb, 1, _ptr(mu_fb), _ptr(scratch), hG[0]), "sfsn_laplace_means(fb)")
+        def stats(fb_tbf, FB, fg, n, mu, sd, st, tag):
+            """The clips' utterance statistics of one model's input; a ragged batch: over each clip's own frames."""
+            if frames is not None:
+                fd = _ptr(frames_dev)
+                if spec.gaussian:
+                    check(L.sfsn_gaussian_stats_ragged(_ptr(ri), fb_tbf, B, F, T, FB, spec.fdrc, fg, n, fd, _ptr(mu), _ptr(sd), _ptr(scratch), st),
+                          f"sfsn_gaussian_stats_ragged({tag})")
+                else:
+                    check(L.sfsn_laplace_means_ragged(_ptr(ri), fb_tbf, B, F, T, FB, spec.fdrc, fg, n, fd, _ptr(mu), _ptr(scratch), st),
+                          f"sfsn_laplace_means_ragged({tag})")
+            elif spec.gaussian:
+                check(L.sfsn_gaussian_stats(_ptr(ri), fb_tbf, B, F, T, FB, spec.fdrc, fg, n, _ptr(mu), _ptr(sd), _ptr(scratch), st),
+                      f"sfsn_gaussian_stats({tag})")
+            else:
+                check(L.sfsn_laplace_means(_ptr(ri), fb_tbf, B, F, T, FB, spec.fdrc, fg, n, _ptr(mu), _ptr(scratch), st), f"sfsn_laplace_means({tag})")
+
+        if spec.laplace and norm_stats is None:
+            stats(None, 0, fg_fb, 1, mu_fb, sd_fb, hG[0], "fb")
         fb_done = run_model([self.fb], fb, [x_fb], 0, feat_fb, "fb", rpw_fb, None, None)
         if spec.laplace:
             # the utterance-level Laplace mean of the sub-band input needs the whole full-band output: no chunk overlap fb -> sb
             if pipeline:
                 gstreams[nl_fb].wait_event(fb_done[-1])
-            if norm_stats is not None:
-                pass
-            elif spec.gaussian:
-                check(L.sfsn_gaussian_stats(_ptr(ri), _ptr(fb_proj), B, F, T, spec.fb_proj, spec.fdrc, fg_sb, ng, _ptr(mu_sb), _ptr(sd_sb),
-                                            _ptr(scratch), hG[nl_fb]), "sfsn_gaussian_stats(sb)")
-            else:
-                check(L.sfsn_laplace_means(_ptr(ri), _ptr(fb_proj), B, F, T, spec.fb_proj, spec.fdrc, fg_sb, ng, _ptr(mu_sb), _ptr(scratch),
-                                           hG[nl_fb]), "sfsn_laplace_means(sb)")
+            if norm_stats is None:
+                stats(_ptr(fb_proj), spec.fb_proj, fg_sb, ng, mu_sb, sd_sb, hG[nl_fb], "sb")
             sb_done = run_model(self.sb, sb, xs, nl_fb, feat_sb, "sb", rpw_sb, post_sb, None, fused_post_sb)
         elif pipeline and self.pipeline_two_phase:
             # full-band model first (its two layers overlapped), then the sub-band models (their two layers overlapped)
@@ -1355,6 +1392,13 @@ class Engine:
             self._errors.watch(None, list({id(sc): sc for _, sc in items}.values()), "; ".join(sorted({w for w, _ in items})))
         self._defer_err = None
 
+        if frames is not None:
+            # the deep filter has written every frame of the padded batch: what lies past a clip's end is zeroed (2 launches)
+            hm = self._handle(main)
+            with self.timed("zero_tail", hm):
+                check(L.sfsn_zero_tail_frames(_ptr(enh_ri), B, S * F, T, 2, _ptr(frames_dev), hm), "sfsn_zero_tail_frames(enh_stft)")
+                check(L.sfsn_zero_tail_frames(_ptr(enh_mag), B, S * F, T, 1, _ptr(frames_dev), hm), "sfsn_zero_tail_frames(enh_mag)")
+
         if want_counts and not want_layers:
             # SynOPs without the fp32 spike tensors: the scans have counted what they wrote (no launch, no pass over
             # the int8 copies); `count_in_scan = False`: round 3's counting launch over the int8 spikes, one launch for all layers
@@ -1363,6 +1407,9 @@ class Engine:
             if in_scan:
                 summ = [SpikeSummary(fb["cnt"][l][0], shapes[l]) for l in range(nl_fb)] + \
                        [SpikeSummary(sb["cnt"][l][g], shapes[nl_fb + g * nl_sb + l]) for g in range(ng) for l in range(nl_sb)]
+            elif frames is not None:
+                rpcs = [1] * nl_fb + [spec.units(g) for g in range(ng) for _ in range(nl_sb)]
+                summ = self._count_spikes_ragged(tens, shapes, rpcs, frames, frames_dev, self._handle(main))
             else:
                 summ = self._count_spikes(tens, shapes, self._handle(main))
             for l in range(nl_fb):

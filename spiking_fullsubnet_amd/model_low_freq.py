@@ -98,22 +98,45 @@ class Separator(_EngineMixin, nn.Module):
         return self._path_spec
 
     @torch.no_grad()
-    def forward_stft(self, complex_stft, want_layers=True, want_membrane=False, want_counts=False, norm_stats=None, return_norm_stats=False):
+    def forward_stft(self, complex_stft, want_layers=True, want_membrane=False, want_counts=False, norm_stats=None, return_norm_stats=False,
+                     frames=None):
+        """``frames``: a ragged batch, clip b has ``frames[b]`` frames (``Engine.forward_stft``)."""
         self._check_mode(complex_stft)
         return self.engine().forward_stft(complex_stft, want_layers=want_layers, want_membrane=want_membrane, want_counts=want_counts,
-                                          norm_stats=norm_stats, return_norm_stats=return_norm_stats)
+                                          norm_stats=norm_stats, return_norm_stats=return_norm_stats, frames=frames)
 
     @torch.no_grad()
-    def norm_stats(self, wave_or_stft):
+    def forward_ragged(self, waves, lengths):
+        """Inference on a batch of clips of different lengths: ``waves`` float32 [B, Lmax] on the device (what lies past a clip's
+        end is ignored), ``lengths`` a sequence or CPU int tensor of B values, ``1 <= L_b <= Lmax`` (``ValueError`` naming the
+        clip otherwise; ``offline_gaussian_norm``: ``L_b >= hop_length``).  Returns the tuple of ``forward()`` on the padded batch in
+        which every clip is the clip run alone, bit for bit -- the offline norms' statistics are each clip's own:
+        ``enhanced_y[b, :L_b]`` and ``enh_mag[b, :, :T_b]`` (zero beyond), and ``ragged.clip_layers(fb_all, sb_all, b, lengths,
+        hop=hop_length)`` for the layer outputs.  Inference only (``_check_mode``)."""
+        y, res = self._forward_ragged(waves, lengths)
+        return y[:, 0], res["enh_mag"][:, 0], res["fb_all"], res["sb_all"]
+
+    @torch.no_grad()
+    def norm_stats(self, wave_or_stft, lengths=None):
         """The calibration pass: an offline forward of samples ``[B, L]`` (or ``[B, 1, L]``) or of a complex64 spectrum ``[B, F, T]``,
-        returning the ``engine.NormStats`` it computed -- what ``streaming(norm_stats=...)`` and ``forward_stft(norm_stats=...)`` take."""
+        returning the ``engine.NormStats`` it computed -- what ``streaming(norm_stats=...)`` and ``forward_stft(norm_stats=...)`` take.
+        ``lengths``: the batch is padded -- the clips' lengths, in samples for a waveform and in frames for a spectrum; the
+        statistics are then each clip's own."""
         x = wave_or_stft
         if not self._path_spec.laplace:
             raise ValueError("norm_stats: this model computes no utterance statistics (cumulative_laplace_norm keeps running means)")
         self._check_mode(x)
+        frames = lengths
         if not torch.is_complex(x):
-            x = self._stft(x.squeeze(1) if x.dim() == 3 else x)
-        return self.engine().forward_stft(x, want_layers=False, return_norm_stats=True)["norm_stats"]
+            x = x.squeeze(1) if x.dim() == 3 else x
+            if lengths is not None:
+                from . import ragged
+                lens = ragged.check_lengths(lengths, x.shape[0], x.shape[-1], self.hop_length, gaussian=self._path_spec.gaussian)
+                frames = ragged.frames_of(lens, self.hop_length)
+                x = self._stft_ragged(x.contiguous(), ragged.upload(lens, x.device))
+            else:
+                x = self._stft(x)
+        return self.engine().forward_stft(x, want_layers=False, return_norm_stats=True, frames=frames)["norm_stats"]
 
     def _kernel_path(self) -> bool:
         return True  # (every constructor option that is accepted is served by the kernels)

@@ -179,6 +179,47 @@ class _EngineMixin:
             raise ValueError(f"Only support 'real_imag', 'complex', and 'mag_phase'. Received {input_type=}")
         return self._istft(c, length)
 
+    def _stft_ragged(self, waves, len_dev):
+        """STFT of a padded batch whose clip b has ``len_dev[b]`` samples (int32 on the device): whatever lies past a clip's end
+        reads as zero.  The ragged kernel where ``_device_fft`` holds, else ``torch.stft`` on the input with the tails zeroed."""
+        if self._device_fft(waves) and waves.dtype == torch.float32:
+            from . import spectral
+            return spectral.stft_ragged(waves, self.n_fft, self.hop_length, len_dev)
+        keep = torch.arange(waves.shape[-1], device=waves.device)[None, :] < len_dev[:, None]
+        return self._stft(torch.where(keep, waves, torch.zeros((), dtype=waves.dtype, device=waves.device)))
+
+    def _forward_ragged(self, waves, lengths):
+        """The body of ``forward_ragged``: (enhanced waveforms [B, S, Lmax], the engine's result dict).  STFT and inverse STFT by
+        the ragged kernels where ``_device_fft`` holds; elsewhere (the wsj0-mix 256-point frames) ATen at the two edges --
+        ``torch.stft`` on the input with the tails zeroed, ``torch.istft`` per clip on its own frames -- with the model in
+        between batched either way."""
+        from . import ragged, spectral
+        if waves.dim() != 2 or waves.dtype != torch.float32 or waves.device.type != "cuda":
+            raise RuntimeError(f"expected a float32 [B, Lmax] tensor on a HIP device, got {waves.dtype} {tuple(waves.shape)} on {waves.device}")
+        self._check_mode(waves)
+        B, Lmax = waves.shape
+        hop = self.hop_length
+        lens = ragged.check_lengths(lengths, B, Lmax, hop, gaussian=self._spec().gaussian)
+        frames = ragged.frames_of(lens, hop)
+        eng = self.engine()
+        with torch.cuda.device(waves.device):
+            both = ragged.upload([lens, frames], waves.device)  # one copy for the whole call
+        len_dev, fr_dev = both[0], both[1]
+        device_fft = self._device_fft(waves)
+        stft = self._stft_ragged(waves, len_dev)
+        res = eng.forward_stft(stft, frames=frames, frames_dev=fr_dev, **self._layer_kwargs())
+        enh = res["enh_stft"]  # [B, S, F, T], zero at frames >= T_b
+        S = enh.shape[1]
+        flat = enh.reshape(B * S, *enh.shape[2:])
+        if device_fft:
+            rows = (lambda v: v) if S == 1 else (lambda v: v.repeat_interleave(S))
+            y = spectral.istft_ragged(flat, self.n_fft, hop, Lmax, rows(fr_dev), rows(len_dev))
+        else:
+            y = torch.zeros((B * S, Lmax), dtype=torch.float32, device=waves.device)
+            for b in range(B):
+                y[b * S:(b + 1) * S, :lens[b]] = self._istft(flat[b * S:(b + 1) * S, :, :frames[b]], length=lens[b])
+        return y.view(B, S, Lmax), res
+
     def _layer_kwargs(self) -> dict:
         if self.layer_outputs not in ("tensors", "counts", "none"):
             raise ValueError(f"layer_outputs must be 'tensors', 'counts' or 'none', got {self.layer_outputs!r}")
@@ -274,10 +315,24 @@ class SpikingFullSubNet(_EngineMixin, nn.Module):
         return self._path_spec
 
     @torch.no_grad()
-    def forward_stft(self, noisy_cmp, want_layers=True, want_membrane=False, want_counts=False):
-        """The hot path alone: complex64 [B, 257, T] -> Engine.forward_stft result dict."""
+    def forward_stft(self, noisy_cmp, want_layers=True, want_membrane=False, want_counts=False, frames=None):
+        """The hot path alone: complex64 [B, 257, T] -> Engine.forward_stft result dict.  ``frames``: a ragged batch, clip b has
+        ``frames[b]`` frames (``Engine.forward_stft``)."""
         self._check_mode(noisy_cmp)
-        return self.engine().forward_stft(noisy_cmp, want_layers=want_layers, want_membrane=want_membrane, want_counts=want_counts)
+        return self.engine().forward_stft(noisy_cmp, want_layers=want_layers, want_membrane=want_membrane, want_counts=want_counts,
+                                          frames=frames)
+
+    @torch.no_grad()
+    def forward_ragged(self, waves, lengths):
+        """Inference on a batch of clips of different lengths: ``waves`` float32 [B, Lmax] on the device (what lies past a clip's
+        end is ignored), ``lengths`` a sequence or CPU int tensor of B values, ``1 <= L_b <= Lmax`` (``ValueError`` naming the
+        clip otherwise).  Returns the tuple of ``forward()`` on the padded batch in which every clip is the clip run alone, bit
+        for bit: ``enhanced_y[b, ..., :L_b]`` and ``enh_mag[b, :, :T_b]`` (zero beyond), and ``ragged.clip_layers(fb_all, sb_all, b,
+        lengths, hop=hop_length)`` for the layer outputs.  Inference only (``_check_mode``)."""
+        y, res = self._forward_ragged(waves, lengths)
+        if self.num_spks > 1:
+            return y, res["fb_all"], res["sb_all"]
+        return y[:, 0], res["enh_mag"][:, 0], res["fb_all"], res["sb_all"]
 
     def _kernel_path(self) -> bool:
         return self.fb_model.kernel_path and all(s.kernel_path for s in self.sb_model.sb_models)
