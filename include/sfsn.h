@@ -89,8 +89,12 @@ int sfsn_w3_unpack(const int8_t* packed, const float* dq, int n_out, int k_in, f
  *     pre_f = zin[t][r][j] + (h . W_hh^T)[j]                               NEURON:140-145
  *     pre_g = zin[t][r][H + j] + (h . W_hh^T)[H + j]                       (unshared weights)
  *           = pre_f + (bias[H + j] - bias[j])                              (shared weights: one product serves both gates)
- *     f = sigmoid(pre_f);  c' = f*c + (1-f)*pre_g;  c'' = fma(c', bn_alpha[j], bn_beta[j])
+ *     f = sigmoid(pre_f);  c' = fma(f, c - pre_g, pre_g);  c'' = fma(c', bn_alpha[j], bn_beta[j])
  *     h' = (c'' >= 0);  carry (h', c'')                                    NEURON:146-153
+ * c' is the reference's f*c + (1-f)*pre_g in the order the kernels evaluate it: the difference c - pre_g rounds before it meets f, so
+ * the two forms differ by about ulp(|c| + |pre_g|) -- nothing for the gates a trained model has, 1e-5 at |pre_g| ~ 100.  The sigmoid is
+ * rcp(1 + exp2(-log2(e) * pre_f)) on the hardware's exp2 / rcp.  tests/scanref.py bounds both forms; the tests cover finite inputs
+ * with |pre_f|, |pre_g| <= 128 (the sigmoid's tails included: f = 0 below about -88.7, f = 1 above about 17) and no denormal results.
  * zin is the time-parallel INPUT TERM INCLUDING bias_ih, as the reference associates it ((x.W_ih^T + bias) + h.W_hh^T):
  *     shared:   zin[.][j] = (x . W_ih^T)[j] + bias[j]            (forget-gate bias; the scan adds the bias difference)
  *     unshared: zin[.][g*H + j] = (x . W_ih^T)[g*H + j] + bias[g*H + j]

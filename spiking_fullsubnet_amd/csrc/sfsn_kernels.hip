@@ -535,6 +535,10 @@ __global__ __launch_bounds__(512) void gsn_scan_split_kernel(const ScanParams p,
     v4f c = have ? *reinterpret_cast<const v4f*>(sg.c_state + (size_t)rowc * H + cc) : v4f{0, 0, 0, 0};
     __syncthreads();
     unsigned cnt = 0, last_pk = 0;
+    // h_state is read whole by every workgroup of a row block (above) and written per tile at the end: a workgroup must not store its
+    // final h before its siblings have read the initial one.  With T >= 2 the exchange of step 0 orders the two (a sibling publishes
+    // only after its read); a single-frame launch has no exchange, so it runs that of its only step as well -- as a barrier.
+    const bool xlast = T == 1;
     for (int t = 0; t < T; ++t) {
         const int8_t* hc = hbuf + (t & 1) * 16 * LDH;
         int8_t* hn = hbuf + ((t & 1) ^ 1) * 16 * LDH;
@@ -573,7 +577,7 @@ __global__ __launch_bounds__(512) void gsn_scan_split_kernel(const ScanParams p,
             c = cy;
             last_pk = pk;
             if (row0 + n < R) {  // rows past R are computed (clamped duplicates) but neither published nor stored
-                if (t + 1 < T) {
+                if (t + 1 < T || xlast) {
                     const unsigned bits = (pk & 1u) | ((pk >> 7) & 2u) | ((pk >> 14) & 4u) | ((pk >> 21) & 8u);
                     __hip_atomic_store(xch + ((size_t)(t & 1) * R + rowc) * H4 + (cc >> 2), ((unsigned)(t + 1) << 4) | bits, __ATOMIC_RELAXED,
                                        __HIP_MEMORY_SCOPE_AGENT);
@@ -587,7 +591,7 @@ __global__ __launch_bounds__(512) void gsn_scan_split_kernel(const ScanParams p,
                 if (sg.membrane) *reinterpret_cast<v4f*>(sg.membrane + ((size_t)t * R + rowc) * H + cc) = cy;
             }
         }
-        if (t + 1 < T) {
+        if (t + 1 < T || xlast) {
             // h_t of my 16 rows, every tile: a piece = the four tagged words of one (row, tile), written by one wave of one workgroup
             int good = 1;
             const unsigned epoch = (unsigned)(t + 1);

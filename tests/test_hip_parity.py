@@ -41,34 +41,48 @@ def hip():
     return L
 
 
-def run_scan(hip, zin, w_hh, bias, alpha, beta, shared, h0=None, c0=None, want_mem=True, split=False, want_spk=True):
+def run_scan(hip, zin, w_hh, bias, alpha, beta, shared, h0=None, c0=None, want_mem=True, split=False, want_spk=True, rows_per_wg=0,
+             bits=24, zin_has_bias=False, canary=False, count=False):
     """x.W_ih^T [T,R,G*H] numpy -> spikes, membrane, spikes_i8, hT, cT (numpy) through sfsn_gsn_layer_scan.
-    The ABI's input term includes bias_ih (forget-gate bias when shared, both gate biases otherwise): added here."""
+    The ABI's input term includes bias_ih (forget-gate bias when shared, both gate biases otherwise): added here.
+    Keywords of tests/test_scan_edges.py: rows_per_wg as the ABI's; bits = 16: weights packed with 16 bits through
+    sfsn_gsn_layer_scan_w16; zin_has_bias: zin is the ABI's input term already; canary: the outputs start as NaN / 0x7f (the live
+    columns of the int8 spikes; their padding columns start as zero); count: a sixth result, the launch's spike counter."""
     from spiking_fullsubnet_amd._lib import ScanSegment, check
     from spiking_fullsubnet_amd.engine import pack_w3
     T, R, GH = zin.shape
     H = bias.shape[0] // 2
-    zin = (zin + bias[:GH]).astype(np.float32)
+    zin = zin.astype(np.float32) if zin_has_bias else (zin + bias[:GH]).astype(np.float32)
     HP = (H + 63) // 64 * 64
-    pk, dq = pack_w3(w_hh)
+    pk, dq = pack_w3(w_hh, bits)
     t = dict(zin=_t(zin), pk=_t(pk), dq=_t(dq), bias=_t(bias), alpha=_t(alpha), beta=_t(beta),
              h=_t(np.zeros((R, H), np.float32) if h0 is None else h0), c=_t(np.zeros((R, H), np.float32) if c0 is None else c0),
              spk=torch.empty((T, R, H), device=DEV) if want_spk else None, s8=torch.zeros((T, R, HP), dtype=torch.int8, device=DEV),
-             mem=torch.empty((T, R, H), device=DEV) if want_mem else None)
+             mem=torch.empty((T, R, H), device=DEV) if want_mem else None, cnt=torch.zeros((1,), dtype=torch.int64, device=DEV))
+    if canary:
+        for k in ("spk", "mem"):
+            if t[k] is not None:
+                t[k].fill_(float("nan"))
+        t["s8"][:, :, :H] = 0x7f
     seg = (ScanSegment * 1)()
     s = seg[0]
     s.zin, s.w_hh, s.w_dq, s.bias, s.bn_alpha, s.bn_beta = _p(t["zin"]), _p(t["pk"]), _p(t["dq"]), _p(t["bias"]), _p(t["alpha"]), _p(t["beta"])
     s.h_state, s.c_state, s.spikes_f32, s.spikes_i8, s.membrane, s.R = _p(t["h"]), _p(t["c"]), _p(t["spk"]), _p(t["s8"]), _p(t["mem"]), R
+    if count:
+        s.spike_count = _p(t["cnt"])
     if split:  # the tiles of a row block split over several workgroups (sfsn_gsn_layer_scan_split)
         scr = torch.zeros((hip.sfsn_scan_split_scratch_bytes(R, H) // 4,), dtype=torch.int32, device=DEV)
         check(hip.sfsn_gsn_layer_scan_split(seg, 1, T, H, int(shared), _p(scr), scr.numel() * 4, None), "scan_split")
         torch.cuda.synchronize()
         assert int(scr[0]) == 0, "a wait of the split scan expired"
+    elif bits == 16:
+        check(hip.sfsn_gsn_layer_scan_w16(seg, 1, T, H, int(shared), rows_per_wg, None), "scan_w16")
     else:
-        check(hip.sfsn_gsn_layer_scan(seg, 1, T, H, int(shared), 0, None), "scan")
+        check(hip.sfsn_gsn_layer_scan(seg, 1, T, H, int(shared), rows_per_wg, None), "scan")
     torch.cuda.synchronize()
-    return (t["spk"].cpu().numpy() if want_spk else None, t["mem"].cpu().numpy() if want_mem else None, t["s8"].cpu().numpy(), t["h"].cpu().numpy(),
-            t["c"].cpu().numpy())
+    res = (t["spk"].cpu().numpy() if want_spk else None, t["mem"].cpu().numpy() if want_mem else None, t["s8"].cpu().numpy(), t["h"].cpu().numpy(),
+           t["c"].cpu().numpy())
+    return res + (int(t["cnt"][0]),) if count else res
 
 
 def make_layer(rng, I, H, shared, bn):
@@ -1478,7 +1492,7 @@ def test_fused_scan_entry_points_reject_what_they_do_not_cover(hip):
     torch.cuda.synchronize()
 
 
-def _run_fused(hip, s_in, sd, alpha, beta, h0, c0, want_f32=True, segs_split=None):
+def _run_fused(hip, s_in, sd, alpha, beta, h0, c0, want_f32=True, segs_split=None, canary=False):
     """sfsn_gsn_layer_scan_fused on int8 input spikes s_in [T, R, HP] (a layer >= 1): fp32 spikes (or None), int8 spikes, h, c, count."""
     from spiking_fullsubnet_amd._lib import FusedInput, ScanSegment, check
     from spiking_fullsubnet_amd.engine import pack_w3
@@ -1495,6 +1509,10 @@ def _run_fused(hip, s_in, sd, alpha, beta, h0, c0, want_f32=True, segs_split=Non
         t = dict(sin=_t(np.ascontiguousarray(s_in[:, r0:r1])), h=_t(h0[r0:r1]), c=_t(c0[r0:r1]),
                  spk=torch.empty((T, r1 - r0, H), device=DEV) if want_f32 else None,
                  s8=torch.zeros((T, r1 - r0, HP), dtype=torch.int8, device=DEV), cnt=torch.zeros((1,), dtype=torch.int64, device=DEV))
+        if canary:  # (tests/test_scan_edges.py: NaN / 0x7f where the launch writes)
+            t["s8"][:, :, :H] = 0x7f
+            if want_f32:
+                t["spk"].fill_(float("nan"))
         s = seg[i]
         s.zin, s.w_hh, s.w_dq, s.bias, s.bn_alpha, s.bn_beta = None, _p(keep[0]), _p(keep[1]), _p(keep[4]), _p(keep[5]), _p(keep[6])
         s.h_state, s.c_state, s.spikes_f32, s.spikes_i8, s.membrane, s.R = _p(t["h"]), _p(t["c"]), _p(t["spk"]), _p(t["s8"]), None, r1 - r0
@@ -1567,7 +1585,7 @@ def test_fused_scan_with_the_io_waves_computing_two_tiles_input_terms_is_bit_ide
     assert res["2"][0][1].any()
 
 
-def _run_fused_x(hip, x, sd, alpha, beta, h0, c0, want_f32=True, segs_split=None):
+def _run_fused_x(hip, x, sd, alpha, beta, h0, c0, want_f32=True, segs_split=None, canary=False):
     """sfsn_gsn_layer_scan_fused_x on fp32 feature rows x [T, R, I] (a layer 0): fp32 spikes (or None), int8 spikes, h, c, count."""
     from spiking_fullsubnet_amd._lib import FusedX, ScanSegment, check
     from spiking_fullsubnet_amd.engine import pack_w3
@@ -1584,6 +1602,10 @@ def _run_fused_x(hip, x, sd, alpha, beta, h0, c0, want_f32=True, segs_split=None
         t = dict(x=_t(np.ascontiguousarray(x[:, r0:r1])), h=_t(h0[r0:r1]), c=_t(c0[r0:r1]),
                  spk=torch.empty((T, r1 - r0, H), device=DEV) if want_f32 else None,
                  s8=torch.zeros((T, r1 - r0, HP), dtype=torch.int8, device=DEV), cnt=torch.zeros((1,), dtype=torch.int64, device=DEV))
+        if canary:  # (tests/test_scan_edges.py: NaN / 0x7f where the launch writes)
+            t["s8"][:, :, :H] = 0x7f
+            if want_f32:
+                t["spk"].fill_(float("nan"))
         s = seg[i]
         s.zin, s.w_hh, s.w_dq, s.bias, s.bn_alpha, s.bn_beta = None, _p(keep[0]), _p(keep[1]), _p(keep[3]), _p(keep[4]), _p(keep[5])
         s.h_state, s.c_state, s.spikes_f32, s.spikes_i8, s.membrane, s.R = _p(t["h"]), _p(t["c"]), _p(t["spk"]), _p(t["s8"]), None, r1 - r0

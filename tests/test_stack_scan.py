@@ -46,10 +46,12 @@ def _cells(rng, I, H, nl):
     return out
 
 
-def run_stack(hip, zin0s, cells, T, H, rpw, lag=4, want_f32=True, h0=None, c0=None, wide=True, xs=None):
+def run_stack(hip, zin0s, cells, T, H, rpw, lag=4, want_f32=True, h0=None, c0=None, wide=True, xs=None, zin_has_bias=False, canary=False):
     """zin0s: per segment [T, R, H] = x . W_ih^T of layer 0 (bias added here).  Returns per layer / segment fp32 spikes,
     int8 spikes and the final states.  wide: give the layers >= 1 an input-term buffer (H <= 256: selects the 16-wave flavour
-    with PROJ workgroups; without it the 8-wave fused-input roles run; H > 256 always needs the buffer)."""
+    with PROJ workgroups; without it the 8-wave fused-input roles run; H > 256 always needs the buffer).
+    Keywords of tests/test_scan_edges.py: zin_has_bias: zin0s are the ABI's input terms already; canary: the outputs start as NaN / 0x7f
+    (the live columns of the int8 spikes)."""
     from spiking_fullsubnet_amd._lib import FusedInput, ScanSegment, check
     from spiking_fullsubnet_amd.engine import pack_w3
     nl, ns = len(cells), len(zin0s)
@@ -67,11 +69,15 @@ def run_stack(hip, zin0s, cells, T, H, rpw, lag=4, want_f32=True, h0=None, c0=No
         for i, z0 in enumerate(zin0s):
             R = z0.shape[1]
             s = segs[l * ns + i]
-            z = _t((z0 + sd["bias_ih"][:H]).astype(np.float32)) if l == 0 else (torch.empty((T, R, H), device=DEV) if (H > 256 or wide) else None)
+            z = _t(z0.astype(np.float32) if zin_has_bias else (z0 + sd["bias_ih"][:H]).astype(np.float32)) if l == 0 else (torch.empty((T, R, H), device=DEV) if (H > 256 or wide) else None)
             h = _t(np.zeros((R, H), np.float32) if h0 is None else h0[l][i])
             c = _t(np.zeros((R, H), np.float32) if c0 is None else c0[l][i])
             spk = torch.empty((T, R, H), device=DEV) if want_f32 else None
             s8 = torch.zeros((T, R, HP), dtype=torch.int8, device=DEV)
+            if canary:
+                s8[:, :, :H] = 0x7f
+                if want_f32:
+                    spk.fill_(float("nan"))
             keep += [z, h, c]
             s.zin, s.w_hh, s.w_dq, s.bias, s.bn_alpha, s.bn_beta = _p(z), _p(pk), _p(dq), _p(bias), _p(al), _p(be)
             s.h_state, s.c_state, s.spikes_f32, s.spikes_i8, s.membrane, s.R = _p(h), _p(c), _p(spk), _p(s8), None, R
