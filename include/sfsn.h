@@ -486,7 +486,13 @@ int sfsn_cum_laplace_norm(float* x /* [T][R][I] */, int T, int R, int I, float* 
  * store carries the spikes AND the launch's tag; consumers poll the payload itself).
  * The recurrent product of a layer is issued before its input has arrived (it needs the previous frame only).
  * Arithmetic is that of sfsn_features / sfsn_spike_proj / sfsn_gsn_layer_scan / sfsn_deepfilter expression by expression;
- * the real-valued input product is sfsn_input_proj_f32's fp32-MFMA form with four accumulators.
+ * the real-valued input product is sfsn_input_proj_f32's fp32-MFMA form with four accumulators.  That one product is NOT
+ * the offline kernels' sum: sfsn_input_proj_f32 adds the chunks into one accumulator, or (64 rows and more) takes the bf16
+ * three-way split.  A layer-0 membrane of a launch therefore agrees with the offline forward's within the rounding of the
+ * input product, not bit for bit (tests/test_hop_edges.py: different low bits on every case; both inside the fp64 bound).
+ * Everything else is bit for bit: layer 0's spikes are the offline forward's wherever no layer-0 membrane lies within that
+ * rounding of the threshold, and from equal layer-0 spikes on, every spike, every membrane of the layers above and the
+ * enhanced spectrum are the offline forward's bits.
  *
  * Shared or separate gate weights (sfsn_hop_desc.unshared), LayerNorm / cumulative Laplace / no normalisation, or the offline
  * Laplace / Gaussian normalisation with the clips' statistics GIVEN (feat.mu, feat.ln_w: see sfsn_hop_seq), H % 16 == 0, H <= 320, I <= 192, P <= 256 (full-band P <= 128), at most

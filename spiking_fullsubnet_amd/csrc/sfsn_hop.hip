@@ -25,6 +25,10 @@
 //
 // Arithmetic: the expressions of features_kernel / spike_proj_kernel / scan_body / deepfilter_kernel; the real-valued input
 // product uses input_proj_kernel's fp32 MFMA operand layout with four accumulators (a quarter of the dependent chain).
+// The four accumulators are another association of the sum than input_proj_kernel's one (and than the bf16 split the offline
+// forward takes from 64 rows on): layer 0's membranes agree with the offline kernels' within the rounding of that product, not
+// bit for bit, and its spikes wherever no membrane lies that close to the threshold; from equal layer-0 spikes on everything is
+// the offline forward's bits (include/sfsn.h; tests/test_hop_edges.py asserts exactly this).
 // Deadlock freedom: producers have lower block indices than their consumers, workgroups are dispatched in index order and the
 // launch is refused unless every workgroup can be resident at once; every spin is bounded all the same (error word).
 #include <hip/hip_runtime.h>

@@ -6,7 +6,10 @@ per-frame LayerNorm; modeling_spiking_fullsubnet.py:434-440, 239-258, 108-112) n
 frames of the *noisy* spectrum with zero padding before the first frame (modeling_spiking_fullsubnet.py:315-346).  A
 session therefore keeps, on the device: the (h, c) state of every layer and ``max(df) - 1`` frames of input history, and
 each ``step`` runs exactly the kernels of the offline forward on ``hop`` new frames.  Outputs are bit-identical to the
-offline forward on the concatenated input (tested).
+offline forward on the concatenated input (tested) -- for the one-launch hop with one reservation: its layer-0 input product sums
+in another association than the offline kernels' (include/sfsn.h), so a layer-0 membrane closer to the threshold than that
+product's rounding (a few 1e-7 of the sum's terms) can spike on one side only; everything is bit-identical from equal layer-0
+spikes on.
 
 Two ways to run a hop.  ``one_launch`` (default where the library covers the model: shared or separate gate weights, at most
 3 layers / 4 groups): ``sfsn_stream_hop`` -- the whole frame in ONE launch of a few dozen small workgroups whose waves hand

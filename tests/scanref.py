@@ -5,8 +5,9 @@ A helper module like frontback.py (not a conftest); numpy only.  Four parts:
 
 * `quantise`: sfsn_w3_pack_bits restated on integers (the weights the device holds: weight quantisation is not part of the error; the
   spike products are exact -- an integer sum times a power-of-two dq), and `layer`: an fp64 GSN layer in eval mode with the semantics
-  of include/sfsn.h ("GSN layer scan"), for the three forms of the input term: a given zin ("zin"), s_in . Wq_ih^T + bias_f ("spike":
-  the fused scans, stack layers >= 1) and x . W_ih^T + bias_f ("x": fused-x, stack layer 0); shared and separate gate weights.
+  of include/sfsn.h ("GSN layer scan"), for the four forms of the input term: a given zin ("zin"), s_in . Wq_ih^T + bias_f ("spike":
+  the fused scans, stack layers >= 1, the streaming hops' layers >= 1), x . W_ih^T + bias_f through the bf16 split ("x": fused-x, stack
+  layer 0) and the same product in plain fp32, any order ("x32": the streaming hops' layer 0); shared and separate gate weights.
   test_scanref_host.py pins it to Oracle("f64").gsn_layer.
 * the bound: a per-element tolerance on the post-BatchNorm membrane of every step, evaluated from fp64 reference quantities with
   u = 2^-24 and propagated along the chain.  Its derivation is in `layer`'s docstring.  No constant is fitted to what a kernel (or an
@@ -99,11 +100,14 @@ def _input_term(p, mode, mut, quant, rnd):
     """(z [T][R][G H], its error bound or None, largest |integer sum| of the input product)."""
     H, kind, bias = p["H"], p["kind"], p["bias"]
     f64 = mode == "f64"
+    if mut == "no_db" and not p["shared"] and kind != "zin":  # separate gates: the cell gate's product takes the forget gate's bias
+        bias = np.concatenate([bias[:H], bias[:H]])
     if kind == "zin":
         z = p["zin"].astype(np.float64 if f64 else F32)
         ez, smax = np.zeros(z.shape), 0
     elif kind == "spike":
         s = p["s_in"][:, :, :H].astype(np.float64)
+        GH = p["W_ih"].shape[0]  # H (shared gates) or 2H (separate: the cell gate's rows follow the forget gate's)
         if quant:
             q, dq = quantise(p["W_ih"], p.get("bits", 24))
             if mut == "drop_d0":
@@ -113,13 +117,32 @@ def _input_term(p, mode, mut, quant, rnd):
                 S = ((S + 2 ** 30) % 2 ** 31) - 2 ** 30
             smax = int(np.abs(S).max())
             if f64:
-                z = S * dq + bias[:H].astype(np.float64)
+                z = S * dq + bias[:GH].astype(np.float64)
                 ez = rnd * np.abs(S * dq) * (np.abs(S) >= 2 ** 24) + rnd * np.abs(z)
             else:
-                z, ez = _fma(S.astype(F32), dq.astype(F32), bias[:H]), None
+                z, ez = _fma(S.astype(F32), dq.astype(F32), bias[:GH]), None
         else:
-            z, ez, smax = s @ p["W_ih"].astype(np.float64).T + bias[:H].astype(np.float64), None, 0
+            z, ez, smax = s @ p["W_ih"].astype(np.float64).T + bias[:GH].astype(np.float64), None, 0
+    elif kind == "x32":
+        x, w = p["x"], p["W_ih"]
+        K, GH = x.shape[-1], w.shape[0]
+        smax = 0
+        if f64:
+            z = x.astype(np.float64) @ w.astype(np.float64).T + bias[:GH].astype(np.float64)
+            a = np.abs(x.astype(np.float64)) @ np.abs(w.astype(np.float64)).T + np.abs(bias[:GH].astype(np.float64))
+            ez = rnd * (K + 1) * a
+        elif mode == "kernel":  # sfsn_hop.hip: chunks of 16 columns dealt to four accumulators, ((a0 + a1) + (a2 + a3)) + b
+            acc = [np.zeros(x.shape[:2] + (GH,), F32) for _ in range(4)]
+            for k in range(K):
+                acc[(k // 16) & 3] = _fma(x[:, :, k, None], w[None, None, :, k], acc[(k // 16) & 3])
+            z, ez = (((acc[0] + acc[1]) + (acc[2] + acc[3])) + bias[:GH]).astype(F32), None
+        else:  # fbh_input_role: one fmaf chain in k order, then the bias
+            acc = np.zeros(x.shape[:2] + (GH,), F32)
+            for k in range(K):
+                acc = _fma(x[:, :, k, None], w[None, None, :, k], acc)
+            z, ez = (acc + bias[:GH]).astype(F32), None
     else:
+        assert kind == "x", kind
         x, w = p["x"], p["W_ih"]
         K = x.shape[-1]
         smax = 0
@@ -219,6 +242,16 @@ def layer(p, quant=True, rnd=RND):
                       additions on partial sums <= (1 + 2^-7) sum |x||w| --, the 5 K small ones in the other -- partial sums <= 2^-7 1.01
                       sum |x||w| --, then (hi + lo) + b, two more: u [(K + 2)(1 + 2^-7) + 5 K 2^-7 1.01] (sum |x||w| + |b|), frontback.linear's
                       gamma(K + 2) with the second accumulator counted (an addition inside the matrix core counts like any other).
+                      "x32" (the streaming hops' layer 0): a plain fp32 product in an order this bound does not know.  K products and the
+                      bias are K + 1 terms; summing them in ANY order is K additions, so no term passes through more than K of them,
+                      and a product that is rounded on its own (not fused) adds one: at most K + 1 roundings on any term, each
+                      relative to a partial sum <= sum |x||w| + |b|: e_z = (K + 1) u (sum |x||w| + |b|).  The two paths it must cover
+                      stay inside it.  sfsn_hop.hip: chunk c of 16 columns goes to accumulator c mod 4 inside mfma_f32_16x16x4f32 (the
+                      order and fusing of the four products of one instruction are the matrix core's own), then ((a0 + a1) + (a2 +
+                      a3)) + b: a term sees its product, at most 16 ceil(K / 64) additions in its accumulator (the
+                      padding columns add zeros, exactly), two that combine the four and the bias's: 1 + 16 ceil(K / 64) + 3 <= K + 1
+                      from K = 19 on (the smallest K a model here has is 38).  sfsn_fullband_hop.hip's fbh_input_role: one fmaf chain in k order from
+                      zero, then + b: term k passes through K - k fused roundings and the bias addition, at most K + 1.
       pre_f           e_pre = e_z + u |S dq| [|S| >= 2^24] (the recombination's one rounding) + u |pre_f| (the fma).
       pre_g           shared: e_g = e_pre + u |b_g - b_f| (the fp32 difference) + u |pre_g| (the addition); separate: as pre_f.
       sigmoid         a = pre_f * (-log2 e): the literal and the product round (2u |a|); E = exp2(a) is off by ln 2 times the argument's
@@ -244,7 +277,7 @@ def fp32_reference_form(p, mut=None):
     return _run(p, "reference", mut)
 
 
-MUTANTS = ["gt", "no_db", "wrap31", "abs_alpha", "bf16_in", "drop_d0"]
+MUTANTS = ["gt", "no_db", "wrap31", "abs_alpha", "bf16_in", "drop_d0"]  # (no_db with separate gates: the cell gate takes the forget gate's bias)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -341,9 +374,11 @@ def _base(rng, H, R, T, shared, kind, I, p_in=0.25):
         xin, wi = rng.standard_normal((T, R, I)), rng.uniform(-s, s, (G * H, I))
         p["zin"] = (xin @ wi.T + p["bias"][:G * H]).astype(F32)
     elif kind == "spike":
-        assert shared
         p["s_in"] = (rng.random((T, R, H)) < p_in).astype(np.int8)
-        p["W_ih"] = rng.uniform(-s, s, (H, H)).astype(F32)
+        p["W_ih"] = rng.uniform(-s, s, (G * H, H)).astype(F32)
+    elif kind == "x32":
+        p["x"] = rng.standard_normal((T, R, I)).astype(F32)
+        p["W_ih"] = rng.uniform(-s, s, (G * H, I)).astype(F32)
     else:
         assert shared and kind == "x"
         p["x"] = rng.standard_normal((T, R, I)).astype(F32)
@@ -361,8 +396,10 @@ def _pin_input(p, cols, value):
         if not p["shared"]:
             p["zin"][:, :, H + cols] = value
     else:
-        d = p["bias"][H + cols] - p["bias"][cols]
+        d = p["bias"][H + cols] - p["bias"][cols] if p["shared"] else 0.0
         p["W_ih"][cols] = 0
+        if not p["shared"]:
+            p["W_ih"][H + cols] = 0
         p["bias"][cols] = value
         p["bias"][H + cols] = value + d
 
@@ -388,7 +425,7 @@ def _saturated(rng, H, R, T, shared, kind, I, bits):
     p["beta"] = np.full(H, 200.0, F32)  # m >= min(c, g) >= -(80 + 40 + 5): y >= 200 - 1.5 125 > 0: every neuron fires at every frame
     if kind == "spike":
         p["s_in"] = np.ones((T, R, H), np.int8)
-        p["W_ih"] = _sat_rows(H, H, bits, -9)  # half the recurrent scale: |pre| < 120
+        p["W_ih"] = _sat_rows(G * H, H, bits, -9)  # half the recurrent scale: |pre| < 120
     return p
 
 
@@ -410,7 +447,7 @@ def _digit_extremes(rng, H, R, T, shared, kind, I, bits):
 
     p["W_hh"] = corner((1 if shared else 2) * H, H)
     if kind == "spike":
-        p["W_ih"] = corner(H, H)
+        p["W_ih"] = corner((1 if shared else 2) * H, H)
     return p
 
 
@@ -427,7 +464,7 @@ def _tails(rng, H, R, T, shared, kind, I, bits):
         s = 1.0 / np.sqrt(H)
         p["W_ih"] = rng.uniform(-s, s, w.shape).astype(F32)  # ... and the product
         bf = rng.uniform(-115, 115, H).astype(F32)
-        p["bias"][H:] = p["bias"][H:] + bf
+        p["bias"][H:] = p["bias"][H:] + bf if shared else rng.uniform(-100, 100, H).astype(F32)  # (separate: a cell gate of its own)
         p["bias"][:H] = bf
     return p
 
@@ -453,7 +490,7 @@ def _row_scales(rng, H, R, T, shared, kind, I, bits):
     p = _base(rng, H, R, T, shared, kind, I)
     p["W_hh"] = _scaled_rows(rng, (1 if shared else 2) * H, H, 5)
     if kind == "spike":
-        p["W_ih"] = _scaled_rows(rng, H, H, 7)
+        p["W_ih"] = _scaled_rows(rng, (1 if shared else 2) * H, H, 7)
     return p
 
 
@@ -512,10 +549,11 @@ CASES = dict(control=_control, saturated=_saturated, digit_extremes=_digit_extre
 T_MAX, R_MAX = 9, 48  # every shape the tests use is a prefix / a row subset of this one
 
 
-def make_case(name, H, shared, kind, I=38, bits=24, R=R_MAX, T=T_MAX):
-    """Case `name` for (H, R, T, gate sharing, kind of input term, I of the real-valued product, weight bits), seeded by all of them.
+def make_case(name, H, shared, kind, I=38, bits=24, R=R_MAX, T=T_MAX, salt=None):
+    """Case `name` for (H, R, T, gate sharing, kind of input term, I of the real-valued product, weight bits), seeded by all of them
+    (and by `salt`, where cells of one geometry in one model want parameters of their own).
     Weights are returned as the device holds them (quantised to `bits`), so packing them again is the identity."""
-    seed = zlib.crc32(repr((name, H, bool(shared), kind, I, bits, R, T)).encode())
+    seed = zlib.crc32(repr((name, H, bool(shared), kind, I, bits, R, T) + (() if salt is None else (salt,))).encode())
     p = CASES[name](np.random.default_rng(seed), H, R, T, bool(shared), kind, I, bits)
     p["bits"], p["name"] = bits, name
     p["W_hh"] = dequantise(p["W_hh"], bits)
@@ -536,3 +574,9 @@ def next_layer(p, ref, name, bits=24):
 GRID = ([(H, True, "zin", 38, 24) for H in (64, 160, 224, 256, 320)] + [(H, False, "zin", 38, 24) for H in (128, 224, 320)]
         + [(H, True, "zin", 38, 16) for H in (160, 224)] + [(H, True, "spike", 38, 24) for H in (224, 256, 320)]
         + [(H, True, "x", I, 24) for H in (224, 256) for I in (38, 64)])
+
+# the (H, shared, kind, I) of every GSN cell the streaming-hop tests plant a case in (tests/hopref.py, test_hop_edges*.py): layer 0 is
+# "x32" with the model's input width, the layers above are "spike"; test_scanref_host.py runs the same checks on them as on GRID
+HOP_GRID = ([(H, True, "x32", I) for H, I in ((48, 64), (32, 38), (32, 94), (320, 64), (224, 158), (256, 64), (64, 38), (268, 257), (20, 257))]
+            + [(H, False, "x32", I) for H, I in ((48, 64), (32, 94), (320, 64), (224, 38))]
+            + [(H, True, "spike", 38) for H in (48, 32, 64, 268, 20)] + [(H, False, "spike", 38) for H in (48, 32, 224, 320)])

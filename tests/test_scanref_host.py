@@ -2,7 +2,8 @@
 pack / unpack; the fp64 layer equals Oracle("f64").gsn_layer on the oracle's own (unquantised) weight handling; both fp32 emulations of
 the step sit inside the derived bound with half of it to spare on every case and geometry test_scan_edges.py runs, with at most 2 % of
 the elements left unasserted; every mutant of the emulation is rejected on its named case; and the arithmetic claims the kernels'
-comments make (integer recombination up to K = 256, float recombination up to K = 320) hold as assertions.
+comments make (integer recombination up to K = 256, float recombination up to K = 320) hold as assertions.  The same pins, criterion and
+mutants for the kinds the streaming hops add (scanref.HOP_GRID: "x32", and "spike" / "x32" with separate gate weights).
 No GPU is needed, but test_quantise_is_the_librarys_packing calls the library's HOST packing functions, so the library must have been
 built (build()), as for tests/test_host_cpu.py; everything else here is numpy and the oracle."""
 import numpy as np
@@ -42,7 +43,8 @@ def test_quantise_is_the_librarys_packing():
 
 
 @pytest.mark.parametrize("name", ["control", "tails"])
-@pytest.mark.parametrize("H,shared,kind", [(64, True, "zin"), (48, False, "zin"), (96, True, "spike"), (80, True, "x")])
+@pytest.mark.parametrize("H,shared,kind", [(64, True, "zin"), (48, False, "zin"), (96, True, "spike"), (80, True, "x"), (96, False, "spike"),
+                                           (80, True, "x32"), (80, False, "x32")])
 def test_reference_equals_the_fp64_oracle(name, H, shared, kind):
     """Unquantised weights on both sides.  The oracle forms its own input product; a given zin goes in as x with an identity W_ih and
     its biases taken out (shared gates: (0, b_g - b_f), so that its two gate sums are zin and zin + (b_g - b_f))."""
@@ -155,6 +157,50 @@ def test_mutants_are_rejected_on_the_real_valued_input_kind(I):
     assert len(_rejected(p, ref, "gt")) == 2
     p, ref = _case("bn_signs", 224, True, "x", I)
     assert len(_rejected(p, ref, "abs_alpha")) == 2
+
+
+HOP_IDS = [f"H{g[0]}-{'shared' if g[1] else 'separate'}-{g[2]}-I{g[3]}" for g in sr.HOP_GRID]
+
+
+@pytest.mark.parametrize("H,shared,kind,I", sr.HOP_GRID, ids=HOP_IDS)
+def test_hop_kinds_are_inside_the_bound_with_half_to_spare(H, shared, kind, I):
+    """The same criterion on the cells of the streaming hops: "x32" (both summation orders: four accumulators by chunk / one fmaf
+    chain) and "spike", shared and separate gate weights."""
+    for name in sr.CASES:
+        p, ref = _case(name, H, shared, kind, I)
+        assert np.isfinite(ref["y"]).all() and np.isfinite(ref["tol"]).all(), name
+        for form in (sr.fp32_kernel_form, sr.fp32_reference_form):
+            out = form(p)
+            assert np.isfinite(out["y"]).all(), (name, form.__name__)
+            res = sr.compare(out["spk"], ref, out["y"])
+            print(f"{name:16s} H={H} I={I} {kind} {form.__name__:20s} ratio {res.ratio:.3f} unasserted {res.unasserted:.5f}")
+            assert res.ok and res.ratio <= 0.5 and res.unasserted <= 0.02, (name, form.__name__, res)
+        if name == "saturated":
+            assert ref["spk"].all(), "a saturated neuron did not fire"
+            if kind == "spike":
+                assert ref["smax"] == H * sr.QMAX
+        if name == "tails":
+            assert np.abs(p["bias"]).max() > 88.8
+
+
+# mutant -> a case that must reject it, for every new (kind, sharing)
+HOP_MUTANT_CASE = dict(gt="threshold", no_db="control", wrap31="saturated", abs_alpha="bn_signs", bf16_in="control", drop_d0="control")
+
+
+@pytest.mark.parametrize("mut", sr.MUTANTS)
+@pytest.mark.parametrize("H,shared,kind,I", [(320, True, "x32", 64), (224, True, "x32", 158), (320, False, "x32", 64), (224, False, "spike", 38),
+                                             (320, False, "spike", 38), (268, True, "x32", 257)])
+def test_mutants_are_rejected_on_the_hop_kinds(H, shared, kind, I, mut):
+    """Both emulations of every mutant fail `compare` on at least one case -- the mutant's own is tried first -- for "x32" (either
+    sharing) and "spike" with separate gates.  (wrap31 folds at +-2^30: a width whose saturated sum stays below that has nothing to
+    reject; none of these is that narrow.  drop_d0 under a wide layer-0 product: the K + 1 roundings of "x32" at K = 158 hide a dropped low digit of the
+    mild weights; `saturated`, whose low digits are all +-127, does not.)"""
+    if mut == "wrap31" and H * sr.QMAX < 2 ** 30:
+        return
+    names = [HOP_MUTANT_CASE[mut]] + [n for n in sr.CASES if n != HOP_MUTANT_CASE[mut]]
+    hit = next((n for n in names if len(_rejected(*_case(n, H, shared, kind, I), mut)) == 2), None)
+    print(f"{mut} H={H} {'shared' if shared else 'separate'} {kind} I={I}: rejected on {hit}")
+    assert hit is not None, (mut, H, shared, kind)
 
 
 def test_arithmetic_claims():
