@@ -262,6 +262,16 @@ typedef struct sfsn_fused_x {
 int sfsn_gsn_layer_scan_fused_x(const sfsn_scan_segment* segs /* host */, const sfsn_fused_x* fin /* host, one per segment */,
                                 int n_segs, int T, int H, void* stream);
 
+/* Layer 0 of several groups in ONE launch at 16 rows per workgroup: the segments of a sfsn_gsn_layer_scan_fused_x call (segs_x / fin_x,
+ * n_x of them; their workgroups come first) and those of a sfsn_gsn_layer_scan(.., shared, 16, ..) call (segs_z, n_z of them, each with
+ * its `zin`) side by side, every workgroup running the kernel body its own entry point would have launched: bit-identical to the two
+ * calls, one launch instead of two in a row.  Each list is checked as its own entry point checks it (the fused-x list first, same
+ * answers in the same order).  SFSN_EUNSUPPORTED -- the caller makes the two calls -- where either list would not take its 16-row
+ * kernel (H > 224, separate gate weights, a membrane output, SFSN_SCAN_V2 / SFSN_FUSED_V2 set), where the two lists differ in their
+ * output set, hold more than SFSN_MAX_SEGMENTS segments together, or one of them is empty. */
+int sfsn_gsn_layer_scan_l0(const sfsn_scan_segment* segs_x /* host */, const sfsn_fused_x* fin_x /* host, one per segment of segs_x */,
+                           int n_x, const sfsn_scan_segment* segs_z /* host */, int n_z, int T, int H, int shared, void* stream);
+
 /* Layer-pipelined stack scan -- replaces StackedGSU.forward (NEURON:50-62) for ALL layers of a stack in ONE launch.
  * The reference runs layer l over all T frames, then layer l+1 (NEURON:56-61); layer l+1 needs frame t of layer l only at
  * frame t, so here every layer's rows get their own workgroups (weights resident for the whole launch) and the workgroups of

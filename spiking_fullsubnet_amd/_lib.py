@@ -222,6 +222,8 @@ def lib() -> ctypes.CDLL:
     L.sfsn_gsn_layer_scan_fused.argtypes = [ctypes.POINTER(ScanSegment), ctypes.POINTER(FusedInput), _I, _I, _I, _P]
     L.sfsn_gsn_layer_scan_fused_x.restype = _I
     L.sfsn_gsn_layer_scan_fused_x.argtypes = [ctypes.POINTER(ScanSegment), ctypes.POINTER(FusedX), _I, _I, _I, _P]
+    L.sfsn_gsn_layer_scan_l0.restype = _I  # segs_x, fin_x, n_x | segs_z, n_z | T, H, shared | stream
+    L.sfsn_gsn_layer_scan_l0.argtypes = [ctypes.POINTER(ScanSegment), ctypes.POINTER(FusedX), _I, ctypes.POINTER(ScanSegment), _I, _I, _I, _I, _P]
     L.sfsn_stack_scratch_bytes.restype = ctypes.c_size_t
     L.sfsn_stack_scratch_bytes.argtypes = [_I, _I, _I]
     L.sfsn_gsn_stack_scan.restype = _I
@@ -345,7 +347,7 @@ EXPORTS = ("sfsn_abi_version", "sfsn_source_hash", "sfsn_strerror", "sfsn_device
            "sfsn_fullband_wave_hop_check", "sfsn_fullband_stream_hop_wave", "sfsn_fullband_hop_spike_slots",
            "sfsn_fullband_stream_hop_counted", "sfsn_recipe_loss_scratch_bytes", "sfsn_recipe_loss",
            "sfsn_pit_sdr_scratch_bytes", "sfsn_pit_sdr", "sfsn_stft_ragged", "sfsn_istft_ragged", "sfsn_laplace_means_ragged",
-           "sfsn_gaussian_stats_ragged", "sfsn_spike_count_rows_ragged", "sfsn_zero_tail_frames")
+           "sfsn_gaussian_stats_ragged", "sfsn_spike_count_rows_ragged", "sfsn_zero_tail_frames", "sfsn_gsn_layer_scan_l0")
 
 
 def check(rc: int, what: str = "") -> None:

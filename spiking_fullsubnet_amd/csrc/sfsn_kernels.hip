@@ -351,6 +351,48 @@ __global__ __launch_bounds__(1024) void gsn_scan_fusedx3_kernel(const ScanParams
     SFSN_WG_STAMP(p.wg_times, 1);
 }
 
+// Layer 0 of ALL sub-band groups at 16 rows per workgroup in one launch (sfsn_gsn_layer_scan_l0): a workgroup whose segment carries
+// feature rows (x_in) runs the FUSEDX3 role above, one whose segment carries an input term (zin) runs round 2's body exactly as
+// gsn_scan_kernel<1, KS, 16, 1, OUT, 0> does -- the choice is wave-uniform (one segment per workgroup), each role keeps its own LDS
+// layout from offset 0 of the allocation (the launch asks for the larger of the two), and neither exchanges anything with the other:
+// bit-identical to the two launches.  The fused-x segments come first (the longer role gets the lower block indices).  With few
+// hardware queues a forward is a serial chain of launches that each hold a fraction of the CUs: one launch of 32 + 20 workgroups lasts
+// as long as its longer role instead of both in a row.  p.lsplit is the fused-x role's (round 2's body has no IO waves).
+template <int KS, int TL, int OUT>
+__global__ __launch_bounds__(1024) void gsn_scan_l0_kernel(const ScanParams p) {
+    extern __shared__ __attribute__((aligned(16))) char scan_smem[];
+    int s = 0;
+    for (int i = 1; i < p.nseg; ++i)
+        if ((int)blockIdx.x >= p.seg[i].tile0) s = i;
+    const ScanSegDev& sg = p.seg[s];
+    const int row0 = ((int)blockIdx.x - sg.tile0) * 16;
+    SFSN_WG_STAMP(p.wg_times, 0);
+    if (sg.x_in != nullptr) {
+        Scan3yRole rl;
+        rl.x = sg.x_in; rl.w_ih = sg.w_ih_f32; rl.I = sg.I; rl.w_hh = sg.w_hh; rl.w_dq = sg.w_dq; rl.bias = sg.bias;
+        rl.bn_alpha = sg.bn_alpha; rl.bn_beta = sg.bn_beta; rl.h_state = sg.h_state; rl.c_state = sg.c_state;
+        rl.spikes_f32 = sg.spikes_f32; rl.spikes_i8 = sg.spikes_i8; rl.R = sg.R; rl.row0 = row0;
+        rl.count = sg.count; rl.lsplit = p.lsplit;
+        if (sg.I > 32) scan3y_role<KS, TL, OUT, 2>(rl, scan_smem, p.T, p.H, p.NT);
+        else scan3y_role<KS, TL, OUT, 1>(rl, scan_smem, p.T, p.H, p.NT);
+    } else {
+        constexpr int NW = 16;  // one output tile per wave, NT <= 14: waves NT .. 15 own none
+        const int tid = threadIdx.x, lane = tid & 63;
+        const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+        const int n = lane & 15, q = lane >> 4;
+        const int R = sg.R;
+        const int rowc = (row0 + n < R) ? row0 + n : R - 1;
+        scan_prologue<1, KS, NW, 1, OUT, 0>(sg, scan_smem, tid, p.H, p.NT, R, row0, 16);
+        if (wave < p.NT)
+            scan_body<1, KS, NW, 1, OUT, 0, 1>(sg.zin, sg.w_hh, sg.spikes_f32, sg.spikes_i8, nullptr, sg.h_state, sg.c_state, scan_smem, p.T,
+                                               p.H, p.NT, R, row0, rowc, n, q, tid, wave, 16, nullptr, nullptr, sg.count);
+        else
+            scan_body<1, KS, NW, 1, OUT, 0, 0>(sg.zin, sg.w_hh, sg.spikes_f32, sg.spikes_i8, nullptr, sg.h_state, sg.c_state, scan_smem, p.T,
+                                               p.H, p.NT, R, row0, rowc, n, q, tid, wave, 16, nullptr, nullptr, sg.count);
+    }
+    SFSN_WG_STAMP(p.wg_times, 1);
+}
+
 // ---- streamed-weights scan: the shapes whose W_hh cannot live in one CU (unshared gates with H > 256: baseline_xl's
 // full-band layers, 2 x 320 x 320 x 3 B = 614 KB against 512 KB of registers + 160 KB of LDS) -------------------------
 // Same arithmetic as gsn_scan_kernel, bit for bit (same digit MFMAs, same epilogue), but every A fragment is fetched
@@ -2306,7 +2348,8 @@ extern "C" int sfsn_debug_vmcnt_table(int* out_host /* [64] */) {
 #ifdef SFSN_EXPERIMENTS
 // the workgroup-stamp probe (sfsn_scan_dev.h): a caller-owned device buffer of 2 x capacity stamps, handed out launch by launch;
 // kind 1 = gsn_scan_kernel, 2 = the fused scan, 3 = the fused-x scan, 4 = the narrow stack launch, 5 = the IO-wave full-band launch
-// (25 slots per workgroup: stamps, then 12 waves x 4 stall counters), 6 = the wide launch (33 slots: 16 waves).  Single-threaded use only.
+// (25 slots per workgroup: stamps, then 12 waves x 4 stall counters), 6 = the wide launch (33 slots: 16 waves), 7 = the one-launch layer 0
+// (gsn_scan_l0_kernel: the fused-x workgroups, then round 2's body).  Single-threaded use only.
 static struct { unsigned long long* buf; int cap, used, nrec; int rec[16384][3]; } g_wgp;
 unsigned long long* sfsn_wgprobe_take(int kind, int n) {
     if (!g_wgp.buf || g_wgp.used + n > g_wgp.cap || g_wgp.nrec >= 16384) return nullptr;
@@ -2395,6 +2438,21 @@ static int launch_scan3(const ScanParams& p, int tiles, int out, int KS, hipStre
     return SFSN_EUNSUPPORTED;
 }
 
+// The per-segment checks of sfsn_gsn_layer_scan, and the segments as the device sees them in dev[0 .. n_segs) (block indices from
+// `tiles` on): shared with sfsn_gsn_layer_scan_l0, which must give the same answers.
+static int zin_segments(const sfsn_scan_segment* segs, int n_segs, int out, int rpw, ScanSegDev* dev, int& tiles) {
+    for (int i = 0; i < n_segs; ++i) {
+        const sfsn_scan_segment& s = segs[i];
+        if (check_segment(s, out, SEG_NEED_ZIN | SEG_MEMBRANE) != SFSN_OK) return SFSN_EINVAL;
+        ScanSegDev& d = dev[i];
+        copy_segment(d, s, 0);
+        d.membrane = s.membrane; d.tile0 = tiles;
+        d.x_in = nullptr; d.w_ih_f32 = nullptr; d.I = 0;  // (what tells the two kinds of segment apart in gsn_scan_l0_kernel)
+        tiles += (s.R + rpw - 1) / rpw;
+    }
+    return SFSN_OK;
+}
+
 static int layer_scan_impl(const sfsn_scan_segment* segs, int n_segs, int T, int H, int shared, int rows_per_wg, int w16, void* stream) {
     if (!segs || n_segs <= 0 || n_segs > SFSN_MAX_SEGMENTS || T < 0 || H <= 0) return SFSN_EINVAL;
     if (H % 16 != 0 || H > SFSN_MAX_HIDDEN) return SFSN_EUNSUPPORTED;
@@ -2424,14 +2482,7 @@ static int layer_scan_impl(const sfsn_scan_segment* segs, int n_segs, int T, int
     // the int8 spikes are always produced (every consumer of a scan in this library reads them)
     int out = 2 | (segs[0].spikes_f32 ? 1 : 0) | (segs[0].membrane ? 4 : 0);
     if (out == 6) return SFSN_EUNSUPPORTED;  // membranes are a test output: request them together with fp32 spikes
-    for (int i = 0; i < n_segs; ++i) {
-        const sfsn_scan_segment& s = segs[i];
-        if (check_segment(s, out, SEG_NEED_ZIN | SEG_MEMBRANE) != SFSN_OK) return SFSN_EINVAL;
-        ScanSegDev& d = p.seg[i];
-        copy_segment(d, s, 0);
-        d.membrane = s.membrane; d.tile0 = tiles;
-        tiles += (s.R + rpw - 1) / rpw;
-    }
+    if (zin_segments(segs, n_segs, out, rpw, p.seg, tiles) != SFSN_OK) return SFSN_EINVAL;
     p.nseg = n_segs; p.T = T; p.H = H; p.NT = H / 16;
 #ifdef SFSN_TIMING_EXPERIMENTS
     if (const char* e = getenv("SFSN_SCAN_DEBUG_OUT")) out = atoi(e);
@@ -2593,6 +2644,25 @@ extern "C" int sfsn_gsn_layer_scan_fused(const sfsn_scan_segment* segs, const sf
     return SFSN_EUNSUPPORTED;
 }
 
+// The per-segment checks of sfsn_gsn_layer_scan_fused_x in their order, and the segments as the device sees them in dev[0 .. n_segs)
+// (16 rows per workgroup, block indices from `tiles` on): shared with sfsn_gsn_layer_scan_l0, which must give the same answers.
+static int fused_x_segments(const sfsn_scan_segment* segs, const sfsn_fused_x* fin, int n_segs, int out, ScanSegDev* dev, int& tiles, int& imax) {
+    for (int i = 0; i < n_segs; ++i) {
+        const sfsn_scan_segment& s = segs[i];
+        if (check_segment(s, out, SEG_NO_ZIN | SEG_DEFER_ALIGN) != SFSN_OK || !fin[i].x || !fin[i].w_ih) return SFSN_EINVAL;
+        if (fin[i].I <= 0 || fin[i].I > 64 || fin[i].I % 2 != 0 || s.R % 16 != 0) return SFSN_EUNSUPPORTED;  // (answers before alignment)
+        if (!aligned16(fin[i].x) || !segment_aligned(s, SEG_NO_ZIN)) return SFSN_EINVAL;
+        ScanSegDev& d = dev[i];
+        copy_segment(d, s, SEG_NO_ZIN);
+        d.membrane = nullptr; d.tile0 = tiles;
+        d.spikes_in = nullptr; d.w_ih = nullptr; d.w_ih_dq = nullptr;
+        d.x_in = fin[i].x; d.w_ih_f32 = fin[i].w_ih; d.I = fin[i].I;
+        if (fin[i].I > imax) imax = fin[i].I;
+        tiles += s.R / 16;
+    }
+    return SFSN_OK;
+}
+
 extern "C" int sfsn_gsn_layer_scan_fused_x(const sfsn_scan_segment* segs, const sfsn_fused_x* fin, int n_segs, int T, int H,
                                            void* stream) {
     if (!segs || !fin || n_segs <= 0 || n_segs > SFSN_MAX_SEGMENTS || T < 0 || H <= 0) return SFSN_EINVAL;
@@ -2604,19 +2674,8 @@ extern "C" int sfsn_gsn_layer_scan_fused_x(const sfsn_scan_segment* segs, const 
     p.lsplit = s3_lsplit_knob();
     int tiles = 0, imax = 0;
     const int out = 2 | (segs[0].spikes_f32 ? 1 : 0);
-    for (int i = 0; i < n_segs; ++i) {
-        const sfsn_scan_segment& s = segs[i];
-        if (check_segment(s, out, SEG_NO_ZIN | SEG_DEFER_ALIGN) != SFSN_OK || !fin[i].x || !fin[i].w_ih) return SFSN_EINVAL;
-        if (fin[i].I <= 0 || fin[i].I > 64 || fin[i].I % 2 != 0 || s.R % 16 != 0) return SFSN_EUNSUPPORTED;  // (answers before alignment)
-        if (!aligned16(fin[i].x) || !segment_aligned(s, SEG_NO_ZIN)) return SFSN_EINVAL;
-        ScanSegDev& d = p.seg[i];
-        copy_segment(d, s, SEG_NO_ZIN);
-        d.membrane = nullptr; d.tile0 = tiles;
-        d.spikes_in = nullptr; d.w_ih = nullptr; d.w_ih_dq = nullptr;
-        d.x_in = fin[i].x; d.w_ih_f32 = fin[i].w_ih; d.I = fin[i].I;
-        if (fin[i].I > imax) imax = fin[i].I;
-        tiles += s.R / 16;
-    }
+    const int rc = fused_x_segments(segs, fin, n_segs, out, p.seg, tiles, imax);
+    if (rc != SFSN_OK) return rc;
     p.nseg = n_segs; p.T = T; p.H = H; p.NT = H / 16;
     const int KS = (H + 63) / 64, HP = KS * 64;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -2643,6 +2702,50 @@ extern "C" int sfsn_gsn_layer_scan_fused_x(const sfsn_scan_segment* segs, const 
     }
     FUSEDX_CASE(3, 2) FUSEDX_CASE(3, 3) FUSEDX_CASE(4, 2) FUSEDX_CASE(4, 3)
 #undef FUSEDX_CASE
+    return SFSN_EUNSUPPORTED;
+}
+
+// Layer 0 of several groups at 16 rows per workgroup in ONE launch (gsn_scan_l0_kernel): the segments of sfsn_gsn_layer_scan_fused_x
+// (block indices first) and those of sfsn_gsn_layer_scan side by side.  Each list gets the answers of its own entry point, the
+// fused-x list first; SFSN_EUNSUPPORTED wherever either list would not run its 16-row kernel of today (scan3y_role / round 2's body
+// at 16 waves), or the two lists differ in their output set: the caller then makes the two calls.
+extern "C" int sfsn_gsn_layer_scan_l0(const sfsn_scan_segment* segs_x, const sfsn_fused_x* fin_x, int n_x, const sfsn_scan_segment* segs_z,
+                                      int n_z, int T, int H, int shared, void* stream) {
+    if (n_x < 0 || n_z < 0 || n_x > SFSN_MAX_SEGMENTS || n_z > SFSN_MAX_SEGMENTS || T < 0 || H <= 0) return SFSN_EINVAL;
+    if (n_x == 0 || n_z == 0) return SFSN_EUNSUPPORTED;  // (the existing entry points serve a single kind of segment)
+    if (!segs_x || !fin_x || !segs_z) return SFSN_EINVAL;
+    if (H % 16 != 0 || H <= 128 || H > 256) return SFSN_EUNSUPPORTED;  // (sfsn_gsn_layer_scan_fused_x's range: inside sfsn_gsn_layer_scan's)
+    ScanParams p;
+    p.rpw = 16;
+    p.w16 = 0;
+    int tiles = 0, imax = 0;
+    const int out = 2 | (segs_x[0].spikes_f32 ? 1 : 0);
+    const int rc = fused_x_segments(segs_x, fin_x, n_x, out, p.seg, tiles, imax);
+    if (rc != SFSN_OK) return rc;
+    p.NT = H / 16;
+    if (p.NT > 14 || getenv("SFSN_FUSED_V2") || getenv("SFSN_SCAN_V2")) return SFSN_EUNSUPPORTED;  // (round 2's fused-x body: 512 threads)
+    const int out_z = 2 | (segs_z[0].spikes_f32 ? 1 : 0) | (segs_z[0].membrane ? 4 : 0);
+    if (out_z == 6) return SFSN_EUNSUPPORTED;
+    ScanSegDev zdev[SFSN_MAX_SEGMENTS];
+    int tiles_z = tiles;
+    if (zin_segments(segs_z, n_z, out_z, 16, zdev, tiles_z) != SFSN_OK) return SFSN_EINVAL;
+    if (!shared || (out_z & 4) || out_z != out || n_x + n_z > SFSN_MAX_SEGMENTS) return SFSN_EUNSUPPORTED;
+    for (int i = 0; i < n_z; ++i) p.seg[n_x + i] = zdev[i];
+    p.nseg = n_x + n_z; p.T = T; p.H = H;
+    p.lsplit = sfsn_knob("SFSN_S3Y_LSPLIT", SFSN_S3Y_LSPLIT, 0, 14);  // the fused-x role's own value (round 2's body has no such knob)
+    const int KS = (H + 63) / 64;
+    const bool tl = (H & 63) != 0 && (H & 63) <= 32;
+    const int lds_x = KS == 3 ? Scan3yCfg<3, 2>::lds_bytes(p.NT) : Scan3yCfg<4, 2>::lds_bytes(p.NT);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+#define L0_CASE(KS_, TL_, OUT_)                                                                                            \
+    if (KS == KS_ && (int)tl == TL_ && out == OUT_) {                                                                      \
+        const int lds_z = ScanCfg<1, KS_, 16, 1, OUT_, 0>::LDS_BYTES, lds = lds_x > lds_z ? lds_x : lds_z;                 \
+        if (lds > 160 * 1024 - 64) return SFSN_EUNSUPPORTED;                                                               \
+        p.wg_times = sfsn_wgprobe_take(7, tiles_z); /* kind 7: fused-x workgroups first, then round 2's body */            \
+        return launch_lds<gsn_scan_l0_kernel<KS_, TL_, OUT_>>(dim3(tiles_z), dim3(1024), lds, st, p);                      \
+    }
+    L0_CASE(3, 0, 2) L0_CASE(3, 0, 3) L0_CASE(3, 1, 2) L0_CASE(3, 1, 3) L0_CASE(4, 1, 2) L0_CASE(4, 1, 3)
+#undef L0_CASE
     return SFSN_EUNSUPPORTED;
 }
 

@@ -409,6 +409,10 @@ class Engine:
         self.lean_skips_proj = os.environ.get("SFSN_LEAN_SKIP_PROJ", "0") == "1"
         self.count_in_scan = os.environ.get("SFSN_COUNT_IN_SCAN", "1") != "0"  # layer_outputs="counts": counted by the scans themselves
         self.pair_scan = os.environ.get("SFSN_PAIR_SCAN", "1") != "0"  # H <= 224 stacks as one launch of FUSED3 roles (see _stack_choice)
+        # layer 0 of the per-layer path at 16 rows per workgroup: the fused-x groups and the groups with an input term in ONE launch
+        # (sfsn_gsn_layer_scan_l0: same results; with few hardware queues a forward is as long as its chain of launches)
+        self.merge_layer0 = os.environ.get("SFSN_L0_MERGE", "1") != "0"
+        self._l0_refused = set()  # geometries the library answered SFSN_EUNSUPPORTED for (the two calls then, without asking again)
         self.stack_rows_per_wg = {"fb": 4, "sb": 8}  # rows per workgroup of every layer of a stack: sum of workgroups <= CUs
         # frames a consumer role that had to wait lets its producers run ahead before it resumes (the hand-offs' hysteresis).  Round 2: 16
         # (every wave of a workgroup stood in the poll); since the IO-wave roles one lane polls, and a launch ends lag + ring frames after
@@ -648,6 +652,33 @@ class Engine:
         self._count("fused_x")
         with self.timed("scanx:" + tag, st):
             check(L.sfsn_gsn_layer_scan_fused_x(segs, fin, len(seqs), nt, H, st), "sfsn_gsn_layer_scan_fused_x")
+
+    def _stage_scan_l0(self, seqs, fx, rest, xs_, zins, states, spks, s8s, t0, nt, st, tag, cnts=None) -> bool:
+        """Layer 0 of the groups `fx` (input product inside the scan) and `rest` (input term in `zins`) in ONE launch at 16 rows per
+        workgroup (sfsn_gsn_layer_scan_l0): the same results as _stage_scan_fused_x + _stage_scan, one link shorter in the forward's
+        chain of launches.  False (nothing launched) where the library refuses the pair; the refusal is remembered per geometry."""
+        H = seqs[0].H
+        key = (H, tuple((xs_[i].shape[1], seqs[i].I) for i in fx), tuple(xs_[i].shape[1] for i in rest), spks[fx[0]] is None)
+        if key in self._l0_refused:
+            return False
+        sx, sz, fin = (ScanSegment * len(fx))(), (ScanSegment * len(rest))(), (FusedX * len(fx))()
+        for k, i in enumerate(fx):
+            cell, R = seqs[i].cells[0], xs_[i].shape[1]
+            fill_segment(sx[k], cell, R, H, t0, None, states[i], s8s[i], spks[i], count=None if cnts is None else cnts[i])
+            fin[k].x = xs_[i].data_ptr() + t0 * R * seqs[i].I * 4
+            fin[k].w_ih, fin[k].I = cell.w_ih_f32.data_ptr(), seqs[i].I
+        for k, i in enumerate(rest):
+            fill_segment(sz[k], seqs[i].cells[0], s8s[i].shape[1], H, t0, zins[i], states[i], s8s[i], spks[i],
+                         count=None if cnts is None else cnts[i])
+        with self.timed("scanx:" + tag, st):
+            rc = self.lib.sfsn_gsn_layer_scan_l0(sx, fin, len(fx), sz, len(rest), nt, H, int(self.spec.shared), st)
+        if rc == _lib.SFSN_EUNSUPPORTED:
+            self._l0_refused.add(key)
+            return False
+        check(rc, "sfsn_gsn_layer_scan_l0")
+        self._count("fused_x")  # (the fused-x scan ran, as after _stage_scan_fused_x) ...
+        self._count("l0_merged")  # ... inside the one launch: fused_x - l0_merged = the separate fused-x calls
+        return True
 
     def _stage_scan_fused(self, seqs, l, states, spks, s8s, t0, nt, st, tag, cnts=None):
         L = self.lib
@@ -1266,7 +1297,11 @@ class Engine:
                             self._stage_input(seqs, l, d["s8"][l - 1], d["zin"][l], t0, nt, hG[si], tag)
                     link(g, sc)
                     # ---- the scan(s)
-                    if l == 0:
+                    if l == 0 and fx and rest and rpw == 16 and self.merge_layer0 and self._stage_scan_l0(
+                            seqs, fx, rest, xs_, d["zin"][0], d["states"][0], d["spk"][0], d["s8"][0], t0, nt, hS[si], tag,
+                            cnts=None if cn is None else cn[0]):
+                        pass  # (both kinds of group in one launch)
+                    elif l == 0:
                         if fx:
                             self._stage_scan_fused_x(pick(seqs, fx), pick(xs_, fx), pick(d["states"][0], fx), pick(d["spk"][0], fx),
                                                      pick(d["s8"][0], fx), t0, nt, hS[si], tag, cnts=None if cn is None else pick(cn[0], fx))
