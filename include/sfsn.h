@@ -967,6 +967,37 @@ int sfsn_spike_count_rows_ragged(const sfsn_row_count* tensors /* host */, int n
 int sfsn_zero_tail_frames(float* x /* [B][rows][T][width] */, int B, int rows, int T, int width,
                           const int32_t* clip_frames /* device [B] */, void* stream);
 
+/* ----------------------------------------------------------------------------------------------------
+ * Scoring a ragged batch: sfsn_pit_sdr with per-clip lengths, plus the clips' own losses and audiozen.metric.SISDR of the matched
+ * rows (csrc/sfsn_pit.hip).  est, ref [clips][sources][n_samples], n_samples the padded row length; clip b is its samples
+ * [0, L_b), L_b = clip_len[b] clamped into [0, n_samples] on the device.  The ragged contract above holds: pair[b], perm[b],
+ * clip_loss[b], the pairwise-mode rows of grad_est and reordered[b][:, :L_b] have the BITS of sfsn_pit_sdr on a contiguous copy of
+ * that clip alone (clips = 1, n_samples = L_b), and with every clip_len[b] = n_samples every output has the bits of sfsn_pit_sdr on
+ * the batch.
+ *   own length   nothing at or past L_b is read, from est or from ref (the padding may hold anything, NaN included); the zero-mean
+ *                divisor and every L of the formulas is L_b; the clip's sums run over its own ceil(L_b / 2048) chunk partials in
+ *                chunk order; a workgroup whose chunk starts at or past L_b adds no partial and, in the second launch, writes zeros
+ *   tails        grad_est and reordered are +0.0f from sample L_b to n_samples; every element of both is stored exactly once
+ *   clip_loss    [clips], PIT mode, nullable: min_p loss_p[b] in fp32
+ *   loss         [1]: the mean of the clips' minima, every clip weighted EQUALLY (added in clip order in fp64): what averaging the
+ *                one-clip calls gives, not a length-weighted mean.  The PIT-mode gradient's weight is 1 / (clips S).
+ *   si_sdr       [clips][sources], PIT mode, nullable: audiozen.metric.SISDR (metric.py:67-101) of ref[b][j] against its matched
+ *                estimate est[b][perm[b][j]]: both minus their own mean over L_b whatever zero_mean says, eps' = 2^-23
+ *                (torch.finfo(float32).eps), proj = (dot s + eps') / (|s|^2 + eps') per sample,
+ *                10 log10((sum proj^2 + eps') / (sum noise^2 + eps') + eps').  Evaluated in fp64 from the centred sums of the first
+ *                launch (sum proj^2 = (dot^2 n + L_b eps'^2) / (n + eps')^2, sum a proj = dot^2 / (n + eps'),
+ *                sum noise^2 = sum a^2 - 2 sum a proj + sum proj^2) by the workgroup that writes pair; rounded to fp32 once.
+ *   L_b < 2      gives whatever the formulas give for that clip (L_b = 0: NaN) and never an out-of-range access.
+ * Scratch is sfsn_pit_sdr_scratch_bytes(clips, sources, n_samples).  Modes, alignment (clip_len, clip_loss and si_sdr included),
+ * sources <= 4 and the 32-bit limit are sfsn_pit_sdr's.  Checked before any launch, in addition to sfsn_pit_sdr's conditions: a NULL
+ * clip_len; clip_loss or si_sdr given together with pair_cot -> SFSN_EINVAL.  Two plain launches, deterministic, capturable.
+ * ---------------------------------------------------------------------------------------------------- */
+int sfsn_pit_sdr_ragged(const float* est, const float* ref /* [clips][sources][n_samples] */, int clips, int sources, int n_samples,
+                        const int32_t* clip_len /* device [clips] */, int zero_mean, float eps, const float* pair_cot /* nullable */,
+                        float* pair /* [clips][S][S] */, int32_t* perm /* [clips][S] */, float* clip_loss /* nullable [clips] */,
+                        float* loss /* [1] */, float* grad_est /* nullable */, float* reordered /* nullable */,
+                        float* si_sdr /* nullable [clips][S] */, void* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

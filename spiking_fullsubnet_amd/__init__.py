@@ -9,7 +9,8 @@ Drop-in modules (same constructor keywords, state-dict names and forward() tuple
 The intel_ndns recipe's training loss (``freq_MAE``, ``mag_MAE``, ``SISNRLoss`` and the fused ``RecipeLoss``) is in
 ``spiking_fullsubnet_amd.loss``; the wsj0-mix recipes' permutation-invariant SI-SDR loss (``PITWrapper(PairwiseNegSDR())``) is in
 ``spiking_fullsubnet_amd.pit``.  Clips of different lengths run in one forward with ``model.forward_ragged(waves, lengths)``
-(``spiking_fullsubnet_amd.ragged``), each bit-identical to the clip run alone.
+(``spiking_fullsubnet_amd.ragged``), each bit-identical to the clip run alone, and are scored in one call with
+``PITWrapper.per_clip(est, ref, lengths)`` and ``metric.SISDR`` (per-clip permutation, loss and SI-SDR, left on the device).
 
 All compute between ``stft`` and ``istft`` runs in hand-written gfx950 kernels behind the C ABI of
 ``include/sfsn.h`` (``csrc/libsfsn_hip.so``).  There is no CPU fallback.
@@ -25,7 +26,8 @@ from . import loss  # noqa: F401
 from .loss import RecipeLoss  # noqa: F401
 from . import pit  # noqa: F401
 from . import ragged  # noqa: F401
-from .pit import PITWrapper, PairwiseNegSDR  # noqa: F401
+from .pit import PITWrapper, PairwiseNegSDR, PerClip  # noqa: F401
+from .metric import SISDR  # noqa: F401
 
 __all__ = ["SpikingFullSubNet", "Separator", "Engine", "PathSpec", "StreamingSession", "Model", "RecipeLoss", "loss", "pit", "PITWrapper",
-           "PairwiseNegSDR"]
+           "PairwiseNegSDR", "PerClip", "SISDR", "metric", "ragged"]

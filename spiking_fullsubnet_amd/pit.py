@@ -15,18 +15,29 @@ second kernel call with the incoming cotangent).  What the kernel does not cover
 float32, a ``ref`` that requires a gradient, more than 4 sources, a ``loss_func`` that is not this module's ``PairwiseNegSDR``, extra
 keyword arguments.  ``reordered`` is NOT differentiable here (in the reference it is; its trainers never use that): it is marked so,
 and a loss built on it raises in autograd instead of losing the gradient silently.
+
+Ragged batches (``lengths=``, the companion of ``model.forward_ragged``): ``est`` and ``ref`` are one padded batch ``[B, S, L]`` and
+clip b is its samples ``[0, L_b)``; what lies past a clip's end is never read.  Every entry point takes ``lengths`` -- a sequence or
+CPU int tensor (checked on the host: one per clip, ``2 <= L_b <= L``, ``ValueError`` naming the clip; uploaded without a
+synchronisation) or an int32 ``[B]`` device tensor (trusted as it is: no host work, so a training step with lengths captures in a
+graph) -- and runs ``sfsn_pit_sdr_ragged``: each clip's ``pair``, ``perm`` and loss have the bits of the call on that clip alone, the
+mean loss weighs every clip equally, ``reordered`` and the gradient are zero past a clip's end.  ``PITWrapper.per_clip`` is the
+evaluation loops' call: per-clip loss, permutation, pairwise losses, reordered estimates and ``audiozen.metric.SISDR`` of the matched
+rows from one forward-only call, all left on the device.
 """
 from __future__ import annotations
 
 import ctypes
+from collections import namedtuple
 from itertools import permutations
 
 import torch
 
-from . import _lib
+from . import _lib, ragged
 from ._lib import check
 
 MAX_SOURCES = 4
+PerClip = namedtuple("PerClip", "loss perm pair reordered si_sdr")  # [B], [B, S] int64, [B, S, S], [B, S, L], [B, S]; all on the device
 
 
 def _inputs(est, ref, what: str):
@@ -51,9 +62,31 @@ def _inputs(est, ref, what: str):
     return (est if est.data_ptr() % 16 == 0 else est.clone()), (ref if ref.data_ptr() % 16 == 0 else ref.clone())
 
 
-def _call(est, ref, zero_mean, eps, pair_cot, want_grad, want_rest):
-    """One sfsn_pit_sdr call on contiguous [B, S, L] tensors -> (pair, perm, loss, grad, reordered); those not asked for are None.
-    want_rest: False (pairwise mode, or no use for them), "scalars" (perm and loss, which PIT mode requires) or "all" (and reordered)."""
+def device_lengths(lengths, batch: int, max_len: int, device, what: str = "lengths"):
+    """``lengths`` as the int32 [batch] device tensor the kernel reads, or None for None.  A sequence or CPU int tensor is checked on
+    the host (one per clip, ``2 <= L_b <= max_len``; ``ValueError`` naming the clip) and uploaded from pinned memory; a device tensor
+    must be int32 of shape [batch] and is trusted (no host work: the kernel clamps it into the row)."""
+    if lengths is None:
+        return None
+    if torch.is_tensor(lengths) and lengths.is_cuda:
+        if lengths.dtype != torch.int32 or tuple(lengths.shape) != (batch,):
+            raise ValueError(f"{what}: a device tensor must be int32 of shape [{batch}] (one length per clip), got {lengths.dtype} "
+                             f"{tuple(lengths.shape)}")
+        lengths = lengths.contiguous()
+        return lengths if lengths.data_ptr() % 16 == 0 else lengths.clone()
+    lens = ragged._as_ints(lengths, what)
+    if len(lens) != batch:
+        raise ValueError(f"{what}: expected one length per clip ({batch}), got {len(lens)}")
+    for b, n in enumerate(lens):
+        if n < 2 or n > max_len:
+            raise ValueError(f"{what}[{b}] = {n}: clip {b} must have between 2 and {max_len} samples (the padded length)")
+    return ragged.upload(lens, device)
+
+
+def _call(est, ref, zero_mean, eps, pair_cot, want_grad, want_rest, clip_len=None, per_clip=False):
+    """One kernel call on contiguous [B, S, L] tensors -> (pair, perm, loss, grad, reordered); those not asked for are None.
+    want_rest: False (pairwise mode, or no use for them), "scalars" (perm and loss, which PIT mode requires) or "all" (and reordered).
+    clip_len None: sfsn_pit_sdr.  An int32 [B] device tensor: sfsn_pit_sdr_ragged; per_clip then appends (clip_loss, si_sdr)."""
     B, S, L = est.shape
     L_ = _lib.lib()
     nbytes = L_.sfsn_pit_sdr_scratch_bytes(B, S, L)
@@ -67,6 +100,15 @@ def _call(est, ref, zero_mean, eps, pair_cot, want_grad, want_rest):
     grad = torch.empty_like(est) if want_grad else None
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     ptr = lambda t: t.data_ptr() if t is not None else None
+    if clip_len is not None:
+        clip_loss = torch.empty(B, dtype=torch.float32, device=dev) if per_clip else None
+        si_sdr = torch.empty(B, S, dtype=torch.float32, device=dev) if per_clip else None
+        with torch.cuda.device(dev):
+            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            check(L_.sfsn_pit_sdr_ragged(est.data_ptr(), ref.data_ptr(), B, S, L, clip_len.data_ptr(), 1 if zero_mean else 0, float(eps),
+                                         ptr(pair_cot), pair.data_ptr(), ptr(perm), ptr(clip_loss), ptr(loss), ptr(grad), ptr(reordered),
+                                         ptr(si_sdr), scratch.data_ptr(), stream), "sfsn_pit_sdr_ragged")
+        return (pair, perm, loss, grad, reordered) + ((clip_loss, si_sdr) if per_clip else ())
     with torch.cuda.device(dev):  # the C ABI launches on the calling thread's current device
         stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         check(L_.sfsn_pit_sdr(est.data_ptr(), ref.data_ptr(), B, S, L, 1 if zero_mean else 0, float(eps), ptr(pair_cot), pair.data_ptr(),
@@ -75,28 +117,29 @@ def _call(est, ref, zero_mean, eps, pair_cot, want_grad, want_rest):
 
 
 class _PairwiseFn(torch.autograd.Function):
-    """(est, ref, zero_mean, eps) -> pair [B, S, S]; backward is a second kernel call in pairwise mode with the incoming cotangent."""
+    """(est, ref, zero_mean, eps, clip_len) -> pair [B, S, S]; backward is a second kernel call in pairwise mode with the incoming
+    cotangent.  clip_len: None or the int32 [B] device tensor of a ragged batch."""
 
     @staticmethod
-    def forward(ctx, est, ref, zero_mean, eps):
+    def forward(ctx, est, ref, zero_mean, eps, clip_len):
         ctx.save_for_backward(est, ref)
-        ctx.args = (zero_mean, eps)
-        return _call(est, ref, zero_mean, eps, None, False, "scalars")[0]
+        ctx.args = (zero_mean, eps, clip_len)
+        return _call(est, ref, zero_mean, eps, None, False, "scalars", clip_len)[0]
 
     @staticmethod
     def backward(ctx, g_pair):
         est, ref = ctx.saved_tensors
         cot = g_pair.to(torch.float32).contiguous()
-        grad = _call(est, ref, ctx.args[0], ctx.args[1], cot, True, False)[3]
-        return grad, None, None, None
+        grad = _call(est, ref, ctx.args[0], ctx.args[1], cot, True, False, ctx.args[2])[3]
+        return grad, None, None, None, None
 
 
 class _PitFn(torch.autograd.Function):
-    """(est, ref, zero_mean, eps) -> (mean_loss, reordered, perm, pair); only mean_loss is differentiable (to est)."""
+    """(est, ref, zero_mean, eps, clip_len) -> (mean_loss, reordered, perm, pair); only mean_loss is differentiable (to est)."""
 
     @staticmethod
-    def forward(ctx, est, ref, zero_mean, eps):
-        pair, perm, loss, grad, reordered = _call(est, ref, zero_mean, eps, None, ctx.needs_input_grad[0], "all")
+    def forward(ctx, est, ref, zero_mean, eps, clip_len):
+        pair, perm, loss, grad, reordered = _call(est, ref, zero_mean, eps, None, ctx.needs_input_grad[0], "all", clip_len)
         ctx.stored = grad
         perm = perm.to(torch.int64)
         ctx.mark_non_differentiable(reordered, perm, pair)
@@ -104,7 +147,7 @@ class _PitFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_loss, *_):
-        return (g_loss * ctx.stored if ctx.stored is not None else None), None, None, None
+        return (g_loss * ctx.stored if ctx.stored is not None else None), None, None, None, None
 
 
 class PairwiseNegSDR:
@@ -114,9 +157,10 @@ class PairwiseNegSDR:
         self.zero_mean = zero_mean
         self.EPS = EPS
 
-    def __call__(self, est, ref):
+    def __call__(self, est, ref, lengths=None):
         est, ref = _inputs(est, ref, "PairwiseNegSDR")
-        return _PairwiseFn.apply(est, ref, bool(self.zero_mean), float(self.EPS))
+        clip_len = device_lengths(lengths, est.shape[0], est.shape[2], est.device)
+        return _PairwiseFn.apply(est, ref, bool(self.zero_mean), float(self.EPS), clip_len)
 
 
 class PITWrapper:
@@ -144,13 +188,29 @@ class PITWrapper:
         """pit.py:96-106: source [B, S, L] gathered along dim 1 by batch_indices [B, S]."""
         return torch.gather(source, 1, batch_indices[:, :, None].expand(-1, -1, source.shape[2]))
 
-    def full(self, est, ref):
-        """(mean_loss, reordered, perm [B, S] int64, pair [B, S, S]) from one kernel call; only mean_loss carries a gradient."""
+    def full(self, est, ref, lengths=None):
+        """(mean_loss, reordered, perm [B, S] int64, pair [B, S, S]) from one kernel call; only mean_loss carries a gradient.
+        ``lengths``: the clips' own lengths in a padded batch (module docstring); mean_loss weighs every clip equally."""
         est, ref = _inputs(est, ref, "PITWrapper")
-        return _PitFn.apply(est, ref, bool(self.loss_func.zero_mean), float(self.loss_func.EPS))
+        clip_len = device_lengths(lengths, est.shape[0], est.shape[2], est.device)
+        return _PitFn.apply(est, ref, bool(self.loss_func.zero_mean), float(self.loss_func.EPS), clip_len)
 
-    def __call__(self, est, ref, **kwargs):
+    @torch.no_grad()
+    def per_clip(self, est, ref, lengths=None):
+        """Forward only, one kernel call, nothing read back: ``PerClip(loss [B], perm [B, S] int64, pair [B, S, S], reordered [B, S, L],
+        si_sdr [B, S])`` -- each clip's smallest permutation loss and ``audiozen.metric.SISDR`` of reference j against its matched
+        estimate.  ``lengths=None``: every clip has the full length."""
+        est, ref = _inputs(est, ref, "PITWrapper")
+        B, S, L = est.shape
+        clip_len = device_lengths(lengths, B, L, est.device)
+        if clip_len is None:
+            clip_len = torch.full((B,), L, dtype=torch.int32, device=est.device)
+        pair, perm, _, _, reordered, clip_loss, si_sdr = _call(est, ref, bool(self.loss_func.zero_mean), float(self.loss_func.EPS), None, False,
+                                                               "all", clip_len, per_clip=True)
+        return PerClip(clip_loss, perm.to(torch.int64), pair, reordered, si_sdr)
+
+    def __call__(self, est, ref, lengths=None, **kwargs):
         if kwargs:
             raise NotImplementedError(f"PITWrapper: extra keyword arguments are not covered ({sorted(kwargs)}): PairwiseNegSDR takes none")
-        mean_loss, reordered, _, _ = self.full(est, ref)
+        mean_loss, reordered, _, _ = self.full(est, ref, lengths)
         return mean_loss, reordered
