@@ -304,6 +304,21 @@ int sfsn_gsn_stack_scan(const sfsn_scan_segment* segs /* host [n_layers][n_segs]
 int sfsn_gsn_stack_scan_x(const sfsn_scan_segment* segs, const sfsn_fused_input* fin, const sfsn_fused_x* fx /* host [n_segs], nullable */,
                           int n_layers, int n_segs, int T, int H, const int* rows_per_wg, int lag, void* scratch, size_t scratch_bytes,
                           void* stream);
+/* Layers 0 AND 1 of a two-layer stack in ONE launch at 16 rows per workgroup: the workgroups of a sfsn_gsn_layer_scan_l0 call (segs_x /
+ * fin_x, then segs_z; either list may be empty, not both) and, behind them, those of the sfsn_gsn_layer_scan_fused call of layer 1
+ * (segs1 / fin1: n_x + n_z entries in the order x then z), every workgroup running the kernel body its own entry point would have
+ * launched.  A layer-1 workgroup trails the layer-0 workgroup of the same 16 rows by a few frames (write-through int8 rows, a progress
+ * counter per workgroup, sc1 loads: the hand-off of sfsn_gsn_stack_scan).  Bit-identical to the two calls.
+ *   fin1[i].spikes_in must be the spikes_i8 of layer-0 segment i and the row counts must agree (SFSN_EINVAL otherwise).
+ *   Each list is checked as its own entry point checks it (fused-x, then the input-term list, then layer 1).
+ *   SFSN_EUNSUPPORTED -- the caller makes the per-layer calls -- where one of the lists would not take its 16-row IO-wave kernel
+ *   (H > 224, separate gate weights, a membrane output, SFSN_SCAN_V2 / SFSN_FUSED_V2 set), where the lists differ in their output set,
+ *   or the layer holds more than SFSN_MAX_SEGMENTS segments.
+ *   lag, scratch (sfsn_stack_scratch_bytes(2, n_x + n_z, rows of a layer) bytes), error word: as for sfsn_gsn_stack_scan. */
+int sfsn_gsn_layer_scan_l01(const sfsn_scan_segment* segs_x /* host */, const sfsn_fused_x* fin_x /* host, one per segment of segs_x */,
+                            int n_x, const sfsn_scan_segment* segs_z /* host */, int n_z, const sfsn_scan_segment* segs1 /* host */,
+                            const sfsn_fused_input* fin1 /* host, one per segment of segs1 */, int T, int H, int shared, int lag,
+                            void* scratch, size_t scratch_bytes, void* stream);
 /* Round 6 (ABI 19): the same launch for weights packed with 16 bits (sfsn_w3_pack_bits(w, n, k, 16, ..): the least significant digit plane
  * of every recurrent / spike-input matrix is zero): the zero plane's matrix instructions are skipped in the IO-wave scan, FUSEDX3 and FUSED3
  * roles of the sub-band pair layout (8 rows per workgroup, no input-term buffers for the layers >= 1, H <= 224) -- the same sums, hence the

@@ -29,6 +29,7 @@
 #include "sfsn_scan3g_dev.h"
 #include "sfsn_feat_dev.h"
 #include "sfsn_host.h"
+#include "sfsn_scan_host.h"
 
 // G = 1: shared gate weights (W [H][*] used for both gates); G = 2: separate forget / cell weights.
 // KS = 64-wide k steps; NW = waves per workgroup; TPW = tiles owned by the first (NT - NW*(TPW-1)) waves, the
@@ -2438,21 +2439,6 @@ static int launch_scan3(const ScanParams& p, int tiles, int out, int KS, hipStre
     return SFSN_EUNSUPPORTED;
 }
 
-// The per-segment checks of sfsn_gsn_layer_scan, and the segments as the device sees them in dev[0 .. n_segs) (block indices from
-// `tiles` on): shared with sfsn_gsn_layer_scan_l0, which must give the same answers.
-static int zin_segments(const sfsn_scan_segment* segs, int n_segs, int out, int rpw, ScanSegDev* dev, int& tiles) {
-    for (int i = 0; i < n_segs; ++i) {
-        const sfsn_scan_segment& s = segs[i];
-        if (check_segment(s, out, SEG_NEED_ZIN | SEG_MEMBRANE) != SFSN_OK) return SFSN_EINVAL;
-        ScanSegDev& d = dev[i];
-        copy_segment(d, s, 0);
-        d.membrane = s.membrane; d.tile0 = tiles;
-        d.x_in = nullptr; d.w_ih_f32 = nullptr; d.I = 0;  // (what tells the two kinds of segment apart in gsn_scan_l0_kernel)
-        tiles += (s.R + rpw - 1) / rpw;
-    }
-    return SFSN_OK;
-}
-
 static int layer_scan_impl(const sfsn_scan_segment* segs, int n_segs, int T, int H, int shared, int rows_per_wg, int w16, void* stream) {
     if (!segs || n_segs <= 0 || n_segs > SFSN_MAX_SEGMENTS || T < 0 || H <= 0) return SFSN_EINVAL;
     if (H % 16 != 0 || H > SFSN_MAX_HIDDEN) return SFSN_EUNSUPPORTED;
@@ -2590,16 +2576,7 @@ extern "C" int sfsn_gsn_layer_scan_fused(const sfsn_scan_segment* segs, const sf
     p.lsplit = s3_lsplit_knob();
     int tiles = 0;
     const int out = 2 | (segs[0].spikes_f32 ? 1 : 0);
-    for (int i = 0; i < n_segs; ++i) {
-        const sfsn_scan_segment& s = segs[i];
-        if (check_segment(s, out, SEG_NO_ZIN) != SFSN_OK) return SFSN_EINVAL;
-        if (!fin[i].spikes_in || !fin[i].w_ih || !fin[i].w_ih_dq || !aligned16(fin[i].spikes_in) || !aligned16(fin[i].w_ih)) return SFSN_EINVAL;
-        ScanSegDev& d = p.seg[i];
-        copy_segment(d, s, SEG_NO_ZIN);
-        d.membrane = nullptr; d.tile0 = tiles;
-        d.spikes_in = fin[i].spikes_in; d.w_ih = fin[i].w_ih; d.w_ih_dq = fin[i].w_ih_dq;
-        tiles += (s.R + 15) / 16;
-    }
+    if (fused_segments(segs, fin, n_segs, out, p.seg, tiles) != SFSN_OK) return SFSN_EINVAL;
     p.nseg = n_segs; p.T = T; p.H = H; p.NT = H / 16;
     const int KS = (H + 63) / 64, HP = KS * 64;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -2642,25 +2619,6 @@ extern "C" int sfsn_gsn_layer_scan_fused(const sfsn_scan_segment* segs, const sf
     FUSED_CASE(3, 2) FUSED_CASE(3, 3) FUSED_CASE(4, 2) FUSED_CASE(4, 3)
 #undef FUSED_CASE
     return SFSN_EUNSUPPORTED;
-}
-
-// The per-segment checks of sfsn_gsn_layer_scan_fused_x in their order, and the segments as the device sees them in dev[0 .. n_segs)
-// (16 rows per workgroup, block indices from `tiles` on): shared with sfsn_gsn_layer_scan_l0, which must give the same answers.
-static int fused_x_segments(const sfsn_scan_segment* segs, const sfsn_fused_x* fin, int n_segs, int out, ScanSegDev* dev, int& tiles, int& imax) {
-    for (int i = 0; i < n_segs; ++i) {
-        const sfsn_scan_segment& s = segs[i];
-        if (check_segment(s, out, SEG_NO_ZIN | SEG_DEFER_ALIGN) != SFSN_OK || !fin[i].x || !fin[i].w_ih) return SFSN_EINVAL;
-        if (fin[i].I <= 0 || fin[i].I > 64 || fin[i].I % 2 != 0 || s.R % 16 != 0) return SFSN_EUNSUPPORTED;  // (answers before alignment)
-        if (!aligned16(fin[i].x) || !segment_aligned(s, SEG_NO_ZIN)) return SFSN_EINVAL;
-        ScanSegDev& d = dev[i];
-        copy_segment(d, s, SEG_NO_ZIN);
-        d.membrane = nullptr; d.tile0 = tiles;
-        d.spikes_in = nullptr; d.w_ih = nullptr; d.w_ih_dq = nullptr;
-        d.x_in = fin[i].x; d.w_ih_f32 = fin[i].w_ih; d.I = fin[i].I;
-        if (fin[i].I > imax) imax = fin[i].I;
-        tiles += s.R / 16;
-    }
-    return SFSN_OK;
 }
 
 extern "C" int sfsn_gsn_layer_scan_fused_x(const sfsn_scan_segment* segs, const sfsn_fused_x* fin, int n_segs, int T, int H,

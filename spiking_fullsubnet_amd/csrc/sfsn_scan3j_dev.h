@@ -185,8 +185,13 @@ struct Scan3jRole {
 // term of the next frame is off the step's dependency chain, so the IO waves (SIMD 2: loader, SIMD 3: storer) compute it for tiles 12
 // (SIMD 0) and 13 (SIMD 1) and hand the four values per lane over through LDS at the step barrier (double-buffered by frame parity):
 // ~3.6 tiles' worth of work on every SIMD instead of 4 / 4 / 3 / 3.  The same instructions on the same operands: bit-identical.
-template <int KS, int TL, int OUT, int OFF = 0>
-__device__ __forceinline__ void scan3j_role(const Scan3jRole& rl, char* smem, int T, int H, int NT) {
+// GATED = 1 (gsn_scan_l01_kernel, sfsn_pair16.hip): the previous layer's int8 rows are written by ANOTHER workgroup of this launch, which
+// publishes its progress in lk->in[0] (StackLink, sfsn_scan_dev.h).  The loader wave alone knows: lane 0 polls before it requests a frame
+// that is not yet known to be published (s3_ensure: relaxed agent-scope loads, s_sleep, bounded; the producer runs lk->lag frames ahead
+// between polls) and fetches with sc1 DMAs; the other waves wait at the step barrier as they do for any late frame.  An expired spin sets
+// the launch's error word and ends the gating: the launch finishes with garbage, the host reports it.  GATED = 0: today's code, lk unused.
+template <int KS, int TL, int OUT, int OFF = 0, bool GATED = false>
+__device__ __forceinline__ void scan3j_role(const Scan3jRole& rl, char* smem, int T, int H, int NT, const StackLink* lk = nullptr) {
     using C = Scan3jCfg<KS>;
     constexpr int RPW = 16, LDH = C::LDH, HP = C::HP, D = C::D, A = C::A, SLOT = C::SLOT, NP = C::NP, NCH = C::NCH;
     constexpr int KSF = TL ? KS - 1 : KS;
@@ -366,11 +371,16 @@ __device__ __forceinline__ void scan3j_role(const Scan3jRole& rl, char* smem, in
         auto issue = [&](int slot, int td) __attribute__((always_inline)) {
             const float* st = reinterpret_cast<const float*>(rl.spikes_in + (size_t)td * frame);
 #pragma unroll
-            for (int p = 0; p < NP; ++p) dma16_to_lds<false>(__builtin_amdgcn_readfirstlane((unsigned)(slot * SLOT + p * 1024)), st, goff[p]);
+            for (int p = 0; p < NP; ++p) dma16_to_lds<GATED>(__builtin_amdgcn_readfirstlane((unsigned)(slot * SLOT + p * 1024)), st, goff[p]);
+        };
+        int avail = GATED ? 0 : T, failed = 0;  // frames known to be published; an expired spin ends the gating
+        auto ensure = [&](int need) __attribute__((always_inline)) {  // frames [0, need) published by my producer
+            if constexpr (GATED) s3_ensure(*lk, need, T, avail, failed, lane);
         };
         S3jHelper<KS, TL> hp;
         if constexpr (OFF) hp.init(rl.w_ih, smem, NT, 12, lane);
         __syncthreads();
+        ensure(A < T ? A : T);  // the prologue requests frames 0 .. min(A, T) - 1 (past the end: clamped copies of the last one)
         for (int s0 = 0; s0 < A; ++s0) issue(s0, s0 < T ? s0 : (T > 0 ? T - 1 : 0));
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_waitcnt(0xc07f);
@@ -383,6 +393,7 @@ __device__ __forceinline__ void scan3j_role(const Scan3jRole& rl, char* smem, in
 #pragma unroll 1
         for (int t = 0; t < T; ++t) {
             const int td = (t + A < T) ? t + A : T - 1;
+            ensure(td + 1);
             issue((t + A) % D, td);  // the slot of frame t - 1: read during step t - 2
             if constexpr (LSF) if (t > 0 && ff.nsf > 0) ff.run(hbuf + (t & 1) * 16 * LDH, rl.spikes_f32 + ((size_t)(t - 1) * R + row0) * H, lane);
             if constexpr (OFF) hp.run(smem, t + 1, PLANE);  // tile 12's input term of frame t + 1 (landed before the barrier of step t - 1)
@@ -505,8 +516,12 @@ struct Scan3yRole {
     int lsplit;
 };
 
-template <int KS, int TL, int OUT, int KSB>
-__device__ __forceinline__ void scan3y_role(const Scan3yRole& rl, char* smem, int T, int H, int NT) {
+// PUB = 1 (gsn_scan_l01_kernel, sfsn_pair16.hip): the int8 rows feed a workgroup of the SAME launch.  The storer wave writes them through
+// (store16_sc1) and, behind a counted wait that leaves only its youngest pf frames' stores in flight, lane 0 publishes "frames < t - pf
+// complete" in lk->out (scan3_role's form; the ordering rule is StackLink's, sfsn_scan_dev.h); T at the end.  The role never waits for
+// anybody, so no spin can expire in it.  The fp32 stores stay plain.  PUB = 0: today's code, lk unused.
+template <int KS, int TL, int OUT, int KSB, bool PUB = false>
+__device__ __forceinline__ void scan3y_role(const Scan3yRole& rl, char* smem, int T, int H, int NT, const StackLink* lk = nullptr) {
     using C = Scan3yCfg<KS, KSB>;
     constexpr int RPW = 16, LDH = C::LDH, HP = C::HP, A = C::A, DX = C::DX, XSLOT = C::XSLOT, NPX = C::NPX, LDX = C::LDX, PLANE = C::PLANE, DP = C::DP;
     constexpr int KSF = TL ? KS - 1 : KS;
@@ -768,21 +783,40 @@ __device__ __forceinline__ void scan3y_role(const Scan3yRole& rl, char* smem, in
             for (int k = 0; k < MAX8; ++k) {
                 if ((ok8 >> k) & 1u) {
                     const v4i d = *reinterpret_cast<const v4i*>(hsrc + l8[k]);
-                    *reinterpret_cast<v4i*>(p8 + (size_t)(64 * k + lane) * 16) = d;
+                    if constexpr (PUB) store16_sc1(p8, (unsigned)((64 * k + lane) * 16), d);
+                    else *reinterpret_cast<v4i*>(p8 + (size_t)(64 * k + lane) * 16) = d;
                     if constexpr (!(OUT & 1)) cnt += popc16(d);
                 }
             }
             if constexpr (F32) ff.run(hsrc, rl.spikes_f32 + ((size_t)ts * R + row0) * H, lane);
         };
+        // PUB: store instructions per frame with at least one live lane (an instruction without live lanes may or may not be issued; more
+        // instructions per frame than counted only make the wait stricter, and so does lane 0's counter store), and the frames of my
+        // stores that may be in flight (see scan3_role)
+        const int rows_live = (R - row0 < RPW) ? R - row0 : RPW;
+        const int spf = (F32 ? ff.nsf : 0) + (rows_live * (HP / 16) + 63) / 64;
+        const int pf = 62 / spf < SFSN_S3_PFMAX ? 62 / spf : SFSN_S3_PFMAX;
         __syncthreads();
         __builtin_amdgcn_s_barrier();
 #pragma unroll 1
         for (int t = 0; t < T; ++t) {
-            if (t > 0) flush(hbuf + (t & 1) * 16 * LDH, t - 1);
+            if (t > 0) {
+                flush(hbuf + (t & 1) * 16 * LDH, t - 1);
+                if constexpr (PUB) {
+                    // my queue holds nothing but these stores and they retire in order: all but the youngest pf frames' worth have
+                    // retired -> frames [0, t - pf) are complete in memory (the int8 rows were written through)
+                    wait_vmcnt_n(pf * spf);
+                    if (lane == 0 && t - pf > 0) stack_publish(*lk, t - pf);
+                }
+            }
             __builtin_amdgcn_s_waitcnt(0xc07f);
             __builtin_amdgcn_s_barrier();
         }
         if (T > 0) flush(hbuf + (T & 1) * 16 * LDH, T - 1);
+        if constexpr (PUB) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if (lane == 0) stack_publish(*lk, T);
+        }
         if constexpr (!(OUT & 1)) wave_count_add(rl.count, cnt);
         return;
     }

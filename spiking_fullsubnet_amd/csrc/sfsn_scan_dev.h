@@ -229,6 +229,28 @@ __device__ __forceinline__ void store16_sc1(void* base_uniform, unsigned byte_of
 #endif
 }
 
+// Every workgroup of a launch with hand-offs (padding blocks too) calls this as its last action: the last one to arrive -- nobody polls
+// any more -- zeroes the progress counters and the exit counter, so that the next launch on this scratch buffer starts clean without a
+// memset in front of it (two fill launches of ~5 us each per stack launch: a third of a streaming hop's stack time).  `p`: the launch's
+// parameters (StackParams, PairParams) with `prog` ([0] error word, [1] workgroups that have exited, [2 + block] frames published by that
+// workgroup) and `nblocks` (the grid size); `word`: an int of the dynamic LDS allocation behind every role's layout (NO static __shared__
+// in these kernels: the LDS-DMA destinations are absolute addresses from 0).
+template <class Params>
+__device__ __forceinline__ void stack_exit_counters(const Params& p, int* word) {
+    // my own counter stores (write-through, issued by this workgroup's publishing wave) must have reached memory before I count
+    // myself out -- otherwise one of them could land after the last workgroup's zeroing.  No cache fence is needed for that:
+    // draining the waves' own store queues is enough (a __threadfence() here cost ~6 us per launch).
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0)
+        *reinterpret_cast<volatile int*>(word) = atomicAdd(p.prog + 1, 1u) == (unsigned)(p.nblocks - 1) ? 1 : 0;
+    __syncthreads();
+    if (*reinterpret_cast<volatile int*>(word)) {
+        for (int i = threadIdx.x; i < p.nblocks; i += blockDim.x) __hip_atomic_store(p.prog + 2 + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (threadIdx.x == 0) __hip_atomic_store(p.prog + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
 template <int G, int KS, int NW, int TPW, int OUT, int LP>
 struct ScanCfg {
     static constexpr int LDH = KS * 64 + 32;  // +32 B row pad: the ds_read_b128 lane groups of a B fragment hit distinct banks

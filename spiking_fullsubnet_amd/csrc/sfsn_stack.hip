@@ -79,24 +79,9 @@ struct StackParams {
 };
 
 
-// Every workgroup (padding blocks too) calls this as its last action: the last one to arrive -- nobody polls any more -- zeroes the
-// progress counters and the exit counter, so that the next launch on this scratch buffer starts clean without a memset in front
-// of it (two fill launches of ~5 us each per stack launch: a third of a streaming hop's stack time).  `word`: the gate word of
-// the dynamic LDS allocation (NO static __shared__ in these kernels: the LDS-DMA destinations are absolute addresses from 0).
-__device__ __forceinline__ void stack_exit(const StackParams& p, int* word) {
-    // my own counter stores (write-through, issued by this workgroup's publishing wave) must have reached memory before I count
-    // myself out -- otherwise one of them could land after the last workgroup's zeroing.  No cache fence is needed for that:
-    // draining the waves' own store queues is enough (a __threadfence() here cost ~6 us per launch).
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0)
-        *reinterpret_cast<volatile int*>(word) = atomicAdd(p.prog + 1, 1u) == (unsigned)(p.nblocks - 1) ? 1 : 0;
-    __syncthreads();
-    if (*reinterpret_cast<volatile int*>(word)) {
-        for (int i = threadIdx.x; i < p.nblocks; i += blockDim.x) __hip_atomic_store(p.prog + 2 + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (threadIdx.x == 0) __hip_atomic_store(p.prog + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
+// Every workgroup (padding blocks too) calls this as its last action (stack_exit_counters, sfsn_scan_dev.h: the last one to arrive
+// zeroes the counters for the next launch on this scratch buffer).  `word`: the gate word of the dynamic LDS allocation.
+__device__ __forceinline__ void stack_exit(const StackParams& p, int* word) { stack_exit_counters(p, word); }
 
 template <int KS>
 struct StackGeom {

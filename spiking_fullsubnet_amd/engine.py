@@ -413,6 +413,11 @@ class Engine:
         # (sfsn_gsn_layer_scan_l0: same results; with few hardware queues a forward is as long as its chain of launches)
         self.merge_layer0 = os.environ.get("SFSN_L0_MERGE", "1") != "0"
         self._l0_refused = set()  # geometries the library answered SFSN_EUNSUPPORTED for (the two calls then, without asking again)
+        # layers 0 AND 1 of a two-layer stack of the per-layer path at 16 rows per workgroup in ONE launch (sfsn_gsn_layer_scan_l01: same
+        # results, layer 1 trailing layer 0 by a few frames; the next link cut from the chain).  Not under graph capture and
+        # not on the staged schedules, which keep their per-layer launches.  SFSN_L01_PAIR=0 / 1 overrides the default.
+        self.pair16 = os.environ.get("SFSN_L01_PAIR", "1") != "0"
+        self._l01_refused = set()
         self.stack_rows_per_wg = {"fb": 4, "sb": 8}  # rows per workgroup of every layer of a stack: sum of workgroups <= CUs
         # frames a consumer role that had to wait lets its producers run ahead before it resumes (the hand-offs' hysteresis).  Round 2: 16
         # (every wave of a workgroup stood in the poll); since the IO-wave roles one lane polls, and a launch ends lag + ring frames after
@@ -678,6 +683,63 @@ class Engine:
         check(rc, "sfsn_gsn_layer_scan_l0")
         self._count("fused_x")  # (the fused-x scan ran, as after _stage_scan_fused_x) ...
         self._count("l0_merged")  # ... inside the one launch: fused_x - l0_merged = the separate fused-x calls
+        return True
+
+    def _stage_scan_l01(self, seqs, fx, rest, xs_, d, t0, nt, st, tag, cn=None) -> bool:
+        """Layers 0 and 1 of a two-layer stack in ONE launch at 16 rows per workgroup (sfsn_gsn_layer_scan_l01): the layer-0 launch of
+        _stage_scan_l0 (or the single call where `fx` or `rest` is empty) and _stage_scan_fused of layer 1 side by side, layer 1 trailing
+        layer 0 by a few frames.  Scratch and error word as in _stage_stack.  False (nothing launched) where the library refuses; the
+        refusal is remembered per geometry."""
+        L = self.lib
+        H = seqs[0].H
+        HP = (H + 63) // 64 * 64
+        order = list(fx) + list(rest)
+        key = (H, tuple((xs_[i].shape[1], seqs[i].I) for i in fx), tuple(xs_[i].shape[1] for i in rest), d["spk"][0][order[0]] is None)
+        if key in self._l01_refused:
+            return False
+        states, spks, s8s, zins = d["states"], d["spk"], d["s8"], d["zin"][0]
+        sx, sz, fin = (ScanSegment * max(len(fx), 1))(), (ScanSegment * max(len(rest), 1))(), (FusedX * max(len(fx), 1))()
+        s1, fin1 = (ScanSegment * len(order))(), (FusedInput * len(order))()
+        for k, i in enumerate(fx):
+            cell, R = seqs[i].cells[0], xs_[i].shape[1]
+            fill_segment(sx[k], cell, R, H, t0, None, states[0][i], s8s[0][i], spks[0][i], count=None if cn is None else cn[0][i])
+            fin[k].x = xs_[i].data_ptr() + t0 * R * seqs[i].I * 4
+            fin[k].w_ih, fin[k].I = cell.w_ih_f32.data_ptr(), seqs[i].I
+        for k, i in enumerate(rest):
+            fill_segment(sz[k], seqs[i].cells[0], s8s[0][i].shape[1], H, t0, zins[i], states[0][i], s8s[0][i], spks[0][i],
+                         count=None if cn is None else cn[0][i])
+        rows = 0
+        for k, i in enumerate(order):
+            cell, R = seqs[i].cells[1], s8s[1][i].shape[1]
+            rows += R
+            pk, dq = cell.w_ih_q[0]
+            fill_segment(s1[k], cell, R, H, t0, None, states[1][i], s8s[1][i], spks[1][i], count=None if cn is None else cn[1][i])
+            fin1[k].spikes_in = s8s[0][i].data_ptr() + t0 * R * HP
+            fin1[k].w_ih, fin1[k].w_ih_dq = pk.data_ptr(), dq.data_ptr()
+        nbytes = L.sfsn_stack_scratch_bytes(2, len(order), rows)
+
+        def make():  # zero-filled once, on the stream the kernel is launched on (see _stage_stack)
+            with torch.cuda.stream(self._tstream(st)):
+                return dict(t=torch.zeros((nbytes // 4,), dtype=torch.int32, device=self.device))
+        scratch = self._workspace(("l01_scratch", tag, len(order), rows, torch.cuda.current_stream(self.device).cuda_stream,
+                                   self._tstream(st).cuda_stream), make)["t"]
+        assert scratch.numel() * 4 >= nbytes
+        with self.timed("stack:" + tag, st):
+            rc = L.sfsn_gsn_layer_scan_l01(sx if fx else None, fin if fx else None, len(fx), sz if rest else None, len(rest), s1, fin1,
+                                           nt, H, int(self.spec.shared), self.stack_lag, _ptr(scratch), nbytes, st)
+        if rc == _lib.SFSN_EUNSUPPORTED:
+            self._l01_refused.add(key)
+            return False
+        check(rc, "sfsn_gsn_layer_scan_l01")
+        if not any(scratch is t for t in self._stack_scratch):
+            self._stack_scratch.append(scratch)
+        if fx:
+            self._count("fused_x")  # (where the layer-0 launch this one replaces would have counted: _stage_scan_l0 / _stage_scan_fused_x)
+            if rest:
+                self._count("l0_merged")
+        self._count("fused")  # layer 1's fused scan ran
+        self._count("l01_pair")
+        self._errors.watch(self._tstream(st), scratch, f"{tag} layers 0+1 rows={rows} frames={nt} lag={self.stack_lag}")
         return True
 
     def _stage_scan_fused(self, seqs, l, states, spks, s8s, t0, nt, st, tag, cnts=None):
@@ -1281,7 +1343,11 @@ class Engine:
             fx = [i for i in range(len(seqs)) if self._fusable_x(seqs[i], xs_[i], rpw, want_membrane)]
             rest = [i for i in range(len(seqs)) if i not in fx]
             cn = d.get("cnt")
+            # layers 0 and 1 of a two-layer stack at 16 rows in one launch (the staged schedules and graph capture keep the per-layer launches)
+            pair = bool(self.pair16 and self.merge_layer0 and nl == 2 and rpw == 16 and fused and not staged
+                        and not torch.cuda.is_current_stream_capturing())
             for c, (t0, nt) in enumerate(bounds):
+                paired = False
                 for l in range(nl):
                     si = first + l
                     g, sc = gstreams[si], sstreams[si]
@@ -1297,7 +1363,11 @@ class Engine:
                             self._stage_input(seqs, l, d["s8"][l - 1], d["zin"][l], t0, nt, hG[si], tag)
                     link(g, sc)
                     # ---- the scan(s)
-                    if l == 0 and fx and rest and rpw == 16 and self.merge_layer0 and self._stage_scan_l0(
+                    if l == 0 and pair and self._stage_scan_l01(seqs, fx, rest, xs_, d, t0, nt, hS[si], tag, cn=cn):
+                        paired = True  # (layer 1 of this chunk ran in the same launch)
+                    elif l == 1 and paired:
+                        pass
+                    elif l == 0 and fx and rest and rpw == 16 and self.merge_layer0 and self._stage_scan_l0(
                             seqs, fx, rest, xs_, d["zin"][0], d["states"][0], d["spk"][0], d["s8"][0], t0, nt, hS[si], tag,
                             cnts=None if cn is None else cn[0]):
                         pass  # (both kinds of group in one launch)
