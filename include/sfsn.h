@@ -902,6 +902,42 @@ int sfsn_recipe_loss(const float* est /* [rows][n_samples] */, const float* tgt 
                      void* scratch, void* stream);
 
 /* ----------------------------------------------------------------------------------------------------
+ * The recipe loss on rows of different lengths in one padded batch, with the REVERB recipe's time-domain L1 as a fourth term
+ * (recipes/reverb/spiking_fullsubnet/trainer.py:34-37: freq_MAE + mag_MAE + F.l1_loss(est_y, ref_y)).  est, tgt [rows][n_samples],
+ * n_samples the padded row stride.  Row r has L_r = row_len[r] samples, clamped on the device into [1025, n_samples] so that a wrong
+ * value never indexes outside the row; T_r = 1 + L_r / 512 frames and N_r = 1025 T_r spectral terms.
+ * Every row term is what sfsn_recipe_loss returns for the row alone (rows = 1, n_samples = L_r), with the bits of that call:
+ *     freq_r, mag_r   reflect padding about the row's own samples 0 and L_r - 1, means over N_r
+ *     sisnr_r         10 log10(ratio + eps) over the row's L_r samples (means and eps as above)
+ *     time_r          sum |e - t| / L_r, summed in fp64
+ * A batch term is the mean of the fp32 row terms, every row weighted equally whatever its length, accumulated in fp64 in row order:
+ *     freq = (1 / rows) sum_r freq_r, likewise mag, sisnr, time;  total = ((c_freq freq + c_mag mag) + c_sdr sisnr) + c_time time
+ * With equal lengths every N_r is the same and this is the reference's mean over the batch.
+ *   row_len   [rows] device int32, 16-byte aligned at its base; NULL: every row has n_samples
+ *   flags     SFSN_LOSS_* bits, 1..15; a term whose bit is clear is reported as 0 and takes no part in total or gradient (SDR and
+ *             TIME, alone or together, run no transform)
+ *   terms     [5] device: freq, mag, sisnr, time, total
+ *   row_terms [rows][4] device or NULL: freq_r, mag_r, sisnr_r, time_r
+ *   grad_est  [rows][n_samples] device or NULL (forward only, the same values): d total / d est.  Row r's share carries the factor
+ *             1 / rows: its spectral coefficients are (float)(c / (rows N_r)), its SI-SNR term has c_sdr / rows, and the time term
+ *             (float)(c_time sgn(e - t) / (rows L_r)), sgn(0) = 0, is added to a sample after the SI-SNR term.  Samples at and beyond
+ *             L_r are written as exactly 0.0f.
+ *   scratch   the scratch-bytes function's size, 16-byte aligned; needs no initialisation and carries nothing between calls
+ * Nothing at or beyond L_r is read, in est or in tgt: the padding may hold anything, NaN included.
+ * Deterministic and capturable like sfsn_recipe_loss: two plain launches sized on the padded row, no atomics, no waits between
+ * workgroups, no host synchronisation; the lengths are read on the device.
+ * Checked before any launch: NULL est, tgt, terms or scratch, a misaligned pointer, rows < 1, flags outside 1..15, n_samples <= 1024
+ * -> SFSN_EINVAL; rows * n_samples or rows * T' * 2048 >= 2^31 (T' of the padded row) -> SFSN_EUNSUPPORTED.  The scratch-bytes
+ * function returns 0 for a shape the call refuses.  (Added without an ABI bump: no existing struct or signature changed.)
+ * ---------------------------------------------------------------------------------------------------- */
+#define SFSN_LOSS_TIME 8
+size_t sfsn_recipe_loss_ragged_scratch_bytes(int rows, int n_samples);
+int sfsn_recipe_loss_ragged(const float* est /* [rows][n_samples] */, const float* tgt /* [rows][n_samples] */, int rows, int n_samples,
+                            const int32_t* row_len /* nullable [rows] */, float c_freq, float c_mag, float c_sdr, float c_time, int flags,
+                            float* terms /* [5] */, float* row_terms /* nullable [rows][4] */, float* grad_est /* nullable */,
+                            void* scratch, void* stream);
+
+/* ----------------------------------------------------------------------------------------------------
  * The wsj0-mix recipes' training loss, PITWrapper(PairwiseNegSDR()) of audiozen/pit.py (recipes/wsj0-mix/spiking_fullsubnet/
  * trainer.py:24-33), and its gradient with respect to the estimates, in one call of two launches.  est, ref [clips][sources][n_samples].
  * For clip b, estimate i and reference j (pit.py:11-56), with a = est[b][i] and r = ref[b][j], each minus its own mean when zero_mean:

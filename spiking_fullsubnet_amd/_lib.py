@@ -86,7 +86,7 @@ TRAIN_MAX_CALLS = 8
 MAX_COUNT_TENSORS = 16
 HOP_MAX_LAYERS = 3
 HOP_MAX_GROUPS = 4
-LOSS_FREQ, LOSS_MAG, LOSS_SDR = 1, 2, 4  # SFSN_LOSS_* (flags of sfsn_recipe_loss)
+LOSS_FREQ, LOSS_MAG, LOSS_SDR, LOSS_TIME = 1, 2, 4, 8  # SFSN_LOSS_* (flags of sfsn_recipe_loss; TIME: sfsn_recipe_loss_ragged only)
 
 
 class HopLayer(ctypes.Structure):
@@ -313,6 +313,10 @@ def lib() -> ctypes.CDLL:
     L.sfsn_recipe_loss_scratch_bytes.argtypes = [_I, _I]
     L.sfsn_recipe_loss.restype = _I  # est, tgt | rows, n_samples | c_freq, c_mag, c_sdr | flags | terms, grad_est, scratch, stream
     L.sfsn_recipe_loss.argtypes = [_P, _P, _I, _I, _F, _F, _F, _I, _P, _P, _P, _P]
+    L.sfsn_recipe_loss_ragged_scratch_bytes.restype = ctypes.c_size_t  # rows, n_samples; 0: refused (host only)
+    L.sfsn_recipe_loss_ragged_scratch_bytes.argtypes = [_I, _I]
+    L.sfsn_recipe_loss_ragged.restype = _I  # est, tgt | rows, n_samples | row_len | c_freq, c_mag, c_sdr, c_time | flags | terms, row_terms, grad_est, scratch, stream
+    L.sfsn_recipe_loss_ragged.argtypes = [_P, _P, _I, _I, _P, _F, _F, _F, _F, _I, _P, _P, _P, _P, _P]
     L.sfsn_pit_sdr_scratch_bytes.restype = ctypes.c_size_t  # clips, sources, n_samples; 0: refused (host only)
     L.sfsn_pit_sdr_scratch_bytes.argtypes = [_I, _I, _I]
     L.sfsn_pit_sdr.restype = _I  # est, ref | clips, sources, n_samples, zero_mean | eps | pair_cot, pair, perm, loss, grad_est, reordered, scratch, stream
@@ -353,7 +357,7 @@ EXPORTS = ("sfsn_abi_version", "sfsn_source_hash", "sfsn_strerror", "sfsn_device
            "sfsn_fullband_stream_hop_counted", "sfsn_recipe_loss_scratch_bytes", "sfsn_recipe_loss",
            "sfsn_pit_sdr_scratch_bytes", "sfsn_pit_sdr", "sfsn_stft_ragged", "sfsn_istft_ragged", "sfsn_laplace_means_ragged",
            "sfsn_gaussian_stats_ragged", "sfsn_spike_count_rows_ragged", "sfsn_zero_tail_frames", "sfsn_gsn_layer_scan_l0",
-           "sfsn_pit_sdr_ragged", "sfsn_gsn_layer_scan_l01")
+           "sfsn_pit_sdr_ragged", "sfsn_gsn_layer_scan_l01", "sfsn_recipe_loss_ragged_scratch_bytes", "sfsn_recipe_loss_ragged")
 
 
 def check(rc: int, what: str = "") -> None:
