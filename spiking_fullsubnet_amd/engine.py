@@ -13,7 +13,7 @@ from __future__ import annotations
 import ctypes
 import os
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional
+from typing import Dict, List, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -284,6 +284,137 @@ def fill_segment(sg: ScanSegment, cell, R: int, H: int, t0: int, zin, state, spi
     sg.spike_count = _ptr(count)
 
 
+STACK_ROWS_PER_WG = {"fb": 4, "sb": 8}  # Engine.stack_rows_per_wg of a fresh engine
+
+
+def stack_rule(shared, nl, H, n_groups, Rs, want_membrane, stack_scan, stack_wide, stack_rows_fb_auto, pair_scan, rows_per_wg, alone, n_cu):
+    """(use the stack launch?, wide flavour?, rows per workgroup) for one stack of `n_groups` sequence models of `nl` layers and hidden
+    size `H` with `Rs` rows each, on a chip of `n_cu` compute units; `alone`: no other forward of the engine is in flight.  Pure:
+    no device, no engine (Engine._stack_choice supplies `alone` and `n_cu`).
+
+    sfsn_gsn_stack_scan runs all layers of a stack in one launch, layer l+1 trailing layer l.  It wins where one layer's
+    workgroups leave most of the chip idle; where a single layer already fills the chip at 4 rows per workgroup the layers
+    side by side get half the CUs each and the input terms' traffic through L2 / HBM doubles up, and full-chip launches
+    in a row are faster.  Measured on MI355X, T=1000, baseline_m sizes (scripts/exp_stack.py), sub-band stack
+    (per-layer scans + input products / narrow stack / wide stack, ms): B=4 1.9 / 1.7 / 1.2, B=16 1.9 / 1.7 / 1.2,
+    B=32 2.0 / 1.7 / 1.95, B=64 1.66 / 1.83 / 2.33; full-band stack (H=320, B rows) 2.26 -> 1.25 at every B.
+    `stack_scan`: "auto" (the rule below), True (always, `stack_rows_per_wg` / `stack_wide` as set), False (never)."""
+    ok = bool(stack_scan and shared and not want_membrane and nl >= 2 and n_groups * (1 + (nl - 1) * 2) <= 24)
+    if not ok:
+        return False, False, 0
+    if stack_scan != "auto":
+        return True, stack_wide, None
+    rows = sum(Rs)
+    if H > 256:  # the full-band model: few rows, PROJ + gated scan roles
+        rp = stack_rows_fb_auto
+        return (rows + rp - 1) // rp * nl + (rows + 15) // 16 <= n_cu, False, rp
+    # round 4: H <= 224 stacks without input-term buffers run their layers >= 1 as FUSED3 roles (the input product inside the
+    # 8-row IO-wave scan): all layers side by side in one launch, no fp32 input term for the layers >= 1.  Every workgroup of
+    # the launch has to be resident beside the full-band stack of the same forward (<= 40 workgroups), and the forward has
+    # to be alone on the chip -- `rows_per_wg` (0 or 8 for the sub-band models) says so: bench.py's timed region, with a
+    # dozen forwards in flight, sets 16 and keeps its per-layer launches.  Measured at B = 64, T = 1000 (scripts/exp_pair.py):
+    # 1.03 ms against 1.43 (scan3 at 4 rows + sfsn_spike_proj), 1.72 (8-wave FUSED roles), 2.4 (PROJ roles).
+    wgs8 = nl * sum((R + 7) // 8 for R in Rs)
+    if pair_scan and alone and H <= 224 and rows_per_wg[1] in (0, 8) and wgs8 <= n_cu - 40:
+        return True, False, 8
+    if rows <= n_cu:       # every layer's workgroups at 8 rows + the PROJ workgroups fit several times over
+        return True, True, 8
+    if rows <= 2 * n_cu:   # 8 rows per workgroup: both layers side by side still fit
+        return True, False, 8
+    return False, False, 0
+
+
+class ForwardPlan(NamedTuple):
+    """The schedule of one forward (plan_forward)."""
+    pipeline: bool   # the time-pipelined schedule: a stream pair per layer, chunks of `pipeline_chunk` frames
+    overlap: bool    # the overlapped schedule: full-band model on one stream, sub-band models one chunk behind on a second
+    bounds: tuple    # ((t0, nt), ...): the chunks of the sequence
+    nt_max: int      # frames of the longest chunk (the chunk-local buffers' size)
+    rpw_fb: int      # rows per workgroup of the per-layer scans, full-band / ...
+    rpw_sb: int      # ... sub-band (0: the library spreads the rows over all CUs)
+    staged: bool     # several streams chained by events
+
+
+def _overlap_bounds(T, sb_rows, overlap_chunks, overlap_fracs, overlap_first):
+    """The chunks of the overlapped schedule."""
+    # a short first chunk: the sub-band models can only start once the full-band model has finished a chunk, so the first
+    # one is the lead-in of the whole forward; the rest is cut evenly (the full-band model is ~2x faster per frame and
+    # stays ahead)
+    first = overlap_first if overlap_first >= 0 else int(round(0.24 * T / 8.0)) * 8
+    first = min(max(int(first), 0), T // 2)
+    fracs = overlap_fracs
+    if not fracs and overlap_first < 0 and overlap_chunks == 3 and T >= 256 and sb_rows < 600:
+        # round 5 (scripts/exp_chunks_ab*_r05.sh, interleaved A/B on two boxes): below ~600 sub-band rows (B <= 32 of
+        # baseline_m) a LONGER lead-in chunk wins -- (.36,.32,.32) T: 2.03-2.06 / 2.13 / 2.34 ms at B = 4 / 16 / 32 against
+        # 2.08-2.10 / 2.19 / 2.39-2.42 with 0.24 T.  At B = 64 the balance sits on a knife edge (full-band chunk c+1 must fit
+        # beside sub-band chunk c): (.32,.33,.35) measured 2.65-2.69 on one box and 2.80-2.82 on the next against 2.70-2.76
+        # for 0.24 T on both, so 0.24 T stays there.
+        fracs = (0.36, 0.32, 0.32)
+    if fracs:  # explicit chunk lengths as fractions of T (experiments: scripts/exp_forward_r04.py)
+        cuts = [int(round(f * T / 8.0)) * 8 for f in fracs]
+        lens = [c for c in cuts if c > 0]
+        lens = lens[:-1] + [T - sum(lens[:-1])] if sum(lens[:-1]) < T else [T]
+        bounds, t0 = [], 0
+        for n_ in lens:
+            bounds.append((t0, n_))
+            t0 += n_
+        return bounds
+    if first:
+        rest = -(-(T - first) // (overlap_chunks - 1))
+        return [(0, first)] + [(t0, min(rest, T - t0)) for t0 in range(first, T, rest)]
+    nt = -(-T // overlap_chunks)
+    return [(t0, min(nt, T - t0)) for t0 in range(0, T, nt)]
+
+
+def plan_forward(spec: PathSpec, B: int, T: int, pipeline: Optional[bool], n_cu: int, want_membrane: bool = False, pipeline_default: bool = False,
+                 pipeline_chunk: int = 128, seq_chunk: int = 0, overlap_chunks: int = 3, overlap_fracs=None, overlap_first: int = -1,
+                 rows_per_wg=(0, 0), fuse_input: bool = True, stack_scan="auto", stack_rows_per_wg=None, stack_wide: bool = True,
+                 stack_rows_fb_auto: int = 4, pair_scan: bool = True) -> ForwardPlan:
+    """Which of the three schedules (sequential, overlapped, pipelined) a forward of B clips of T frames runs, its chunks and its rows
+    per scan workgroup.  `pipeline`: the caller's argument (None: the engine's default); the other keywords are the Engine attributes
+    of the same names (defaults: a fresh engine's), `n_cu` the chip's compute units.  Pure: no device, no engine, no environment."""
+    chunk = pipeline_chunk
+    if pipeline is None:
+        pipeline = pipeline_default and chunk > 0 and T >= 2 * chunk
+    if spec.cum_laplace:
+        pipeline = False  # (the running-mean state and its scratch are per forward, not per stage: single-stream order only)
+    Rs_sb = [B * spec.units(g) for g in range(spec.n_groups)]
+    # sequential schedule: optionally still cut the sequence into chunks (single stream): the chunk-sized input-term
+    # buffer is then produced and consumed while it is still in the 256 MB Infinity Cache instead of making a round
+    # trip through HBM (745 MB per sub-band layer at B=64, T=1000)
+    overlap = bool(not pipeline and overlap_chunks > 1 and not spec.laplace and not spec.cum_laplace and not (0 < seq_chunk < T)
+                   and T >= 96 * overlap_chunks)
+    if overlap and stack_scan is True:
+        # forced stack launches for both models: side by side on two streams they must not ask for more workgroups than the
+        # chip has compute units -- in-launch hand-offs rely on producers being resident (the "auto" rule never gets here)
+        def blocks(nl, H, n_groups, Rs, tag):
+            use, wide, rp = stack_rule(spec.shared, nl, H, n_groups, Rs, want_membrane, stack_scan, stack_wide, stack_rows_fb_auto,
+                                       pair_scan, rows_per_wg, True, n_cu)
+            rp = rp or (stack_rows_per_wg or STACK_ROWS_PER_WG)[tag]
+            scan = sum(-(-R // rp) for R in Rs)
+            proj = sum(-(-R // 16) for R in Rs) if (wide or H > 256) else 0
+            return (nl * (scan + 7) // 8 * 8 + (nl - 1) * (proj + 7) // 8 * 8) if use else 0
+        b_fb = blocks(spec.fb_layers, spec.fb_hidden, 1, [B], "fb")
+        b_sb = blocks(spec.sb_layers, spec.sb_hidden, spec.n_groups, Rs_sb, "sb")
+        if b_fb and b_sb and b_fb + b_sb > n_cu:
+            overlap = False
+    if overlap:
+        bounds = _overlap_bounds(T, sum(Rs_sb), overlap_chunks, overlap_fracs, overlap_first)
+        nt_max = max(n for _, n in bounds)
+    else:
+        nt_max = chunk if pipeline else (seq_chunk if 0 < seq_chunk < T else T)
+        bounds = [(t0, min(nt_max, T - t0)) for t0 in range(0, T, nt_max)]
+    rpw_fb, rpw_sb = (16, 16) if pipeline else rows_per_wg
+    if rpw_sb == 0 and fuse_input and spec.shared and 128 < spec.sb_hidden <= 256 and (sum(Rs_sb) + 7) // 8 > n_cu:
+        # Many sub-band rows (baseline_l: 43 units per clip = 2752 rows at B = 64): left to itself the library spreads them at 8
+        # rows per workgroup (344 workgroups: two rounds on 256 compute units, round 2's body for 16 tiles) behind a separate
+        # layer-0 input product and a layer-2 spike product (5.6 GB of fp32 input terms written and read).  At 16 rows per workgroup
+        # the launch is one round and the fused-input kernels apply (input products inside the scan, defined at 16 rows): said
+        # explicitly here whenever 8 rows would not fit the chip in one round.
+        rpw_sb = 16
+    return ForwardPlan(bool(pipeline), overlap, tuple(bounds), nt_max, rpw_fb, rpw_sb, bool(pipeline or overlap))
+
+
 class ErrorWords:
     """The error words of launches with bounded in-launch waits (first word of a launch's scratch buffer, sticky: non-zero = a
     hand-off wait expired, the results are invalid).  A word travels to pinned host memory behind its launch and is looked at
@@ -346,6 +477,67 @@ class ErrorWords:
         self.poll(block=True)
 
 
+@dataclass
+class _ModelRun:
+    """One of the two models of a forward (full-band, sub-band) as the launch loop sees it."""
+    tag: str                 # "fb" | "sb"
+    seqs: list               # its sequence models (_Seq): one, or one per sub-band group
+    d: dict                  # their per-forward tensors (_alloc_stack)
+    xs: list                 # feature rows per sequence model, [T, R, I]
+    first: int               # index of its layer 0 among the forward's stages (streams)
+    rpw: int                 # rows per workgroup of its per-layer scans
+    fg: object               # FeatureGroup array of its feature launch
+    fb_proj: Optional[torch.Tensor]  # sub-band: the full-band model's output, read by the features and the statistics
+    dims: tuple              # (B, F, T, width of fb_proj, fdrc) of the feature launches
+    mu: Optional[torch.Tensor]       # offline norms: the clips' statistics of its input ...
+    sd: Optional[torch.Tensor]       # ... (offline_gaussian_norm only)
+    cum0: int                # cumulative_laplace_norm: index of its first running-mean state
+
+
+@dataclass
+class _Forward:
+    """What one forward's steps share: its plan, tensors and streams, and what a step reports to a later one."""
+    plan: ForwardPlan
+    ri: torch.Tensor         # the input as [B, F, T, 2] float32
+    want_layers: bool
+    want_membrane: bool
+    frames: Optional[list]   # ragged batch: the clips' lengths, on the host / ...
+    frames_dev: Optional[torch.Tensor]  # ... on the device
+    fbm: _ModelRun
+    sbm: _ModelRun
+    enh: torch.Tensor
+    enh_ri: torch.Tensor
+    enh_mag: torch.Tensor
+    dfg: object              # DfGroup array of the deep filter
+    stats_scratch: Optional[torch.Tensor]
+    cum: Optional[dict]      # cumulative_laplace_norm: running-mean states and scratch
+    zero: Optional[torch.Tensor]  # the scans' state buffer while it waits for the feature launch that zeroes it (then None)
+    in_scan: bool            # the scans count their spikes
+    write_proj: bool         # the coefficient rows are wanted
+    main: Optional[torch.cuda.Stream] = None  # the calling stream; per stage: the streams of the scans / of the time-parallel kernels ...
+    sstreams: list = field(default_factory=list)
+    gstreams: list = field(default_factory=list)
+    hS: list = field(default_factory=list)    # ... and their handles for the C ABI
+    hG: list = field(default_factory=list)
+    x_skipped: dict = field(default_factory=lambda: dict(fb=set(), sb=set()))  # feature rows a fused feature launch did not write
+    proj_skipped: bool = False  # the fused epilogue ran and left the coefficient rows unwritten
+
+    def link(self, src, dst) -> None:
+        """dst waits for everything enqueued on src so far (no-op on the sequential path)."""
+        if self.plan.staged and src is not dst:
+            dst.wait_event(_record(src))
+
+
+def _record(stream) -> torch.cuda.Event:
+    ev = torch.cuda.Event()
+    ev.record(stream)
+    return ev
+
+
+def _pick(lst, idx):
+    return [lst[i] for i in idx]
+
+
 class Engine:
     """Packed weights + launch sequence for one model on one device."""
 
@@ -362,6 +554,7 @@ class Engine:
         if self.device.type != "cuda":
             raise RuntimeError("spiking_fullsubnet_amd runs on a HIP device only (no CPU path); move the module to 'cuda'")
         self.lib = _lib.lib()
+        self.n_cu = torch.cuda.get_device_properties(self.device).multi_processor_count  # asked once: the schedule rules read it per forward
         for H in (spec.fb_hidden, spec.sb_hidden):
             if H % 16 != 0 or H > _lib.MAX_HIDDEN:
                 raise NotImplementedError(f"hidden size {H}: the gfx950 scan holds W_hh register-resident for H % 16 == 0, H <= {_lib.MAX_HIDDEN}")
@@ -418,7 +611,7 @@ class Engine:
         # not on the staged schedules, which keep their per-layer launches.  SFSN_L01_PAIR=0 / 1 overrides the default.
         self.pair16 = os.environ.get("SFSN_L01_PAIR", "1") != "0"
         self._l01_refused = set()
-        self.stack_rows_per_wg = {"fb": 4, "sb": 8}  # rows per workgroup of every layer of a stack: sum of workgroups <= CUs
+        self.stack_rows_per_wg = dict(STACK_ROWS_PER_WG)  # rows per workgroup of every layer of a stack: sum of workgroups <= CUs
         # frames a consumer role that had to wait lets its producers run ahead before it resumes (the hand-offs' hysteresis).  Round 2: 16
         # (every wave of a workgroup stood in the poll); since the IO-wave roles one lane polls, and a launch ends lag + ring frames after
         # its first layer does: 16 / 8 / 4 / 2 / 1 -> strict forward 2.74-2.76 / 2.65-2.70 / 2.62 / 2.63 / 2.63 ms (scripts/exp_lag_r05.sh)
@@ -759,48 +952,19 @@ class Engine:
             check(L.sfsn_gsn_layer_scan_fused(segs, fin, len(seqs), nt, H, st), "sfsn_gsn_layer_scan_fused")
 
     def _stack_choice(self, seqs, Rs, want_membrane):
-        """(use the stack launch?, wide flavour?, rows per workgroup) for one stack of sequence models.
-
-        sfsn_gsn_stack_scan runs all layers of a stack in one launch, layer l+1 trailing layer l.  It wins where one layer's
-        workgroups leave most of the chip idle; where a single layer already fills the chip at 4 rows per workgroup the layers
-        side by side get half the CUs each and the input terms' traffic through L2 / HBM doubles up, and full-chip launches
-        in a row are faster.  Measured on MI355X, T=1000, baseline_m sizes (scripts/exp_stack.py), sub-band stack
-        (per-layer scans + input products / narrow stack / wide stack, ms): B=4 1.9 / 1.7 / 1.2, B=16 1.9 / 1.7 / 1.2,
-        B=32 2.0 / 1.7 / 1.95, B=64 1.66 / 1.83 / 2.33; full-band stack (H=320, B rows) 2.26 -> 1.25 at every B.
-        `stack_scan`: "auto" (the rule below), True (always, `stack_rows_per_wg` / `stack_wide` as set), False (never)."""
-        nl, H = len(seqs[0].cells), seqs[0].H
-        ok = bool(self.stack_scan and self.spec.shared and not want_membrane and nl >= 2
-                  and len(seqs) * (1 + (nl - 1) * 2) <= 24)
-        if not ok:
-            return False, False, 0
-        tag_rpw = self.stack_rows_per_wg
-        if self.stack_scan != "auto":
-            return True, self.stack_wide, None
-        rows = sum(Rs)
-        n_cu = torch.cuda.get_device_properties(self.device).multi_processor_count
-        if H > 256:  # the full-band model: few rows, PROJ + gated scan roles
-            rp = self.stack_rows_fb_auto
-            return (rows + rp - 1) // rp * nl + (rows + 15) // 16 <= n_cu, False, rp
-        # round 4: H <= 224 stacks without input-term buffers run their layers >= 1 as FUSED3 roles (the input product inside the
-        # 8-row IO-wave scan): all layers side by side in one launch, no fp32 input term for the layers >= 1.  Every workgroup of
-        # the launch has to be resident beside the full-band stack of the same forward (<= 40 workgroups), and the forward has
-        # to be alone on the chip -- `rows_per_wg` (0 or 8 for the sub-band models) says so: bench.py's timed region, with a
-        # dozen forwards in flight, sets 16 and keeps its per-layer launches.  Measured at B = 64, T = 1000 (scripts/exp_pair.py):
-        # 1.03 ms against 1.43 (scan3 at 4 rows + sfsn_spike_proj), 1.72 (8-wave FUSED roles), 2.4 (PROJ roles).
-        wgs8 = nl * sum((R + 7) // 8 for R in Rs)
+        """(use the stack launch?, wide flavour?, rows per workgroup) for one stack of sequence models: `stack_rule` with what only the
+        engine knows -- the chip's compute units and whether the forward has the chip to itself."""
+        H = seqs[0].H
         # (the launch assumes the forward has the chip to itself: its 2 x 104 workgroups wait for each other inside the launch.  A second
         #  forward of this engine still in flight on another stream (its end-of-forward event has not fired) takes the per-layer
         #  launches instead: round-4 advisor finding.  Work of OTHER processes or libraries cannot be seen from here; the waits
-        #  are bounded and reported.)
-        me = torch.cuda.current_stream(self.device).cuda_stream
-        alone = all(ev.query() for k, ev in self._last_forward.items() if k != me)
-        if self.pair_scan and alone and H <= 224 and self.rows_per_wg[1] in (0, 8) and wgs8 <= n_cu - 40:
-            return True, False, 8
-        if rows <= n_cu:       # every layer's workgroups at 8 rows + the PROJ workgroups fit several times over
-            return True, True, 8
-        if rows <= 2 * n_cu:   # 8 rows per workgroup: both layers side by side still fit
-            return True, False, 8
-        return False, False, 0
+        #  are bounded and reported.)  Asked only where the rule reads it: the "auto" rule of an H <= 256 stack.
+        alone = True
+        if self.stack_scan == "auto" and H <= 256:
+            me = torch.cuda.current_stream(self.device).cuda_stream
+            alone = all(ev.query() for k, ev in self._last_forward.items() if k != me)
+        return stack_rule(self.spec.shared, len(seqs[0].cells), H, len(seqs), Rs, want_membrane, self.stack_scan, self.stack_wide,
+                          self.stack_rows_fb_auto, self.pair_scan, self.rows_per_wg, alone, self.n_cu)
 
     def _stack_x_groups(self, seqs, xs_, nt, wide, rpw_stack, want_membrane=False):
         """Groups whose LAYER 0 takes its real-valued input product inside the stack launch (FUSEDX3 role, sfsn_gsn_stack_scan_x):
@@ -1017,8 +1181,7 @@ class Engine:
             Engine._hip = ctypes.CDLL("libamdhip64.so")
             Engine._hip.hipExtStreamCreateWithCUMask.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
             Engine._hip.hipExtStreamCreateWithCUMask.restype = ctypes.c_int
-        n_cu = torch.cuda.get_device_properties(self.device).multi_processor_count
-        words = (n_cu + 31) // 32
+        words = (self.n_cu + 31) // 32
         mask = (ctypes.c_uint32 * words)()
         for c in cus:
             mask[c // 32] |= (1 << (c % 32))
@@ -1036,8 +1199,7 @@ class Engine:
             # CU ids are (32-bit mask word w, bit b) = w*32 + b; measured on MI355X (scripts/exp_cumask.py): a mask word
             # is one XCD, and masks are honoured when every word enables a contiguous bit range.  Pools are therefore bit
             # COLUMNS: the same range of CUs in every XCD -- each pool spans all eight L2s.
-            n_cu = torch.cuda.get_device_properties(self.device).multi_processor_count
-            words = n_cu // 32
+            words = self.n_cu // 32
             def columns(b0, b1, w0=0, w1=None):
                 return [w * 32 + b for w in range(w0, words if w1 is None else w1) for b in range(b0, b1)]
             pools, col = [], 0
@@ -1136,7 +1298,7 @@ class Engine:
         """complex64 [B, n_fft/2+1, T] on the device -> dict(enh_stft [B,S,F,T] complex64, enh_mag [B,S,F,T],
         fb_all, sb_all (the reference's all_layer_outputs lists; spike entries are None when want_layers=False)).
 
-        Schedule.  The four recurrent scans of a model (full-band layer 1/2, sub-band layer 1/2) are each a chain of T
+        Schedule (plan_forward).  The four recurrent scans of a model (full-band layer 1/2, sub-band layer 1/2) are each a chain of T
         dependent steps that occupies only a fraction of the chip, and layer l+1 / the sub-band model need frame t of
         their producer only at frame t.  With ``pipeline`` (default: live front-end and T >= 2 chunks) the sequence is
         cut into chunks of ``pipeline_chunk`` frames and the stages run as a software pipeline on separate HIP streams
@@ -1145,9 +1307,44 @@ class Engine:
         arithmetic; tested).  The frozen front-end's utterance-level Laplace mean needs the whole full-band output, so
         only its two layer pairs overlap.
         """
-        spec, L = self.spec, self.lib
+        spec = self.spec
         self._defer_err = None  # (a forward that raised half way must not leave the next one's error words uncollected)
         want_layers = want_layers or want_membrane  # membranes are a test output of the fp32-spike kernel variant
+        B, F, T = self._validate(stft)
+        plan = plan_forward(spec, B, T, pipeline, self.n_cu, want_membrane, pipeline_default=self.pipeline_default,
+                            pipeline_chunk=self.pipeline_chunk, seq_chunk=self.seq_chunk, overlap_chunks=self.overlap_chunks,
+                            overlap_fracs=self.overlap_fracs, overlap_first=self.overlap_first, rows_per_wg=self.rows_per_wg,
+                            fuse_input=self.fuse_input, stack_scan=self.stack_scan, stack_rows_per_wg=self.stack_rows_per_wg,
+                            stack_wide=self.stack_wide, stack_rows_fb_auto=self.stack_rows_fb_auto, pair_scan=self.pair_scan)
+        f = self._alloc_forward(stft, plan, want_layers, want_membrane, want_counts, norm_stats, frames, frames_dev)
+        self._open_streams(f)
+        fbm, sbm, gs_sb = f.fbm, f.sbm, f.gstreams[spec.fb_layers]
+        if spec.laplace and norm_stats is None:
+            self._stats(f, fbm)
+        fb_done = self._run_model(f, fbm, None)
+        if spec.laplace:
+            # the utterance-level Laplace mean of the sub-band input needs the whole full-band output: no chunk overlap fb -> sb
+            if plan.pipeline:
+                gs_sb.wait_event(fb_done[-1])
+            if norm_stats is None:
+                self._stats(f, sbm)
+            self._run_model(f, sbm, None)
+        elif plan.pipeline and self.pipeline_two_phase:
+            # full-band model first (its two layers overlapped), then the sub-band models (their two layers overlapped)
+            gs_sb.wait_event(fb_done[-1])
+            self._run_model(f, sbm, None)
+        else:
+            self._run_model(f, sbm, fb_done if plan.staged else None)
+        self._join(f)
+        if frames is not None:
+            self._zero_tail(f)
+        if want_counts and not want_layers:
+            self._summaries(f)
+        return self._result(f)
+
+    def _validate(self, stft):
+        """(B, F, T) of a forward's input, or the error that says what is wrong with it."""
+        spec = self.spec
         if stft.device != self.device or stft.dtype != torch.complex64 or stft.dim() != 3:
             raise RuntimeError(f"expected a complex64 [B, F, T] tensor on {self.device}, got {stft.dtype} {tuple(stft.shape)} on {stft.device}")
         B, F, T = stft.shape
@@ -1158,71 +1355,15 @@ class Engine:
             if (hi - lo) % c != 0:
                 raise ValueError(f"Number of frequency bins must be divisible by the center frequency.GOT: ctr_freq={c}, "
                                  f"upper_cutoff_freq={hi}, lower_cutoff_freq={lo}")
-        dev = self.device
-        main = torch.cuda.current_stream(dev)
-        ri = torch.view_as_real(stft.contiguous())  # [B, F, T, 2] float32 view, no copy
-        f32 = dict(dtype=torch.float32, device=dev)
-        chunk = self.pipeline_chunk
-        if pipeline is None:
-            pipeline = self.pipeline_default and chunk > 0 and T >= 2 * chunk
-        if spec.cum_laplace:
-            pipeline = False  # (the running-mean state and its scratch are per forward, not per stage: single-stream order only)
-        # sequential schedule: optionally still cut the sequence into chunks (single stream): the chunk-sized input-term
-        # buffer is then produced and consumed while it is still in the 256 MB Infinity Cache instead of making a round
-        # trip through HBM (745 MB per sub-band layer at B=64, T=1000)
-        overlap = bool(not pipeline and self.overlap_chunks > 1 and not spec.laplace and not spec.cum_laplace and not (0 < self.seq_chunk < T)
-                       and T >= 96 * self.overlap_chunks)
-        if overlap and self.stack_scan is True:
-            # forced stack launches for both models: side by side on two streams they must not ask for more workgroups than the
-            # chip has compute units -- in-launch hand-offs rely on producers being resident (the "auto" rule never gets here)
-            def blocks(seqs, Rs, tag):
-                use, wide, rp = self._stack_choice(seqs, Rs, want_membrane)
-                rp = rp or self.stack_rows_per_wg[tag]
-                nl = len(seqs[0].cells)
-                scan = sum(-(-R // rp) for R in Rs)
-                proj = sum(-(-R // 16) for R in Rs) if (wide or seqs[0].H > 256) else 0
-                return (nl * (scan + 7) // 8 * 8 + (nl - 1) * (proj + 7) // 8 * 8) if use else 0
-            n_cu = torch.cuda.get_device_properties(dev).multi_processor_count
-            b_fb, b_sb = blocks([self.fb], [B], "fb"), blocks(self.sb, [B * spec.units(g) for g in range(spec.n_groups)], "sb")
-            if b_fb and b_sb and b_fb + b_sb > n_cu:
-                overlap = False
-        if overlap:
-            # a short first chunk: the sub-band models can only start once the full-band model has finished a chunk, so the first
-            # one is the lead-in of the whole forward; the rest is cut evenly (the full-band model is ~2x faster per frame and
-            # stays ahead)
-            first = self.overlap_first if self.overlap_first >= 0 else int(round(0.24 * T / 8.0)) * 8
-            first = min(max(int(first), 0), T // 2)
-            fracs = self.overlap_fracs
-            if (not fracs and self.overlap_first < 0 and self.overlap_chunks == 3 and T >= 256
-                    and B * sum(spec.units(g) for g in range(spec.n_groups)) < 600):
-                # round 5 (scripts/exp_chunks_ab*_r05.sh, interleaved A/B on two boxes): below ~600 sub-band rows (B <= 32 of
-                # baseline_m) a LONGER lead-in chunk wins -- (.36,.32,.32) T: 2.03-2.06 / 2.13 / 2.34 ms at B = 4 / 16 / 32 against
-                # 2.08-2.10 / 2.19 / 2.39-2.42 with 0.24 T.  At B = 64 the balance sits on a knife edge (full-band chunk c+1 must fit
-                # beside sub-band chunk c): (.32,.33,.35) measured 2.65-2.69 on one box and 2.80-2.82 on the next against 2.70-2.76
-                # for 0.24 T on both, so 0.24 T stays there.
-                fracs = (0.36, 0.32, 0.32)
-            if fracs:  # explicit chunk lengths as fractions of T (experiments: scripts/exp_forward_r04.py)
-                cuts = [int(round(f * T / 8.0)) * 8 for f in fracs]
-                lens = [c for c in cuts if c > 0]
-                lens = lens[:-1] + [T - sum(lens[:-1])] if sum(lens[:-1]) < T else [T]
-                bounds, t0 = [], 0
-                for n_ in lens:
-                    bounds.append((t0, n_))
-                    t0 += n_
-            elif first:
-                rest = -(-(T - first) // (self.overlap_chunks - 1))
-                bounds = [(0, first)] + [(t0, min(rest, T - t0)) for t0 in range(first, T, rest)]
-            else:
-                nt = -(-T // self.overlap_chunks)
-                bounds = [(t0, min(nt, T - t0)) for t0 in range(0, T, nt)]
-            nt_max = max(n for _, n in bounds)
-        else:
-            nt_max = chunk if pipeline else (self.seq_chunk if 0 < self.seq_chunk < T else T)
-            bounds = [(t0, min(nt_max, T - t0)) for t0 in range(0, T, nt_max)]
-        S, ng = spec.num_spks, spec.n_groups
-        nl_fb, nl_sb = spec.fb_layers, spec.sb_layers
+        return B, F, T
 
-        # ---------------- tensors
+    def _alloc_forward(self, stft, plan, want_layers, want_membrane, want_counts, norm_stats, frames, frames_dev) -> _Forward:
+        """Every tensor of one forward (API outputs fresh, scratch cached: _alloc_stack) and the two models' launch arguments."""
+        spec, dev = self.spec, self.device
+        B, F, T = stft.shape
+        S, ng, nl_fb, nl_sb = spec.num_spks, spec.n_groups, spec.fb_layers, spec.sb_layers
+        f32 = dict(dtype=torch.float32, device=dev)
+        ri = torch.view_as_real(stft.contiguous())  # [B, F, T, 2] float32 view, no copy
         x_fb = torch.empty((T, B, spec.fb_in), **f32)
         xs = [torch.empty((T, B * spec.units(g), spec.sb_input_size(g)), **f32) for g in range(ng)]
         # the zero initial state of every scan of the forward: ONE buffer, zeroed by the forward's first feature launch (every scan
@@ -1237,20 +1378,17 @@ class Engine:
         n_cnt = (nl_fb + ng * nl_sb) if in_scan else 0
         n_cnt_f = (2 * n_cnt + 3) // 4 * 4
         state_flat = torch.empty((n_fb + n_sb + n_cnt_f,), **f32) if fold else torch.zeros((n_fb + n_sb + n_cnt_f,), **f32)
-        zero_job = [state_flat] if fold else []
         cnt_all = state_flat[n_fb + n_sb:n_fb + n_sb + 2 * n_cnt].view(torch.int64) if in_scan else None
-        fb = self._alloc_stack([self.fb], [B], T, nt_max, want_layers, want_membrane, "fb", state_flat[:n_fb],
+        fb = self._alloc_stack([self.fb], [B], T, plan.nt_max, want_layers, want_membrane, "fb", state_flat[:n_fb],
                                None if cnt_all is None else cnt_all[:nl_fb])
-        sb = self._alloc_stack(self.sb, [x.shape[1] for x in xs], T, nt_max, want_layers, want_membrane, "sb", state_flat[n_fb:n_fb + n_sb],
-                               None if cnt_all is None else cnt_all[nl_fb:])
+        sb = self._alloc_stack(self.sb, [x.shape[1] for x in xs], T, plan.nt_max, want_layers, want_membrane, "sb",
+                               state_flat[n_fb:n_fb + n_sb], None if cnt_all is None else cnt_all[nl_fb:])
         enh = torch.empty((B, S, F, T), dtype=torch.complex64, device=dev)
-        enh_mag = torch.empty((B, S, F, T), **f32)
-        enh_ri = torch.view_as_real(enh)
         dfg = (DfGroup * ng)()
         for g in range(ng):
             dfg[g].proj, dfg[g].n_units, dfg[g].fc, dfg[g].df = _ptr(sb["proj"][g]), spec.units(g), spec.ctr[g], spec.df[g]
         mu_fb = mu_sb = sd_fb = sd_sb = scratch = None
-        if norm_stats is not None:  # (validated by forward_stft) the clips' statistics as given: no statistics launches below
+        if norm_stats is not None:  # (validated by forward_stft) the clips' statistics as given: no statistics launches
             mu_fb, mu_sb = norm_stats.mu_fb.contiguous().view(1, B), norm_stats.mu_sb.contiguous()
             if spec.gaussian:
                 sd_fb, sd_sb = norm_stats.sd_fb.contiguous().view(1, B), norm_stats.sd_sb.contiguous()
@@ -1259,237 +1397,208 @@ class Engine:
             if spec.gaussian:
                 sd_fb, sd_sb = torch.empty((1, B), **f32), torch.empty((ng, B), **f32)
             scratch = torch.empty(((5 if spec.gaussian else 1) * B * (F - 1 + spec.fb_proj) + 2,), **f32)
-        fg_fb = self._feature_groups("fb", [x_fb], mu_fb, sd_fb)
-        fg_sb = self._feature_groups("sb", xs, mu_sb, sd_sb)
-        fb_proj = fb["proj"][0]
-
-        # ---------------- streams: sequential = the current stream; pipelined = per stage one scan stream (own CUs) and one
-        #                  stream for its time-parallel kernels (shared CU pool), chained by events
-        n_stage = nl_fb + nl_sb
-        if pipeline:
-            rpw_fb, rpw_sb = 16, 16
-            fb_tiles = (B + rpw_fb - 1) // rpw_fb
-            sb_tiles = sum((x.shape[1] + rpw_sb - 1) // rpw_sb for x in xs)
-            sstreams, gstreams = self._pipeline_streams(nl_fb, nl_sb, fb_tiles, sb_tiles)
-            fork = torch.cuda.Event()
-            fork.record(main)
-            for s_ in sstreams + gstreams:
-                s_.wait_event(fork)
-        elif overlap:
-            if self._ov_streams is None:
-                self._ov_streams = {}
-            if main.cuda_stream not in self._ov_streams:  # a pair per calling stream: forwards in flight stay independent
-                self._ov_streams[main.cuda_stream] = (torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev))
-            sa, sb_ = self._ov_streams[main.cuda_stream]
-            self._defer_err = []
-            sstreams = gstreams = [sa] * nl_fb + [sb_] * nl_sb
-            rpw_fb, rpw_sb = self.rows_per_wg
-            fork = torch.cuda.Event()
-            fork.record(main)
-            sa.wait_event(fork)
-            sb_.wait_event(fork)
-        else:
-            sstreams = gstreams = [main] * n_stage
-            rpw_fb, rpw_sb = self.rows_per_wg
-        if rpw_sb == 0 and self.fuse_input and spec.shared and 128 < self.sb[0].H <= 256:
-            # Many sub-band rows (baseline_l: 43 units per clip = 2752 rows at B = 64): left to itself the library spreads them at 8
-            # rows per workgroup (344 workgroups: two rounds on 256 compute units, round 2's body for 16 tiles) behind a separate
-            # layer-0 input product and a layer-2 spike product (5.6 GB of fp32 input terms written and read).  At 16 rows per workgroup
-            # the launch is one round and the fused-input kernels apply (input products inside the scan, defined at 16 rows): said
-            # explicitly here whenever 8 rows would not fit the chip in one round.
-            n_cu = torch.cuda.get_device_properties(dev).multi_processor_count
-            rows_sb = sum(x.shape[1] for x in xs)
-            if (rows_sb + 7) // 8 > n_cu:
-                rpw_sb = 16
-        staged = pipeline or overlap  # several streams chained by events
-        hS = [self._handle(s_) for s_ in sstreams]
-        hG = [self._handle(s_) for s_ in gstreams]
-
-        def link(src, dst):
-            """dst waits for everything enqueued on src so far (no-op on the sequential path)."""
-            if staged and src is not dst:
-                ev = torch.cuda.Event()
-                ev.record(src)
-                dst.wait_event(ev)
-
-        # per-chunk completion events of the producers the next model / layer gates on
-        def run_model(seqs, d, xs_, first, feat_fn, tag, rpw, post_fn, gate_events, fused_post=None):
-            nl = len(seqs[0].cells)
-            fused = self._fusable(seqs, rpw, want_membrane)
-            done = []
-            pick = lambda lst, idx: [lst[i] for i in idx]
-            use_stack, wide, rpw_stack = self._stack_choice(seqs, [x.shape[1] for x in xs_], want_membrane)
-            if not pipeline and use_stack:
-                # all layers in one launch: features, layer 0's input term, the stack scan, the projection
-                g, hg = gstreams[first], hG[first]
-                for c, (t0, nt) in enumerate(bounds):
-                    if staged and gate_events is not None:
-                        g.wait_event(gate_events[c])
-                    xg = self._stack_x_groups(seqs, xs_, nt, wide, rpw_stack or self.stack_rows_per_wg[tag], want_membrane)
-                    zr = [i for i in range(len(seqs)) if i not in xg]
-                    if not feat_fn(t0, nt, hg, (zr, pick(d["zin"][0], zr))) and zr:  # (True: one launch made the rows and the input terms)
-                        self._stage_input(pick(seqs, zr), 0, pick(xs_, zr), pick(d["zin"][0], zr), t0, nt, hg, tag)
-                    self._stage_stack(seqs, d, t0, nt, hS[first], tag, wide, rpw_stack, xs_=xs_, xg=xg)
-                    if fused_post is None or not fused_post(t0, nt, hg):  # (the two-launch epilogue reads the same tensors)
-                        self._stage_proj(seqs, d["s8"][nl - 1], d["proj"], t0, nt, hg, tag)
-                        if post_fn is not None:
-                            post_fn(t0, nt, hg)
-                    if staged:
-                        ev = torch.cuda.Event()
-                        ev.record(g)
-                        done.append(ev)
-                return done
-            # layer 0: groups whose real-valued input product can run inside the scan / the rest (input product first)
-            fx = [i for i in range(len(seqs)) if self._fusable_x(seqs[i], xs_[i], rpw, want_membrane)]
-            rest = [i for i in range(len(seqs)) if i not in fx]
-            cn = d.get("cnt")
-            # layers 0 and 1 of a two-layer stack at 16 rows in one launch (the staged schedules and graph capture keep the per-layer launches)
-            pair = bool(self.pair16 and self.merge_layer0 and nl == 2 and rpw == 16 and fused and not staged
-                        and not torch.cuda.is_current_stream_capturing())
-            for c, (t0, nt) in enumerate(bounds):
-                paired = False
-                for l in range(nl):
-                    si = first + l
-                    g, sc = gstreams[si], sstreams[si]
-                    # ---- what the scan of this layer consumes
-                    if l == 0:
-                        if staged and gate_events is not None:
-                            g.wait_event(gate_events[c])
-                        if not feat_fn(t0, nt, hG[si], (rest, pick(d["zin"][0], rest))) and rest:
-                            self._stage_input(pick(seqs, rest), 0, pick(xs_, rest), pick(d["zin"][0], rest), t0, nt, hG[si], tag)
-                    else:
-                        link(sstreams[si - 1], g)  # previous layer's scan of this chunk
-                        if not fused:
-                            self._stage_input(seqs, l, d["s8"][l - 1], d["zin"][l], t0, nt, hG[si], tag)
-                    link(g, sc)
-                    # ---- the scan(s)
-                    if l == 0 and pair and self._stage_scan_l01(seqs, fx, rest, xs_, d, t0, nt, hS[si], tag, cn=cn):
-                        paired = True  # (layer 1 of this chunk ran in the same launch)
-                    elif l == 1 and paired:
-                        pass
-                    elif l == 0 and fx and rest and rpw == 16 and self.merge_layer0 and self._stage_scan_l0(
-                            seqs, fx, rest, xs_, d["zin"][0], d["states"][0], d["spk"][0], d["s8"][0], t0, nt, hS[si], tag,
-                            cnts=None if cn is None else cn[0]):
-                        pass  # (both kinds of group in one launch)
-                    elif l == 0:
-                        if fx:
-                            self._stage_scan_fused_x(pick(seqs, fx), pick(xs_, fx), pick(d["states"][0], fx), pick(d["spk"][0], fx),
-                                                     pick(d["s8"][0], fx), t0, nt, hS[si], tag, cnts=None if cn is None else pick(cn[0], fx))
-                        if rest:
-                            self._stage_scan(pick(seqs, rest), 0, pick(d["zin"][0], rest), pick(d["states"][0], rest), pick(d["spk"][0], rest),
-                                             pick(d["s8"][0], rest), pick(d["mem"][0], rest), t0, nt, hS[si], tag, rpw,
-                                             cnts=None if cn is None else pick(cn[0], rest))
-                    elif fused:
-                        self._stage_scan_fused(seqs, l, d["states"][l], d["spk"][l], d["s8"], t0, nt, hS[si], tag, cnts=None if cn is None else cn[l])
-                    else:
-                        self._stage_scan(seqs, l, d["zin"][l], d["states"][l], d["spk"][l], d["s8"][l], d["mem"][l], t0, nt, hS[si], tag, rpw,
-                                         cnts=None if cn is None else cn[l])
-                    if staged:
-                        link(sc, g)  # the chunk-local zin buffer is reused by the next chunk's input product
-                    # ---- after the last layer: projection and whatever follows the model
-                    if l == nl - 1 and (fused_post is None or not fused_post(t0, nt, hG[si])):
-                        self._stage_proj(seqs, d["s8"][l], d["proj"], t0, nt, hG[si], tag)
-                        if post_fn is not None:
-                            post_fn(t0, nt, hG[si])
-                    if l == nl - 1:
-                        if staged:
-                            ev = torch.cuda.Event()
-                            ev.record(g)
-                            done.append(ev)
-            return done
-
         cum = None
         if spec.cum_laplace:
             # cumulative_laplace_norm: the rows leave sfsn_features unnormalised and are divided by their running means (state per
             # row, so a sequence fed in pieces continues where it stopped)
             rows = [B] + [x.shape[1] for x in xs]
-            cum = dict(state=[torch.zeros((R,), **f32) for R in rows], scratch=torch.empty((nt_max * max(rows),), **f32))
+            cum = dict(state=[torch.zeros((R,), **f32) for R in rows], scratch=torch.empty((plan.nt_max * max(rows),), **f32))
+        fb_proj = fb["proj"][0]
+        fbm = _ModelRun("fb", [self.fb], fb, [x_fb], 0, plan.rpw_fb, self._feature_groups("fb", [x_fb], mu_fb, sd_fb), None,
+                        (B, F, T, 0, spec.fdrc), mu_fb, sd_fb, 0)
+        sbm = _ModelRun("sb", self.sb, sb, xs, nl_fb, plan.rpw_sb, self._feature_groups("sb", xs, mu_sb, sd_sb), fb_proj,
+                        (B, F, T, spec.fb_proj, spec.fdrc), mu_sb, sd_sb, 1)
+        return _Forward(plan=plan, ri=ri, want_layers=want_layers, want_membrane=want_membrane, frames=frames, frames_dev=frames_dev,
+                        fbm=fbm, sbm=sbm, enh=enh, enh_ri=torch.view_as_real(enh), enh_mag=torch.empty((B, S, F, T), **f32), dfg=dfg,
+                        stats_scratch=scratch, cum=cum, zero=state_flat if fold else None, in_scan=in_scan,
+                        # round 6: projection + deep filter of a chunk in one launch; in the lean modes the coefficient rows are not written
+                        write_proj=bool(want_layers or want_membrane or not self.lean_skips_proj))
 
-        def cum_norm(x, i, t0, nt, st):
-            R, I = x.shape[1], x.shape[2]
-            check(L.sfsn_cum_laplace_norm(ctypes.c_void_p(x.data_ptr() + t0 * R * I * 4), nt, R, I, _ptr(cum["state"][i]), t0,
-                                          _ptr(cum["scratch"]), st), "sfsn_cum_laplace_norm")
-
-        # feature rows a fused launch did not write (layer_outputs "counts" / "none": nobody reads them)
-        x_skipped = dict(fb=set(), sb=set())
-        dims_fb, dims_sb = (B, F, T, 0, spec.fdrc), (B, F, T, spec.fb_proj, spec.fdrc)
-
-        def feat_fb(t0, nt, st, proj=None):
-            z = zero_job.pop() if zero_job else None  # (the first full-band feature launch of the forward carries the state zeroing)
-            if proj is not None and cum is None and self._stage_featproj(fg_fb, [self.fb], proj[0], proj[1], ri, None, dims_fb, t0, nt, z,
-                                                                         want_layers, st, "fb"):
-                if not want_layers:
-                    x_skipped["fb"].update(proj[0])
-                return True
-            with self.timed("features:fb", st):
-                check(L.sfsn_features_z(_ptr(ri), None, B, F, T, 0, spec.fdrc, fg_fb, 1, t0, nt, None if z is None else _ptr(z),
-                                        0 if z is None else z.numel() * 4, st), "sfsn_features(fb)")
-                if cum is not None:
-                    cum_norm(x_fb, 0, t0, nt, st)
-            return False
-
-        def feat_sb(t0, nt, st, proj=None):
-            if proj is not None and cum is None and self._stage_featproj(fg_sb, self.sb, proj[0], proj[1], ri, fb_proj, dims_sb, t0, nt, None,
-                                                                         want_layers, st, "sb"):
-                if not want_layers:
-                    x_skipped["sb"].update(proj[0])
-                return True
-            with self.timed("features:sb", st):
-                check(L.sfsn_features(_ptr(ri), _ptr(fb_proj), B, F, T, spec.fb_proj, spec.fdrc, fg_sb, ng, t0, nt, st), "sfsn_features(sb)")
-                if cum is not None:
-                    for g in range(ng):
-                        cum_norm(xs[g], 1 + g, t0, nt, st)
-            return False
-
-        def post_sb(t0, nt, st):
-            with self.timed("deepfilter", st):
-                check(L.sfsn_deepfilter(_ptr(ri), B, F, T, S, dfg, ng, _ptr(enh_ri), _ptr(enh_mag), t0, nt, st), "sfsn_deepfilter")
-
-        # round 6: projection + deep filter of a chunk in one launch; in the lean modes the coefficient rows are not written at all
-        write_proj = bool(want_layers or want_membrane or not self.lean_skips_proj)
-        proj_skipped = [False]
-
-        def fused_post_sb(t0, nt, st):
-            if not self._stage_projdf(self.sb, sb["s8"][nl_sb - 1], sb["proj"], ri, enh_ri, enh_mag, (B, F, T, S), t0, nt, st, write_proj):
-                return False
-            proj_skipped[0] = not write_proj
-            return True
-
-        def stats(fb_tbf, FB, fg, n, mu, sd, st, tag):
-            """The clips' utterance statistics of one model's input; a ragged batch: over each clip's own frames."""
-            if frames is not None:
-                fd = _ptr(frames_dev)
-                if spec.gaussian:
-                    check(L.sfsn_gaussian_stats_ragged(_ptr(ri), fb_tbf, B, F, T, FB, spec.fdrc, fg, n, fd, _ptr(mu), _ptr(sd), _ptr(scratch), st),
-                          f"sfsn_gaussian_stats_ragged({tag})")
-                else:
-                    check(L.sfsn_laplace_means_ragged(_ptr(ri), fb_tbf, B, F, T, FB, spec.fdrc, fg, n, fd, _ptr(mu), _ptr(scratch), st),
-                          f"sfsn_laplace_means_ragged({tag})")
-            elif spec.gaussian:
-                check(L.sfsn_gaussian_stats(_ptr(ri), fb_tbf, B, F, T, FB, spec.fdrc, fg, n, _ptr(mu), _ptr(sd), _ptr(scratch), st),
-                      f"sfsn_gaussian_stats({tag})")
-            else:
-                check(L.sfsn_laplace_means(_ptr(ri), fb_tbf, B, F, T, FB, spec.fdrc, fg, n, _ptr(mu), _ptr(scratch), st), f"sfsn_laplace_means({tag})")
-
-        if spec.laplace and norm_stats is None:
-            stats(None, 0, fg_fb, 1, mu_fb, sd_fb, hG[0], "fb")
-        fb_done = run_model([self.fb], fb, [x_fb], 0, feat_fb, "fb", rpw_fb, None, None)
-        if spec.laplace:
-            # the utterance-level Laplace mean of the sub-band input needs the whole full-band output: no chunk overlap fb -> sb
-            if pipeline:
-                gstreams[nl_fb].wait_event(fb_done[-1])
-            if norm_stats is None:
-                stats(_ptr(fb_proj), spec.fb_proj, fg_sb, ng, mu_sb, sd_sb, hG[nl_fb], "sb")
-            sb_done = run_model(self.sb, sb, xs, nl_fb, feat_sb, "sb", rpw_sb, post_sb, None, fused_post_sb)
-        elif pipeline and self.pipeline_two_phase:
-            # full-band model first (its two layers overlapped), then the sub-band models (their two layers overlapped)
-            gstreams[nl_fb].wait_event(fb_done[-1])
-            sb_done = run_model(self.sb, sb, xs, nl_fb, feat_sb, "sb", rpw_sb, post_sb, None, fused_post_sb)
+    def _open_streams(self, f: _Forward) -> None:
+        """The streams of the forward's stages: sequential = the current stream; pipelined = per stage one scan stream (own CUs) and one
+        stream for its time-parallel kernels (shared CU pool), chained by events; overlapped = one stream per model."""
+        spec, plan, dev = self.spec, f.plan, self.device
+        nl_fb, nl_sb = spec.fb_layers, spec.sb_layers
+        main = f.main = torch.cuda.current_stream(dev)
+        if plan.pipeline:
+            fb_tiles = (f.fbm.xs[0].shape[1] + plan.rpw_fb - 1) // plan.rpw_fb
+            sb_tiles = sum((x.shape[1] + plan.rpw_sb - 1) // plan.rpw_sb for x in f.sbm.xs)
+            f.sstreams, f.gstreams = self._pipeline_streams(nl_fb, nl_sb, fb_tiles, sb_tiles)
+            forked = f.sstreams + f.gstreams
+        elif plan.overlap:
+            if self._ov_streams is None:
+                self._ov_streams = {}
+            if main.cuda_stream not in self._ov_streams:  # a pair per calling stream: forwards in flight stay independent
+                self._ov_streams[main.cuda_stream] = (torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev))
+            sa, sb_ = forked = self._ov_streams[main.cuda_stream]
+            self._defer_err = []
+            f.sstreams = f.gstreams = [sa] * nl_fb + [sb_] * nl_sb
         else:
-            sb_done = run_model(self.sb, sb, xs, nl_fb, feat_sb, "sb", rpw_sb, post_sb, fb_done if staged else None, fused_post_sb)
-        if staged:
-            for s_ in {id(x): x for x in sstreams + gstreams}.values():
-                link(s_, main)
+            f.sstreams = f.gstreams = [main] * (nl_fb + nl_sb)
+            forked = ()
+        if forked:
+            fork = torch.cuda.Event()
+            fork.record(main)
+            for s_ in forked:
+                s_.wait_event(fork)
+        f.hS = [self._handle(s_) for s_ in f.sstreams]
+        f.hG = [self._handle(s_) for s_ in f.gstreams]
+
+    def _stats(self, f: _Forward, m: _ModelRun) -> None:
+        """The clips' utterance statistics of one model's input; a ragged batch: over each clip's own frames."""
+        spec, L = self.spec, self.lib
+        B, F, T, FB, fdrc = m.dims
+        ri, fb_tbf, n, mu, sd, scratch = _ptr(f.ri), _ptr(m.fb_proj), len(m.seqs), _ptr(m.mu), _ptr(m.sd), _ptr(f.stats_scratch)
+        st, tag = f.hG[m.first], m.tag
+        if f.frames is not None:
+            fd = _ptr(f.frames_dev)
+            if spec.gaussian:
+                check(L.sfsn_gaussian_stats_ragged(ri, fb_tbf, B, F, T, FB, fdrc, m.fg, n, fd, mu, sd, scratch, st), f"sfsn_gaussian_stats_ragged({tag})")
+            else:
+                check(L.sfsn_laplace_means_ragged(ri, fb_tbf, B, F, T, FB, fdrc, m.fg, n, fd, mu, scratch, st), f"sfsn_laplace_means_ragged({tag})")
+        elif spec.gaussian:
+            check(L.sfsn_gaussian_stats(ri, fb_tbf, B, F, T, FB, fdrc, m.fg, n, mu, sd, scratch, st), f"sfsn_gaussian_stats({tag})")
+        else:
+            check(L.sfsn_laplace_means(ri, fb_tbf, B, F, T, FB, fdrc, m.fg, n, mu, scratch, st), f"sfsn_laplace_means({tag})")
+
+    def _features(self, f: _Forward, m: _ModelRun, t0, nt, st, proj) -> bool:
+        """The feature rows of one model's chunk.  `proj` = (groups, their chunk-local input-term buffers): True when one launch made
+        the rows AND those groups' layer-0 input terms (_stage_featproj), False when the caller still owes the input terms."""
+        L = self.lib
+        B, F, T, FB, fdrc = m.dims
+        z = None
+        if m.tag == "fb":
+            z, f.zero = f.zero, None  # (the first full-band feature launch of the forward carries the state zeroing)
+        if f.cum is None and self._stage_featproj(m.fg, m.seqs, proj[0], proj[1], f.ri, m.fb_proj, m.dims, t0, nt, z, f.want_layers, st, m.tag):
+            if not f.want_layers:  # feature rows a fused launch did not write (layer_outputs "counts" / "none": nobody reads them)
+                f.x_skipped[m.tag].update(proj[0])
+            return True
+        with self.timed("features:" + m.tag, st):
+            if m.tag == "fb":
+                check(L.sfsn_features_z(_ptr(f.ri), None, B, F, T, 0, fdrc, m.fg, 1, t0, nt, None if z is None else _ptr(z),
+                                        0 if z is None else z.numel() * 4, st), "sfsn_features(fb)")
+            else:
+                check(L.sfsn_features(_ptr(f.ri), _ptr(m.fb_proj), B, F, T, FB, fdrc, m.fg, len(m.seqs), t0, nt, st), "sfsn_features(sb)")
+            if f.cum is not None:
+                for i, x in enumerate(m.xs):
+                    R, I = x.shape[1], x.shape[2]
+                    check(L.sfsn_cum_laplace_norm(ctypes.c_void_p(x.data_ptr() + t0 * R * I * 4), nt, R, I, _ptr(f.cum["state"][m.cum0 + i]), t0,
+                                                  _ptr(f.cum["scratch"]), st), "sfsn_cum_laplace_norm")
+        return False
+
+    def _epilogue(self, f: _Forward, m: _ModelRun, t0, nt, st) -> None:
+        """What follows a model's last layer on a chunk: its projection and, behind the sub-band models, the deep filter -- the two in
+        one launch where the library covers the shapes (the two-launch epilogue reads the same tensors)."""
+        if m.tag == "sb":
+            B, F, T = m.dims[:3]
+            S = self.spec.num_spks
+            if self._stage_projdf(m.seqs, m.d["s8"][-1], m.d["proj"], f.ri, f.enh_ri, f.enh_mag, (B, F, T, S), t0, nt, st, f.write_proj):
+                f.proj_skipped = not f.write_proj
+                return
+        self._stage_proj(m.seqs, m.d["s8"][-1], m.d["proj"], t0, nt, st, m.tag)
+        if m.tag == "sb":
+            with self.timed("deepfilter", st):
+                check(self.lib.sfsn_deepfilter(_ptr(f.ri), B, F, T, S, f.dfg, len(m.seqs), _ptr(f.enh_ri), _ptr(f.enh_mag), t0, nt, st),
+                      "sfsn_deepfilter")
+
+    def _run_model(self, f: _Forward, m: _ModelRun, gate_events) -> list:
+        """One model over every chunk of the forward.  gate_events: per chunk, what its first launch waits for (the full-band model's
+        chunk, on the staged schedules).  Returns the per-chunk completion events (staged schedules; else empty)."""
+        use_stack, wide, rpw_stack = self._stack_choice(m.seqs, [x.shape[1] for x in m.xs], f.want_membrane)
+        if not f.plan.pipeline and use_stack:
+            return self._run_model_stack(f, m, gate_events, wide, rpw_stack)
+        return self._run_model_layers(f, m, gate_events)
+
+    def _run_model_stack(self, f, m, gate_events, wide, rpw_stack) -> list:
+        """All layers in one launch per chunk: features, layer 0's input term, the stack scan, the epilogue."""
+        seqs, d, xs_, tag, staged = m.seqs, m.d, m.xs, m.tag, f.plan.staged
+        g, hg, done = f.gstreams[m.first], f.hG[m.first], []
+        for c, (t0, nt) in enumerate(f.plan.bounds):
+            if staged and gate_events is not None:
+                g.wait_event(gate_events[c])
+            xg = self._stack_x_groups(seqs, xs_, nt, wide, rpw_stack or self.stack_rows_per_wg[tag], f.want_membrane)
+            zr = [i for i in range(len(seqs)) if i not in xg]
+            if not self._features(f, m, t0, nt, hg, (zr, _pick(d["zin"][0], zr))) and zr:
+                self._stage_input(_pick(seqs, zr), 0, _pick(xs_, zr), _pick(d["zin"][0], zr), t0, nt, hg, tag)
+            self._stage_stack(seqs, d, t0, nt, f.hS[m.first], tag, wide, rpw_stack, xs_=xs_, xg=xg)
+            self._epilogue(f, m, t0, nt, hg)
+            if staged:
+                done.append(_record(g))
+        return done
+
+    def _run_model_layers(self, f, m, gate_events) -> list:
+        """A launch per layer (and its input product, where the scan does not form it itself) per chunk."""
+        seqs, d, xs_, tag, rpw, staged = m.seqs, m.d, m.xs, m.tag, m.rpw, f.plan.staged
+        nl = len(seqs[0].cells)
+        fused = self._fusable(seqs, rpw, f.want_membrane)
+        done = []
+        # layer 0: groups whose real-valued input product can run inside the scan / the rest (input product first)
+        fx = [i for i in range(len(seqs)) if self._fusable_x(seqs[i], xs_[i], rpw, f.want_membrane)]
+        rest = [i for i in range(len(seqs)) if i not in fx]
+        # layers 0 and 1 of a two-layer stack at 16 rows in one launch (the staged schedules and graph capture keep the per-layer launches)
+        pair = bool(self.pair16 and self.merge_layer0 and nl == 2 and rpw == 16 and fused and not staged
+                    and not torch.cuda.is_current_stream_capturing())
+        for c, (t0, nt) in enumerate(f.plan.bounds):
+            paired = False
+            for l in range(nl):
+                si = m.first + l
+                g, sc = f.gstreams[si], f.sstreams[si]
+                # ---- what the scan of this layer consumes
+                if l == 0:
+                    if staged and gate_events is not None:
+                        g.wait_event(gate_events[c])
+                    if not self._features(f, m, t0, nt, f.hG[si], (rest, _pick(d["zin"][0], rest))) and rest:
+                        self._stage_input(_pick(seqs, rest), 0, _pick(xs_, rest), _pick(d["zin"][0], rest), t0, nt, f.hG[si], tag)
+                else:
+                    f.link(f.sstreams[si - 1], g)  # previous layer's scan of this chunk
+                    if not fused:
+                        self._stage_input(seqs, l, d["s8"][l - 1], d["zin"][l], t0, nt, f.hG[si], tag)
+                f.link(g, sc)
+                # ---- the scan(s)
+                if l == 0:
+                    paired = self._scan_layer0(m, fx, rest, pair, t0, nt, f.hS[si])
+                elif l == 1 and paired:
+                    pass  # (layer 1 of this chunk ran in layer 0's launch)
+                elif fused:
+                    self._stage_scan_fused(seqs, l, d["states"][l], d["spk"][l], d["s8"], t0, nt, f.hS[si], tag,
+                                           cnts=None if d["cnt"] is None else d["cnt"][l])
+                else:
+                    self._stage_scan(seqs, l, d["zin"][l], d["states"][l], d["spk"][l], d["s8"][l], d["mem"][l], t0, nt, f.hS[si], tag, rpw,
+                                     cnts=None if d["cnt"] is None else d["cnt"][l])
+                if staged:
+                    f.link(sc, g)  # the chunk-local zin buffer is reused by the next chunk's input product
+                # ---- after the last layer: projection and whatever follows the model
+                if l == nl - 1:
+                    self._epilogue(f, m, t0, nt, f.hG[si])
+                    if staged:
+                        done.append(_record(g))
+        return done
+
+    def _scan_layer0(self, m: _ModelRun, fx, rest, pair, t0, nt, st) -> bool:
+        """Layer 0 of a model on one chunk, in as few launches as the library takes: with layer 1 (True: layer 1 ran too), both kinds of
+        group in one launch, or the fused-x groups and the rest one after the other."""
+        seqs, d, xs_, tag = m.seqs, m.d, m.xs, m.tag
+        cn = d["cnt"]
+        cn0 = None if cn is None else cn[0]
+        if pair and self._stage_scan_l01(seqs, fx, rest, xs_, d, t0, nt, st, tag, cn=cn):
+            return True
+        if fx and rest and m.rpw == 16 and self.merge_layer0 and self._stage_scan_l0(
+                seqs, fx, rest, xs_, d["zin"][0], d["states"][0], d["spk"][0], d["s8"][0], t0, nt, st, tag, cnts=cn0):
+            return False  # (both kinds of group in one launch)
+        if fx:
+            self._stage_scan_fused_x(_pick(seqs, fx), _pick(xs_, fx), _pick(d["states"][0], fx), _pick(d["spk"][0], fx),
+                                     _pick(d["s8"][0], fx), t0, nt, st, tag, cnts=None if cn is None else _pick(cn0, fx))
+        if rest:
+            self._stage_scan(_pick(seqs, rest), 0, _pick(d["zin"][0], rest), _pick(d["states"][0], rest), _pick(d["spk"][0], rest),
+                             _pick(d["s8"][0], rest), _pick(d["mem"][0], rest), t0, nt, st, tag, m.rpw,
+                             cnts=None if cn is None else _pick(cn0, rest))
+        return False
+
+    def _join(self, f: _Forward) -> None:
+        """The calling stream waits for every stream of the forward; the forward's deferred error words are collected behind it."""
+        if f.plan.staged:
+            for s_ in {id(x): x for x in f.sstreams + f.gstreams}.values():
+                f.link(s_, f.main)
         if self._defer_err:
             # the error words of this forward's stack launches: one maximum, one copy to pinned memory, on a stream of its own behind
             # the joined forward (nothing of the forward waits for it)
@@ -1497,40 +1606,49 @@ class Engine:
             self._errors.watch(None, list({id(sc): sc for _, sc in items}.values()), "; ".join(sorted({w for w, _ in items})))
         self._defer_err = None
 
-        if frames is not None:
-            # the deep filter has written every frame of the padded batch: what lies past a clip's end is zeroed (2 launches)
-            hm = self._handle(main)
-            with self.timed("zero_tail", hm):
-                check(L.sfsn_zero_tail_frames(_ptr(enh_ri), B, S * F, T, 2, _ptr(frames_dev), hm), "sfsn_zero_tail_frames(enh_stft)")
-                check(L.sfsn_zero_tail_frames(_ptr(enh_mag), B, S * F, T, 1, _ptr(frames_dev), hm), "sfsn_zero_tail_frames(enh_mag)")
+    def _zero_tail(self, f: _Forward) -> None:
+        """A ragged batch: the deep filter has written every frame of the padded batch; what lies past a clip's end is zeroed (2 launches)."""
+        B, S, F, T = f.enh_mag.shape
+        hm = self._handle(f.main)
+        with self.timed("zero_tail", hm):
+            check(self.lib.sfsn_zero_tail_frames(_ptr(f.enh_ri), B, S * F, T, 2, _ptr(f.frames_dev), hm), "sfsn_zero_tail_frames(enh_stft)")
+            check(self.lib.sfsn_zero_tail_frames(_ptr(f.enh_mag), B, S * F, T, 1, _ptr(f.frames_dev), hm), "sfsn_zero_tail_frames(enh_mag)")
 
-        if want_counts and not want_layers:
-            # SynOPs without the fp32 spike tensors: the scans have counted what they wrote (no launch, no pass over
-            # the int8 copies); `count_in_scan = False`: round 3's counting launch over the int8 spikes, one launch for all layers
-            tens = [fb["s8"][l][0] for l in range(nl_fb)] + [sb["s8"][l][g] for g in range(ng) for l in range(nl_sb)]
-            shapes = [(T, B, self.fb.H)] * nl_fb + [(T, xs[g].shape[1], self.sb[g].H) for g in range(ng) for _ in range(nl_sb)]
-            if in_scan:
-                summ = [SpikeSummary(fb["cnt"][l][0], shapes[l]) for l in range(nl_fb)] + \
-                       [SpikeSummary(sb["cnt"][l][g], shapes[nl_fb + g * nl_sb + l]) for g in range(ng) for l in range(nl_sb)]
-            elif frames is not None:
-                rpcs = [1] * nl_fb + [spec.units(g) for g in range(ng) for _ in range(nl_sb)]
-                summ = self._count_spikes_ragged(tens, shapes, rpcs, frames, frames_dev, self._handle(main))
-            else:
-                summ = self._count_spikes(tens, shapes, self._handle(main))
-            for l in range(nl_fb):
-                fb["spk"][l][0] = summ[l]
-            for g in range(ng):
-                for l in range(nl_sb):
-                    sb["spk"][l][g] = summ[nl_fb + g * nl_sb + l]
+    def _summaries(self, f: _Forward) -> None:
+        """layer_outputs="counts": a SpikeSummary in the place of every spike tensor.  SynOPs without the fp32 spike tensors (SURVEY 8f
+        rank 1): the scans have counted what they wrote (no launch, no pass over the int8 copies); `count_in_scan = False`: round 3's
+        counting launch over the int8 spikes, one launch for all layers; a ragged batch: per clip, over each clip's own frames."""
+        spec, fb, sb, xs = self.spec, f.fbm.d, f.sbm.d, f.sbm.xs
+        ng, nl_fb, nl_sb = spec.n_groups, spec.fb_layers, spec.sb_layers
+        T, B = f.fbm.xs[0].shape[:2]
+        tens = [fb["s8"][l][0] for l in range(nl_fb)] + [sb["s8"][l][g] for g in range(ng) for l in range(nl_sb)]
+        shapes = [(T, B, self.fb.H)] * nl_fb + [(T, xs[g].shape[1], self.sb[g].H) for g in range(ng) for _ in range(nl_sb)]
+        if f.in_scan:
+            summ = [SpikeSummary(fb["cnt"][l][0], shapes[l]) for l in range(nl_fb)] + \
+                   [SpikeSummary(sb["cnt"][l][g], shapes[nl_fb + g * nl_sb + l]) for g in range(ng) for l in range(nl_sb)]
+        elif f.frames is not None:
+            rpcs = [1] * nl_fb + [spec.units(g) for g in range(ng) for _ in range(nl_sb)]
+            summ = self._count_spikes_ragged(tens, shapes, rpcs, f.frames, f.frames_dev, self._handle(f.main))
+        else:
+            summ = self._count_spikes(tens, shapes, self._handle(f.main))
+        for l in range(nl_fb):
+            fb["spk"][l][0] = summ[l]
+        for g in range(ng):
+            for l in range(nl_sb):
+                sb["spk"][l][g] = summ[nl_fb + g * nl_sb + l]
 
-        def outs(x, d, i, skipped, no_proj=False):
-            if i in skipped:  # never written: the entry keeps its shape (compute_neuronops reads size(-1)) and nothing else
+    def _result(self, f: _Forward) -> dict:
+        fb, sb, plan = f.fbm.d, f.sbm.d, f.plan
+        ng, nl_fb, nl_sb = self.spec.n_groups, self.spec.fb_layers, self.spec.sb_layers
+
+        def outs(m, i, no_proj=False):
+            x, pr = m.xs[i], m.d["proj"][i]
+            if i in f.x_skipped[m.tag]:  # never written: the entry keeps its shape (compute_neuronops reads size(-1)) and nothing else
                 x = torch.empty(x.shape, dtype=x.dtype, device="meta")
-            pr = d["proj"][i]
             if no_proj:  # (lean modes through sfsn_proj_deepfilter: the coefficient rows stayed in LDS)
                 pr = torch.empty(pr.shape, dtype=pr.dtype, device="meta")
-            return [x] + [d["spk"][l][i] for l in range(len(d["spk"]))] + [pr]
-        return dict(enh_stft=enh, enh_mag=enh_mag, fb_all=outs(x_fb, fb, 0, x_skipped["fb"]),
-                    sb_all=[outs(xs[g], sb, g, x_skipped["sb"], proj_skipped[0]) for g in range(ng)],
+            return [x] + [m.d["spk"][l][i] for l in range(len(m.d["spk"]))] + [pr]
+        return dict(enh_stft=f.enh, enh_mag=f.enh_mag, fb_all=outs(f.fbm, 0), sb_all=[outs(f.sbm, g, f.proj_skipped) for g in range(ng)],
                     fb_mem=[fb["mem"][l][0] for l in range(nl_fb)], sb_mem=[[sb["mem"][l][g] for l in range(nl_sb)] for g in range(ng)],
-                    mu_fb=mu_fb, mu_sb=mu_sb, sd_fb=sd_fb, sd_sb=sd_sb, pipelined=bool(pipeline), overlapped=overlap, n_chunks=len(bounds))
+                    mu_fb=f.fbm.mu, mu_sb=f.sbm.mu, sd_fb=f.fbm.sd, sd_sb=f.sbm.sd, pipelined=plan.pipeline, overlapped=plan.overlap,
+                    n_chunks=len(plan.bounds))
