@@ -183,8 +183,14 @@ int sfsn_gsn_train_step_bwd(const float* dz_next /* [R][G*H] d_z of step t+1, nu
 /* A whole layer call in ONE launch (ABI 14; ABI <= 13 enqueued T step launches): forward (t = 0 .. T-1) or backward (t = T-1 .. 0).
  * The workgroups stay resident for all T steps -- weight tile, carried membrane (forward) / its gradient (backward) in LDS -- and
  * exchange what a step needs from other workgroups through the L2 (csrc/sfsn_train.hip: packed spikes / d_z written through, one
- * publish counter per row block; the BatchNorm partial sums as for the step entries).  Arithmetic is the step entries', value for
- * value.  Tensors as for the step entries with a leading [T]: z [T][R][G*H]; spikes, u, xhat, f, g, dh_up [T][R][H]; invstd [T][H];
+ * publish counter per row block; the BatchNorm partial sums as for the step entries).  Every expression but the two products
+ * (h_{t-1} . W_hh^T forward, d_z_{t+1} . W_hh backward) is the step entries', operation for operation; the products differ in
+ * SUMMATION ORDER -- the step entries run one fma chain in k order, these kernels v_mfma_f32_16x16x4_f32 (k = 16 s + 4 q + e, the
+ * four q of an instruction summed inside it) -- so the two families agree within rounding, not bit for bit: a membrane closer to the
+ * threshold than the rounding error of u (tests/trainref.py: fwd_bound's bound on u) may spike in one and not in the other.  Both
+ * lie within that fp64 bound on the same inputs (tests/test_train_edges.py); a call cut into chunks of frames (below) equals the
+ * uncut call bit for bit.  Tensors as for the step entries with a leading [T]: z [T][R][G*H]; spikes, u, xhat, f, g, dh_up
+ * [T][R][H]; invstd [T][H];
  * d_gates [T][R][2H]; d_z [T][R][H] (shared; NULL otherwise).  Zero initial state (MODEL:100-106).  `zero` and `dc_work` are unused
  * (kept for the ABI-13 call shape; may be NULL).  `scratch`: sfsn_train_seq_scratch_bytes(R, H) bytes, ZEROED by the caller before the
  * call, one buffer per call (forward and backward use their own); its last four 32-bit words hold the error word as before. */

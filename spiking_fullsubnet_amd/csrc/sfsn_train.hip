@@ -444,7 +444,8 @@ extern "C" int sfsn_gsn_train_step_bwd(const float* dz_next, const float* w_hh, 
 //     stores; a per-row-block counter counts the tile workgroups that have published a step (their stores drained by vmcnt before
 //     the add); readers poll the counter (one thread), then read with sc1 loads.
 // All workgroups of the launch must be resident (train_geometry keeps the grid under 220 blocks of 256 threads); every spin is
-// bounded (error word, the host raises).  Arithmetic and its order are the step kernels', value for value.
+// bounded (error word, the host raises).  Every expression but the two products is the step kernels', operation for operation; the
+// products run on the matrix pipe below and differ from the step kernels' fma chains in summation order (sfsn.h).
 __device__ __forceinline__ bool tr_wait_counter(const unsigned* cnt, unsigned want, unsigned* err) {
     int good = 1;
     if (threadIdx.x == 0) {
