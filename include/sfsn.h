@@ -1007,6 +1007,14 @@ int sfsn_pit_sdr(const float* est, const float* ref /* [clips][sources][n_sample
  *                               owns each counter, no atomics.
  *   sfsn_zero_tail_frames       x [B][rows][T][width] float: frames t >= clip_frames[b] := 0 (each element stored once; the rest
  *                               of x is not touched).  T * width < 2^31.
+ *   sfsn_fullband_proj_deepfilter_ragged  sfsn_fullband_proj_deepfilter (csrc/sfsn_fullband.hip) with T_b = clip_frames[b] clamped into
+ *                               [0, T].  Frames t0 <= t < min(t0 + nt, T_b): enh_ri, enh_mag and proj of clip b have the bits of the
+ *                               sibling on that clip alone (every clip_frames[b] = T: of the sibling on the batch).  Frames
+ *                               max(t0, T_b) <= t < t0 + nt: enh_ri and enh_mag (where given) are stored as 0, once, and proj is not
+ *                               written; nothing of stft_ri or spikes_i8 at frames >= T_b is read (skipped, not multiplied by zero:
+ *                               the padding may hold NaN), and a 16-frame tile wholly past T_b loads no weights and issues no MFMA.
+ *                               Outside [t0, t0 + nt) nothing is touched.  The sibling's SFSN_EINVAL / SFSN_EUNSUPPORTED cases.
+ *                               (Added without an ABI bump: no struct or signature changed.)
  * ---------------------------------------------------------------------------------------------------- */
 int sfsn_stft_ragged(const float* wave /* [B][L] */, int B, int L, int n_fft, int hop, const float* window,
                      float* stft_ri /* [B][n_fft/2+1][T][2] */, int T, const int32_t* clip_len /* device [B] */, void* stream);
@@ -1023,6 +1031,11 @@ int sfsn_spike_count_rows_ragged(const sfsn_row_count* tensors /* host */, int n
                                  const int32_t* clip_frames /* device [B] */, int B, void* stream);
 int sfsn_zero_tail_frames(float* x /* [B][rows][T][width] */, int B, int rows, int T, int width,
                           const int32_t* clip_frames /* device [B] */, void* stream);
+int sfsn_fullband_proj_deepfilter_ragged(const float* stft_ri /* [B][F][T][2] */, const int8_t* spikes_i8 /* [T][B][pad64(H)] */, int H,
+                                         const int8_t* w_packed, const float* w_dq, const float* bias, int act, int B, int F, int T,
+                                         int S, int df, float* proj /* [T][B][2 df S F], nullable */,
+                                         float* enh_ri /* [B][S][F][T][2] */, float* enh_mag /* [B][S][F][T], nullable */, int t0,
+                                         int nt, const int32_t* clip_frames /* device [B] */, void* stream);
 
 /* ----------------------------------------------------------------------------------------------------
  * Scoring a ragged batch: sfsn_pit_sdr with per-clip lengths, plus the clips' own losses and audiozen.metric.SISDR of the matched

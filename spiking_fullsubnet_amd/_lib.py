@@ -334,6 +334,8 @@ def lib() -> ctypes.CDLL:
     L.sfsn_spike_count_rows_ragged.argtypes = [ctypes.POINTER(RowCount), _I, _I, _I, _P, _I, _P]
     L.sfsn_zero_tail_frames.restype = _I  # x | B, rows, T, width | clip_frames, stream
     L.sfsn_zero_tail_frames.argtypes = [_P, _I, _I, _I, _I, _P, _P]
+    L.sfsn_fullband_proj_deepfilter_ragged.restype = _I  # sfsn_fullband_proj_deepfilter's arguments up to nt | clip_frames, stream
+    L.sfsn_fullband_proj_deepfilter_ragged.argtypes = L.sfsn_fullband_proj_deepfilter.argtypes[:-1] + [_P, _P]
     L.sfsn_pit_sdr_ragged.restype = _I  # est, ref | clips, sources, n_samples | clip_len | zero_mean | eps | pair_cot, pair, perm, clip_loss, loss, grad_est, reordered, si_sdr, scratch, stream
     L.sfsn_pit_sdr_ragged.argtypes = [_P, _P, _I, _I, _I, _P, _I, _F] + [_P] * 10
     if L.sfsn_abi_version() != ABI_VERSION:
@@ -357,7 +359,8 @@ EXPORTS = ("sfsn_abi_version", "sfsn_source_hash", "sfsn_strerror", "sfsn_device
            "sfsn_fullband_stream_hop_counted", "sfsn_recipe_loss_scratch_bytes", "sfsn_recipe_loss",
            "sfsn_pit_sdr_scratch_bytes", "sfsn_pit_sdr", "sfsn_stft_ragged", "sfsn_istft_ragged", "sfsn_laplace_means_ragged",
            "sfsn_gaussian_stats_ragged", "sfsn_spike_count_rows_ragged", "sfsn_zero_tail_frames", "sfsn_gsn_layer_scan_l0",
-           "sfsn_pit_sdr_ragged", "sfsn_gsn_layer_scan_l01", "sfsn_recipe_loss_ragged_scratch_bytes", "sfsn_recipe_loss_ragged")
+           "sfsn_pit_sdr_ragged", "sfsn_gsn_layer_scan_l01", "sfsn_recipe_loss_ragged_scratch_bytes", "sfsn_recipe_loss_ragged",
+           "sfsn_fullband_proj_deepfilter_ragged")
 
 
 def check(rc: int, what: str = "") -> None:

@@ -268,11 +268,123 @@ __global__ __launch_bounds__(256) void fullband_projdf_kernel(const FbdfParams p
     }
 }
 
-extern "C" int sfsn_fullband_proj_deepfilter(const float* stft_ri, const int8_t* spikes_i8, int H, const int8_t* w_packed, const float* w_dq,
-                                             const float* bias, int act, int B, int F, int T, int S, int df, float* proj, float* enh_ri,
-                                             float* enh_mag, int t0, int nt, void* stream) {
+// The length-aware sibling (sfsn_fullband_proj_deepfilter_ragged): fullband_projdf_kernel's item, expression for expression, except that
+// clip b ends at T_b = clip_frames[b] clamped into [0, T] and the item's window at t1 = min(p.t1, T_b).  The lanes of frames >= t1 re-read
+// frame t1 - 1, as the lanes past the window do above, so nothing at or past T_b is read; those still inside the window store 0.  An item
+// whose tile starts at or past t1 stores its zeros and returns before any spike or weight load.  (A kernel of its own, not a flag on the
+// one above, whose code object stays what it was: scripts/device_code_digest.py, profiles/cirm_ragged.md.)
+template <int KS>
+__global__ __launch_bounds__(256) void fullband_projdf_ragged_kernel(const FbdfParams p, const int32_t* __restrict__ clip_frames) {
+    constexpr int KP = KS * 64;
+    const int lane = threadIdx.x & 63;
+    const int item = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+    if (item >= p.items) return;  // wave-uniform
+    const int fb = item % p.NFB, bt = item / p.NFB;
+    const int tile = bt % p.ntile, b = bt / p.ntile;
+    const int m = lane & 15, q = lane >> 4;
+    const int B = p.B, F = p.F, T = p.T, S = p.S, df = p.df;
+    const int t = p.t0 + tile * 16 + m;
+    const int tb = clip_frames[b];  // (b < B: one read per wave, before any other address depends on it)
+    const int Tb = tb < 0 ? 0 : (tb > T ? T : tb);
+    const int t1 = Tb < p.t1 ? Tb : p.t1;
+    if (p.t0 + tile * 16 >= t1) {  // wave-uniform: the whole tile lies past the clip's end
+        if (t < p.t1) {
+            for (int s_ = 0; s_ < S; ++s_) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int f = fb * 16 + q * 4 + r;
+                    if (f >= F) continue;
+                    const size_t o = (((size_t)b * S + s_) * F + f) * T + t;
+                    *reinterpret_cast<float2*>(p.enh + 2 * o) = make_float2(0.0f, 0.0f);
+                    if (p.mag) p.mag[o] = 0.0f;
+                }
+            }
+        }
+        return;
+    }
+    const bool tv = t < t1;
+    const int tl = tv ? t : t1 - 1;  // frames past the window re-read the last one (nothing of theirs is stored)
+    const int8_t* srow = p.s + ((size_t)tl * B + b) * KP + q * 16;
+    v4i bfr[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) bfr[ks] = *reinterpret_cast<const v4i*>(srow + ks * 64);
+    const int fbase = fb * 16 + q * 4;
+    // spectrum rows of this lane's four bins (a bin past F re-reads bin F - 1; its results are not stored)
+    const float* xrow[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int f = fbase + r < F ? fbase + r : F - 1;
+        xrow[r] = p.stft + ((size_t)b * F + f) * T * 2;
+    }
+    const size_t prow = ((size_t)t * B + b) * p.P;
+    for (int s_ = 0; s_ < S; ++s_) {
+        float yr[4] = {0.0f, 0.0f, 0.0f, 0.0f}, yi[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        for (int d = 0; d < df; ++d) {
+            float cf[2][4];
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const int j = (c * df + d) * S + s_;  // the reference's (c, d, s) column block
+                const int ct = fb * p.NCT + j;        // its packed row tile
+                v4i wa[KS][3];
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+                    for (int dp = 0; dp < 3; ++dp)
+                        wa[ks][dp] = *reinterpret_cast<const v4i*>(p.w + ((((size_t)dp * p.NTT + ct) * KS + ks) * 64 + lane) * 16);
+                v4i a0 = {0, 0, 0, 0}, a1 = {0, 0, 0, 0}, a2 = {0, 0, 0, 0};
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks) {
+                    a0 = __builtin_amdgcn_mfma_i32_16x16x64_i8(wa[ks][0], bfr[ks], a0, 0, 0, 0);
+                    a1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(wa[ks][1], bfr[ks], a1, 0, 0, 0);
+                    a2 = __builtin_amdgcn_mfma_i32_16x16x64_i8(wa[ks][2], bfr[ks], a2, 0, 0, 0);
+                }
+                const v4f dqv = *reinterpret_cast<const v4f*>(p.dq + ct * 16 + q * 4);
+                const v4f bv = p.bias ? *reinterpret_cast<const v4f*>(p.bias + ct * 16 + q * 4) : v4f{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float v = fbd_coef(a0[r], a1[r], a2[r], dqv[r], bv[r]);  // = sfsn_spike_proj's output
+                    if (p.proj && tv && fbase + r < F) p.proj[prow + (size_t)j * F + fbase + r] = v;
+                    cf[c][r] = fbd_act(v, p.act);
+                }
+            }
+            const int ts = tl - (df - 1) + d;
+            const int tsc = ts < 0 ? 0 : ts;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float2 xv = *reinterpret_cast<const float2*>(xrow[r] + (size_t)tsc * 2);
+                if (ts < 0) xv = make_float2(0.0f, 0.0f);
+                fbd_tap(yr[r], yi[r], xv, cf[0][r], cf[1][r]);
+            }
+        }
+        if (tv) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int f = fbase + r;
+                if (f >= F) continue;
+                const size_t o = (((size_t)b * S + s_) * F + f) * T + t;
+                *reinterpret_cast<float2*>(p.enh + 2 * o) = make_float2(yr[r], yi[r]);
+                if (p.mag) p.mag[o] = fbd_mag(yr[r], yi[r]);
+            }
+        } else if (t < p.t1) {  // inside the window, past the clip's end
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int f = fbase + r;
+                if (f >= F) continue;
+                const size_t o = (((size_t)b * S + s_) * F + f) * T + t;
+                *reinterpret_cast<float2*>(p.enh + 2 * o) = make_float2(0.0f, 0.0f);
+                if (p.mag) p.mag[o] = 0.0f;
+            }
+        }
+    }
+}
+
+// the two entries' common host side; clip_frames selects the length-aware kernel
+static int fbd_launch(const float* stft_ri, const int8_t* spikes_i8, int H, const int8_t* w_packed, const float* w_dq, const float* bias,
+                      int act, int B, int F, int T, int S, int df, float* proj, float* enh_ri, float* enh_mag, int t0, int nt,
+                      const int32_t* clip_frames, bool ragged, void* stream) {
     if (!stft_ri || !spikes_i8 || !w_packed || !w_dq || !enh_ri || H <= 0 || B <= 0 || F <= 0 || T <= 0 || S <= 0 || df <= 0)
         return SFSN_EINVAL;
+    if (ragged && (!clip_frames || (reinterpret_cast<uintptr_t>(clip_frames) & 3u))) return SFSN_EINVAL;
     if (act < SFSN_ACT_NONE || act > SFSN_ACT_RELU) return SFSN_EINVAL;
     if (t0 < 0 || nt <= 0 || t0 + nt > T) return SFSN_EINVAL;
     if (!fbd_aligned16(spikes_i8) || !fbd_aligned16(w_packed) || !fbd_aligned16(w_dq) || !fbd_aligned16(bias) ||
@@ -291,12 +403,28 @@ extern "C" int sfsn_fullband_proj_deepfilter(const float* stft_ri, const int8_t*
     p.items = (int)items;
     const unsigned grid = (unsigned)((items + 3) / 4);
     hipStream_t st = static_cast<hipStream_t>(stream);
-#define FBD_CASE(KS_)                                                                             \
-    if (KS == KS_) {                                                                              \
-        hipLaunchKernelGGL(fullband_projdf_kernel<KS_>, dim3(grid), dim3(256), 0, st, p);         \
-        return hipGetLastError() == hipSuccess ? SFSN_OK : SFSN_EHIP;                             \
+#define FBD_CASE(KS_)                                                                                              \
+    if (KS == KS_) {                                                                                               \
+        if (ragged)                                                                                                \
+            hipLaunchKernelGGL(fullband_projdf_ragged_kernel<KS_>, dim3(grid), dim3(256), 0, st, p, clip_frames);  \
+        else                                                                                                       \
+            hipLaunchKernelGGL(fullband_projdf_kernel<KS_>, dim3(grid), dim3(256), 0, st, p);                      \
+        return hipGetLastError() == hipSuccess ? SFSN_OK : SFSN_EHIP;                                              \
     }
     FBD_CASE(1) FBD_CASE(2) FBD_CASE(3) FBD_CASE(4) FBD_CASE(5)
 #undef FBD_CASE
     return SFSN_EUNSUPPORTED;
+}
+
+extern "C" int sfsn_fullband_proj_deepfilter(const float* stft_ri, const int8_t* spikes_i8, int H, const int8_t* w_packed, const float* w_dq,
+                                             const float* bias, int act, int B, int F, int T, int S, int df, float* proj, float* enh_ri,
+                                             float* enh_mag, int t0, int nt, void* stream) {
+    return fbd_launch(stft_ri, spikes_i8, H, w_packed, w_dq, bias, act, B, F, T, S, df, proj, enh_ri, enh_mag, t0, nt, nullptr, false, stream);
+}
+
+extern "C" int sfsn_fullband_proj_deepfilter_ragged(const float* stft_ri, const int8_t* spikes_i8, int H, const int8_t* w_packed,
+                                                    const float* w_dq, const float* bias, int act, int B, int F, int T, int S, int df,
+                                                    float* proj, float* enh_ri, float* enh_mag, int t0, int nt,
+                                                    const int32_t* clip_frames, void* stream) {
+    return fbd_launch(stft_ri, spikes_i8, H, w_packed, w_dq, bias, act, B, F, T, S, df, proj, enh_ri, enh_mag, t0, nt, clip_frames, true, stream);
 }

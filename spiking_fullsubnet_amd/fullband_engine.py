@@ -7,6 +7,8 @@ model, through the same C ABI:
                                    (sfsn_input_proj_f32 where K = F <= 192)
     sfsn_gsn_stack_scan            every GSN layer in one launch (shared gates; per-layer scans otherwise)
     sfsn_fullband_proj_deepfilter  projection + activation + deep filter + |.|      -> enh [B][S][F][T]
+                                   (a ragged batch, ``forward_stft(frames=)``: sfsn_fullband_proj_deepfilter_ragged, which stops at
+                                   each clip's own last frame and writes the zeros behind it)
 
 Hidden sizes that are not a multiple of 16 (the recipe's H = 268) are padded to Hp = ceil16(H) when packing: zero rows and columns
 in W_ih / W_hh / W_proj, and the padded neurons are held silent (``pad_cell``).  The int8 digit products of the real neurons are
@@ -21,7 +23,7 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ragged
 from ._lib import MAX_COUNT_TENSORS, FusedInput, RowCount, ScanSegment, check
 from .engine import ErrorWords, SpikeSummary, _dev, _ptr, fill_segment, fold_batchnorm, pack_w3
 
@@ -218,12 +220,15 @@ class FullbandEngine:
         """Raise if a hand-off wait of an earlier stack launch expired (synchronises)."""
         self._errors.check()
 
-    def _launch_frames(self, ri, B: int, T: int, t0: int, nt: int, stack: bool, ws: dict, x, states, spk, proj, enh, mag) -> None:
+    def _launch_frames(self, ri, B: int, T: int, t0: int, nt: int, stack: bool, ws: dict, x, states, spk, proj, enh, mag,
+                       frames_dev: Optional[torch.Tensor] = None) -> None:
         """The launch sequence of the model on frames [t0, t0 + nt) of the spectrum ri [B, F, T, 2], on torch's current stream:
         features -> layer 0's input term -> the GSN layers from `states` (updated in place) -> projection + deep filter.
         forward_stft runs it on (0, T) from zero states; a streaming session (fullband_streaming.py) on the `hop` new frames behind
         its history, with the states carried.  x [T, B, F], spk[l] [T, B, Hp] or None, proj [T, B, P] or None, enh [B, S, F, T, 2],
-        mag [B, S, F, T] or None are whole-spectrum buffers; ws = _make_workspace(B, nt, T, stack)."""
+        mag [B, S, F, T] or None are whole-spectrum buffers; ws = _make_workspace(B, nt, T, stack).  frames_dev (int32 [B] on the
+        device): a ragged batch -- the last launch is the length-aware one: enh / mag are zero and proj is not written at frames
+        >= frames_dev[b].  The launches before it are the same: the model is causal."""
         spec, L, Hp, G, F = self.spec, self.lib, self.Hp, self.G, self.F
         st, dev, nl, S = self._stream(), self.device, spec.layers, spec.num_spks
         check(L.sfsn_fullband_features(_ptr(ri), B, F, T, spec.fdrc, _ptr(self.ln_w), _ptr(self.ln_b), 1e-5, _ptr(x), t0, nt, st),
@@ -275,25 +280,42 @@ class FullbandEngine:
                 fill_segment(seg[0], self.layers[l], B, Hp, t0, zin, states[l], ws["s8"][l], spk[l])
                 check(L.sfsn_gsn_layer_scan(seg, 1, nt, Hp, int(spec.shared), 0, st), "sfsn_gsn_layer_scan")
                 self._count("layer_scan")
-        check(L.sfsn_fullband_proj_deepfilter(_ptr(ri), _ptr(ws["s8"][-1]), Hp, _ptr(self.proj_q), _ptr(self.proj_dq), _ptr(self.proj_b),
-                                              spec.act, B, F, T, S, spec.df, _ptr(proj), _ptr(enh), _ptr(mag), t0, nt, st),
-              "sfsn_fullband_proj_deepfilter")
-        self._count("projdf")
+        args = (_ptr(ri), _ptr(ws["s8"][-1]), Hp, _ptr(self.proj_q), _ptr(self.proj_dq), _ptr(self.proj_b), spec.act, B, F, T, S, spec.df,
+                _ptr(proj), _ptr(enh), _ptr(mag), t0, nt)
+        if frames_dev is None:
+            check(L.sfsn_fullband_proj_deepfilter(*args, st), "sfsn_fullband_proj_deepfilter")
+            self._count("projdf")
+        else:
+            check(L.sfsn_fullband_proj_deepfilter_ragged(*args, _ptr(frames_dev), st), "sfsn_fullband_proj_deepfilter_ragged")
+            self._count("projdf_ragged")
 
     @torch.no_grad()
-    def forward_stft(self, noisy_cmp: torch.Tensor, want_layers: bool = False, want_counts: bool = False) -> dict:
+    def forward_stft(self, noisy_cmp: torch.Tensor, want_layers: bool = False, want_counts: bool = False, frames=None,
+                     frames_dev: Optional[torch.Tensor] = None) -> dict:
         """complex64 [B, F, T] on the device -> dict(enh_stft complex [B, S, F, T], enh_mag [B, S, F, T] (num_spks == 1) or None,
         all_layers = [x [T, B, F], spikes [T, B, H] per layer, proj [T, B, P]] when want_layers, else None).  want_counts: also
         clip_counts, int64 [layers, B] -- every layer's spikes per clip, counted on the device from the int8 spikes the scans write
         (one sfsn_spike_count_rows launch); without want_layers no fp32 spike or projection tensor is allocated and all_layers is
         [x] + [SpikeSummary(count over the clips, (T, B, H)) per layer] + [proj (T, B, P), shape only (a meta tensor)]: all that
-        metric.compute_synops / compute_neuronops read."""
+        metric.compute_synops / compute_neuronops read.
+
+        ``frames`` -- a ragged batch (``ragged.py``): a length-B sequence of ints, clip b has ``frames[b]`` frames
+        (``1 <= frames[b] <= T``; ``ValueError`` naming the clip otherwise) and the rest of its row is padding.  Over its own frames
+        clip b is the clip run alone, bit for bit.  ``enh_stft`` / ``enh_mag`` are zero at frames ``>= frames[b]`` (the length-aware
+        epilogue writes the zeros and does no work there); ``clip_counts[l, b]`` counts clip b's own frames and the spike entries of
+        ``all_layers`` are ``ragged.ClipSpikeSummary``; with want_layers ``proj`` is zero past a clip's end while ``x`` and the spike
+        tensors keep what the model computed on the padding (``ragged.clip_layers`` slices).  The lengths go to the device once,
+        without a host synchronisation (``frames_dev``: they are there already, as int32 [B])."""
         spec, L, Hp, G, F = self.spec, self.lib, self.Hp, self.G, self.F
         if noisy_cmp.device != self.device or noisy_cmp.dtype != torch.complex64 or noisy_cmp.ndim != 3 or noisy_cmp.shape[1] != F:
             raise ValueError(f"expected complex64 [B, {F}, T] on {self.device}, got {noisy_cmp.dtype} {tuple(noisy_cmp.shape)} "
                              f"on {noisy_cmp.device}")
-        self._errors.poll()
         B, _, T = noisy_cmp.shape
+        if frames is not None:
+            frames = ragged.check_frames(frames, B, T)
+            if frames_dev is None:
+                frames_dev = ragged.upload(frames, self.device)
+        self._errors.poll()
         ri = torch.view_as_real(noisy_cmp.contiguous())
         st, dev, nl, S = self._stream(), self.device, spec.layers, spec.num_spks
         f32 = dict(dtype=torch.float32, device=dev)
@@ -305,8 +327,9 @@ class FullbandEngine:
         spk = [torch.empty((T, B, Hp), **f32) if want_layers else None for _ in range(nl)]
         enh = torch.empty((B, S, F, T, 2), **f32)
         mag = torch.empty((B, S, F, T), **f32) if S == 1 else None
-        proj = torch.empty((T, B, spec.P), **f32) if want_layers else None
-        self._launch_frames(ri, B, T, 0, T, stack, ws, x, states, spk, proj, enh, mag)
+        # (a ragged batch: the epilogue leaves proj alone past a clip's end, so it starts out zero)
+        proj = (torch.empty if frames is None else torch.zeros)((T, B, spec.P), **f32) if want_layers else None
+        self._launch_frames(ri, B, T, 0, T, stack, ws, x, states, spk, proj, enh, mag, frames_dev)
         out = dict(enh_stft=torch.view_as_complex(enh), enh_mag=mag, all_layers=None)
         if want_counts:  # SynOPs without the fp32 spike tensors: the workspace's int8 spikes [T][B][HP8] (pad columns zero), a row per clip
             counts = out["clip_counts"] = torch.zeros((nl, B), dtype=torch.int64, device=dev)
@@ -315,11 +338,17 @@ class FullbandEngine:
                 for j in range(len(arr)):
                     arr[j].spikes_i8, arr[j].T, arr[j].R, arr[j].HP, arr[j].rows_per_clip = _ptr(ws["s8"][l0 + j]), T, B, self.HP8, 1
                     arr[j].counts = _ptr(counts[l0 + j])
-                check(L.sfsn_spike_count_rows(arr, len(arr), 0, T, st), "sfsn_spike_count_rows")
+                if frames is None:
+                    check(L.sfsn_spike_count_rows(arr, len(arr), 0, T, st), "sfsn_spike_count_rows")
+                else:  # each clip's own frames
+                    check(L.sfsn_spike_count_rows_ragged(arr, len(arr), 0, T, _ptr(frames_dev), B, st), "sfsn_spike_count_rows_ragged")
                 self._count("spike_count")
         if want_layers:
             out["all_layers"] = [x] + [s[:, :, :self.H] for s in spk] + [proj]
         elif want_counts:
-            out["all_layers"] = [x] + [SpikeSummary(c, (T, B, self.H)) for c in counts.sum(1)] + \
-                                [torch.empty((T, B, spec.P), dtype=torch.float32, device="meta")]
+            if frames is None:
+                summaries = [SpikeSummary(c, (T, B, self.H)) for c in counts.sum(1)]
+            else:
+                summaries = [ragged.ClipSpikeSummary(c, (T, B, self.H), frames) for c in counts]
+            out["all_layers"] = [x] + summaries + [torch.empty((T, B, spec.P), dtype=torch.float32, device="meta")]
         return out

@@ -10,7 +10,8 @@ return values (:206-245).  A recipe switches over by changing only
 
 In ``eval()`` mode a GSN model runs everything between ``stft`` and ``istft`` on the gfx950 kernels through ``FullbandEngine``; an
 LSTM model runs its sequence model on ATen (``training.sequence_model``) and the deep filter as torch operations.  ``streaming()``
-opens a frame-by-frame session of a GSN model (``fullband_streaming.py``).  Spike counts for SynOPs: ``layer_outputs = "counts"``
+opens a frame-by-frame session of a GSN model (``fullband_streaming.py``); ``forward_ragged(waves, lengths)`` runs a padded batch of
+clips of different lengths, every clip as if it ran alone (``ragged.py``).  Spike counts for SynOPs: ``layer_outputs = "counts"``
 (the two-speaker ``forward``), ``forward_stft(want_counts=True)`` and ``streaming(count_spikes=True)`` + ``session.spike_summary``.
 
 In ``train()`` mode -- or in ``eval()`` mode with grad enabled and an input that requires grad (or ``autograd_in_eval = True``) --
@@ -97,12 +98,43 @@ class Model(_EngineMixin, nn.Module):
                                         count_spikes=count_spikes)
 
     @torch.no_grad()
-    def forward_stft(self, noisy_cmp, want_layers=False, want_counts=False):
-        """The hot path alone (GSN models): complex64 [B, F, T] -> ``FullbandEngine.forward_stft``'s result dict."""
+    def forward_stft(self, noisy_cmp, want_layers=False, want_counts=False, frames=None):
+        """The hot path alone (GSN models): complex64 [B, F, T] -> ``FullbandEngine.forward_stft``'s result dict.  ``frames``: a
+        ragged batch, clip b has ``frames[b]`` frames."""
         if self.fb_model.sequence_model_name == "LSTM":
             raise NotImplementedError("forward_stft runs the GSN kernels: an LSTM model runs on ATen (call the module itself)")
         self._check_mode(noisy_cmp)
-        return self.engine().forward_stft(noisy_cmp, want_layers=want_layers, want_counts=want_counts)
+        return self.engine().forward_stft(noisy_cmp, want_layers=want_layers, want_counts=want_counts, frames=frames)
+
+    @torch.no_grad()
+    def forward_ragged(self, waves, lengths):
+        """Inference on a batch of clips of different lengths (GSN models): ``waves`` float32 [B, Lmax] on the device (what lies past
+        a clip's end is ignored), ``lengths`` a sequence or CPU int tensor of B values, ``1 <= L_b <= Lmax`` (``ValueError`` naming
+        the clip otherwise).  Returns ``forward()``'s tuple on the padded batch -- ``(enh_y [B, S, Lmax], [layers])`` for
+        ``num_spks > 1``, ``(enh_y [B, Lmax], enh_mag [B, F, T])`` for one speaker -- in which every clip is the clip run alone, bit
+        for bit: ``enh_y[b, ..., :L_b]`` and ``enh_mag[b, :, :T_b]`` (zero beyond), and ``ragged.clip_layers(layers, [], b, lengths,
+        hop=hop_length)[0]`` for clip b's layer list.  Inference only (``_check_mode``)."""
+        if self.fb_model.sequence_model_name == "LSTM":
+            raise NotImplementedError("forward_ragged runs the GSN kernels: an LSTM model runs on ATen, one clip per call")
+        y, res = self._forward_ragged(waves, lengths)
+        if self.num_spks > 1:
+            return y, [self._layer_list(res, waves.shape[0])]
+        return y[:, 0], res["enh_mag"][:, 0]
+
+    def _forward_kwargs(self):
+        # (one speaker returns no layer list; two speakers: layer_outputs says what stands in for the fp32 spike tensors)
+        return self._layer_kwargs() if self.num_spks > 1 else dict(want_layers=False, want_counts=False)
+
+    def _gaussian_norm(self) -> bool:
+        return False
+
+    def _layer_list(self, res, batch_size):
+        layers = res["all_layers"]
+        if layers is None:  # "none": the list keeps its length and the shapes of its two ends
+            T, F, P = res["enh_stft"].shape[-1], self.fb_input_size, self._fb_spec.P
+            layers = [torch.empty((T, batch_size, F), device="meta")] + [None] * self._fb_spec.layers + \
+                     [torch.empty((T, batch_size, P), device="meta")]
+        return layers
 
     def forward(self, input):
         assert input.ndim == 2, f"Input tensor must be 2D, but got {input.ndim}D."
@@ -124,15 +156,9 @@ class Model(_EngineMixin, nn.Module):
 
     def _forward_gsn(self, input):
         batch_size, sequence_length = input.shape
-        # (one speaker returns no layer list; two speakers: layer_outputs says what stands in for the fp32 spike tensors)
-        kw = self._layer_kwargs() if self.num_spks > 1 else dict(want_layers=False, want_counts=False)
-        res = self.engine().forward_stft(self._stft(input), **kw)
+        res = self.engine().forward_stft(self._stft(input), **self._forward_kwargs())
         mag = res["enh_mag"][:, 0] if res["enh_mag"] is not None else None
-        layers = res["all_layers"]
-        if layers is None and self.num_spks > 1:  # "none": the list keeps its length and the shapes of its two ends
-            T, F, P = res["enh_stft"].shape[-1], self.fb_input_size, self._fb_spec.P
-            layers = [torch.empty((T, batch_size, F), device="meta")] + [None] * self._fb_spec.layers + \
-                     [torch.empty((T, batch_size, P), device="meta")]
+        layers = self._layer_list(res, batch_size) if self.num_spks > 1 else None
         return self._finish(res["enh_stft"], mag, layers, batch_size, sequence_length)
 
     def _forward_lstm(self, input):

@@ -199,7 +199,7 @@ class _EngineMixin:
         self._check_mode(waves)
         B, Lmax = waves.shape
         hop = self.hop_length
-        lens = ragged.check_lengths(lengths, B, Lmax, hop, gaussian=self._spec().gaussian)
+        lens = ragged.check_lengths(lengths, B, Lmax, hop, gaussian=self._gaussian_norm())
         frames = ragged.frames_of(lens, hop)
         eng = self.engine()
         with torch.cuda.device(waves.device):
@@ -207,7 +207,7 @@ class _EngineMixin:
         len_dev, fr_dev = both[0], both[1]
         device_fft = self._device_fft(waves)
         stft = self._stft_ragged(waves, len_dev)
-        res = eng.forward_stft(stft, frames=frames, frames_dev=fr_dev, **self._layer_kwargs())
+        res = eng.forward_stft(stft, frames=frames, frames_dev=fr_dev, **self._forward_kwargs())
         enh = res["enh_stft"]  # [B, S, F, T], zero at frames >= T_b
         S = enh.shape[1]
         flat = enh.reshape(B * S, *enh.shape[2:])
@@ -224,6 +224,14 @@ class _EngineMixin:
         if self.layer_outputs not in ("tensors", "counts", "none"):
             raise ValueError(f"layer_outputs must be 'tensors', 'counts' or 'none', got {self.layer_outputs!r}")
         return dict(want_layers=self.layer_outputs == "tensors", want_counts=self.layer_outputs == "counts")
+
+    def _forward_kwargs(self) -> dict:
+        """What forward() asks of the engine's forward_stft (the cIRM-GSN module asks for no layers with one speaker)."""
+        return self._layer_kwargs()
+
+    def _gaussian_norm(self) -> bool:
+        """offline_gaussian_norm in the front-end: a clip needs two frames (the cIRM-GSN module has no PathSpec and no such norm)."""
+        return self._spec().gaussian
 
     def _spec(self) -> PathSpec:  # pragma: no cover - provided by subclasses
         raise NotImplementedError
