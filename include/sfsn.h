@@ -658,6 +658,43 @@ int sfsn_stream_hop_resident(const sfsn_hop_desc* desc /* host */, void* doorbel
  * input arrived, frame computed, deep filter done, exit (scripts/exp_hop.py prints them per stage). */
 int sfsn_hop_stages(const sfsn_hop_desc* desc /* host */, int* out /* host [cap][4] */, int cap);
 
+/* Priming (csrc/sfsn_prime.hip): the state N / hop launches of sfsn_stream_hop on a recorded prefix of N frames would have left, written
+ * in ONE launch from what the OFFLINE kernels computed for that prefix -- for the listed clips of the descriptor only; every other
+ * clip's rows, the tagged scratch (spikes, spec_g, enh_g) and launch_index are left as they are.  `src` describes tensors of Bp clips;
+ * clips[i] (an index of desc's batch, distinct, n_clips >= 1) takes the prefix of source clip b0 + i.  With k = desc->launch_index:
+ *   layer.h[k & 1]  <- the last frame's spikes (row N - 1 of spikes_i8), layer.c <- the membrane (c), in the hop's row layout;
+ *   cum[k & 1]      <- the rows' running sums (sfsn_cum_laplace_norm's cum_state: the hop adds the same row sums in the same order);
+ *   hist_ri         <- the last D noisy frames of the bins the groups cover (zeros before the prefix's first frame);
+ *   spike_slots     <- slot (row, j) = the spikes of neurons 4j .. 4j + 3 of `row` over the N frames (REPLACED, not added to);
+ *   wave_state      <- wave_tail, the last 512 input samples; ola_state <- the overlap-add partial sums the last three frames of enh_ri
+ *                      leave for the padded positions not yet emitted (sfsn_hop_wave_dev.h's arithmetic in ascending frame order).
+ * The caller then sets clip_start[clips[i]] = k - N / hop (unsigned, wrap-safe): launch k gives those clips frame index N / hop and reads
+ * the state above.  An origin equal to k would make launch k read the state as ZERO -- which is what N = 0 means (waveform mode only:
+ * a clip whose one call of samples has made no frame yet; everything but wave_state is written as zero).
+ * Bit for bit what the launches would have left wherever the offline forward and the hop agree bit for bit (see above: all but layer
+ * 0's membranes, which are the offline forward's here).  Plain stores, no atomics; ordered on `stream` like any launch.
+ * SFSN_EINVAL: NULL desc / clips / src, n_clips < 1, an index outside [0, desc->B) or listed twice, N % hop != 0, N < hop (waveform
+ * mode: N < 0), b0 + n_clips > Bp, a missing or misaligned source pointer (c: 16 bytes; stft_ri, enh_ri: 8; the others: 4).
+ * SFSN_EUNSUPPORTED: a descriptor sfsn_stream_hop refuses, more than 256 listed clips (prime them in several calls). */
+typedef struct sfsn_prime_layer {
+    const int8_t* spikes_i8; /* [N][Bp * n_units][pad64(H)] the layer's int8 spikes of the prefix (bytes 0 / 1) */
+    const float* c;          /* [Bp * n_units][H] its membrane after frame N - 1 (c_state)                      */
+} sfsn_prime_layer;
+typedef struct sfsn_prime_seq {
+    sfsn_prime_layer layer[SFSN_HOP_MAX_LAYERS];
+    const float* cum;        /* SFSN_NORM_CUMLAPLACE: [Bp * n_units] the running sums after frame N - 1; NULL otherwise */
+} sfsn_prime_seq;
+typedef struct sfsn_prime_src {
+    int Bp, N, b0;
+    const float* stft_ri;    /* [Bp][F][N][2] the noisy prefix (NULL if D == 0 or N == 0)                     */
+    const float* enh_ri;     /* waveform mode: [Bp][S][F][N][2] the enhanced prefix (NULL if N == 0)           */
+    const float* wave_tail;  /* waveform mode: [Bp][512] the last 512 input samples, zeros in front of a shorter input */
+    sfsn_prime_seq fb;
+    sfsn_prime_seq sb[SFSN_HOP_MAX_GROUPS];
+} sfsn_prime_src;
+int sfsn_hop_prime(const sfsn_hop_desc* desc /* host */, const int* clips /* host */, int n_clips, const sfsn_prime_src* src /* host */,
+                   void* stream);
+
 /* ----------------------------------------------------------------------------------------------------
  * Spike counts -- the only thing the reference's energy proxy reads from the spike tensors:
  * compute_synops (audiozen/metric.py:303-327) uses torch.gt(layer_output, 0).float().mean() per layer.  Counting the

@@ -107,6 +107,19 @@ class HopDesc(ctypes.Structure):
                 ("clip_start", _P), ("spike_slots", _P)]
 
 
+class PrimeLayer(ctypes.Structure):  # sfsn_prime_layer
+    _fields_ = [("spikes_i8", _P), ("c", _P)]
+
+
+class PrimeSeq(ctypes.Structure):  # sfsn_prime_seq
+    _fields_ = [("layer", PrimeLayer * HOP_MAX_LAYERS), ("cum", _P)]
+
+
+class PrimeSrc(ctypes.Structure):  # sfsn_prime_src
+    _fields_ = [("Bp", _I), ("N", _I), ("b0", _I), ("stft_ri", _P), ("enh_ri", _P), ("wave_tail", _P), ("fb", PrimeSeq),
+                ("sb", PrimeSeq * HOP_MAX_GROUPS)]
+
+
 FULLBAND_HOP_MAX_LAYERS = 4
 
 
@@ -132,7 +145,7 @@ def _sources():
     """The files the library is made of, in the order the Makefile hashes them (SRCS)."""
     return [os.path.join(_HERE, "..", "include", "sfsn.h")] + [
         os.path.join(CSRC, f) for f in ("sfsn_scan_dev.h", "sfsn_scan3_dev.h", "sfsn_scan3i_dev.h", "sfsn_scan3x_dev.h", "sfsn_scan3w_dev.h", "sfsn_scan3j_dev.h", "sfsn_scan3g_dev.h", "sfsn_feat_dev.h", "sfsn_fft_dev.h", "sfsn_hop_dev.h", "sfsn_hop_wave_dev.h", "sfsn_fullband_dev.h", "sfsn_host.h", "sfsn_scan_host.h", "sfsn_kernels.hip", "sfsn_stack.hip", "sfsn_hop.hip", "sfsn_fft.hip", "sfsn_train.hip",
-                                  "sfsn_featproj.hip", "sfsn_projdf.hip", "sfsn_fullband.hip", "sfsn_fullband_train.hip", "sfsn_fullband_hop.hip", "sfsn_loss.hip", "sfsn_pit.hip", "sfsn_ragged.hip", "sfsn_pair16.hip", "sfsn_pack.cpp")]
+                                  "sfsn_featproj.hip", "sfsn_projdf.hip", "sfsn_fullband.hip", "sfsn_fullband_train.hip", "sfsn_fullband_hop.hip", "sfsn_loss.hip", "sfsn_pit.hip", "sfsn_ragged.hip", "sfsn_pair16.hip", "sfsn_prime.hip", "sfsn_pack.cpp")]
 
 
 def source_hash() -> str:
@@ -275,6 +288,8 @@ def lib() -> ctypes.CDLL:
     L.sfsn_hop_stages.argtypes = [ctypes.POINTER(HopDesc), ctypes.POINTER(_I), _I]
     L.sfsn_stream_hop.restype = _I
     L.sfsn_stream_hop.argtypes = [ctypes.POINTER(HopDesc), _P]
+    L.sfsn_hop_prime.restype = _I
+    L.sfsn_hop_prime.argtypes = [ctypes.POINTER(HopDesc), ctypes.POINTER(_I), _I, ctypes.POINTER(PrimeSrc), _P]
     L.sfsn_stream_hop_resident.restype = _I
     L.sfsn_stream_hop_resident.argtypes = [ctypes.POINTER(HopDesc), _P, ctypes.c_uint, _P]
     L.sfsn_spike_count.restype = _I
@@ -360,7 +375,7 @@ EXPORTS = ("sfsn_abi_version", "sfsn_source_hash", "sfsn_strerror", "sfsn_device
            "sfsn_pit_sdr_scratch_bytes", "sfsn_pit_sdr", "sfsn_stft_ragged", "sfsn_istft_ragged", "sfsn_laplace_means_ragged",
            "sfsn_gaussian_stats_ragged", "sfsn_spike_count_rows_ragged", "sfsn_zero_tail_frames", "sfsn_gsn_layer_scan_l0",
            "sfsn_pit_sdr_ragged", "sfsn_gsn_layer_scan_l01", "sfsn_recipe_loss_ragged_scratch_bytes", "sfsn_recipe_loss_ragged",
-           "sfsn_fullband_proj_deepfilter_ragged")
+           "sfsn_fullband_proj_deepfilter_ragged", "sfsn_hop_prime")
 
 
 def check(rc: int, what: str = "") -> None:

@@ -600,6 +600,7 @@ class Engine:
         # meta tensor, like the feature rows a fused feature launch skips.  Off by default: `layer_outputs = "counts"` promises the
         # projection tensor (tests).  bench.py's no-layer-outputs leg switches it on and says so.
         self.lean_skips_proj = os.environ.get("SFSN_LEAN_SKIP_PROJ", "0") == "1"
+        self._l0_hop = None  # set around a forward by StreamingSession.prime (per-kernel tier): see _stage_input
         self.count_in_scan = os.environ.get("SFSN_COUNT_IN_SCAN", "1") != "0"  # layer_outputs="counts": counted by the scans themselves
         self.pair_scan = os.environ.get("SFSN_PAIR_SCAN", "1") != "0"  # H <= 224 stacks as one launch of FUSED3 roles (see _stack_choice)
         # layer 0 of the per-layer path at 16 rows per workgroup: the fused-x groups and the groups with an input term in ONE launch
@@ -734,6 +735,18 @@ class Engine:
                     else:
                         pk, dq = cell.w_ih_q[g]
                         jobs.append((src.data_ptr() + t0 * R * src.shape[2], pk.data_ptr(), dq.data_ptr(), bp, zp, M, H, H, G * H))
+            if l == 0 and self._l0_hop is not None:
+                # (StreamingSession.prime, per-kernel tier) the real-valued product in the form a streaming step takes: below 64 rows
+                # sfsn_input_proj_f32 adds the chunks into one accumulator, from 64 rows on it takes the bf16 split -- another rounding
+                # (include/sfsn.h).  Whole frames per call, fewer than 64 rows each: the step's bits at a fraction of its launches.
+                P = ctypes.c_void_p
+                for (a_, w_, _, b_, z_, M, K, N, ld), src in zip(jobs, [s_ for s_ in srcs for _ in range(seqs[0].cells[0].G)]):
+                    R = src.shape[1]
+                    step = self._l0_hop * R if self._l0_hop * R >= 64 else 63 // R * R  # (64 rows and more: the step's own call)
+                    for r0 in range(0, M, step):
+                        check(L.sfsn_input_proj_f32(P(a_ + r0 * K * 4), P(w_), P(b_), P(z_ + r0 * ld * 4), min(step, M - r0), K, N, ld, st),
+                              "sfsn_input_proj_f32")
+                return
             if self.merge_products and 1 < len(jobs) <= _lib.MAX_SEGMENTS:
                 # the products of a stage in ONE launch (a block range per job, every job its own tiling: the same results)
                 if l == 0:
@@ -1252,8 +1265,11 @@ class Engine:
 
     def forward_stft(self, stft: torch.Tensor, want_layers: bool = True, want_membrane: bool = False, pipeline: Optional[bool] = None,
                      want_counts: bool = False, norm_stats: Optional[NormStats] = None, return_norm_stats: bool = False,
-                     frames=None, frames_dev: Optional[torch.Tensor] = None) -> dict:
+                     frames=None, frames_dev: Optional[torch.Tensor] = None, _end_state: bool = False) -> dict:
         """See ``_forward_stft``; runs with this engine's device current (the C ABI launches on the calling thread's device).
+
+        ``_end_state`` (internal: ``StreamingSession.prime``) -- the result also carries ``"end_state"``, what the forward leaves behind
+        its last frame (``_end_state_of``); not with ``frames``.
 
         ``frames`` -- a ragged batch (``ragged.py``): a length-B sequence of ints, clip b has ``frames[b]`` frames
         (``1 <= frames[b] <= T``; ``ValueError`` otherwise) and the rest of its row is padding.  The launches of the model are the
@@ -1270,13 +1286,15 @@ class Engine:
             raise ValueError("return_norm_stats: this model computes no utterance statistics")
         if frames is not None:
             from . import ragged
+            if _end_state:
+                raise ValueError("_end_state: not with a ragged batch (the clips end at different frames)")
             frames = ragged.check_frames(frames, stft.shape[0] if stft.dim() == 3 else -1, stft.shape[-1],
                                          gaussian=self.spec.gaussian and norm_stats is None)
         with torch.cuda.device(self.device):
             self._errors.poll()
             if frames is not None and frames_dev is None:
                 frames_dev = ragged.upload(frames, self.device)
-            out = self._forward_stft(stft, want_layers, want_membrane, pipeline, want_counts, norm_stats, frames, frames_dev)
+            out = self._forward_stft(stft, want_layers, want_membrane, pipeline, want_counts, norm_stats, frames, frames_dev, _end_state)
             if return_norm_stats:
                 out["norm_stats"] = NormStats(out["mu_fb"][0], out["mu_sb"], None if out["sd_fb"] is None else out["sd_fb"][0],
                                               out["sd_sb"]).clone()
@@ -1294,7 +1312,8 @@ class Engine:
             return out
 
     def _forward_stft(self, stft: torch.Tensor, want_layers: bool = True, want_membrane: bool = False, pipeline: Optional[bool] = None,
-                      want_counts: bool = False, norm_stats: Optional[NormStats] = None, frames=None, frames_dev=None) -> dict:
+                      want_counts: bool = False, norm_stats: Optional[NormStats] = None, frames=None, frames_dev=None,
+                      end_state: bool = False) -> dict:
         """complex64 [B, n_fft/2+1, T] on the device -> dict(enh_stft [B,S,F,T] complex64, enh_mag [B,S,F,T],
         fb_all, sb_all (the reference's all_layer_outputs lists; spike entries are None when want_layers=False)).
 
@@ -1340,7 +1359,35 @@ class Engine:
             self._zero_tail(f)
         if want_counts and not want_layers:
             self._summaries(f)
-        return self._result(f)
+        out = self._result(f)
+        if end_state:
+            out["end_state"] = self._end_state_of(f, want_counts)
+        return out
+
+    def _end_state_of(self, f: _Forward, want_counts: bool) -> dict:
+        """What a forward leaves behind its last frame, for a streaming session that goes on from there (``StreamingSession.prime``):
+        ``fb`` / ``sb``: ``states[l][i] = (h, c)`` of layer l, sequence model i after the last frame (the ABI's h_state / c_state) and
+        ``s8[l][i]`` the int8 spikes of every frame [T, R, pad64(H)] (row T - 1: the last frame's); ``cum``: the running sums of
+        cumulative_laplace_norm per sequence model (full-band first), else None; ``counts``: with ``want_counts`` the spikes per
+        (layer, clip), int64 [fb layers + groups x sb layers, B] in ``spike_summary``'s order, else None.  The states and the spikes
+        are the forward's own buffers, in stream order: the spikes are valid until the next forward on this stream."""
+        spec, fb, sb = self.spec, f.fbm.d, f.sbm.d
+        ng, nl_fb, nl_sb = spec.n_groups, spec.fb_layers, spec.sb_layers
+        counts = None
+        if want_counts:
+            T, B = f.fbm.xs[0].shape[:2]
+            tens = [(fb["s8"][l][0], 1) for l in range(nl_fb)] + [(sb["s8"][l][g], spec.units(g)) for g in range(ng) for l in range(nl_sb)]
+            counts = torch.zeros((len(tens), B), dtype=torch.int64, device=self.device)
+            hm = self._handle(f.main)
+            for i0 in range(0, len(tens), _lib.MAX_COUNT_TENSORS):
+                part = tens[i0:i0 + _lib.MAX_COUNT_TENSORS]
+                arr = (RowCount * len(part))()
+                for j, (t, rpc) in enumerate(part):
+                    arr[j].spikes_i8, arr[j].T, arr[j].R, arr[j].HP, arr[j].rows_per_clip = t.data_ptr(), t.shape[0], t.shape[1], t.shape[2], rpc
+                    arr[j].counts = counts.data_ptr() + 8 * (i0 + j) * B
+                check(self.lib.sfsn_spike_count_rows(arr, len(part), 0, T, hm), "sfsn_spike_count_rows")
+        return dict(fb=dict(states=fb["states"], s8=fb["s8"]), sb=dict(states=sb["states"], s8=sb["s8"]),
+                    cum=None if f.cum is None else f.cum["state"], counts=counts)
 
     def _validate(self, stft):
         """(B, F, T) of a forward's input, or the error that says what is wrong with it."""
@@ -1469,7 +1516,7 @@ class Engine:
         z = None
         if m.tag == "fb":
             z, f.zero = f.zero, None  # (the first full-band feature launch of the forward carries the state zeroing)
-        if f.cum is None and self._stage_featproj(m.fg, m.seqs, proj[0], proj[1], f.ri, m.fb_proj, m.dims, t0, nt, z, f.want_layers, st, m.tag):
+        if f.cum is None and self._l0_hop is None and self._stage_featproj(m.fg, m.seqs, proj[0], proj[1], f.ri, m.fb_proj, m.dims, t0, nt, z, f.want_layers, st, m.tag):
             if not f.want_layers:  # feature rows a fused launch did not write (layer_outputs "counts" / "none": nobody reads them)
                 f.x_skipped[m.tag].update(proj[0])
             return True
@@ -1505,7 +1552,7 @@ class Engine:
         """One model over every chunk of the forward.  gate_events: per chunk, what its first launch waits for (the full-band model's
         chunk, on the staged schedules).  Returns the per-chunk completion events (staged schedules; else empty)."""
         use_stack, wide, rpw_stack = self._stack_choice(m.seqs, [x.shape[1] for x in m.xs], f.want_membrane)
-        if not f.plan.pipeline and use_stack:
+        if not f.plan.pipeline and use_stack and self._l0_hop is None:
             return self._run_model_stack(f, m, gate_events, wide, rpw_stack)
         return self._run_model_layers(f, m, gate_events)
 
@@ -1533,11 +1580,11 @@ class Engine:
         fused = self._fusable(seqs, rpw, f.want_membrane)
         done = []
         # layer 0: groups whose real-valued input product can run inside the scan / the rest (input product first)
-        fx = [i for i in range(len(seqs)) if self._fusable_x(seqs[i], xs_[i], rpw, f.want_membrane)]
+        fx = [i for i in range(len(seqs)) if self._l0_hop is None and self._fusable_x(seqs[i], xs_[i], rpw, f.want_membrane)]
         rest = [i for i in range(len(seqs)) if i not in fx]
         # layers 0 and 1 of a two-layer stack at 16 rows in one launch (the staged schedules and graph capture keep the per-layer launches)
         pair = bool(self.pair16 and self.merge_layer0 and nl == 2 and rpw == 16 and fused and not staged
-                    and not torch.cuda.is_current_stream_capturing())
+                    and not torch.cuda.is_current_stream_capturing() and self._l0_hop is None)
         for c, (t0, nt) in enumerate(f.plan.bounds):
             paired = False
             for l in range(nl):

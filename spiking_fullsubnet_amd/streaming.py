@@ -29,6 +29,12 @@ bit for bit.  The one-launch hop gives every clip its own origin (``sfsn_hop_des
 began) and reads a restarted clip's state as zero in that launch -- no synchronisation, and a resident launch keeps running.  The
 per-kernel sequence zeroes the clips' rows of the states and the history with stream-ordered fills.
 
+Priming: ``prime(stft, clips)`` / ``prime_wave(samples, clips)`` start the listed clips' utterances from a RECORDED prefix instead of
+from silence (a clip joining mid-call, a seek, a reconnect, a backlog).  The prefix runs on the offline kernels
+(``Engine.forward_stft(..., _end_state=True)``); the one-launch hop takes its end state in one launch (``sfsn_hop_prime``,
+csrc/sfsn_prime.hip) and the clips' origins move back by the prefix's launches, so that the next hop continues at frame N; the
+per-kernel sequence takes it as stream-ordered row copies into its states, history and counts.  Not for resident sessions.
+
 Spike counts: a session opened with ``count_spikes=True`` counts every layer's spikes per clip as it runs, and
 ``spike_summary(clips)`` returns them in the form of the offline forward's ``layer_outputs="counts"`` lists, so that
 ``metric.compute_synops`` / ``compute_neuronops`` give each clip's current utterance's SynOPs and NeuronOPs.  The one-launch hop
@@ -46,7 +52,7 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from ._lib import DfGroup, HopDesc, HOP_MAX_GROUPS, HOP_MAX_LAYERS, MAX_COUNT_TENSORS, NORM_CUMLAPLACE, RowCount, check
+from ._lib import DfGroup, HopDesc, HOP_MAX_GROUPS, HOP_MAX_LAYERS, MAX_COUNT_TENSORS, NORM_CUMLAPLACE, PrimeSrc, RowCount, check
 from .engine import Engine, NormStats, SpikeSummary, _ptr
 
 
@@ -131,6 +137,7 @@ class StreamingSession:
         self._hop = None
         self.waveform = bool(waveform)  # step_wave(): samples in, samples out (STFT and inverse STFT inside the launch)
         self._wave_calls = 0
+        self._primed = False  # prime_wave() has run: the clips' own frame indices decide what a call returns (see step_wave)
         self.host_io = bool(host_io)  # waveform mode: samples come from and go to (pinned) host memory, no copy launches
         if self.host_io and not waveform:
             raise ValueError("host_io goes with waveform=True")
@@ -421,6 +428,7 @@ class StreamingSession:
             if self.resident:
                 self._hop["host"]["origin_np"][:] = self._hop["parts"][0]["desc"].launch_index  # (the kernel has ended)
             self._wave_calls = 0
+            self._primed = False
         if self._rows is not None:
             self._rows.zero_()
         self.frames_done = 0
@@ -511,6 +519,206 @@ class StreamingSession:
             for i in mine:  # (a fill behind the queued launches: none of them sees the new origin)
                 part["origin"][i:i + 1].fill_(self._as_i32(org))
             part["desc"].clip_start = part["origin"].data_ptr()  # from now on the launches take the clips' own origins
+
+    # ---- priming: a recorded prefix through the offline kernels, its end state into the session ---------------------------------
+    def _prime_clips(self, clips, n_given: int):
+        """(clip indices in the caller's order, the permutation that sorts them or None) of a prime call; checked like
+        set_norm_stats' clips."""
+        if clips is None:
+            idx = list(range(self.B))
+        else:
+            if isinstance(clips, (torch.Tensor, np.ndarray)) and clips.ndim != 1:
+                raise TypeError("clips: a 1-D tensor or a sequence of clip indices")
+            items = clips.tolist() if isinstance(clips, (torch.Tensor, np.ndarray)) else list(clips)
+            if any(isinstance(i, bool) or not isinstance(i, (int, np.integer)) for i in items):
+                raise TypeError("clips: integer clip indices")
+            idx = [int(i) for i in items]
+            bad = [i for i in idx if not 0 <= i < self.B]
+            if bad:
+                raise IndexError(f"clip index {bad[0]} out of range for a session of {self.B} clips")
+            if len(set(idx)) != len(idx):
+                raise ValueError("prime: clip indices must be distinct")
+            if not idx:
+                raise ValueError("prime: no clip selected")
+        if n_given != len(idx):
+            raise RuntimeError(f"prime: a prefix of {n_given} clips for {len(idx)} clip indices")
+        order = sorted(range(len(idx)), key=idx.__getitem__)
+        return idx, (None if order == list(range(len(idx))) else order)
+
+    @staticmethod
+    def _runs(local):
+        """Ascending indices as (first, count) runs of consecutive ones (one stream-ordered fill / copy per run)."""
+        runs = []
+        for i in local:
+            if runs and runs[-1][0] + runs[-1][1] == i:
+                runs[-1][1] += 1
+            else:
+                runs.append([i, 1])
+        return runs
+
+    def _prime_sorted(self, stft, idx, tail=None):
+        """The transplant.  ``stft``: complex64 [len(idx), F, N] contiguous, or None (waveform mode, no frame yet); ``idx`` ascending;
+        ``tail``: waveform mode, float32 [len(idx), 512].  Returns the prefix's forward (None without frames).  Everything on torch's
+        current stream."""
+        eng, spec = self.eng, self.eng.spec
+        n, N, hop, ng = len(idx), (0 if stft is None else stft.shape[-1]), self.hop, spec.n_groups
+        out = es = None
+        if N:
+            ns = None if self._stats is None else (self._stats if n == self.B else self._stats.select(idx))
+            # (the per-kernel sequence's layer-0 membranes are those of ITS input product, the form below 64 rows: the prefix takes it too)
+            eng._l0_hop = hop if self._hop is None else None
+            try:
+                out = eng.forward_stft(stft, want_layers=False, want_counts=self._rows is not None, norm_stats=ns, _end_state=True)
+            finally:
+                eng._l0_hop = None
+            es = out["end_state"]
+        units = [1] + [spec.units(g) for g in range(ng)]
+        if self._hop is None:
+            # the per-kernel sequence: row copies into the states, the history and the counts the (captured) launches read and write
+            for d, e, us in ((self.fb, es["fb"], units[:1]), (self.sb, es["sb"], units[1:])):
+                for mine, theirs in zip(d["states"], e["states"]):
+                    for (h, c), (hs, cs), u in zip(mine, theirs, us):
+                        j0 = 0  # (idx ascends: a run of consecutive clips is a run of consecutive rows on both sides)
+                        for b0, m in self._runs(idx):
+                            h[b0 * u:(b0 + m) * u].copy_(hs[j0 * u:(j0 + m) * u])
+                            c[b0 * u:(b0 + m) * u].copy_(cs[j0 * u:(j0 + m) * u])
+                            j0 += m
+            Th = self.Th
+            for j, b in enumerate(idx):  # the last D + hop frames, zeros in front of a shorter prefix
+                if N >= Th:
+                    self.hist[b].copy_(stft[j, :, N - Th:])
+                else:
+                    self.hist[b, :, :Th - N].zero_()
+                    self.hist[b, :, Th - N:].copy_(stft[j])
+                if self._rows is not None:
+                    self._rows[:, b].copy_(es["counts"][:, j])
+            return out
+        L = eng.lib
+        st = ctypes.c_void_p(_raw_stream(self._dev_index))
+        src = PrimeSrc()
+        src.Bp, src.N = n, N
+        if N:
+            src.stft_ri = torch.view_as_real(stft).data_ptr()
+            src.enh_ri = torch.view_as_real(out["enh_stft"]).data_ptr()
+            for dst, e, gi in [(src.fb, es["fb"], 0)] + [(src.sb[g], es["sb"], g) for g in range(ng)]:
+                for l in range(len(e["s8"])):
+                    dst.layer[l].spikes_i8, dst.layer[l].c = e["s8"][l][gi].data_ptr(), e["states"][l][gi][1].data_ptr()
+            if es["cum"] is not None:
+                src.fb.cum = es["cum"][0].data_ptr()
+                for g in range(ng):
+                    src.sb[g].cum = es["cum"][1 + g].data_ptr()
+        if tail is not None:
+            src.wave_tail = tail.data_ptr()
+        for part in self._hop["parts"]:
+            pos = [j for j, b in enumerate(idx) if part["b0"] <= b < part["b0"] + part["nb"]]
+            if not pos:
+                continue
+            d = part["desc"]
+            # the clips' origin: launch_index is the next launch, which gives them frame index N / hop.  (N = 0, a waveform clip
+            # whose first call has made no frame: the origin IS the next launch, which reads the state as zero -- as it must -- and
+            # the samples from wave_state, which no origin makes it skip)
+            org = self._as_i32(d.launch_index - N // hop)
+            for j0 in range(0, len(pos), 256):  # (the launch takes 256 clip indices in its arguments)
+                local = [idx[j] - part["b0"] for j in pos[j0:j0 + 256]]
+                src.b0 = pos[j0]
+                arr = (ctypes.c_int * len(local))(*local)
+                with torch.cuda.device(self.dev):
+                    rc = L.sfsn_hop_prime(part["ref"], arr, len(local), ctypes.byref(src), st)
+                if rc:
+                    check(rc, "sfsn_hop_prime")
+            for b0, m in self._runs([idx[j] - part["b0"] for j in pos]):  # (fills behind the queued launches, as in _reset_clips)
+                part["origin"][b0:b0 + m].fill_(org)
+            d.clip_start = part["origin"].data_ptr()
+        return out
+
+    def prime(self, stft: torch.Tensor, clips=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Start a new utterance on ``clips`` (``None``: every clip) whose first ``N`` frames are the recorded prefix ``stft`` --
+        complex64 [len(clips), F, N] on the device, row i for ``clips[i]`` -- at the speed of the offline forward instead of
+        ``N / hop`` calls of ``step``.  Returns the prefix's ``(enh_stft [.., S, F, N], enh_mag)``; the next ``step`` continues as if
+        the prefix had been streamed: bit for bit in the per-kernel tier, and in the one-launch tier with that tier's one
+        reservation (layer 0's membranes are the offline forward's, which differ from the hop's in their low bits -- include/sfsn.h).
+        Whatever state the clips held is replaced; the other clips go on untouched.  ``N`` is a multiple of ``hop``, at least
+        ``hop`` (``ValueError``): a clip's origin is a launch index.  A frozen model with an offline norm runs the prefix with the
+        session's current statistics of those clips.  Ordered on torch's current stream, no synchronisation, like
+        ``reset(clips=...)``.  Not on resident sessions (``NotImplementedError``); every listed clip gets the same ``N``."""
+        if self.resident:
+            raise NotImplementedError("prime: not on a resident session (resident=True): its launch holds the state while it runs")
+        if self.waveform:
+            raise RuntimeError("this session was opened with waveform=True: use prime_wave(samples)")
+        idx, order = self._prime_clips(clips, stft.shape[0] if isinstance(stft, torch.Tensor) and stft.dim() == 3 else -1)
+        if stft.device != self.dev or stft.dtype != torch.complex64 or stft.shape[1] != self.F:
+            raise RuntimeError(f"expected complex64 {(len(idx), self.F, 'N')} on {self.dev}, got {stft.dtype} {tuple(stft.shape)} on {stft.device}")
+        N = stft.shape[2]
+        if N < self.hop or N % self.hop != 0:
+            raise ValueError(f"prime: {N} frames is not a positive multiple of the session's hop ({self.hop})")
+        perm = None
+        if order is not None:
+            perm = torch.tensor(order, dtype=torch.long).to(self.dev, non_blocking=True)
+            stft, idx = stft.index_select(0, perm), [idx[j] for j in order]
+        out = self._prime_sorted(stft.contiguous(), idx)
+        if clips is None:  # the whole session: as after reset() and N frames of step()
+            self.frames_done = N
+            self._clip_f0[:] = 0
+        else:
+            self._clip_f0[idx] = self.frames_done - N
+        enh, mag = out["enh_stft"], out["enh_mag"]
+        if perm is not None:
+            inv = torch.empty_like(perm)
+            inv[perm] = torch.arange(len(order), device=self.dev)
+            enh, mag = enh.index_select(0, inv), mag.index_select(0, inv)
+        return enh, mag
+
+    def prime_wave(self, samples: torch.Tensor, clips=None) -> torch.Tensor:
+        """``prime`` for waveform sessions (``host_io`` included; device tensors in and out): ``samples`` float32
+        [len(clips), 128 * c], ``c >= 1`` calls' worth.  Returns [.., S, 128 * c], the concatenation of what ``c`` calls of
+        ``step_wave`` would have returned (the first three blocks are zero).  The prefix has the frames ``0 .. c - 2``: the two
+        further frames torch.stft(center=True) makes of these samples look into samples not yet heard and are not used; ``c = 1``
+        has no frame, its samples only enter the STFT state."""
+        if self.resident:
+            raise NotImplementedError("prime_wave: not on a resident session (resident=True): its launch holds the state while it runs")
+        if not self.waveform:
+            raise RuntimeError("open the session with waveform=True")
+        idx, order = self._prime_clips(clips, samples.shape[0] if isinstance(samples, torch.Tensor) and samples.dim() == 2 else -1)
+        if samples.device != self.dev or samples.dtype != torch.float32:
+            raise RuntimeError(f"expected float32 {(len(idx), '128 * c')} on {self.dev}, got {samples.dtype} {tuple(samples.shape)} on {samples.device}")
+        Ls = samples.shape[1]
+        if Ls < 128 or Ls % 128 != 0:
+            raise ValueError(f"prime_wave: {Ls} samples is not a positive multiple of 128")
+        from . import spectral
+        c, n, S = Ls // 128, len(idx), self.eng.spec.num_spks
+        perm = None
+        if order is not None:
+            perm = torch.tensor(order, dtype=torch.long).to(self.dev, non_blocking=True)
+            samples, idx = samples.index_select(0, perm), [idx[j] for j in order]
+        samples = samples.contiguous()
+        tail = samples[:, -512:].contiguous() if Ls >= 512 else torch.nn.functional.pad(samples, (512 - Ls, 0))
+        stft = spectral.stft(samples, 512, 128)[:, :, :c - 1].contiguous() if c > 1 else None  # frames 0 .. c - 2 (see above)
+        out = self._prime_sorted(stft, idx, tail=tail)
+        res = torch.zeros((n, S, Ls), dtype=torch.float32, device=self.dev)
+        if c > 3:  # calls 3 .. c - 1 return samples [0, 128 (c - 3)): complete with frame c - 2, the last one the prefix has
+            res[:, :, 384:] = spectral.istft(out["enh_stft"].reshape(n * S, self.F, c - 1), 512, 128, length=128 * (c - 3)).view(n, S, -1)
+        if clips is None:  # the whole session: as after reset() and c calls of step_wave()
+            self._wave_calls, self.frames_done = c, c - 1
+            self._clip_c0[:] = 0
+        else:
+            if self._wave_calls == 0:
+                # nobody has called yet, and the session's first call launches nothing: count it as made, with every other clip's
+                # utterance beginning at the next call (origin = the launch after the next: that launch is their first call)
+                self._wave_calls = 1
+                self._clip_c0[:] = 1
+                listed = set(idx)
+                for part in self._hop["parts"]:
+                    others = [b - part["b0"] for b in range(part["b0"], part["b0"] + part["nb"]) if b not in listed]
+                    for b0, m in self._runs(others):
+                        part["origin"][b0:b0 + m].fill_(self._as_i32(part["desc"].launch_index + 1))
+                    part["desc"].clip_start = part["origin"].data_ptr()
+            self._clip_c0[idx] = self._wave_calls - c
+        self._primed = True
+        if perm is not None:
+            inv = torch.empty_like(perm)
+            inv[perm] = torch.arange(len(order), device=self.dev)
+            res = res.index_select(0, inv)
+        return res
 
     @property
     def clip_frames(self) -> np.ndarray:
@@ -719,7 +927,7 @@ class StreamingSession:
                 part["st"]["state"][:, 384:].copy_(samples[part["b0"]:part["b0"] + part["nb"]])
             return torch.zeros_like(out)
         self._launch_hops(samples.data_ptr(), 128 * 4, "wave_in", frame_index=c - 1)
-        if c < 3:  # padded positions torch.istft trims
+        if c < 3 and not self._primed:  # padded positions torch.istft trims (primed clips: the launch mutes each clip by its own index)
             return torch.zeros_like(out)
         return out.clone() if copy else out
 
@@ -822,4 +1030,4 @@ class StreamingSession:
                 self._stop_resident()
                 self.check_errors()
                 target = self._ring_resident(c) & 0xFFFFFFFF
-        return torch.zeros_like(host["out"]) if c < 3 else host["out"]
+        return torch.zeros_like(host["out"]) if c < 3 and not self._primed else host["out"]
