@@ -485,6 +485,23 @@ typedef struct sfsn_projdf_group {
 int sfsn_proj_deepfilter(const float* stft_ri /* [B][F][T][2] */, int B, int F, int T, int S, int H,
                          const sfsn_projdf_group* groups /* host */, int n_groups, float* enh_ri /* [B][S][F][T][2] */,
                          float* enh_mag /* [B][S][F][T], nullable */, int t0, int nt /* frames [t0, t0+nt) */, void* stream);
+/* sfsn_gsn_layer_scan_l01 AND sfsn_proj_deepfilter of the frames [t0, t0 + nt) in ONE launch: behind the workgroups of the two layers
+ * a few epilogue workgroups follow layer 1 a 16-frame tile or two behind (layer 1 publishes its int8 rows as layer 0 does; the epilogue
+ * polls the counters of the layer-1 workgroups that hold its clips' rows).  Bit-identical to the two calls.
+ *   The scan lists are those of sfsn_gsn_layer_scan_l01 with T = nt: their tensors start at frame t0.  The groups, the spectra and
+ *   t0 / nt are those of sfsn_proj_deepfilter: their tensors start at frame 0 of the sequence, so for every group there must be one
+ *   layer-1 segment with R = B * n_units and spikes_i8 = groups[i].spikes_i8 + t0 * R * pad64(H), and n_groups = n_x + n_z
+ *   (SFSN_EINVAL otherwise).  Each list is checked as its own entry point checks it (x, z, layer 1, groups), then the ties.
+ *   SFSN_EUNSUPPORTED wherever one of the two entry points refuses, and where a group's P = 2*fc*df*S exceeds 192.
+ *   nt = 0: SFSN_OK, nothing launched.  scratch, lag, error word: as for sfsn_gsn_layer_scan_l01 (the same size function).
+ *   The environment variable SFSN_L01E_WGS sets the number of epilogue workgroups (dealt over the groups by the bytes they move, at
+ *   least one per job and at most one per clip). */
+int sfsn_gsn_layer_scan_l01_projdf(const sfsn_scan_segment* segs_x /* host */, const sfsn_fused_x* fin_x /* host */, int n_x,
+                                   const sfsn_scan_segment* segs_z /* host */, int n_z, const sfsn_scan_segment* segs1 /* host */,
+                                   const sfsn_fused_input* fin1 /* host */, int H, int shared, int lag, void* scratch,
+                                   size_t scratch_bytes, const float* stft_ri /* [B][F][T][2] */, int B, int F, int T, int S,
+                                   const sfsn_projdf_group* groups /* host */, int n_groups, float* enh_ri /* [B][S][F][T][2] */,
+                                   float* enh_mag /* [B][S][F][T], nullable */, int t0, int nt, void* stream);
 
 /* ----------------------------------------------------------------------------------------------------
  * Streaming sessions (BASELINE configs[4]): the input history the deep filter reaches back into (MODEL:331-333: df - 1 frames

@@ -6,7 +6,8 @@
 The region is taken as every dispatch from the start of the `--forwards`-last `gsn_stack_fb_kernel` on (one per forward).  Printed, as
 one JSON object: the region's length and dispatch count, the queues and streams seen, kernels running at once and the resident scan
 workgroups (summed grids of the running `gsn_scan*` / `gsn_stack*` kernels, one workgroup per CU, as a share of 256 CUs) over the
-inner 80 % of the region, time-weighted; the chain of one forward (a stream's dispatches up to and including a `projdf_kernel`, first
+inner 80 % of the region, time-weighted; the chain of one forward (a stream's dispatches up to and including a `projdf_kernel` or,
+where the epilogue runs inside the scan launch, a `gsn_scan_l01e_kernel`, first
 start to last end, and the sum of its spans), median over the forwards that lie inside the region; the median span per kernel.
 Reads the file only."""
 import argparse
@@ -82,7 +83,7 @@ def main():
         cur = []
         for r in (r for r in reg if r["s"] == s):
             cur.append(r)
-            if r["name"].startswith("projdf_kernel"):
+            if r["name"].startswith(("projdf_kernel", "gsn_scan_l01e_kernel")):  # (a forward's last launch, either way)
                 if any(x["name"].startswith("gsn_stack_fb_kernel") for x in cur) and cur[0]["name"].startswith("features_kernel"):
                     chains.append((max(x["t1"] for x in cur) - cur[0]["t0"]) / 1e3)
                     sums.append(sum(x["t1"] - x["t0"] for x in cur) / 1e3)

@@ -145,7 +145,7 @@ def _sources():
     """The files the library is made of, in the order the Makefile hashes them (SRCS)."""
     return [os.path.join(_HERE, "..", "include", "sfsn.h")] + [
         os.path.join(CSRC, f) for f in ("sfsn_scan_dev.h", "sfsn_scan3_dev.h", "sfsn_scan3i_dev.h", "sfsn_scan3x_dev.h", "sfsn_scan3w_dev.h", "sfsn_scan3j_dev.h", "sfsn_scan3g_dev.h", "sfsn_feat_dev.h", "sfsn_fft_dev.h", "sfsn_hop_dev.h", "sfsn_hop_wave_dev.h", "sfsn_fullband_dev.h", "sfsn_host.h", "sfsn_scan_host.h", "sfsn_kernels.hip", "sfsn_stack.hip", "sfsn_hop.hip", "sfsn_fft.hip", "sfsn_train.hip",
-                                  "sfsn_featproj.hip", "sfsn_projdf.hip", "sfsn_fullband.hip", "sfsn_fullband_train.hip", "sfsn_fullband_hop.hip", "sfsn_loss.hip", "sfsn_pit.hip", "sfsn_ragged.hip", "sfsn_pair16.hip", "sfsn_prime.hip", "sfsn_pack.cpp")]
+                                  "sfsn_featproj.hip", "sfsn_projdf.hip", "sfsn_fullband.hip", "sfsn_fullband_train.hip", "sfsn_fullband_hop.hip", "sfsn_loss.hip", "sfsn_pit.hip", "sfsn_ragged.hip", "sfsn_pair16.hip", "sfsn_pair16e.hip", "sfsn_prime.hip", "sfsn_pack.cpp")]
 
 
 def source_hash() -> str:
@@ -240,6 +240,12 @@ def lib() -> ctypes.CDLL:
     L.sfsn_gsn_layer_scan_l01.restype = _I  # segs_x, fin_x, n_x | segs_z, n_z | segs1, fin1 | T, H, shared, lag | scratch, scratch_bytes, stream
     L.sfsn_gsn_layer_scan_l01.argtypes = [ctypes.POINTER(ScanSegment), ctypes.POINTER(FusedX), _I, ctypes.POINTER(ScanSegment), _I,
                                           ctypes.POINTER(ScanSegment), ctypes.POINTER(FusedInput), _I, _I, _I, _I, _P, ctypes.c_size_t, _P]
+    # segs_x, fin_x, n_x | segs_z, n_z | segs1, fin1 | H, shared, lag | scratch, scratch_bytes | stft, B, F, T, S | groups, n_groups |
+    # enh_ri, enh_mag | t0, nt | stream
+    L.sfsn_gsn_layer_scan_l01_projdf.restype = _I
+    L.sfsn_gsn_layer_scan_l01_projdf.argtypes = [ctypes.POINTER(ScanSegment), ctypes.POINTER(FusedX), _I, ctypes.POINTER(ScanSegment), _I,
+                                                 ctypes.POINTER(ScanSegment), ctypes.POINTER(FusedInput), _I, _I, _I, _P, ctypes.c_size_t,
+                                                 _P, _I, _I, _I, _I, ctypes.POINTER(ProjDfGroup), _I, _P, _P, _I, _I, _P]
     L.sfsn_stack_scratch_bytes.restype = ctypes.c_size_t
     L.sfsn_stack_scratch_bytes.argtypes = [_I, _I, _I]
     L.sfsn_gsn_stack_scan.restype = _I
@@ -375,7 +381,7 @@ EXPORTS = ("sfsn_abi_version", "sfsn_source_hash", "sfsn_strerror", "sfsn_device
            "sfsn_pit_sdr_scratch_bytes", "sfsn_pit_sdr", "sfsn_stft_ragged", "sfsn_istft_ragged", "sfsn_laplace_means_ragged",
            "sfsn_gaussian_stats_ragged", "sfsn_spike_count_rows_ragged", "sfsn_zero_tail_frames", "sfsn_gsn_layer_scan_l0",
            "sfsn_pit_sdr_ragged", "sfsn_gsn_layer_scan_l01", "sfsn_recipe_loss_ragged_scratch_bytes", "sfsn_recipe_loss_ragged",
-           "sfsn_fullband_proj_deepfilter_ragged", "sfsn_hop_prime")
+           "sfsn_fullband_proj_deepfilter_ragged", "sfsn_hop_prime", "sfsn_gsn_layer_scan_l01_projdf")
 
 
 def check(rc: int, what: str = "") -> None:

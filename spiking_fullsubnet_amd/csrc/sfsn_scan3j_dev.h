@@ -190,7 +190,11 @@ struct Scan3jRole {
 // that is not yet known to be published (s3_ensure: relaxed agent-scope loads, s_sleep, bounded; the producer runs lk->lag frames ahead
 // between polls) and fetches with sc1 DMAs; the other waves wait at the step barrier as they do for any late frame.  An expired spin sets
 // the launch's error word and ends the gating: the launch finishes with garbage, the host reports it.  GATED = 0: today's code, lk unused.
-template <int KS, int TL, int OUT, int OFF = 0, bool GATED = false>
+// PUB = 1 (gsn_scan_l01e_kernel, sfsn_pair16e.hip): the int8 rows feed the epilogue workgroups of the SAME launch -- scan3y_role's
+// publishing storer (below): write-through stores, a counted wait, "frames < t - pf complete" in lk->out, T behind the last frame (also
+// after the loader's spin has expired: the storer never learns of it and nobody may wait for this workgroup).  Both the plain and the OFF
+// form; the fp32 stores (storer and loader share) stay plain, the compute waves are untouched.  PUB = 0: today's code.
+template <int KS, int TL, int OUT, int OFF = 0, bool GATED = false, bool PUB = false>
 __device__ __forceinline__ void scan3j_role(const Scan3jRole& rl, char* smem, int T, int H, int NT, const StackLink* lk = nullptr) {
     using C = Scan3jCfg<KS>;
     constexpr int RPW = 16, LDH = C::LDH, HP = C::HP, D = C::D, A = C::A, SLOT = C::SLOT, NP = C::NP, NCH = C::NCH;
@@ -428,7 +432,8 @@ __device__ __forceinline__ void scan3j_role(const Scan3jRole& rl, char* smem, in
             for (int k = 0; k < MAX8; ++k) {
                 if ((ok8 >> k) & 1u) {
                     const v4i d = *reinterpret_cast<const v4i*>(hsrc + l8[k]);
-                    *reinterpret_cast<v4i*>(p8 + (size_t)(64 * k + lane) * 16) = d;
+                    if constexpr (PUB) store16_sc1(p8, (unsigned)((64 * k + lane) * 16), d);
+                    else *reinterpret_cast<v4i*>(p8 + (size_t)(64 * k + lane) * 16) = d;
                     if constexpr (!(OUT & 1)) cnt += popc16(d);  // (live rows only; the pad columns of the state buffer hold zeros)
                 }
             }
@@ -436,6 +441,14 @@ __device__ __forceinline__ void scan3j_role(const Scan3jRole& rl, char* smem, in
         };
         S3jHelper<KS, TL> hp;
         if constexpr (OFF) hp.init(rl.w_ih, smem, NT, 13, lane);
+        // PUB: store instructions per frame with at least one live lane and the frames of my stores that may be in flight (scan3y_role's
+        // storer: my queue holds nothing but these stores -- the OFF form's input product reads LDS only -- and they retire in order)
+        int spf = 1, pf = 1;
+        if constexpr (PUB) {
+            const int rows_live = (R - row0 < RPW) ? R - row0 : RPW;
+            spf = (F32 ? ff.nsf : 0) + (rows_live * (HP / 16) + 63) / 64;
+            pf = 62 / spf < SFSN_S3_PFMAX ? 62 / spf : SFSN_S3_PFMAX;
+        }
         __syncthreads();
         __builtin_amdgcn_s_barrier();
         if constexpr (OFF) {
@@ -445,12 +458,22 @@ __device__ __forceinline__ void scan3j_role(const Scan3jRole& rl, char* smem, in
         }
 #pragma unroll 1
         for (int t = 0; t < T; ++t) {
-            if (t > 0) flush(hbuf + (t & 1) * 16 * LDH, t - 1);  // = h_{t-1}
+            if (t > 0) {
+                flush(hbuf + (t & 1) * 16 * LDH, t - 1);         // = h_{t-1}
+                if constexpr (PUB) {
+                    wait_vmcnt_n(pf * spf);                      // all but my youngest pf frames' stores have retired
+                    if (lane == 0 && t - pf > 0) stack_publish(*lk, t - pf);
+                }
+            }
             if constexpr (OFF) hp.run(smem, t + 1, PLANE);       // tile 13's input term of frame t + 1
             __builtin_amdgcn_s_waitcnt(0xc07f);                  // my LDS reads are done before the buffer is rewritten (step t + 1)
             __builtin_amdgcn_s_barrier();
         }
         if (T > 0) flush(hbuf + (T & 1) * 16 * LDH, T - 1);
+        if constexpr (PUB) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if (lane == 0) stack_publish(*lk, T);
+        }
         if constexpr (!(OUT & 1)) wave_count_add(rl.count, cnt);
         return;
     }

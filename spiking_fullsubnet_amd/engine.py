@@ -521,6 +521,7 @@ class _Forward:
     hG: list = field(default_factory=list)
     x_skipped: dict = field(default_factory=lambda: dict(fb=set(), sb=set()))  # feature rows a fused feature launch did not write
     proj_skipped: bool = False  # the fused epilogue ran and left the coefficient rows unwritten
+    epi_chunk: Optional[tuple] = None  # (t0, nt) of the sub-band chunk whose epilogue ran inside its scan launch (_stage_scan_l01)
 
     def link(self, src, dst) -> None:
         """dst waits for everything enqueued on src so far (no-op on the sequential path)."""
@@ -612,6 +613,13 @@ class Engine:
         # not on the staged schedules, which keep their per-layer launches.  SFSN_L01_PAIR=0 / 1 overrides the default.
         self.pair16 = os.environ.get("SFSN_L01_PAIR", "1") != "0"
         self._l01_refused = set()
+        # ... and the sub-band epilogue (sfsn_proj_deepfilter's work) as a third tier of workgroups of that launch
+        # (sfsn_gsn_layer_scan_l01_projdf: same results; the epilogue follows layer 1 a 16-frame tile or two behind and its launch leaves
+        # the forward's chain).  Taken only where the pair launch AND the one-launch epilogue would be taken.  ON by default: +2.1 % / +3.75 %
+        # on bench.py's timed region at four hardware queues, 16 of 16 pairs (profiles/l01_epilogue_one_launch.md).  SFSN_L01_PROJDF=0 / 1
+        # overrides the default.
+        self.pair16_epilogue = os.environ.get("SFSN_L01_PROJDF", "1") != "0"
+        self._l01e_refused = set()
         self.stack_rows_per_wg = dict(STACK_ROWS_PER_WG)  # rows per workgroup of every layer of a stack: sum of workgroups <= CUs
         # frames a consumer role that had to wait lets its producers run ahead before it resumes (the hand-offs' hysteresis).  Round 2: 16
         # (every wave of a workgroup stood in the poll); since the IO-wave roles one lane polls, and a launch ends lag + ring frames after
@@ -891,11 +899,13 @@ class Engine:
         self._count("l0_merged")  # ... inside the one launch: fused_x - l0_merged = the separate fused-x calls
         return True
 
-    def _stage_scan_l01(self, seqs, fx, rest, xs_, d, t0, nt, st, tag, cn=None) -> bool:
+    def _stage_scan_l01(self, seqs, fx, rest, xs_, d, t0, nt, st, tag, cn=None, epi=None) -> bool:
         """Layers 0 and 1 of a two-layer stack in ONE launch at 16 rows per workgroup (sfsn_gsn_layer_scan_l01): the layer-0 launch of
         _stage_scan_l0 (or the single call where `fx` or `rest` is empty) and _stage_scan_fused of layer 1 side by side, layer 1 trailing
         layer 0 by a few frames.  Scratch and error word as in _stage_stack.  False (nothing launched) where the library refuses; the
-        refusal is remembered per geometry."""
+        refusal is remembered per geometry.  `epi` (the forward and its sub-band model, where the chunk's epilogue may join the launch):
+        sfsn_gsn_layer_scan_l01_projdf with _stage_projdf's arguments; it notes the chunk in f.epi_chunk, and a refusal (remembered per
+        geometry) leaves today's launch."""
         L = self.lib
         H = seqs[0].H
         HP = (H + 63) // 64 * 64
@@ -930,9 +940,32 @@ class Engine:
         scratch = self._workspace(("l01_scratch", tag, len(order), rows, torch.cuda.current_stream(self.device).cuda_stream,
                                    self._tstream(st).cuda_stream), make)["t"]
         assert scratch.numel() * 4 >= nbytes
-        with self.timed("stack:" + tag, st):
-            rc = L.sfsn_gsn_layer_scan_l01(sx if fx else None, fin if fx else None, len(fx), sz if rest else None, len(rest), s1, fin1,
-                                           nt, H, int(self.spec.shared), self.stack_lag, _ptr(scratch), nbytes, st)
+        rc = _lib.SFSN_EUNSUPPORTED
+        ekey = key + (None if epi is None else (epi[0].write_proj, epi[1].dims[:3]),)
+        if epi is not None and ekey not in self._l01e_refused:
+            f, m = epi
+            B, F, T = m.dims[:3]
+            spec = self.spec
+            arr = (ProjDfGroup * len(seqs))()
+            for g, (a, seq, s8, y) in enumerate(zip(arr, seqs, s8s[1], d["proj"])):
+                a.spikes_i8, a.w_packed, a.w_dq, a.bias = s8.data_ptr(), seq.proj_q.data_ptr(), seq.proj_dq.data_ptr(), seq.proj_b.data_ptr()
+                a.proj = y.data_ptr() if f.write_proj else None
+                a.n_units, a.fc, a.df = spec.units(g), spec.ctr[g], spec.df[g]
+            with self.timed("stack:" + tag, st):
+                rc = L.sfsn_gsn_layer_scan_l01_projdf(sx if fx else None, fin if fx else None, len(fx), sz if rest else None, len(rest), s1, fin1,
+                                                      H, int(self.spec.shared), self.stack_lag, _ptr(scratch), nbytes, _ptr(f.ri), B, F, T,
+                                                      spec.num_spks, arr, len(seqs), _ptr(f.enh_ri), _ptr(f.enh_mag), t0, nt, st)
+            if rc == _lib.SFSN_EUNSUPPORTED:
+                self._l01e_refused.add(ekey)
+            else:
+                check(rc, "sfsn_gsn_layer_scan_l01_projdf")
+                f.epi_chunk = (t0, nt)
+                self._count("projdf")  # (the one-launch epilogue ran, as after _stage_projdf) ...
+                self._count("l01_projdf")  # ... inside the scan launch
+        if rc == _lib.SFSN_EUNSUPPORTED:
+            with self.timed("stack:" + tag, st):
+                rc = L.sfsn_gsn_layer_scan_l01(sx if fx else None, fin if fx else None, len(fx), sz if rest else None, len(rest), s1, fin1,
+                                               nt, H, int(self.spec.shared), self.stack_lag, _ptr(scratch), nbytes, st)
         if rc == _lib.SFSN_EUNSUPPORTED:
             self._l01_refused.add(key)
             return False
@@ -1539,6 +1572,10 @@ class Engine:
         if m.tag == "sb":
             B, F, T = m.dims[:3]
             S = self.spec.num_spks
+            if f.epi_chunk == (t0, nt):  # (the chunk's scan launch carried it: _stage_scan_l01)
+                f.epi_chunk = None
+                f.proj_skipped = not f.write_proj
+                return
             if self._stage_projdf(m.seqs, m.d["s8"][-1], m.d["proj"], f.ri, f.enh_ri, f.enh_mag, (B, F, T, S), t0, nt, st, f.write_proj):
                 f.proj_skipped = not f.write_proj
                 return
@@ -1603,7 +1640,7 @@ class Engine:
                 f.link(g, sc)
                 # ---- the scan(s)
                 if l == 0:
-                    paired = self._scan_layer0(m, fx, rest, pair, t0, nt, f.hS[si])
+                    paired = self._scan_layer0(m, fx, rest, pair, t0, nt, f.hS[si], f)
                 elif l == 1 and paired:
                     pass  # (layer 1 of this chunk ran in layer 0's launch)
                 elif fused:
@@ -1621,13 +1658,15 @@ class Engine:
                         done.append(_record(g))
         return done
 
-    def _scan_layer0(self, m: _ModelRun, fx, rest, pair, t0, nt, st) -> bool:
+    def _scan_layer0(self, m: _ModelRun, fx, rest, pair, t0, nt, st, f=None) -> bool:
         """Layer 0 of a model on one chunk, in as few launches as the library takes: with layer 1 (True: layer 1 ran too), both kinds of
         group in one launch, or the fused-x groups and the rest one after the other."""
         seqs, d, xs_, tag = m.seqs, m.d, m.xs, m.tag
         cn = d["cnt"]
         cn0 = None if cn is None else cn[0]
-        if pair and self._stage_scan_l01(seqs, fx, rest, xs_, d, t0, nt, st, tag, cn=cn):
+        # (the chunk's epilogue inside the pair launch: only where _epilogue would take the one-launch epilogue)
+        epi = (f, m) if (pair and f is not None and self.pair16_epilogue and self.fuse_projdf and tag == "sb") else None
+        if pair and self._stage_scan_l01(seqs, fx, rest, xs_, d, t0, nt, st, tag, cn=cn, epi=epi):
             return True
         if fx and rest and m.rpw == 16 and self.merge_layer0 and self._stage_scan_l0(
                 seqs, fx, rest, xs_, d["zin"][0], d["states"][0], d["spk"][0], d["s8"][0], t0, nt, st, tag, cnts=cn0):
