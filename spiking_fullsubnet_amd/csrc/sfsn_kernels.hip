@@ -26,6 +26,7 @@
 #include "sfsn_scan_dev.h"
 #include "sfsn_scan3_dev.h"
 #include "sfsn_scan3j_dev.h"
+#include "sfsn_pair_dev.h"
 #include "sfsn_scan3g_dev.h"
 #include "sfsn_feat_dev.h"
 #include "sfsn_host.h"
@@ -318,17 +319,8 @@ __global__ __launch_bounds__(512) void gsn_scan_fused_kernel(const ScanParams p)
 template <int KS, int TL, int OUT, int OFF = 0>
 __global__ __launch_bounds__(1024) void gsn_scan_fused3_kernel(const ScanParams p) {
     extern __shared__ __attribute__((aligned(16))) char scan_smem[];
-    int s = 0;
-    for (int i = 1; i < p.nseg; ++i)
-        if ((int)blockIdx.x >= p.seg[i].tile0) s = i;
-    const ScanSegDev& sg = p.seg[s];
-    Scan3jRole rl;
-    rl.spikes_in = sg.spikes_in; rl.w_ih = sg.w_ih; rl.w_ih_dq = sg.w_ih_dq; rl.w_hh = sg.w_hh; rl.w_dq = sg.w_dq; rl.bias = sg.bias;
-    rl.bn_alpha = sg.bn_alpha; rl.bn_beta = sg.bn_beta; rl.h_state = sg.h_state; rl.c_state = sg.c_state;
-    rl.spikes_f32 = sg.spikes_f32; rl.spikes_i8 = sg.spikes_i8; rl.R = sg.R; rl.row0 = ((int)blockIdx.x - sg.tile0) * 16;
-    rl.count = sg.count; rl.lsplit = p.lsplit;
     SFSN_WG_STAMP(p.wg_times, 0);
-    scan3j_role<KS, TL, OUT, OFF>(rl, scan_smem, p.T, p.H, p.NT);
+    layer1_role16<KS, TL, OUT, OFF, false, false>(p, (int)blockIdx.x, scan_smem, nullptr);
     SFSN_WG_STAMP(p.wg_times, 1);
 }
 
@@ -336,19 +328,9 @@ __global__ __launch_bounds__(1024) void gsn_scan_fused3_kernel(const ScanParams 
 template <int KS, int TL, int OUT>
 __global__ __launch_bounds__(1024) void gsn_scan_fusedx3_kernel(const ScanParams p) {
     extern __shared__ __attribute__((aligned(16))) char scan_smem[];
-    int s = 0;
-    for (int i = 1; i < p.nseg; ++i)
-        if ((int)blockIdx.x >= p.seg[i].tile0) s = i;
-    const ScanSegDev& sg = p.seg[s];
-    Scan3yRole rl;
-    rl.x = sg.x_in; rl.w_ih = sg.w_ih_f32; rl.I = sg.I; rl.w_hh = sg.w_hh; rl.w_dq = sg.w_dq; rl.bias = sg.bias;
-    rl.bn_alpha = sg.bn_alpha; rl.bn_beta = sg.bn_beta; rl.h_state = sg.h_state; rl.c_state = sg.c_state;
-    rl.spikes_f32 = sg.spikes_f32; rl.spikes_i8 = sg.spikes_i8; rl.R = sg.R; rl.row0 = ((int)blockIdx.x - sg.tile0) * 16;
-    rl.count = sg.count; rl.lsplit = p.lsplit;
+    const ScanSegDev& sg = p.seg[scan_segment_of(p, (int)blockIdx.x)];
     SFSN_WG_STAMP(p.wg_times, 0);
-    // (the k-chunk count is compile time: a wave-uniform `if` around operand loads makes hipcc drain lgkmcnt at every merge)
-    if (sg.I > 32) scan3y_role<KS, TL, OUT, 2>(rl, scan_smem, p.T, p.H, p.NT);
-    else scan3y_role<KS, TL, OUT, 1>(rl, scan_smem, p.T, p.H, p.NT);
+    scan3y_role16<KS, TL, OUT, false>(p, sg, ((int)blockIdx.x - sg.tile0) * 16, scan_smem, nullptr);
     SFSN_WG_STAMP(p.wg_times, 1);
 }
 
@@ -362,35 +344,8 @@ __global__ __launch_bounds__(1024) void gsn_scan_fusedx3_kernel(const ScanParams
 template <int KS, int TL, int OUT>
 __global__ __launch_bounds__(1024) void gsn_scan_l0_kernel(const ScanParams p) {
     extern __shared__ __attribute__((aligned(16))) char scan_smem[];
-    int s = 0;
-    for (int i = 1; i < p.nseg; ++i)
-        if ((int)blockIdx.x >= p.seg[i].tile0) s = i;
-    const ScanSegDev& sg = p.seg[s];
-    const int row0 = ((int)blockIdx.x - sg.tile0) * 16;
     SFSN_WG_STAMP(p.wg_times, 0);
-    if (sg.x_in != nullptr) {
-        Scan3yRole rl;
-        rl.x = sg.x_in; rl.w_ih = sg.w_ih_f32; rl.I = sg.I; rl.w_hh = sg.w_hh; rl.w_dq = sg.w_dq; rl.bias = sg.bias;
-        rl.bn_alpha = sg.bn_alpha; rl.bn_beta = sg.bn_beta; rl.h_state = sg.h_state; rl.c_state = sg.c_state;
-        rl.spikes_f32 = sg.spikes_f32; rl.spikes_i8 = sg.spikes_i8; rl.R = sg.R; rl.row0 = row0;
-        rl.count = sg.count; rl.lsplit = p.lsplit;
-        if (sg.I > 32) scan3y_role<KS, TL, OUT, 2>(rl, scan_smem, p.T, p.H, p.NT);
-        else scan3y_role<KS, TL, OUT, 1>(rl, scan_smem, p.T, p.H, p.NT);
-    } else {
-        constexpr int NW = 16;  // one output tile per wave, NT <= 14: waves NT .. 15 own none
-        const int tid = threadIdx.x, lane = tid & 63;
-        const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-        const int n = lane & 15, q = lane >> 4;
-        const int R = sg.R;
-        const int rowc = (row0 + n < R) ? row0 + n : R - 1;
-        scan_prologue<1, KS, NW, 1, OUT, 0>(sg, scan_smem, tid, p.H, p.NT, R, row0, 16);
-        if (wave < p.NT)
-            scan_body<1, KS, NW, 1, OUT, 0, 1>(sg.zin, sg.w_hh, sg.spikes_f32, sg.spikes_i8, nullptr, sg.h_state, sg.c_state, scan_smem, p.T,
-                                               p.H, p.NT, R, row0, rowc, n, q, tid, wave, 16, nullptr, nullptr, sg.count);
-        else
-            scan_body<1, KS, NW, 1, OUT, 0, 0>(sg.zin, sg.w_hh, sg.spikes_f32, sg.spikes_i8, nullptr, sg.h_state, sg.c_state, scan_smem, p.T,
-                                               p.H, p.NT, R, row0, rowc, n, q, tid, wave, 16, nullptr, nullptr, sg.count);
-    }
+    layer0_role16<KS, TL, OUT, false>(p, (int)blockIdx.x, scan_smem, nullptr);
     SFSN_WG_STAMP(p.wg_times, 1);
 }
 
@@ -2594,9 +2549,8 @@ extern "C" int sfsn_gsn_layer_scan_fused(const sfsn_scan_segment* segs, const sf
         // Measured (B = 64, T = 1000, 52 workgroups, ms per launch, scripts/exp_s3joff_r06.py): without fp32 spikes 1.320 -> 1.238; WITH
         // them 1.333 -> 1.466 -- there the IO waves' fp32 stores (~1,400 clk per step between them) already fill SIMDs 2 / 3 up to the
         // four-tile SIMDs' level (what SFSN_S3J_LSPLIT = 6 balanced), so the form is taken for OUT = 2 only.  SFSN_S3J_OFF = 0 / 1 / 2:
-        // never / OUT = 2 only (default) / always (A/B runs).
-        const int offm = getenv("SFSN_S3J_OFF") ? atoi(getenv("SFSN_S3J_OFF")) : 1;
-        if (p.NT == 14 && KS == 4 && tl && Scan3jCfg<4>::lds_bytes_off(14) <= 160 * 1024 - 64 && (offm == 2 || (offm == 1 && out == 2))) {
+        // never / OUT = 2 only (default) / always (A/B runs): s3j_off_form, sfsn_scan_host.h.
+        if (s3j_off_form(p.NT, KS, tl, out) && Scan3jCfg<4>::lds_bytes_off(14) <= 160 * 1024 - 64) {
             const int ldso = Scan3jCfg<4>::lds_bytes_off(14);
 #define FUSED3O_CASE(OUT_)                                                                                                 \
     if (out == OUT_) {                                                                                                     \
@@ -2693,11 +2647,10 @@ extern "C" int sfsn_gsn_layer_scan_l0(const sfsn_scan_segment* segs_x, const sfs
     p.lsplit = sfsn_knob("SFSN_S3Y_LSPLIT", SFSN_S3Y_LSPLIT, 0, 14);  // the fused-x role's own value (round 2's body has no such knob)
     const int KS = (H + 63) / 64;
     const bool tl = (H & 63) != 0 && (H & 63) <= 32;
-    const int lds_x = KS == 3 ? Scan3yCfg<3, 2>::lds_bytes(p.NT) : Scan3yCfg<4, 2>::lds_bytes(p.NT);
     hipStream_t st = static_cast<hipStream_t>(stream);
 #define L0_CASE(KS_, TL_, OUT_)                                                                                            \
     if (KS == KS_ && (int)tl == TL_ && out == OUT_) {                                                                      \
-        const int lds_z = ScanCfg<1, KS_, 16, 1, OUT_, 0>::LDS_BYTES, lds = lds_x > lds_z ? lds_x : lds_z;                 \
+        const int lds = layer0_lds_bytes<KS_, OUT_>(p.NT);                                                                 \
         if (lds > 160 * 1024 - 64) return SFSN_EUNSUPPORTED;                                                               \
         p.wg_times = sfsn_wgprobe_take(7, tiles_z); /* kind 7: fused-x workgroups first, then round 2's body */            \
         return launch_lds<gsn_scan_l0_kernel<KS_, TL_, OUT_>>(dim3(tiles_z), dim3(1024), lds, st, p);                      \

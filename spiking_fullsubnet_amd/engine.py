@@ -857,17 +857,56 @@ class Engine:
         return bool(self.fuse_input and self.spec.shared and 128 < seq.H <= 256 and rpw == 16 and not want_membrane
                     and seq.I % 2 == 0 and seq.I <= 64 and x.shape[1] % 16 == 0)
 
+    # ---- the argument arrays of the 16-row scan entry points, for the groups `idx` of `seqs` (an empty list gives arrays of one unused
+    #      entry: ctypes has no empty array to pass).  states / spks / s8s / cnts: the layer's, indexed by group.
+    @staticmethod
+    def _segs_fused_x(seqs, idx, xs_, states, spks, s8s, H, t0, cnts=None):
+        """Layer 0 with the input product inside the scan: (ScanSegment array, FusedX array)."""
+        segs, fin = (ScanSegment * max(len(idx), 1))(), (FusedX * max(len(idx), 1))()
+        for k, i in enumerate(idx):
+            cell, R = seqs[i].cells[0], xs_[i].shape[1]
+            fill_segment(segs[k], cell, R, H, t0, None, states[i], s8s[i], spks[i], count=None if cnts is None else cnts[i])
+            fin[k].x = xs_[i].data_ptr() + t0 * R * seqs[i].I * 4
+            fin[k].w_ih, fin[k].I = cell.w_ih_f32.data_ptr(), seqs[i].I
+        return segs, fin
+
+    @staticmethod
+    def _segs_zin(seqs, idx, zins, states, spks, s8s, H, t0, cnts=None):
+        """Layer 0 with its input term in `zins`: ScanSegment array."""
+        segs = (ScanSegment * max(len(idx), 1))()
+        for k, i in enumerate(idx):
+            fill_segment(segs[k], seqs[i].cells[0], s8s[i].shape[1], H, t0, zins[i], states[i], s8s[i], spks[i],
+                         count=None if cnts is None else cnts[i])
+        return segs
+
+    @staticmethod
+    def _segs_fused(seqs, idx, l, states, spks, s8_in, s8s, H, t0, cnts=None):
+        """Layer l >= 1 with the input product of the int8 spikes `s8_in` inside the scan: (ScanSegment array, FusedInput array)."""
+        HP = (H + 63) // 64 * 64
+        segs, fin = (ScanSegment * max(len(idx), 1))(), (FusedInput * max(len(idx), 1))()
+        for k, i in enumerate(idx):
+            cell, R = seqs[i].cells[l], s8s[i].shape[1]
+            pk, dq = cell.w_ih_q[0]
+            fill_segment(segs[k], cell, R, H, t0, None, states[i], s8s[i], spks[i], count=None if cnts is None else cnts[i])
+            fin[k].spikes_in = s8_in[i].data_ptr() + t0 * R * HP
+            fin[k].w_ih, fin[k].w_ih_dq = pk.data_ptr(), dq.data_ptr()
+        return segs, fin
+
+    def _projdf_groups(self, seqs, s8s, projs, write_proj):
+        """The groups of the sub-band epilogue (last-layer spikes `s8s`, coefficient rows `projs`): ProjDfGroup array."""
+        spec = self.spec
+        arr = (ProjDfGroup * len(seqs))()
+        for g, (a, seq, s8, y) in enumerate(zip(arr, seqs, s8s, projs)):
+            a.spikes_i8, a.w_packed, a.w_dq, a.bias = s8.data_ptr(), seq.proj_q.data_ptr(), seq.proj_dq.data_ptr(), seq.proj_b.data_ptr()
+            a.proj = y.data_ptr() if write_proj else None
+            a.n_units, a.fc, a.df = spec.units(g), spec.ctr[g], spec.df[g]
+        return arr
+
     def _stage_scan_fused_x(self, seqs, xs_, states, spks, s8s, t0, nt, st, tag, cnts=None):
         """Layer 0 of the given sequence models, input product inside the scan."""
         L = self.lib
         H = seqs[0].H
-        segs = (ScanSegment * len(seqs))()
-        fin = (FusedX * len(seqs))()
-        for i, (seq, x) in enumerate(zip(seqs, xs_)):
-            cell, R = seq.cells[0], x.shape[1]
-            fill_segment(segs[i], cell, R, H, t0, None, states[i], s8s[i], spks[i], count=None if cnts is None else cnts[i])
-            fin[i].x = x.data_ptr() + t0 * R * seq.I * 4
-            fin[i].w_ih, fin[i].I = cell.w_ih_f32.data_ptr(), seq.I
+        segs, fin = self._segs_fused_x(seqs, range(len(seqs)), xs_, states, spks, s8s, H, t0, cnts)
         self._count("fused_x")
         with self.timed("scanx:" + tag, st):
             check(L.sfsn_gsn_layer_scan_fused_x(segs, fin, len(seqs), nt, H, st), "sfsn_gsn_layer_scan_fused_x")
@@ -880,15 +919,8 @@ class Engine:
         key = (H, tuple((xs_[i].shape[1], seqs[i].I) for i in fx), tuple(xs_[i].shape[1] for i in rest), spks[fx[0]] is None)
         if key in self._l0_refused:
             return False
-        sx, sz, fin = (ScanSegment * len(fx))(), (ScanSegment * len(rest))(), (FusedX * len(fx))()
-        for k, i in enumerate(fx):
-            cell, R = seqs[i].cells[0], xs_[i].shape[1]
-            fill_segment(sx[k], cell, R, H, t0, None, states[i], s8s[i], spks[i], count=None if cnts is None else cnts[i])
-            fin[k].x = xs_[i].data_ptr() + t0 * R * seqs[i].I * 4
-            fin[k].w_ih, fin[k].I = cell.w_ih_f32.data_ptr(), seqs[i].I
-        for k, i in enumerate(rest):
-            fill_segment(sz[k], seqs[i].cells[0], s8s[i].shape[1], H, t0, zins[i], states[i], s8s[i], spks[i],
-                         count=None if cnts is None else cnts[i])
+        sx, fin = self._segs_fused_x(seqs, fx, xs_, states, spks, s8s, H, t0, cnts)
+        sz = self._segs_zin(seqs, rest, zins, states, spks, s8s, H, t0, cnts)
         with self.timed("scanx:" + tag, st):
             rc = self.lib.sfsn_gsn_layer_scan_l0(sx, fin, len(fx), sz, len(rest), nt, H, int(self.spec.shared), st)
         if rc == _lib.SFSN_EUNSUPPORTED:
@@ -908,30 +940,16 @@ class Engine:
         geometry) leaves today's launch."""
         L = self.lib
         H = seqs[0].H
-        HP = (H + 63) // 64 * 64
         order = list(fx) + list(rest)
         key = (H, tuple((xs_[i].shape[1], seqs[i].I) for i in fx), tuple(xs_[i].shape[1] for i in rest), d["spk"][0][order[0]] is None)
         if key in self._l01_refused:
             return False
         states, spks, s8s, zins = d["states"], d["spk"], d["s8"], d["zin"][0]
-        sx, sz, fin = (ScanSegment * max(len(fx), 1))(), (ScanSegment * max(len(rest), 1))(), (FusedX * max(len(fx), 1))()
-        s1, fin1 = (ScanSegment * len(order))(), (FusedInput * len(order))()
-        for k, i in enumerate(fx):
-            cell, R = seqs[i].cells[0], xs_[i].shape[1]
-            fill_segment(sx[k], cell, R, H, t0, None, states[0][i], s8s[0][i], spks[0][i], count=None if cn is None else cn[0][i])
-            fin[k].x = xs_[i].data_ptr() + t0 * R * seqs[i].I * 4
-            fin[k].w_ih, fin[k].I = cell.w_ih_f32.data_ptr(), seqs[i].I
-        for k, i in enumerate(rest):
-            fill_segment(sz[k], seqs[i].cells[0], s8s[0][i].shape[1], H, t0, zins[i], states[0][i], s8s[0][i], spks[0][i],
-                         count=None if cn is None else cn[0][i])
-        rows = 0
-        for k, i in enumerate(order):
-            cell, R = seqs[i].cells[1], s8s[1][i].shape[1]
-            rows += R
-            pk, dq = cell.w_ih_q[0]
-            fill_segment(s1[k], cell, R, H, t0, None, states[1][i], s8s[1][i], spks[1][i], count=None if cn is None else cn[1][i])
-            fin1[k].spikes_in = s8s[0][i].data_ptr() + t0 * R * HP
-            fin1[k].w_ih, fin1[k].w_ih_dq = pk.data_ptr(), dq.data_ptr()
+        cn0, cn1 = (None, None) if cn is None else (cn[0], cn[1])
+        sx, fin = self._segs_fused_x(seqs, fx, xs_, states[0], spks[0], s8s[0], H, t0, cn0)
+        sz = self._segs_zin(seqs, rest, zins, states[0], spks[0], s8s[0], H, t0, cn0)
+        s1, fin1 = self._segs_fused(seqs, order, 1, states[1], spks[1], s8s[0], s8s[1], H, t0, cn1)
+        rows = sum(s8s[1][i].shape[1] for i in order)
         nbytes = L.sfsn_stack_scratch_bytes(2, len(order), rows)
 
         def make():  # zero-filled once, on the stream the kernel is launched on (see _stage_stack)
@@ -946,11 +964,7 @@ class Engine:
             f, m = epi
             B, F, T = m.dims[:3]
             spec = self.spec
-            arr = (ProjDfGroup * len(seqs))()
-            for g, (a, seq, s8, y) in enumerate(zip(arr, seqs, s8s[1], d["proj"])):
-                a.spikes_i8, a.w_packed, a.w_dq, a.bias = s8.data_ptr(), seq.proj_q.data_ptr(), seq.proj_dq.data_ptr(), seq.proj_b.data_ptr()
-                a.proj = y.data_ptr() if f.write_proj else None
-                a.n_units, a.fc, a.df = spec.units(g), spec.ctr[g], spec.df[g]
+            arr = self._projdf_groups(seqs, s8s[1], d["proj"], f.write_proj)
             with self.timed("stack:" + tag, st):
                 rc = L.sfsn_gsn_layer_scan_l01_projdf(sx if fx else None, fin if fx else None, len(fx), sz if rest else None, len(rest), s1, fin1,
                                                       H, int(self.spec.shared), self.stack_lag, _ptr(scratch), nbytes, _ptr(f.ri), B, F, T,
@@ -984,15 +998,7 @@ class Engine:
     def _stage_scan_fused(self, seqs, l, states, spks, s8s, t0, nt, st, tag, cnts=None):
         L = self.lib
         H = seqs[0].H
-        HP = (H + 63) // 64 * 64
-        segs = (ScanSegment * len(seqs))()
-        fin = (FusedInput * len(seqs))()
-        for i, seq in enumerate(seqs):
-            cell, R = seq.cells[l], s8s[l][i].shape[1]
-            pk, dq = cell.w_ih_q[0]
-            fill_segment(segs[i], cell, R, H, t0, None, states[i], s8s[l][i], spks[i], count=None if cnts is None else cnts[i])
-            fin[i].spikes_in = s8s[l - 1][i].data_ptr() + t0 * R * HP
-            fin[i].w_ih, fin[i].w_ih_dq = pk.data_ptr(), dq.data_ptr()
+        segs, fin = self._segs_fused(seqs, range(len(seqs)), l, states, spks, s8s[l - 1], s8s[l], H, t0, cnts)
         self._count("fused")
         with self.timed("scanf:" + tag, st):
             check(L.sfsn_gsn_layer_scan_fused(segs, fin, len(seqs), nt, H, st), "sfsn_gsn_layer_scan_fused")
@@ -1128,12 +1134,7 @@ class Engine:
         if not self.fuse_projdf:
             return False
         B, F, T, S = dims
-        spec = self.spec
-        arr = (ProjDfGroup * len(seqs))()
-        for g, (a, seq, s8, y) in enumerate(zip(arr, seqs, s8s, projs)):
-            a.spikes_i8, a.w_packed, a.w_dq, a.bias = s8.data_ptr(), seq.proj_q.data_ptr(), seq.proj_dq.data_ptr(), seq.proj_b.data_ptr()
-            a.proj = y.data_ptr() if write_proj else None
-            a.n_units, a.fc, a.df = spec.units(g), spec.ctr[g], spec.df[g]
+        arr = self._projdf_groups(seqs, s8s, projs, write_proj)
         with self.timed("projdf", st):
             rc = self.lib.sfsn_proj_deepfilter(_ptr(ri), B, F, T, S, seqs[0].H, arr, len(seqs), _ptr(enh_ri), _ptr(enh_mag), t0, nt, st)
         if rc == _lib.SFSN_EUNSUPPORTED:
