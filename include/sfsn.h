@@ -712,6 +712,42 @@ typedef struct sfsn_prime_src {
 int sfsn_hop_prime(const sfsn_hop_desc* desc /* host */, const int* clips /* host */, int n_clips, const sfsn_prime_src* src /* host */,
                    void* stream);
 
+/* Moving a clip (csrc/sfsn_state.hip): the carried state of the listed clips out into a self-contained blob per clip, and from such a
+ * blob into the listed clips of this or another descriptor of the same geometry -- ONE launch each way, ordered on `stream` like any
+ * launch, plain stores, nothing waits inside it.  The state is COPIED, not recomputed, so a moved clip continues bit for bit, layer 0
+ * included (priming has a reservation there).  Every other clip's rows, the tagged scratch (spikes, spec_g, enh_g) and launch_index are
+ * left as they are.  With k = desc->launch_index, export READS and import WRITES the half of every double-buffered array that launch k
+ * reads (h[k & 1], cum[k & 1]); the two descriptors' parities may differ -- the blob has none.
+ *
+ * Blob of sfsn_hop_state_export: one clip = sfsn_hop_state_bytes(desc) bytes, blob row i = clips[i] (import: row b0 + i -> clips[i]).
+ * Sections in this order, each starting at the next multiple of 16 bytes, the total rounded up to a multiple of 16:
+ *   for every sequence (the full-band model, then groups 0 .. n_groups - 1) and every layer of it, with units = feat.n_units:
+ *       h      int8  [units][H]      the last frame's spike bytes (the pad columns H .. pad64(H) - 1 of the session's rows are not state)
+ *       c      float [units][H]      the membranes
+ *   cum        float [units]         for every sequence with SFSN_NORM_CUMLAPLACE, in sequence order: the rows' running sums
+ *   slots      u32   [units][H / 4]  only if desc->spike_slots: for every sequence and layer, in that order
+ *   hist       float [fcov][D][2]    only if D > 0: the last D noisy frames of the bins 0 .. fcov - 1 the groups cover
+ *                                    (fcov = max over groups of feat.lo + feat.n_units * fc; the hop keeps no history of the others)
+ *   wave       float [512]           only in waveform mode (wave_in != NULL): wave_state, the last 512 input samples
+ *   ola        float [S][512]        only in waveform mode: ola_state
+ * sfsn_hop_state_bytes is host only (no device needed) and returns 0 for a descriptor sfsn_stream_hop refuses.
+ *
+ * The clip's ORIGIN is not in the blob: it is not device state of the hop, clip_start is the caller's array.  At export the caller
+ * notes age = launch_index - clip_start[b] of the source (unsigned difference); after an import it writes, with a stream-ordered fill
+ * behind the queued launches, clip_start[b'] = launch_index - age of the destination (unsigned, wrap-safe).  age may be -1 (a waveform
+ * clip that has not made its first call yet: its origin is the launch after the destination's next one) and may exceed the
+ * destination's launch_index.  age == 0 makes the next launch read the state as zero, which is then what it is.
+ *
+ * SFSN_EINVAL, before any launch: NULL desc / clips / blob, n_clips < 1, an index outside [0, desc->B) or listed twice, b0 < 0, a blob
+ * pointer that is not 16-byte aligned, a NULL or 4-byte-misaligned state pointer.  SFSN_EUNSUPPORTED: more than 256 clips (the caller
+ * splits the list), B > 65535, a descriptor sfsn_stream_hop refuses.
+ * (Added without an ABI bump: no existing struct or signature changed.) */
+size_t sfsn_hop_state_bytes(const sfsn_hop_desc* desc /* host */);
+int sfsn_hop_state_export(const sfsn_hop_desc* desc /* host */, const int* clips /* host */, int n_clips,
+                          void* blob /* device [n_clips][bytes] */, void* stream);
+int sfsn_hop_state_import(const sfsn_hop_desc* desc /* host */, const int* clips /* host */, int n_clips,
+                          const void* blob /* device [..][bytes] */, int b0 /* first blob row */, void* stream);
+
 /* ----------------------------------------------------------------------------------------------------
  * Spike counts -- the only thing the reference's energy proxy reads from the spike tensors:
  * compute_synops (audiozen/metric.py:303-327) uses torch.gt(layer_output, 0).float().mean() per layer.  Counting the
@@ -930,6 +966,30 @@ typedef struct {
 
 int sfsn_fullband_wave_hop_check(int Hp, int n_layers, int F, int S, int df, int B, int unshared);
 int sfsn_fullband_stream_hop_wave(const sfsn_fullband_wave_desc* desc, void* stream);
+
+/* Moving a clip of a cIRM-GSN session (csrc/sfsn_state.hip): sfsn_hop_state_export / sfsn_hop_state_import for sfsn_fullband_hop_desc --
+ * the same launch, the same rules (one launch, plain stores, the half of h and hist_ri that launch launch_index reads, scratch and z0
+ * untouched, the origin kept by the caller: clip_start[b'] = launch_index - age) and the same return codes.  What lives outside the
+ * descriptor is handed over as the launches take it: spike_slots as sfsn_fullband_stream_hop_counted does (NULL: the session does not
+ * count), wave_state and ola_state of a sfsn_fullband_wave_desc whose `hop` is `desc` (both NULL: a spectrum session; one NULL:
+ * SFSN_EINVAL; with spike_slots: SFSN_EUNSUPPORTED, the waveform launch has no counted form).
+ *
+ * Blob of sfsn_fullband_hop_state_export: one clip = sfsn_fullband_hop_state_bytes(desc, counted, wave) bytes.  Sections in this order,
+ * each starting at the next multiple of 16 bytes, the total rounded up to a multiple of 16:
+ *   for every layer:   h int8 [Hp] the last frame's spike bytes,  c float [Hp] the membranes
+ *   slots  u32   [Hp / 4]      only if counted: for every layer
+ *   hist   float [F][D][2]     only if D > 0: the last D noisy frames
+ *   wave   float [512]         only in waveform mode: wave_state
+ *   ola    float [S][512]      only in waveform mode: ola_state
+ * sfsn_fullband_hop_state_bytes is host only; 0: outside sfsn_fullband_hop_check (wave: sfsn_fullband_wave_hop_check), or counted with wave.
+ * (Added without an ABI bump: no existing struct or signature changed.) */
+size_t sfsn_fullband_hop_state_bytes(const sfsn_fullband_hop_desc* desc, int counted, int wave);
+int sfsn_fullband_hop_state_export(const sfsn_fullband_hop_desc* desc, const unsigned* spike_slots /* nullable */,
+                                   const float* wave_state /* nullable */, const float* ola_state /* nullable */, const int* clips /* host */,
+                                   int n_clips, void* blob /* device [n_clips][bytes] */, void* stream);
+int sfsn_fullband_hop_state_import(const sfsn_fullband_hop_desc* desc, unsigned* spike_slots /* nullable */, float* wave_state /* nullable */,
+                                   float* ola_state /* nullable */, const int* clips /* host */, int n_clips,
+                                   const void* blob /* device [..][bytes] */, int b0 /* first blob row */, void* stream);
 
 /* ----------------------------------------------------------------------------------------------------
  * The intel_ndns recipe's training loss (recipes/intel_ndns/spiking_fullsubnet/trainer.py:24-48 on audiozen/loss.py) and its

@@ -23,6 +23,7 @@ from .model_low_freq import Separator  # noqa: F401
 from .modeling_spiking_fullsubnet import SpikingFullSubNet  # noqa: F401
 from .modeling_cirm_gsn import Model  # noqa: F401
 from .streaming import StreamingSession  # noqa: F401
+from .clip_state import ClipState  # noqa: F401
 from . import loss  # noqa: F401
 from .loss import RecipeLoss, ReverbRecipeLoss  # noqa: F401
 from . import pit  # noqa: F401
@@ -31,4 +32,4 @@ from .pit import PITWrapper, PairwiseNegSDR, PerClip  # noqa: F401
 from .metric import SISDR  # noqa: F401
 
 __all__ = ["SpikingFullSubNet", "Separator", "Engine", "PathSpec", "StreamingSession", "Model", "RecipeLoss", "loss", "pit", "PITWrapper",
-           "PairwiseNegSDR", "PerClip", "SISDR", "metric", "ragged", "ReverbRecipeLoss"]
+           "PairwiseNegSDR", "PerClip", "SISDR", "metric", "ragged", "ReverbRecipeLoss", "ClipState"]

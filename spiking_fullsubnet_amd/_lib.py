@@ -145,7 +145,7 @@ def _sources():
     """The files the library is made of, in the order the Makefile hashes them (SRCS)."""
     return [os.path.join(_HERE, "..", "include", "sfsn.h")] + [
         os.path.join(CSRC, f) for f in ("sfsn_scan_dev.h", "sfsn_scan3_dev.h", "sfsn_scan3i_dev.h", "sfsn_scan3x_dev.h", "sfsn_scan3w_dev.h", "sfsn_scan3j_dev.h", "sfsn_scan3g_dev.h", "sfsn_feat_dev.h", "sfsn_fft_dev.h", "sfsn_hop_dev.h", "sfsn_hop_wave_dev.h", "sfsn_fullband_dev.h", "sfsn_host.h", "sfsn_scan_host.h", "sfsn_pair_dev.h", "sfsn_projdf_dev.h", "sfsn_kernels.hip", "sfsn_stack.hip", "sfsn_hop.hip", "sfsn_fft.hip", "sfsn_train.hip",
-                                  "sfsn_featproj.hip", "sfsn_projdf.hip", "sfsn_fullband.hip", "sfsn_fullband_train.hip", "sfsn_fullband_hop.hip", "sfsn_loss.hip", "sfsn_pit.hip", "sfsn_ragged.hip", "sfsn_pair16.hip", "sfsn_pair16e.hip", "sfsn_prime.hip", "sfsn_pack.cpp")]
+                                  "sfsn_featproj.hip", "sfsn_projdf.hip", "sfsn_fullband.hip", "sfsn_fullband_train.hip", "sfsn_fullband_hop.hip", "sfsn_loss.hip", "sfsn_pit.hip", "sfsn_ragged.hip", "sfsn_pair16.hip", "sfsn_pair16e.hip", "sfsn_prime.hip", "sfsn_state.hip", "sfsn_pack.cpp")]
 
 
 def source_hash() -> str:
@@ -296,6 +296,12 @@ def lib() -> ctypes.CDLL:
     L.sfsn_stream_hop.argtypes = [ctypes.POINTER(HopDesc), _P]
     L.sfsn_hop_prime.restype = _I
     L.sfsn_hop_prime.argtypes = [ctypes.POINTER(HopDesc), ctypes.POINTER(_I), _I, ctypes.POINTER(PrimeSrc), _P]
+    L.sfsn_hop_state_bytes.restype = ctypes.c_size_t  # per clip; 0: a descriptor the hop refuses (host only)
+    L.sfsn_hop_state_bytes.argtypes = [ctypes.POINTER(HopDesc)]
+    L.sfsn_hop_state_export.restype = _I  # desc, clips, n_clips, blob, stream
+    L.sfsn_hop_state_export.argtypes = [ctypes.POINTER(HopDesc), ctypes.POINTER(_I), _I, _P, _P]
+    L.sfsn_hop_state_import.restype = _I  # desc, clips, n_clips, blob, b0, stream
+    L.sfsn_hop_state_import.argtypes = [ctypes.POINTER(HopDesc), ctypes.POINTER(_I), _I, _P, _I, _P]
     L.sfsn_stream_hop_resident.restype = _I
     L.sfsn_stream_hop_resident.argtypes = [ctypes.POINTER(HopDesc), _P, ctypes.c_uint, _P]
     L.sfsn_spike_count.restype = _I
@@ -330,6 +336,12 @@ def lib() -> ctypes.CDLL:
     L.sfsn_fullband_wave_hop_check.argtypes = [_I] * 7
     L.sfsn_fullband_stream_hop_wave.restype = _I
     L.sfsn_fullband_stream_hop_wave.argtypes = [ctypes.POINTER(FullbandWaveDesc), _P]
+    L.sfsn_fullband_hop_state_bytes.restype = ctypes.c_size_t  # desc, counted, wave; 0: not covered (host only)
+    L.sfsn_fullband_hop_state_bytes.argtypes = [ctypes.POINTER(FullbandHopDesc), _I, _I]
+    L.sfsn_fullband_hop_state_export.restype = _I  # desc, spike_slots, wave_state, ola_state | clips, n_clips | blob, stream
+    L.sfsn_fullband_hop_state_export.argtypes = [ctypes.POINTER(FullbandHopDesc), _P, _P, _P, ctypes.POINTER(_I), _I, _P, _P]
+    L.sfsn_fullband_hop_state_import.restype = _I  # desc, spike_slots, wave_state, ola_state | clips, n_clips | blob, b0, stream
+    L.sfsn_fullband_hop_state_import.argtypes = [ctypes.POINTER(FullbandHopDesc), _P, _P, _P, ctypes.POINTER(_I), _I, _P, _I, _P]
     L.sfsn_recipe_loss_scratch_bytes.restype = ctypes.c_size_t  # rows, n_samples; 0: refused (host only)
     L.sfsn_recipe_loss_scratch_bytes.argtypes = [_I, _I]
     L.sfsn_recipe_loss.restype = _I  # est, tgt | rows, n_samples | c_freq, c_mag, c_sdr | flags | terms, grad_est, scratch, stream
@@ -381,7 +393,9 @@ EXPORTS = ("sfsn_abi_version", "sfsn_source_hash", "sfsn_strerror", "sfsn_device
            "sfsn_pit_sdr_scratch_bytes", "sfsn_pit_sdr", "sfsn_stft_ragged", "sfsn_istft_ragged", "sfsn_laplace_means_ragged",
            "sfsn_gaussian_stats_ragged", "sfsn_spike_count_rows_ragged", "sfsn_zero_tail_frames", "sfsn_gsn_layer_scan_l0",
            "sfsn_pit_sdr_ragged", "sfsn_gsn_layer_scan_l01", "sfsn_recipe_loss_ragged_scratch_bytes", "sfsn_recipe_loss_ragged",
-           "sfsn_fullband_proj_deepfilter_ragged", "sfsn_hop_prime", "sfsn_gsn_layer_scan_l01_projdf")
+           "sfsn_fullband_proj_deepfilter_ragged", "sfsn_hop_prime", "sfsn_gsn_layer_scan_l01_projdf",
+           "sfsn_hop_state_bytes", "sfsn_hop_state_export", "sfsn_hop_state_import", "sfsn_fullband_hop_state_bytes",
+           "sfsn_fullband_hop_state_export", "sfsn_fullband_hop_state_import")
 
 
 def check(rc: int, what: str = "") -> None:

@@ -38,6 +38,11 @@ Spike counts (``count_spikes=True``, spectrum sessions): the session counts ever
 launch's spikes into per-lane slots (``sfsn_fullband_stream_hop_counted``, still one launch per hop; a restarted clip's slots read as
 zero); the per-kernel sequence ends with one per-clip count launch (``sfsn_spike_count_rows``), captured with the rest.
 
+Moving a clip: ``export_state(clips)`` / ``import_state(state, clips)`` copy the clips' carried state out of the session (a
+``clip_state.ClipState``) and into slots of this or another session of the same geometry and tier, where the clips continue bit for bit:
+one launch each way on the one-launch kernel (``sfsn_fullband_hop_state_export`` / ``_import``, csrc/sfsn_state.hip), row copies in the
+per-kernel sequence; stream-ordered, no synchronisation.  These sessions have no ``prime``: an import is their warm start.
+
 Not covered here: ``resident`` sessions, ``count_spikes`` together with ``waveform``, waveform sessions beyond 16 clips or with
 separate gate weights, and LSTM models.
 """
@@ -463,6 +468,125 @@ class FullbandStreamingSession:
             self.hist[b].zero_()
             if self._rows is not None:
                 self._rows[:, b].zero_()
+
+    # ---- moving a clip: its state out of its slot, and into a slot of this or another session ------------------------------------
+    def _state_signature(self) -> tuple:
+        """What two sessions must share for a clip to move between them (clip_state.py): tier, call geometry, model geometry."""
+        cached = getattr(self, "_signature", None)
+        if cached is not None:
+            return cached
+        import dataclasses
+        sig = [("model", "cirm_gsn"), ("tier", "one_launch" if self._hop is not None else "per_kernel"), ("hop", self.hop),
+               ("waveform", self.waveform), ("count_spikes", self.count_spikes), ("F", self.F), ("Hp", self.eng.Hp)]
+        sig += [(k, v) for k, v in dataclasses.asdict(self.eng.spec).items() if k != "bn"]
+        self._signature = tuple(sig)
+        return self._signature
+
+    def _state_parts(self) -> list:
+        """The per-kernel sequence's carried state as (section, [B, n] view): what a later step reads before it writes."""
+        parts = []
+        for l in range(self.eng.spec.layers):
+            parts += [(f"l{l}.h", self._flat[l, 0]), (f"l{l}.c", self._flat[l, 1])]
+        parts.append(("hist", torch.view_as_real(self.hist).view(self.B, -1)))
+        if self._rows is not None:
+            parts.append(("rows", self._rows.t()))
+        return parts
+
+    def _state_layout(self):
+        """((section, start, stop), ...), bytes of one clip's blob in this session's tier (clip_state.py); fixed at construction."""
+        cached = getattr(self, "_layout", None)
+        if cached is None:
+            cached = self._layout = self._make_state_layout()
+        return cached
+
+    def _make_state_layout(self):
+        from .clip_state import fullband_sections, layout_of
+        if self._hop is None:
+            return layout_of([(name, t.shape[1] * t.element_size()) for name, t in self._state_parts()])
+        layout, nbytes = fullband_sections(self.eng.spec.layers, self.eng.Hp, self.count_spikes, self.F, self.D, self.waveform, self.S)
+        assert nbytes == self.eng.lib.sfsn_fullband_hop_state_bytes(self._hop["ref"], int(self.count_spikes), int(self.waveform)), \
+            "clip_state.fullband_sections restates include/sfsn.h"
+        return layout, nbytes
+
+    def _state_pointers(self):
+        """(spike_slots, wave_state, ola_state) as the state launches take them (None: not part of this session)."""
+        h = self._hop
+        slots = ctypes.c_void_p(h["slots"].data_ptr()) if h["slots"] is not None else None
+        if self.waveform:
+            return slots, ctypes.c_void_p(h["wave"]["state"].data_ptr()), ctypes.c_void_p(h["wave"]["ola"].data_ptr())
+        return slots, None, None
+
+    def clip_calls(self) -> np.ndarray:
+        """Waveform sessions: int64 [B], the step_wave / step_wave_host calls of each clip's utterance."""
+        return self._calls - self._clip_c0
+
+    def export_state(self, clips=None):
+        """The carried state of ``clips`` (``None``: every clip) as a ``ClipState`` of ``len(clips)`` rows, row i = ``clips[i]``: what
+        ``import_state`` needs to continue those clips, bit for bit, in other slots of this session or in another session of equal
+        signature (``clip_state.py``).  cIRM-GSN sessions have no ``prime``: this is their warm start.  The one-launch hop copies
+        the state in one launch (``sfsn_fullband_hop_state_export``), the per-kernel sequence with stream-ordered row copies.  The
+        session is not changed.  Ordered on torch's current stream, no synchronisation; may return before the copy has run."""
+        from .clip_state import ClipState, clip_list, gather_rows
+        idx = clip_list(clips, self.B, "export_state")
+        layout, nbytes = self._state_layout()
+        if self._hop is None:
+            sel = torch.tensor(idx, dtype=torch.long).to(self.dev, non_blocking=True)
+            blob = gather_rows(self._state_parts(), sel, nbytes, layout)
+        else:
+            # (no fill launch in front of the copy where the sections tile the row; the padding between sections reads as zero)
+            alloc = torch.empty if sum(b - a for _, a, b in layout) == nbytes else torch.zeros
+            blob = alloc((len(idx), nbytes), dtype=torch.uint8, device=self.dev)
+            slots, wstate, ola = self._state_pointers()
+            arr = (ctypes.c_int * len(idx))(*idx)  # (B <= 16: one launch)
+            with torch.cuda.device(self.dev):
+                rc = self.eng.lib.sfsn_fullband_hop_state_export(self._hop["ref"], slots, wstate, ola, arr, len(idx), ctypes.c_void_p(blob.data_ptr()),
+                                                                 ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream))
+            if rc:
+                check(rc, "sfsn_fullband_hop_state_export")
+        return ClipState(blob, self.clip_frames()[idx], self.clip_calls()[idx] if self.waveform else None, None, self._state_signature(),
+                         layout)
+
+    def import_state(self, state, clips=None) -> None:
+        """Row i of ``state`` (an ``export_state`` result of a session of equal signature, on this session's device) becomes clip
+        ``clips[i]`` (``None``: every clip); the next step continues it exactly where the export left it, bit for bit; all other
+        clips go on untouched.  Ordered on torch's current stream, no synchronisation.  The weights are NOT compared: importing
+        into a session of another model of the same geometry is the caller's decision.  Refusals as for
+        ``StreamingSession.import_state``."""
+        from .clip_state import check_import, clip_list, scatter_rows
+        idx = clip_list(clips, self.B, "import_state")
+        check_import(state, idx, self.dev)
+        state.check_signature(self._state_signature())
+        layout, nbytes = self._state_layout()
+        if state.layout != layout or state.blob.shape[1] != nbytes:
+            raise ValueError("import_state: the state's blob layout is not this session's")
+        blob = state.blob.contiguous()
+        if self._hop is None:
+            sel = torch.tensor(idx, dtype=torch.long).to(self.dev, non_blocking=True)
+            scatter_rows(self._state_parts(), sel, blob, layout)
+            self._clip_f0[idx] = self.frames_done - state.frames
+            return
+        h = self._hop
+        slots, wstate, ola = self._state_pointers()
+        arr = (ctypes.c_int * len(idx))(*idx)
+        with torch.cuda.device(self.dev):
+            rc = self.eng.lib.sfsn_fullband_hop_state_import(h["ref"], slots, wstate, ola, arr, len(idx), ctypes.c_void_p(blob.data_ptr()), 0,
+                                                             ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream))
+        if rc:
+            check(rc, "sfsn_fullband_hop_state_import")
+        # the clips' origins (include/sfsn.h): the next launch gives each the frame index it had at export -- a waveform clip's is its
+        # calls minus one (-1: its first call is still to come).  Fills behind the queued launches, as in _reset_clips
+        ages = [int(state.calls[j]) - 1 if self.waveform else int(state.frames[j]) // self.hop for j in range(len(idx))]
+        j = 0
+        while j < len(idx):  # (one fill per run of consecutive clips of one age: clips that moved together)
+            m = 1
+            while j + m < len(idx) and idx[j + m] == idx[j] + m and ages[j + m] == ages[j]:
+                m += 1
+            h["origin"][idx[j]:idx[j] + m].fill_(self._as_i32(h["desc"].launch_index - ages[j]))
+            j += m
+        if self.waveform:
+            self._clip_c0[idx] = self._calls - state.calls
+        else:
+            self._clip_f0[idx] = self.frames_done - state.frames
 
     def clip_frames(self) -> np.ndarray:
         """int64 [B]: the frames each clip has seen since its own utterance began (waveform sessions, as the kernel counts them: the

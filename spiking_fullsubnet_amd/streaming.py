@@ -35,6 +35,12 @@ from silence (a clip joining mid-call, a seek, a reconnect, a backlog).  The pre
 csrc/sfsn_prime.hip) and the clips' origins move back by the prefix's launches, so that the next hop continues at frame N; the
 per-kernel sequence takes it as stream-ordered row copies into its states, history and counts.  Not for resident sessions.
 
+Moving a clip: ``export_state(clips)`` copies the clips' carried state out of the session (a ``clip_state.ClipState``: one self-contained
+blob per clip) and ``import_state(state, clips)`` puts it into slots of this or another session of the same geometry and tier, where
+the clips continue bit for bit, layer 0 included -- compaction, rebalancing, pause / resume, rewind, fork.  One launch each way in the
+one-launch tier (``sfsn_hop_state_export`` / ``sfsn_hop_state_import``, csrc/sfsn_state.hip; the clips' origins move with them), row
+copies in the per-kernel tier; stream-ordered, no synchronisation.  Not for resident sessions.
+
 Spike counts: a session opened with ``count_spikes=True`` counts every layer's spikes per clip as it runs, and
 ``spike_summary(clips)`` returns them in the form of the offline forward's ``layer_outputs="counts"`` lists, so that
 ``metric.compute_synops`` / ``compute_neuronops`` give each clip's current utterance's SynOPs and NeuronOPs.  The one-launch hop
@@ -719,6 +725,163 @@ class StreamingSession:
             inv[perm] = torch.arange(len(order), device=self.dev)
             res = res.index_select(0, inv)
         return res
+
+    # ---- moving a clip: its state out of its slot, and into a slot of this or another session ------------------------------------
+    def _state_signature(self) -> tuple:
+        """What two sessions must share for a clip to move between them (clip_state.py): the tier, the call geometry and every
+        number of the model's geometry -- not the weights."""
+        cached = getattr(self, "_signature", None)
+        if cached is not None:
+            return cached
+        import dataclasses
+        sig = [("model", "spiking_fullsubnet"), ("tier", "one_launch" if self._hop is not None else "per_kernel"), ("hop", self.hop),
+               ("waveform", self.waveform), ("count_spikes", self.count_spikes), ("given_stats", self._stats is not None)]
+        sig += [(k, tuple(v) if isinstance(v, list) else v) for k, v in dataclasses.asdict(self.eng.spec).items()
+                if k not in ("bn", "proj_name")]
+        self._signature = tuple(sig)
+        return self._signature
+
+    def _state_parts(self) -> list:
+        """The per-kernel sequence's carried state as (section, [B, n] view): what a later step reads before it writes."""
+        B, ng = self.B, self.eng.spec.n_groups
+        parts = []
+        for d, names in ((self.fb, ["fb"]), (self.sb, [f"sb{g}" for g in range(ng)])):
+            for gi, name in enumerate(names):
+                for l, layer in enumerate(d["states"]):
+                    h, c = layer[gi]
+                    parts += [(f"{name}.l{l}.h", h.view(B, -1)), (f"{name}.l{l}.c", c.view(B, -1))]
+        parts.append(("hist", torch.view_as_real(self.hist).view(B, -1)))
+        if self._rows is not None:
+            parts.append(("rows", self._rows.t()))
+        return parts
+
+    def _state_layout(self):
+        """((section, start, stop), ...), bytes of one clip's blob in this session's tier (clip_state.py); fixed at construction."""
+        cached = getattr(self, "_layout", None)
+        if cached is None:
+            cached = self._layout = self._make_state_layout()
+        return cached
+
+    def _make_state_layout(self):
+        from .clip_state import hop_sections, layout_of
+        if self._hop is None:
+            return layout_of([(name, t.shape[1] * t.element_size()) for name, t in self._state_parts()])
+        spec, eng, d = self.eng.spec, self.eng, self._hop["desc"]
+        ng = spec.n_groups
+        seqs = [("fb", 1, eng.fb.H, spec.fb_layers)] + [(f"sb{g}", spec.units(g), eng.sb[g].H, spec.sb_layers) for g in range(ng)]
+        fcov = max(d.sb[g].feat.lo + d.sb[g].feat.n_units * d.sb[g].fc for g in range(ng))
+        layout, nbytes = hop_sections(seqs, spec.cum_laplace, self.count_spikes, fcov, self.D, self.waveform, spec.num_spks)
+        assert nbytes == eng.lib.sfsn_hop_state_bytes(self._hop["parts"][0]["ref"]), "clip_state.hop_sections restates include/sfsn.h"
+        return layout, nbytes
+
+    def _part_runs(self, idx) -> list:
+        """[part, first position, local clip indices] for runs of consecutive positions of ``idx`` that lie in one part, 256 at most
+        (what one sfsn_hop_state_export / _import launch takes: consecutive blob rows, clip indices in its arguments)."""
+        runs = []
+        for j, b in enumerate(idx):
+            part = next(p for p in self._hop["parts"] if p["b0"] <= b < p["b0"] + p["nb"])
+            if runs and runs[-1][0] is part and len(runs[-1][2]) < 256:
+                runs[-1][2].append(b - part["b0"])
+            else:
+                runs.append([part, j, [b - part["b0"]]])
+        return runs
+
+    def export_state(self, clips=None):
+        """The carried state of ``clips`` (``None``: every clip) as a ``ClipState`` of ``len(clips)`` rows, row i = ``clips[i]``: what
+        ``import_state`` needs to continue those clips, bit for bit, in other slots of this session or in another session of equal
+        signature (same model geometry, tier, hop, waveform / counting mode; see ``clip_state.py``) -- to compact a half-empty
+        session into a smaller one, rebalance, pause a call (``state.to("cpu")``), rewind or fork it.  The one-launch tier copies the
+        state in one launch per part touched (``sfsn_hop_state_export``); the per-kernel sequence gathers the clips' rows with
+        stream-ordered copies.  The session is not changed: the clips go on here as well unless the caller resets them.  Ordered on
+        torch's current stream with no synchronisation, like ``reset(clips=...)``: the state is that behind every step queued so
+        far, and the call may return before the copy has run.  Not on resident sessions (``NotImplementedError``)."""
+        from .clip_state import ClipState, clip_list, gather_rows
+        if self.resident:
+            raise NotImplementedError("export_state: not on a resident session (resident=True): its launch holds the state while it runs")
+        idx = clip_list(clips, self.B, "export_state")
+        layout, nbytes = self._state_layout()
+        if self._hop is None:
+            sel = torch.tensor(idx, dtype=torch.long).to(self.dev, non_blocking=True)
+            blob = gather_rows(self._state_parts(), sel, nbytes, layout)
+        else:
+            # (no fill launch in front of the copy where the sections tile the row; the padding between sections reads as zero)
+            alloc = torch.empty if sum(b - a for _, a, b in layout) == nbytes else torch.zeros
+            blob = alloc((len(idx), nbytes), dtype=torch.uint8, device=self.dev)
+            st = ctypes.c_void_p(_raw_stream(self._dev_index))
+            for part, j0, local in self._part_runs(idx):
+                arr = (ctypes.c_int * len(local))(*local)
+                with torch.cuda.device(self.dev):
+                    rc = self.eng.lib.sfsn_hop_state_export(part["ref"], arr, len(local), ctypes.c_void_p(blob.data_ptr() + j0 * nbytes), st)
+                if rc:
+                    check(rc, "sfsn_hop_state_export")
+        stats = None
+        if self._stats is not None:
+            s = self._stats.select(idx)
+            stats = (s.mu_fb, s.mu_sb, s.sd_fb, s.sd_sb)
+        return ClipState(blob, self.clip_frames[idx], self.clip_calls[idx] if self.waveform else None, stats, self._state_signature(),
+                         layout)
+
+    def import_state(self, state, clips=None) -> None:
+        """Row i of ``state`` (an ``export_state`` result of a session of equal signature, on this session's device) becomes clip
+        ``clips[i]`` (``None``: every clip): whatever the slot held is replaced, ``clip_frames`` / ``clip_calls`` and, for a frozen
+        model with given statistics, the clip's statistics follow, and the next ``step`` continues the clip exactly where the
+        export left it -- bit for bit in both tiers, layer 0 included (the state is copied, not recomputed as by ``prime``).  All
+        other clips go on untouched.  Ordered on torch's current stream, no synchronisation: every step queued after it sees it.
+        The weights are NOT compared: importing into a session of another model of the same geometry is the caller's decision.
+        ``ValueError``: a signature mismatch (named), duplicate indices; ``IndexError``: an index out of range; ``TypeError``: wrong
+        types; ``RuntimeError``: a state on another device (``state.to(...)`` first), a row count other than ``len(clips)``;
+        ``NotImplementedError``: a resident session."""
+        from .clip_state import check_import, clip_list, scatter_rows
+        if self.resident:
+            raise NotImplementedError("import_state: not on a resident session (resident=True): its launch holds the state while it runs")
+        idx = clip_list(clips, self.B, "import_state")
+        check_import(state, idx, self.dev)
+        state.check_signature(self._state_signature())
+        layout, nbytes = self._state_layout()
+        if state.layout != layout or state.blob.shape[1] != nbytes:
+            raise ValueError("import_state: the state's blob layout is not this session's")
+        blob = state.blob.contiguous()
+        if self._stats is not None:
+            self.set_norm_stats(NormStats(*state.stats), clips=idx)
+        if self._hop is None:
+            sel = torch.tensor(idx, dtype=torch.long).to(self.dev, non_blocking=True)
+            scatter_rows(self._state_parts(), sel, blob, layout)
+            self._clip_f0[idx] = self.frames_done - state.frames
+            return
+        if self.waveform and self._wave_calls == 0:
+            # nobody has called yet, and the session's first call launches nothing: count it as made, with every other clip's
+            # utterance beginning at the next call (as prime_wave does)
+            self._wave_calls = 1
+            self._clip_c0[:] = 1
+            listed = set(idx)
+            for part in self._hop["parts"]:
+                others = [b - part["b0"] for b in range(part["b0"], part["b0"] + part["nb"]) if b not in listed]
+                for b0, m in self._runs(others):
+                    part["origin"][b0:b0 + m].fill_(self._as_i32(part["desc"].launch_index + 1))
+                part["desc"].clip_start = part["origin"].data_ptr()
+        st = ctypes.c_void_p(_raw_stream(self._dev_index))
+        for part, j0, local in self._part_runs(idx):
+            arr = (ctypes.c_int * len(local))(*local)
+            with torch.cuda.device(self.dev):
+                rc = self.eng.lib.sfsn_hop_state_import(part["ref"], arr, len(local), ctypes.c_void_p(blob.data_ptr()), j0, st)
+            if rc:
+                check(rc, "sfsn_hop_state_import")
+            # the clips' origins (include/sfsn.h): the next launch gives each the frame index it had at export.  Fills behind the
+            # queued launches, as in _reset_clips
+            ages = [int(state.calls[j0 + i]) - 1 if self.waveform else int(state.frames[j0 + i]) // self.hop for i in range(len(local))]
+            i = 0
+            while i < len(local):  # (one fill per run of consecutive clips of one age: clips that moved together)
+                m = 1
+                while i + m < len(local) and local[i + m] == local[i] + m and ages[i + m] == ages[i]:
+                    m += 1
+                part["origin"][local[i]:local[i] + m].fill_(self._as_i32(part["desc"].launch_index - ages[i]))
+                i += m
+            part["desc"].clip_start = part["origin"].data_ptr()
+        if self.waveform:
+            self._clip_c0[idx] = self._wave_calls - state.calls
+            self._primed = True  # the launch mutes each clip by its own frame index (see step_wave)
+        else:
+            self._clip_f0[idx] = self.frames_done - state.frames
 
     @property
     def clip_frames(self) -> np.ndarray:
