@@ -2540,6 +2540,7 @@ extern "C" int sfsn_gsn_layer_scan_fused(const sfsn_scan_segment* segs, const sf
         const bool tl = (H & 63) != 0 && (H & 63) <= 32;
         const int lds3 = KS == 3 ? Scan3jCfg<3>::lds_bytes(p.NT) : Scan3jCfg<4>::lds_bytes(p.NT);
         p.lsplit = sfsn_knob("SFSN_S3J_LSPLIT", SFSN_S3J_LSPLIT, 0, 14);  // fp32 store instructions per frame the loader wave takes (A/B runs)
+        p.stagger = s3j_stagger();
 #define FUSED3_CASE(KS_, TL_, OUT_)                                                                                        \
     if (KS == KS_ && (int)tl == TL_ && out == OUT_ && lds3 <= 160 * 1024 - 64) {                                           \
         p.wg_times = sfsn_wgprobe_take(2, tiles);                                                                          \
@@ -2596,6 +2597,7 @@ extern "C" int sfsn_gsn_layer_scan_fused_x(const sfsn_scan_segment* segs, const 
         const bool tl = (H & 63) != 0 && (H & 63) <= 32;
         const int lds3 = KS == 3 ? Scan3yCfg<3, 2>::lds_bytes(p.NT) : Scan3yCfg<4, 2>::lds_bytes(p.NT);
         p.lsplit = sfsn_knob("SFSN_S3Y_LSPLIT", SFSN_S3Y_LSPLIT, 0, 14);
+        p.stagger = s3j_stagger();
 #define FUSEDX3_CASE(KS_, TL_, OUT_)                                                                                       \
     if (KS == KS_ && (int)tl == TL_ && out == OUT_ && lds3 <= 160 * 1024 - 64) {                                           \
         p.wg_times = sfsn_wgprobe_take(3, tiles);                                                                          \
@@ -2645,6 +2647,7 @@ extern "C" int sfsn_gsn_layer_scan_l0(const sfsn_scan_segment* segs_x, const sfs
     for (int i = 0; i < n_z; ++i) p.seg[n_x + i] = zdev[i];
     p.nseg = n_x + n_z; p.T = T; p.H = H;
     p.lsplit = sfsn_knob("SFSN_S3Y_LSPLIT", SFSN_S3Y_LSPLIT, 0, 14);  // the fused-x role's own value (round 2's body has no such knob)
+    p.stagger = s3j_stagger();
     const int KS = (H + 63) / 64;
     const bool tl = (H & 63) != 0 && (H & 63) <= 32;
     hipStream_t st = static_cast<hipStream_t>(stream);

@@ -20,29 +20,29 @@ __device__ __forceinline__ int scan_segment_of(const ScanParams& p, int block) {
     return s;
 }
 
-__device__ __forceinline__ Scan3yRole scan3y_role_of(const ScanSegDev& sg, int row0, int lsplit) {
+__device__ __forceinline__ Scan3yRole scan3y_role_of(const ScanSegDev& sg, int row0, int lsplit, int stagger) {
     Scan3yRole rl;
     rl.x = sg.x_in; rl.w_ih = sg.w_ih_f32; rl.I = sg.I; rl.w_hh = sg.w_hh; rl.w_dq = sg.w_dq; rl.bias = sg.bias;
     rl.bn_alpha = sg.bn_alpha; rl.bn_beta = sg.bn_beta; rl.h_state = sg.h_state; rl.c_state = sg.c_state;
     rl.spikes_f32 = sg.spikes_f32; rl.spikes_i8 = sg.spikes_i8; rl.R = sg.R; rl.row0 = row0;
-    rl.count = sg.count; rl.lsplit = lsplit;
+    rl.count = sg.count; rl.lsplit = lsplit; rl.stagger = stagger;
     return rl;
 }
 
-__device__ __forceinline__ Scan3jRole scan3j_role_of(const ScanSegDev& sg, int row0, int lsplit) {
+__device__ __forceinline__ Scan3jRole scan3j_role_of(const ScanSegDev& sg, int row0, int lsplit, int stagger) {
     Scan3jRole rl;
     rl.spikes_in = sg.spikes_in; rl.w_ih = sg.w_ih; rl.w_ih_dq = sg.w_ih_dq; rl.w_hh = sg.w_hh; rl.w_dq = sg.w_dq; rl.bias = sg.bias;
     rl.bn_alpha = sg.bn_alpha; rl.bn_beta = sg.bn_beta; rl.h_state = sg.h_state; rl.c_state = sg.c_state;
     rl.spikes_f32 = sg.spikes_f32; rl.spikes_i8 = sg.spikes_i8; rl.R = sg.R; rl.row0 = row0;
-    rl.count = sg.count; rl.lsplit = lsplit;
+    rl.count = sg.count; rl.lsplit = lsplit; rl.stagger = stagger;
     return rl;
 }
 
-// A segment with feature rows, its 16 rows from row0: scan3y_role.  p0.lsplit is that role's.
+// A segment with feature rows, its 16 rows from row0: scan3y_role.  p0.lsplit and p0.stagger are that role's.
 // (the k-chunk count is compile time: a wave-uniform `if` around operand loads makes hipcc drain lgkmcnt at every merge)
 template <int KS, int TL, int OUT, bool PUB>
 __device__ __forceinline__ void scan3y_role16(const ScanParams& p0, const ScanSegDev& sg, int row0, char* smem, const StackLink* lk) {
-    const Scan3yRole rl = scan3y_role_of(sg, row0, p0.lsplit);
+    const Scan3yRole rl = scan3y_role_of(sg, row0, p0.lsplit, p0.stagger);
     if (sg.I > 32) scan3y_role<KS, TL, OUT, 2, PUB>(rl, smem, p0.T, p0.H, p0.NT, lk);
     else scan3y_role<KS, TL, OUT, 1, PUB>(rl, smem, p0.T, p0.H, p0.NT, lk);
 }
@@ -74,11 +74,11 @@ __device__ __forceinline__ void layer0_role16(const ScanParams& p0, int block, c
     }
 }
 
-// Layer 1 (any layer with a fused input), block `block1` of p1: scan3j_role.  OFF / GATED / PUB: its forms; p1.lsplit is its own.
+// Layer 1 (any layer with a fused input), block `block1` of p1: scan3j_role.  OFF / GATED / PUB: its forms; p1.lsplit and p1.stagger are its own.
 template <int KS, int TL, int OUT, int OFF, bool GATED, bool PUB>
 __device__ __forceinline__ void layer1_role16(const ScanParams& p1, int block1, char* smem, const StackLink* lk) {
     const ScanSegDev& sg = p1.seg[scan_segment_of(p1, block1)];
-    const Scan3jRole rl = scan3j_role_of(sg, (block1 - sg.tile0) * 16, p1.lsplit);
+    const Scan3jRole rl = scan3j_role_of(sg, (block1 - sg.tile0) * 16, p1.lsplit, p1.stagger);
     scan3j_role<KS, TL, OUT, OFF, GATED, PUB>(rl, smem, p1.T, p1.H, p1.NT, lk);
 }
 #endif

@@ -34,6 +34,47 @@
 #define SFSN_S3J_LSPLIT 6
 #endif
 
+// ---- the stagger of a SIMD's compute waves (both roles of this file) -------------------------------------------------------------
+// A 1024-thread workgroup puts waves w, w + 4, w + 8, w + 12 on one SIMD (scripts/micro/wave_simd_map.hip): a wave's slot is wave >> 2,
+// and the waves of one slot sit on four different SIMDs.  Every compute wave runs the same three blocks per step -- R (recurrent
+// matrix instructions), E (epilogue, vector), P (input product of the next frame, matrix + a short vector tail) -- and with one order
+// for all of them a SIMD's four waves multiply together and then run their epilogues together.  Two masks over the slots, carried in
+// Scan3jRole / Scan3yRole::stagger:
+//   order (bits 0-3): a slot in the mask passes the step barrier BEFORE its input product instead of behind it.  Its sequence
+//       B P(0) R(0) E(0) B P(1) R(1) E(1) B ... is the other slots' B P(0) R(0) E(0) P(1) B R(1) E(1) P(2) B ... with every barrier one
+//       block earlier: between two barriers it runs P R E ("head order": the input term of frame t at the head of step t) beside
+//       the others' R E P.  The same instructions on the same operands in both orders, the same number of barriers in prologue,
+//       loop and tail (one per step, whichever side of P), no second loop body and no register.  A head-order wave ends with one
+//       surplus product behind the last barrier (a landed slot, the value unused).
+//       Ring-slot lifetime: a head-order wave reads frame t's slot BETWEEN the barriers of steps t - 1 and t, one step later than the
+//       others.  scan3j_role: the loader requests frame t + A during step t into slot (t + A) % D = (t - 1) % D (D = A + 1), so frame
+//       t's slot is next written by the request of loader step t + 1, which the loader issues behind the barrier of step t -- the one
+//       the head-order wave passes only with its reads of that slot complete (lgkmcnt(0) in front of every barrier).  Frame t landed
+//       before the barrier of step t - 2 (the loader's counted wait).  scan3y_role: loader step t converts frame t + 3 into plane
+//       slot (t + 3) % DP = (t - 2) % DP; frame t's planes (written at step t - 3) are next overwritten by the conversion of loader
+//       step t + 2: two barriers behind the read.  The prologue's frames: loader step 0 writes slot A (planes: slot 3), never frame 0's.
+//       The OFF form (served tiles, mailbox hand-off at the barrier) keeps the barrier behind the product for every slot.
+//   priority (bits 4-7): a slot in the mask runs one s_setprio 1 before its main loop (VALU issue is arbitrated by priority, then age).
+// SFSN_S3J_STAGGER=<order mask>[,<priority mask>] in the environment is read on every call (A/B runs, tests/test_scan_stagger.py);
+// 0 keeps every slot's barrier behind the product and sets no priority (the order before the stagger).  Measured: profiles/scan_stagger.md.
+// Default: slot 3 in head order AND at priority 1 -- compute waves 12 and 13, the fourth tiles of the two SIMDs that carry four (the
+// other two SIMDs carry three tiles and an IO wave).  B = 64, T = 1000, alone on the chip, fp32 spikes, ms per launch, setting 0 ->
+// default: the layers 0 + 1 + epilogue launch 1.568 -> 1.523, scan3y_role alone 1.354 -> 1.316, scan3j_role alone 1.318 -> 1.340
+// (that role alone prefers the order without the priority: 1.265; inside the gated launch it trails layer 0).
+#ifndef SFSN_S3J_STAGGER_ORDER
+#define SFSN_S3J_STAGGER_ORDER 8
+#endif
+#ifndef SFSN_S3J_STAGGER_PRIO
+#define SFSN_S3J_STAGGER_PRIO 8
+#endif
+
+// A wave-uniform flag as the compiler may not see through it: the test at each use stays one scalar compare in front of its branch.
+// (Tested once outside the loop, the flag becomes a lane mask that every trip turns into the second branch's with two vector instructions.)
+__device__ __forceinline__ int s3j_opaque(int x) {
+    asm volatile("" : "+s"(x));
+    return x;
+}
+
 template <int KS>
 struct Scan3jCfg {
     static constexpr int RPW = 16, HP = KS * 64, LDH = HP + 32, NCH = HP / 16;
@@ -176,6 +217,7 @@ struct Scan3jRole {
     int R, row0;
     unsigned long long* count;  // nullable: a launch without fp32 spikes adds the number of spikes it wrote
     int lsplit;                 // fp32 store instructions per frame issued by the loader wave (the storer takes the rest)
+    int stagger;                // bits 0-3: wave slots in head order, bits 4-7: wave slots at priority 1 (file head)
 };
 
 // TL = 1: H mod 64 in (0, 32]: the last k-step of the RECURRENT product is one 16x16x32 instruction (scan3i_role's form).
@@ -260,6 +302,7 @@ __device__ __forceinline__ void scan3j_role(const Scan3jRole& rl, char* smem, in
         v4f z = {0.f, 0.f, 0.f, 0.f};                 // the input term of my four values at the NEXT frame to be finished
 
         const bool served = OFF && ct >= 12;  // (wave-uniform) my input terms come from an IO wave's mailbox
+        const int head = OFF ? 0 : (rl.stagger >> (wave >> 2)) & 1;  // (wave-uniform) my slot passes the step barrier before the product
         const char* mbox = smem + C::mbox_off(NT) + (ct >= 12 ? ct - 12 : 0) * 1024 + lane * 16;
         unsigned slot = 0;                    // (wave-uniform) the ring slot of the next frame to be finished, as a byte offset
         auto in_product = [&]() __attribute__((always_inline)) {
@@ -313,14 +356,22 @@ __device__ __forceinline__ void scan3j_role(const Scan3jRole& rl, char* smem, in
             }
             *reinterpret_cast<unsigned*>(hn + hoff) = pk;
             __builtin_amdgcn_sched_barrier(0);
-            // off the chain: the input term of the next frame (the loader clamps frames past the end to the last one: harmless work)
+            // off the chain: the input term of the next frame (the loader clamps frames past the end to the last one: harmless work),
+            // the step barrier in front of it (head order) or behind it: one barrier per step either way (file head)
+            if (s3j_opaque(head) != 0) {
+                __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
+                __builtin_amdgcn_s_barrier();
+            }
             if (!served) in_product();
-            __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
-            __builtin_amdgcn_s_barrier();
+            if (s3j_opaque(head) == 0) {
+                __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
+                __builtin_amdgcn_s_barrier();
+            }
         };
 
         __syncthreads();                       // initial state in hbuf[0], W_ih planes and constants in LDS
         __builtin_amdgcn_s_barrier();          // the loader's prologue frames (0 .. A - 1) have landed
+        if ((rl.stagger >> (4 + (wave >> 2))) & 1) __builtin_amdgcn_s_setprio(1);  // once, never flipped
         if (!served) in_product();
         if constexpr (OFF) {
             __builtin_amdgcn_s_waitcnt(0xc07f);
@@ -537,6 +588,7 @@ struct Scan3yRole {
     int R, row0;
     unsigned long long* count;
     int lsplit;
+    int stagger;          // as Scan3jRole::stagger
 };
 
 // PUB = 1 (gsn_scan_l01_kernel, sfsn_pair16.hip): the int8 rows feed a workgroup of the SAME launch.  The storer wave writes them through
@@ -622,6 +674,7 @@ __device__ __forceinline__ void scan3y_role(const Scan3yRole& rl, char* smem, in
         const unsigned xoff = (unsigned)(C::PL_OFF + (n * LDX + q * 8) * 2);  // my B fragment: row n, k = 32 ks + 8 q .. + 7 of a plane
         const char* cq = smem + C::CST_OFF + cj * 4;
         v4f z = {0.f, 0.f, 0.f, 0.f};
+        const int head = (rl.stagger >> (wave >> 2)) & 1;  // (wave-uniform) my slot passes the step barrier before the product
         // the input term of the next frame to be finished (plane slot frame % DP, carried as a wave-uniform byte offset) -> z: the product
         // sequence of input_proj_bf3_kernel, instruction for instruction
         unsigned pslot = 0;
@@ -690,13 +743,20 @@ __device__ __forceinline__ void scan3y_role(const Scan3yRole& rl, char* smem, in
             }
             *reinterpret_cast<unsigned*>(hn + hoff) = pk;
             __builtin_amdgcn_sched_barrier(0);
+            if (s3j_opaque(head) != 0) {         // (one barrier per step on either side of the product: scan3j_role)
+                __builtin_amdgcn_s_waitcnt(0xc07f);
+                __builtin_amdgcn_s_barrier();
+            }
             in_product();                        // off the chain (frames past the end: the loader converts clamped copies of the last one)
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-            __builtin_amdgcn_s_barrier();
+            if (s3j_opaque(head) == 0) {
+                __builtin_amdgcn_s_waitcnt(0xc07f);
+                __builtin_amdgcn_s_barrier();
+            }
         };
 
         __syncthreads();                       // initial state, W_ih pieces 2 / 3 and constants in LDS
         __builtin_amdgcn_s_barrier();          // the loader's planes of frames 0 .. 2
+        if ((rl.stagger >> (4 + (wave >> 2))) & 1) __builtin_amdgcn_s_setprio(1);
         in_product();
         // two steps per trip; an odd T ends with one more step on buffer 0
         int t = 0;

@@ -52,6 +52,8 @@ struct ScanParams {
     int rpw;             // rows per workgroup (16, 8 or 4): fewer rows per CU = less HBM traffic per CU per step
     int w16;             // 1: 16-bit weights, digit plane 0 is zero (sfsn_gsn_layer_scan_w16): the scan3 kernels skip it
     int lsplit;          // 8-row IO-wave scans: fp32 store instructions per frame issued by the loader wave (SFSN_S3_LSPLIT)
+    int stagger;         // 16-row IO-wave roles only (sfsn_scan3j_dev.h, SFSN_S3J_STAGGER): bits 0-3 the wave slots in head order, bits 4-7
+                         // those at priority 1.  It sits in what was padding: no other member moves and no other kernel reads it
     unsigned long long* wg_times;  // EXPERIMENTS builds: [2 x workgroups] 100 MHz stamps of every workgroup's first and last instruction
 };
 

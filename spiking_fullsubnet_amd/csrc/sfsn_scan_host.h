@@ -67,6 +67,17 @@ static inline bool s3j_off_form(int NT, int KS, bool tl, int out) {
     const int offm = getenv("SFSN_S3J_OFF") ? atoi(getenv("SFSN_S3J_OFF")) : 1;
     return NT == 14 && KS == 4 && tl && (offm == 2 || (offm == 1 && out == 2));
 }
+// The stagger of the 16-row roles' compute waves (sfsn_scan3j_dev.h): wave slots in head order (bits 0-3) and at priority 1 (bits
+// 4-7).  SFSN_S3J_STAGGER=<order mask>[,<priority mask>] is read on every call, in every build (tests switch it inside one process).
+static inline int s3j_stagger() {
+    int order = SFSN_S3J_STAGGER_ORDER, prio = SFSN_S3J_STAGGER_PRIO;
+    if (const char* e = getenv("SFSN_S3J_STAGGER")) {
+        char* end = nullptr;
+        order = (int)strtol(e, &end, 0);
+        prio = (end && *end == ',') ? (int)strtol(end + 1, nullptr, 0) : 0;
+    }
+    return (order & 15) | ((prio & 15) << 4);
+}
 // Dynamic LDS of a layer-0 workgroup (the larger of scan3y_role's layout and round 2's), and of a workgroup that may run any role of
 // a layers 0+1 launch or `more` bytes of another one (rounded to 16: the exit word sits behind it).
 template <int KS, int OUT>
@@ -145,6 +156,7 @@ static inline int pair_lists_together(PairLists& pl, int T, int H, const void* s
     p1.nseg = pl.n0; p1.T = T; p1.H = H; p1.NT = pl.NT;
     p0.lsplit = sfsn_knob("SFSN_S3Y_LSPLIT", SFSN_S3Y_LSPLIT, 0, 14);
     p1.lsplit = sfsn_knob("SFSN_S3J_LSPLIT", SFSN_S3J_LSPLIT, 0, 14);
+    p0.stagger = p1.stagger = s3j_stagger();
     pl.KS = (H + 63) / 64;
     pl.tl = (H & 63) != 0 && (H & 63) <= 32;
     // layer 1 as sfsn_gsn_layer_scan_fused launches it
