@@ -712,6 +712,76 @@ typedef struct sfsn_prime_src {
 int sfsn_hop_prime(const sfsn_hop_desc* desc /* host */, const int* clips /* host */, int n_clips, const sfsn_prime_src* src /* host */,
                    void* stream);
 
+/* A backlog on a clip that is ALREADY RUNNING (csrc/sfsn_prime.hip): N new frames through the OFFLINE kernels, started from the state
+ * the session carries instead of from zero, and their end state handed back -- what N / hop launches of sfsn_stream_hop would have
+ * computed and left, at offline speed.  Two launches around the offline kernels, for the listed clips of the descriptor only
+ * (distinct indices, 1 <= n_clips <= 256); every other clip's rows, the tagged scratch (spikes, spec_g, enh_g) and launch_index are
+ * left as they are.  Plain loads and stores, no atomics, nothing waits; ordered on `stream` like any launch.  k = desc->launch_index.
+ *
+ * sfsn_hop_seed: the offline kernels' START tensors, rows b0 + i of tensors of Bp clips for clips[i]:
+ *   layer.h   <- h[k & 1] as fp32 0 / 1 [Bp * n_units][H] (a scan's h_state), layer.c <- c (its c_state);
+ *   cum       <- cum[k & 1], the rows' running sums (sfsn_cum_laplace_norm's cum_state; its frames_before is (k - clip_start) * hop);
+ *   stft_ri   <- frames [0, D) of every row [F][T][2] = hist_ri, the last D noisy frames (zeros for the bins the hop keeps no history
+ *                of: no group covers them, nobody reads them).  The caller puts the N new frames at [T - N, T), T >= D + N, and runs
+ *                the offline stages on those frames of the buffer, so that the deep filter reaches back into real history;
+ *   wave_ctx  <- waveform mode: wave_state[128 .. 512), the 384 samples the next frame begins with, at the front of a row of
+ *                wave_stride floats (the caller appends the new samples: frame j of the backlog is the centred frame j + 2 of that
+ *                row on sfsn_stft).
+ * desc->clip_start is read: a clip whose origin equals k (a restarted or never-stepped clip: the hop reads its state as zero in launch
+ * k, whatever memory holds) is written as zeros everywhere but wave_ctx (its first call has left [0 x 384 | samples] in wave_state).
+ *
+ * sfsn_hop_advance: the continuing form of sfsn_hop_prime.  `src` holds the offline kernels' results for the N new frames:
+ *   layer.h[k & 1], layer.c, cum[k & 1] <- row N - 1 of spikes_i8, c, cum (the end state of the backlog);
+ *   hist_ri     <- the last D frames of stft_ri's rows of T frames, [history | new]: N < D keeps the tail of the old history;
+ *   spike_slots <- ADDED to: slot (row, j) += the spikes of neurons 4j .. 4j + 3 of `row` over the N frames (a clip whose origin
+ *                  equals k: replaced, the hop reads its slot as zero);
+ *   wave_state  <- wave_tail, the last 512 input samples; ola_state <- continued in the hop's order: the carried partial sums first
+ *                  (zero for a clip whose origin equals k), then frames T - N .. T - 1 of enh_ri's rows in ascending order
+ *                  (sfsn_hop_wave_dev.h's arithmetic and envelope); wave_out[b0 + i][s][128 j ..] <- the block launch k + j would
+ *                  have written (zero while the clip's frame index k + j - clip_start is < 2).
+ * The caller then moves clip_start[clips[i]] back by N / hop (unsigned, wrap-safe) with a stream-ordered device operation behind the
+ * queued launches: launch k continues at the clip's frame index + N / hop.  For a clip whose origin was k that is k - N / hop,
+ * sfsn_hop_prime's formula.  clip_start == NULL: no clip is fresh, frame indices come from desc->frame_index.
+ *
+ * Exactness: sfsn_hop_prime's one reservation and no other.  The layer-0 membranes written back are the offline kernels', which
+ * differ from the hop's in their low bits (the layer-0 input product sums in another association).  Where no layer-0 membrane of the
+ * backlog lies within that rounding of the threshold, every spike, every higher-layer membrane, every output and every count is that
+ * of the launch sequence, bit for bit.
+ * SFSN_EINVAL, before any launch: a NULL desc / clips / dst / src, n_clips < 1, an index outside [0, desc->B) or listed twice,
+ * b0 + n_clips > Bp, N % hop != 0, N < hop, T < D + N (seed: T < D), wave_stride < 384, a missing or misaligned pointer (h, c: 16
+ * bytes; stft_ri, enh_ri, wave_out: 8; the others: 4).  SFSN_EUNSUPPORTED: a descriptor sfsn_stream_hop refuses, more than 256
+ * listed clips (the caller splits the list), B > 65535.  (Added without an ABI bump: no existing struct or signature changed.) */
+typedef struct sfsn_seed_layer {
+    float* h;                /* [Bp * n_units][H] fp32 0 / 1 */
+    float* c;                /* [Bp * n_units][H]            */
+} sfsn_seed_layer;
+typedef struct sfsn_seed_seq {
+    sfsn_seed_layer layer[SFSN_HOP_MAX_LAYERS];
+    float* cum;              /* SFSN_NORM_CUMLAPLACE: [Bp * n_units]; NULL otherwise */
+} sfsn_seed_seq;
+typedef struct sfsn_seed_dst {
+    int Bp, T, b0;
+    int wave_stride;         /* waveform mode: floats per row of wave_ctx (>= 384)                   */
+    float* stft_ri;          /* [Bp][F][T][2]: frames [0, D) are written (NULL if D == 0)            */
+    float* wave_ctx;         /* waveform mode: [Bp][wave_stride], samples [0, 384) are written       */
+    sfsn_seed_seq fb;
+    sfsn_seed_seq sb[SFSN_HOP_MAX_GROUPS];
+} sfsn_seed_dst;
+typedef struct sfsn_advance_src {
+    int Bp, N, b0;
+    int T;                   /* frames per row of stft_ri / enh_ri; the N new frames are the last ones  */
+    const float* stft_ri;    /* [Bp][F][T][2] [history | new] (NULL if D == 0)                          */
+    const float* enh_ri;     /* waveform mode: [Bp][S][F][T][2] the enhanced frames                     */
+    const float* wave_tail;  /* waveform mode: [Bp][512] the last 512 input samples                     */
+    float* wave_out;         /* waveform mode: [Bp][S][128 * N] out                                     */
+    sfsn_prime_seq fb;       /* spikes_i8: the N new frames' [N][Bp * n_units][pad64(H)]; c, cum: after the last one */
+    sfsn_prime_seq sb[SFSN_HOP_MAX_GROUPS];
+} sfsn_advance_src;
+int sfsn_hop_seed(const sfsn_hop_desc* desc /* host */, const int* clips /* host */, int n_clips, const sfsn_seed_dst* dst /* host */,
+                  void* stream);
+int sfsn_hop_advance(const sfsn_hop_desc* desc /* host */, const int* clips /* host */, int n_clips, const sfsn_advance_src* src /* host */,
+                     void* stream);
+
 /* Moving a clip (csrc/sfsn_state.hip): the carried state of the listed clips out into a self-contained blob per clip, and from such a
  * blob into the listed clips of this or another descriptor of the same geometry -- ONE launch each way, ordered on `stream` like any
  * launch, plain stores, nothing waits inside it.  The state is COPIED, not recomputed, so a moved clip continues bit for bit, layer 0

@@ -120,6 +120,24 @@ class PrimeSrc(ctypes.Structure):  # sfsn_prime_src
                 ("sb", PrimeSeq * HOP_MAX_GROUPS)]
 
 
+class SeedLayer(ctypes.Structure):  # sfsn_seed_layer
+    _fields_ = [("h", _P), ("c", _P)]
+
+
+class SeedSeq(ctypes.Structure):  # sfsn_seed_seq
+    _fields_ = [("layer", SeedLayer * HOP_MAX_LAYERS), ("cum", _P)]
+
+
+class SeedDst(ctypes.Structure):  # sfsn_seed_dst
+    _fields_ = [("Bp", _I), ("T", _I), ("b0", _I), ("wave_stride", _I), ("stft_ri", _P), ("wave_ctx", _P), ("fb", SeedSeq),
+                ("sb", SeedSeq * HOP_MAX_GROUPS)]
+
+
+class AdvanceSrc(ctypes.Structure):  # sfsn_advance_src
+    _fields_ = [("Bp", _I), ("N", _I), ("b0", _I), ("T", _I), ("stft_ri", _P), ("enh_ri", _P), ("wave_tail", _P), ("wave_out", _P),
+                ("fb", PrimeSeq), ("sb", PrimeSeq * HOP_MAX_GROUPS)]
+
+
 FULLBAND_HOP_MAX_LAYERS = 4
 
 
@@ -296,6 +314,10 @@ def lib() -> ctypes.CDLL:
     L.sfsn_stream_hop.argtypes = [ctypes.POINTER(HopDesc), _P]
     L.sfsn_hop_prime.restype = _I
     L.sfsn_hop_prime.argtypes = [ctypes.POINTER(HopDesc), ctypes.POINTER(_I), _I, ctypes.POINTER(PrimeSrc), _P]
+    L.sfsn_hop_seed.restype = _I  # desc, clips, n_clips, dst, stream
+    L.sfsn_hop_seed.argtypes = [ctypes.POINTER(HopDesc), ctypes.POINTER(_I), _I, ctypes.POINTER(SeedDst), _P]
+    L.sfsn_hop_advance.restype = _I  # desc, clips, n_clips, src, stream
+    L.sfsn_hop_advance.argtypes = [ctypes.POINTER(HopDesc), ctypes.POINTER(_I), _I, ctypes.POINTER(AdvanceSrc), _P]
     L.sfsn_hop_state_bytes.restype = ctypes.c_size_t  # per clip; 0: a descriptor the hop refuses (host only)
     L.sfsn_hop_state_bytes.argtypes = [ctypes.POINTER(HopDesc)]
     L.sfsn_hop_state_export.restype = _I  # desc, clips, n_clips, blob, stream
@@ -395,7 +417,7 @@ EXPORTS = ("sfsn_abi_version", "sfsn_source_hash", "sfsn_strerror", "sfsn_device
            "sfsn_pit_sdr_ragged", "sfsn_gsn_layer_scan_l01", "sfsn_recipe_loss_ragged_scratch_bytes", "sfsn_recipe_loss_ragged",
            "sfsn_fullband_proj_deepfilter_ragged", "sfsn_hop_prime", "sfsn_gsn_layer_scan_l01_projdf",
            "sfsn_hop_state_bytes", "sfsn_hop_state_export", "sfsn_hop_state_import", "sfsn_fullband_hop_state_bytes",
-           "sfsn_fullband_hop_state_export", "sfsn_fullband_hop_state_import")
+           "sfsn_fullband_hop_state_export", "sfsn_fullband_hop_state_import", "sfsn_hop_seed", "sfsn_hop_advance")
 
 
 def check(rc: int, what: str = "") -> None:

@@ -522,6 +522,8 @@ class _Forward:
     x_skipped: dict = field(default_factory=lambda: dict(fb=set(), sb=set()))  # feature rows a fused feature launch did not write
     proj_skipped: bool = False  # the fused epilogue ran and left the coefficient rows unwritten
     epi_chunk: Optional[tuple] = None  # (t0, nt) of the sub-band chunk whose epilogue ran inside its scan launch (_stage_scan_l01)
+    lead: int = 0            # a forward with a start (_start_buffers): history frames in front of the new ones; the stages run behind them
+    frames_before: int = 0   # ... and the frames the clips had seen before (cumulative_laplace_norm's denominator)
 
     def link(self, src, dst) -> None:
         """dst waits for everything enqueued on src so far (no-op on the sequential path)."""
@@ -1159,6 +1161,23 @@ class Engine:
             out.append(row)
         return out
 
+    def _start_buffers(self, n: int, N: int, lead: int, frames_before: int = 0) -> dict:
+        """The start of a forward that continues ``n`` running clips by ``N`` frames (``forward_stft(start["stft"], _end_state=start)``),
+        for the caller to fill: ``fb`` / ``sb``: ``[l][i] = (h, c)`` of layer l, sequence model i as the scans take them (fp32 0 / 1
+        spikes, membranes; views of ``state_flat``, the forward's state buffer); ``cum``: the running sums per sequence model
+        (cumulative_laplace_norm, else None); ``stft``: complex64 [n, F, lead + N], ``lead`` frames of history and the new frames."""
+        spec, dev = self.spec, self.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        Rs = [n * spec.units(g) for g in range(spec.n_groups)]
+        n_fb = 2 * spec.fb_layers * n * self.fb.H
+        n_sb = 2 * spec.sb_layers * sum(Rs) * self.sb[0].H
+        flat = torch.empty((n_fb + n_sb,), **f32)
+        return dict(state_flat=flat, fb=self._zero_states([n], self.fb.H, spec.fb_layers, flat[:n_fb]),
+                    sb=self._zero_states(Rs, self.sb[0].H, spec.sb_layers, flat[n_fb:]),
+                    cum=[torch.empty((R,), **f32) for R in [n] + Rs] if spec.cum_laplace else None,
+                    stft=torch.empty((n, spec.n_fft // 2 + 1, lead + N), dtype=torch.complex64, device=dev),
+                    lead=lead, frames_before=frames_before)
+
     def _alloc_stack(self, seqs, Rs, T, nt_max, want_layers, want_membrane, tag, state_flat=None, counts=None):
         """Per-forward tensors of a stack of sequence models sharing (H, L): API outputs are fresh, scratch is cached."""
         dev, H, G, nl = self.device, seqs[0].H, seqs[0].cells[0].G, len(seqs[0].cells)
@@ -1299,11 +1318,16 @@ class Engine:
 
     def forward_stft(self, stft: torch.Tensor, want_layers: bool = True, want_membrane: bool = False, pipeline: Optional[bool] = None,
                      want_counts: bool = False, norm_stats: Optional[NormStats] = None, return_norm_stats: bool = False,
-                     frames=None, frames_dev: Optional[torch.Tensor] = None, _end_state: bool = False) -> dict:
+                     frames=None, frames_dev: Optional[torch.Tensor] = None, _end_state=False) -> dict:
         """See ``_forward_stft``; runs with this engine's device current (the C ABI launches on the calling thread's device).
 
         ``_end_state`` (internal: ``StreamingSession.prime``) -- the result also carries ``"end_state"``, what the forward leaves behind
-        its last frame (``_end_state_of``); not with ``frames``.
+        its last frame (``_end_state_of``); not with ``frames``.  A START instead of ``True`` (internal: ``StreamingSession.advance``;
+        the dict ``_start_buffers`` made, filled by the caller): the forward continues clips that are already running.  ``stft`` is
+        then the start's ``[lead + N]``-frame buffer -- ``lead`` frames of history in front of the N new ones -- and the stages run
+        on frames ``[lead, lead + N)`` of it from the start's (h, c) per layer and sequence model, its cumulative sums and
+        ``frames_before``, so that the deep filter reaches back into real history; the first feature launch does not zero the state
+        buffer; the results are those of the N new frames.  Without a start the launches are exactly the same as ever.
 
         ``frames`` -- a ragged batch (``ragged.py``): a length-B sequence of ints, clip b has ``frames[b]`` frames
         (``1 <= frames[b] <= T``; ``ValueError`` otherwise) and the rest of its row is padding.  The launches of the model are the
@@ -1347,7 +1371,7 @@ class Engine:
 
     def _forward_stft(self, stft: torch.Tensor, want_layers: bool = True, want_membrane: bool = False, pipeline: Optional[bool] = None,
                       want_counts: bool = False, norm_stats: Optional[NormStats] = None, frames=None, frames_dev=None,
-                      end_state: bool = False) -> dict:
+                      end_state=False) -> dict:
         """complex64 [B, n_fft/2+1, T] on the device -> dict(enh_stft [B,S,F,T] complex64, enh_mag [B,S,F,T],
         fb_all, sb_all (the reference's all_layer_outputs lists; spike entries are None when want_layers=False)).
 
@@ -1364,15 +1388,23 @@ class Engine:
         self._defer_err = None  # (a forward that raised half way must not leave the next one's error words uncollected)
         want_layers = want_layers or want_membrane  # membranes are a test output of the fp32-spike kernel variant
         B, F, T = self._validate(stft)
-        plan = plan_forward(spec, B, T, pipeline, self.n_cu, want_membrane, pipeline_default=self.pipeline_default,
+        start = end_state if isinstance(end_state, dict) else None
+        lead = 0 if start is None else int(start["lead"])
+        if start is not None and (stft.data_ptr() != start["stft"].data_ptr() or tuple(stft.shape) != tuple(start["stft"].shape) or T <= lead):
+            raise ValueError("_end_state: a start runs on its own [history | new] buffer (Engine._start_buffers)")
+        plan = plan_forward(spec, B, T - lead, pipeline, self.n_cu, want_membrane, pipeline_default=self.pipeline_default,
                             pipeline_chunk=self.pipeline_chunk, seq_chunk=self.seq_chunk, overlap_chunks=self.overlap_chunks,
                             overlap_fracs=self.overlap_fracs, overlap_first=self.overlap_first, rows_per_wg=self.rows_per_wg,
                             fuse_input=self.fuse_input, stack_scan=self.stack_scan, stack_rows_per_wg=self.stack_rows_per_wg,
                             stack_wide=self.stack_wide, stack_rows_fb_auto=self.stack_rows_fb_auto, pair_scan=self.pair_scan)
-        f = self._alloc_forward(stft, plan, want_layers, want_membrane, want_counts, norm_stats, frames, frames_dev)
+        if lead:  # the chunks of the N new frames, behind the history
+            plan = plan._replace(bounds=tuple((t0 + lead, nt) for t0, nt in plan.bounds))
+        f = self._alloc_forward(stft, plan, want_layers, want_membrane, want_counts, norm_stats, frames, frames_dev, start)
         self._open_streams(f)
         fbm, sbm, gs_sb = f.fbm, f.sbm, f.gstreams[spec.fb_layers]
         if spec.laplace and norm_stats is None:
+            if start is not None:
+                raise ValueError("_end_state: a start of a model with an offline norm needs norm_stats (the clips' statistics so far)")
             self._stats(f, fbm)
         fb_done = self._run_model(f, fbm, None)
         if spec.laplace:
@@ -1391,7 +1423,7 @@ class Engine:
         self._join(f)
         if frames is not None:
             self._zero_tail(f)
-        if want_counts and not want_layers:
+        if want_counts and not want_layers and start is None:  # (a start's caller takes the per-clip counts of the end state)
             self._summaries(f)
         out = self._result(f)
         if end_state:
@@ -1410,6 +1442,7 @@ class Engine:
         counts = None
         if want_counts:
             T, B = f.fbm.xs[0].shape[:2]
+            t0 = f.lead  # (a forward with a start: the new frames only)
             tens = [(fb["s8"][l][0], 1) for l in range(nl_fb)] + [(sb["s8"][l][g], spec.units(g)) for g in range(ng) for l in range(nl_sb)]
             counts = torch.zeros((len(tens), B), dtype=torch.int64, device=self.device)
             hm = self._handle(f.main)
@@ -1419,8 +1452,11 @@ class Engine:
                 for j, (t, rpc) in enumerate(part):
                     arr[j].spikes_i8, arr[j].T, arr[j].R, arr[j].HP, arr[j].rows_per_clip = t.data_ptr(), t.shape[0], t.shape[1], t.shape[2], rpc
                     arr[j].counts = counts.data_ptr() + 8 * (i0 + j) * B
-                check(self.lib.sfsn_spike_count_rows(arr, len(part), 0, T, hm), "sfsn_spike_count_rows")
-        return dict(fb=dict(states=fb["states"], s8=fb["s8"]), sb=dict(states=sb["states"], s8=sb["s8"]),
+                check(self.lib.sfsn_spike_count_rows(arr, len(part), t0, T - t0, hm), "sfsn_spike_count_rows")
+
+        def s8(d):  # (a forward with a start: the new frames' rows)
+            return [[t[f.lead:] for t in row] for row in d["s8"]] if f.lead else d["s8"]
+        return dict(fb=dict(states=fb["states"], s8=s8(fb)), sb=dict(states=sb["states"], s8=s8(sb)),
                     cum=None if f.cum is None else f.cum["state"], counts=counts)
 
     def _validate(self, stft):
@@ -1438,13 +1474,15 @@ class Engine:
                                  f"upper_cutoff_freq={hi}, lower_cutoff_freq={lo}")
         return B, F, T
 
-    def _alloc_forward(self, stft, plan, want_layers, want_membrane, want_counts, norm_stats, frames, frames_dev) -> _Forward:
+    def _alloc_forward(self, stft, plan, want_layers, want_membrane, want_counts, norm_stats, frames, frames_dev, start=None) -> _Forward:
         """Every tensor of one forward (API outputs fresh, scratch cached: _alloc_stack) and the two models' launch arguments."""
         spec, dev = self.spec, self.device
         B, F, T = stft.shape
         S, ng, nl_fb, nl_sb = spec.num_spks, spec.n_groups, spec.fb_layers, spec.sb_layers
         f32 = dict(dtype=torch.float32, device=dev)
         ri = torch.view_as_real(stft.contiguous())  # [B, F, T, 2] float32 view, no copy
+        if start is not None:
+            assert stft.is_contiguous()
         x_fb = torch.empty((T, B, spec.fb_in), **f32)
         xs = [torch.empty((T, B * spec.units(g), spec.sb_input_size(g)), **f32) for g in range(ng)]
         # the zero initial state of every scan of the forward: ONE buffer, zeroed by the forward's first feature launch (every scan
@@ -1455,10 +1493,14 @@ class Engine:
         # layer_outputs="counts": the scans count the spikes they write (sfsn_scan_segment.spike_count) -- the int64 counters sit behind
         # the states in the same zeroed buffer (two floats each; the buffer's length stays a multiple of 16 bytes)
         # (a ragged batch counts each clip's own frames after the forward: the in-scan counter is per tensor, not per clip)
-        in_scan = bool(want_counts and not want_layers and self.count_in_scan and frames is None)
+        in_scan = bool(want_counts and not want_layers and self.count_in_scan and frames is None and start is None)
         n_cnt = (nl_fb + ng * nl_sb) if in_scan else 0
         n_cnt_f = (2 * n_cnt + 3) // 4 * 4
-        state_flat = torch.empty((n_fb + n_sb + n_cnt_f,), **f32) if fold else torch.zeros((n_fb + n_sb + n_cnt_f,), **f32)
+        if start is not None:  # the scans go on from the caller's states: nothing zeroes them
+            state_flat, fold = start["state_flat"], False
+            assert state_flat.numel() == n_fb + n_sb and state_flat.dtype == torch.float32 and state_flat.device == dev
+        else:
+            state_flat = torch.empty((n_fb + n_sb + n_cnt_f,), **f32) if fold else torch.zeros((n_fb + n_sb + n_cnt_f,), **f32)
         cnt_all = state_flat[n_fb + n_sb:n_fb + n_sb + 2 * n_cnt].view(torch.int64) if in_scan else None
         fb = self._alloc_stack([self.fb], [B], T, plan.nt_max, want_layers, want_membrane, "fb", state_flat[:n_fb],
                                None if cnt_all is None else cnt_all[:nl_fb])
@@ -1483,7 +1525,8 @@ class Engine:
             # cumulative_laplace_norm: the rows leave sfsn_features unnormalised and are divided by their running means (state per
             # row, so a sequence fed in pieces continues where it stopped)
             rows = [B] + [x.shape[1] for x in xs]
-            cum = dict(state=[torch.zeros((R,), **f32) for R in rows], scratch=torch.empty((plan.nt_max * max(rows),), **f32))
+            cum = dict(state=[torch.zeros((R,), **f32) for R in rows] if start is None else start["cum"],
+                       scratch=torch.empty((plan.nt_max * max(rows),), **f32))
         fb_proj = fb["proj"][0]
         fbm = _ModelRun("fb", [self.fb], fb, [x_fb], 0, plan.rpw_fb, self._feature_groups("fb", [x_fb], mu_fb, sd_fb), None,
                         (B, F, T, 0, spec.fdrc), mu_fb, sd_fb, 0)
@@ -1493,7 +1536,8 @@ class Engine:
                         fbm=fbm, sbm=sbm, enh=enh, enh_ri=torch.view_as_real(enh), enh_mag=torch.empty((B, S, F, T), **f32), dfg=dfg,
                         stats_scratch=scratch, cum=cum, zero=state_flat if fold else None, in_scan=in_scan,
                         # round 6: projection + deep filter of a chunk in one launch; in the lean modes the coefficient rows are not written
-                        write_proj=bool(want_layers or want_membrane or not self.lean_skips_proj))
+                        write_proj=bool(want_layers or want_membrane or not self.lean_skips_proj),
+                        lead=0 if start is None else int(start["lead"]), frames_before=0 if start is None else int(start["frames_before"]))
 
     def _open_streams(self, f: _Forward) -> None:
         """The streams of the forward's stages: sequential = the current stream; pipelined = per stage one scan stream (own CUs) and one
@@ -1563,7 +1607,8 @@ class Engine:
             if f.cum is not None:
                 for i, x in enumerate(m.xs):
                     R, I = x.shape[1], x.shape[2]
-                    check(L.sfsn_cum_laplace_norm(ctypes.c_void_p(x.data_ptr() + t0 * R * I * 4), nt, R, I, _ptr(f.cum["state"][m.cum0 + i]), t0,
+                    check(L.sfsn_cum_laplace_norm(ctypes.c_void_p(x.data_ptr() + t0 * R * I * 4), nt, R, I, _ptr(f.cum["state"][m.cum0 + i]),
+                                                  t0 - f.lead + f.frames_before,
                                                   _ptr(f.cum["scratch"]), st), "sfsn_cum_laplace_norm")
         return False
 
@@ -1735,7 +1780,8 @@ class Engine:
             if no_proj:  # (lean modes through sfsn_proj_deepfilter: the coefficient rows stayed in LDS)
                 pr = torch.empty(pr.shape, dtype=pr.dtype, device="meta")
             return [x] + [m.d["spk"][l][i] for l in range(len(m.d["spk"]))] + [pr]
-        return dict(enh_stft=f.enh, enh_mag=f.enh_mag, fb_all=outs(f.fbm, 0), sb_all=[outs(f.sbm, g, f.proj_skipped) for g in range(ng)],
+        enh, enh_mag = (f.enh[..., f.lead:], f.enh_mag[..., f.lead:]) if f.lead else (f.enh, f.enh_mag)  # (a start: the new frames)
+        return dict(enh_stft=enh, enh_mag=enh_mag, fb_all=outs(f.fbm, 0), sb_all=[outs(f.sbm, g, f.proj_skipped) for g in range(ng)],
                     fb_mem=[fb["mem"][l][0] for l in range(nl_fb)], sb_mem=[[sb["mem"][l][g] for l in range(nl_sb)] for g in range(ng)],
                     mu_fb=f.fbm.mu, mu_sb=f.sbm.mu, sd_fb=f.fbm.sd, sd_sb=f.sbm.sd, pipelined=plan.pipeline, overlapped=plan.overlap,
                     n_chunks=len(plan.bounds))

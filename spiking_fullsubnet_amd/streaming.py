@@ -35,6 +35,14 @@ from silence (a clip joining mid-call, a seek, a reconnect, a backlog).  The pre
 csrc/sfsn_prime.hip) and the clips' origins move back by the prefix's launches, so that the next hop continues at frame N; the
 per-kernel sequence takes it as stream-ordered row copies into its states, history and counts.  Not for resident sessions.
 
+A backlog: ``advance(stft, clips)`` / ``advance_wave(samples, clips)`` run many frames at once on clips that are ALREADY RUNNING (a
+network stall that ends, a paused call that resumes, a file that goes live; chunked long-form processing) -- the offline kernels
+started from the state the session carries (``Engine.forward_stft(..., _end_state=start)``: (h, c), running sums and ``frames_before``
+in, D frames of history in front of the new ones) and their end state handed back.  The one-launch hop gives its state in one launch
+(``sfsn_hop_seed``) and takes the end state in one (``sfsn_hop_advance``: counts added to, the overlap-add accumulator continued),
+then the clips' origins move back by the backlog's launches; the per-kernel sequence uses row copies.  A fresh clip reads as zero:
+``advance`` on it equals ``prime``.  Not for resident sessions.
+
 Moving a clip: ``export_state(clips)`` copies the clips' carried state out of the session (a ``clip_state.ClipState``: one self-contained
 blob per clip) and ``import_state(state, clips)`` puts it into slots of this or another session of the same geometry and tier, where
 the clips continue bit for bit, layer 0 included -- compaction, rebalancing, pause / resume, rewind, fork.  One launch each way in the
@@ -58,7 +66,8 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from ._lib import DfGroup, HopDesc, HOP_MAX_GROUPS, HOP_MAX_LAYERS, MAX_COUNT_TENSORS, NORM_CUMLAPLACE, PrimeSrc, RowCount, check
+from ._lib import (AdvanceSrc, DfGroup, HopDesc, HOP_MAX_GROUPS, HOP_MAX_LAYERS, MAX_COUNT_TENSORS, NORM_CUMLAPLACE, PrimeSrc, RowCount,
+                   SeedDst, check)
 from .engine import Engine, NormStats, SpikeSummary, _ptr
 
 
@@ -527,8 +536,8 @@ class StreamingSession:
             part["desc"].clip_start = part["origin"].data_ptr()  # from now on the launches take the clips' own origins
 
     # ---- priming: a recorded prefix through the offline kernels, its end state into the session ---------------------------------
-    def _prime_clips(self, clips, n_given: int):
-        """(clip indices in the caller's order, the permutation that sorts them or None) of a prime call; checked like
+    def _prime_clips(self, clips, n_given: int, what: str = "prime"):
+        """(clip indices in the caller's order, the permutation that sorts them or None) of a prime / advance call; checked like
         set_norm_stats' clips."""
         if clips is None:
             idx = list(range(self.B))
@@ -543,11 +552,11 @@ class StreamingSession:
             if bad:
                 raise IndexError(f"clip index {bad[0]} out of range for a session of {self.B} clips")
             if len(set(idx)) != len(idx):
-                raise ValueError("prime: clip indices must be distinct")
+                raise ValueError(f"{what}: clip indices must be distinct")
             if not idx:
-                raise ValueError("prime: no clip selected")
+                raise ValueError(f"{what}: no clip selected")
         if n_given != len(idx):
-            raise RuntimeError(f"prime: a prefix of {n_given} clips for {len(idx)} clip indices")
+            raise RuntimeError(f"{what}: {'a prefix' if what.startswith('prime') else 'a backlog'} of {n_given} clips for {len(idx)} clip indices")
         order = sorted(range(len(idx)), key=idx.__getitem__)
         return idx, (None if order == list(range(len(idx))) else order)
 
@@ -720,6 +729,210 @@ class StreamingSession:
                     part["desc"].clip_start = part["origin"].data_ptr()
             self._clip_c0[idx] = self._wave_calls - c
         self._primed = True
+        if perm is not None:
+            inv = torch.empty_like(perm)
+            inv[perm] = torch.arange(len(order), device=self.dev)
+            res = res.index_select(0, inv)
+        return res
+
+    # ---- a backlog on running clips: the offline kernels from the carried state, their end state back into the session -----------
+    def _advance_sorted(self, stft, idx, samples=None):
+        """``stft``: complex64 [len(idx), F, N], or None in waveform mode, where ``samples`` float32 [len(idx), 128 * N] contiguous
+        give the frames; ``idx`` ascending.  Returns (the forward of the N new frames, the waveform blocks or None).  Everything on
+        torch's current stream."""
+        eng, spec, L = self.eng, self.eng.spec, self.eng.lib
+        n, hop, D, ng, dev = len(idx), self.hop, self.D, spec.n_groups, self.dev
+        N = stft.shape[-1] if samples is None else samples.shape[1] // 128
+        T = D + N
+        start = eng._start_buffers(n, N, D, frames_before=int(self.clip_frames[idx[0]]))
+        buf = start["stft"]
+        units = [1] + [spec.units(g) for g in range(ng)]
+        st = ctypes.c_void_p(_raw_stream(self._dev_index))
+        wbuf = None
+        if self._hop is None:
+            # the per-kernel sequence: the clips' rows of its states and the last D frames of its history window
+            sel = torch.tensor(idx, dtype=torch.long).to(dev, non_blocking=True)
+            for d, e, us in ((self.fb, start["fb"], units[:1]), (self.sb, start["sb"], units[1:])):
+                for mine, theirs in zip(d["states"], e):
+                    for (h, c), (hs, cs), u in zip(mine, theirs, us):
+                        hs.view(n, -1).copy_(h.view(self.B, -1).index_select(0, sel))
+                        cs.view(n, -1).copy_(c.view(self.B, -1).index_select(0, sel))
+            if D:
+                buf[:, :, :D].copy_(self.hist.index_select(0, sel)[:, :, hop:])
+        else:
+            dst = SeedDst()
+            dst.Bp, dst.T = n, T
+            if D:
+                dst.stft_ri = torch.view_as_real(buf).data_ptr()
+            if samples is not None:  # [384 samples of context | the new samples]
+                wbuf = torch.empty((n, 384 + 128 * N), dtype=torch.float32, device=dev)
+                dst.wave_ctx, dst.wave_stride = wbuf.data_ptr(), wbuf.shape[1]
+            for o, e, gi in [(dst.fb, start["fb"], 0)] + [(dst.sb[g], start["sb"], g) for g in range(ng)]:
+                for l in range(len(e)):
+                    o.layer[l].h, o.layer[l].c = e[l][gi][0].data_ptr(), e[l][gi][1].data_ptr()
+            if start["cum"] is not None:
+                dst.fb.cum = start["cum"][0].data_ptr()
+                for g in range(ng):
+                    dst.sb[g].cum = start["cum"][1 + g].data_ptr()
+            for part in self._hop["parts"]:
+                pos = [j for j, b in enumerate(idx) if part["b0"] <= b < part["b0"] + part["nb"]]
+                if not pos:
+                    continue
+                part["desc"].clip_start = part["origin"].data_ptr()  # the clips' own origins from now on (they say which clip is fresh)
+                for j0 in range(0, len(pos), 256):  # (a launch takes 256 clip indices in its arguments)
+                    local = [idx[j] - part["b0"] for j in pos[j0:j0 + 256]]
+                    dst.b0 = pos[j0]
+                    arr = (ctypes.c_int * len(local))(*local)
+                    with torch.cuda.device(dev):
+                        rc = L.sfsn_hop_seed(part["ref"], arr, len(local), ctypes.byref(dst), st)
+                    if rc:
+                        check(rc, "sfsn_hop_seed")
+        if samples is not None:
+            from . import spectral
+            wbuf[:, 384:].copy_(samples)
+            # frame j of the backlog covers samples [128 j, 128 j + 512) of the buffer: the centred frame j + 2
+            stft = spectral.stft(wbuf, 512, 128)[:, :, 2:2 + N]
+        buf[:, :, D:].copy_(stft)
+        ns = None if self._stats is None else (self._stats if n == self.B else self._stats.select(idx))
+        # (the per-kernel sequence's layer-0 membranes are those of ITS input product, the form below 64 rows: the backlog takes it too)
+        eng._l0_hop = hop if self._hop is None else None
+        try:
+            out = eng.forward_stft(buf, want_layers=False, want_counts=self._rows is not None, norm_stats=ns, _end_state=start)
+        finally:
+            eng._l0_hop = None
+        es = out["end_state"]
+        if self._hop is None:
+            for d, e, us in ((self.fb, es["fb"], units[:1]), (self.sb, es["sb"], units[1:])):
+                for mine, theirs in zip(d["states"], e["states"]):
+                    for (h, c), (hs, cs), u in zip(mine, theirs, us):
+                        j0 = 0  # (idx ascends: a run of consecutive clips is a run of consecutive rows on both sides)
+                        for b0, m in self._runs(idx):
+                            h[b0 * u:(b0 + m) * u].copy_(hs[j0 * u:(j0 + m) * u])
+                            c[b0 * u:(b0 + m) * u].copy_(cs[j0 * u:(j0 + m) * u])
+                            j0 += m
+            for j, b in enumerate(idx):  # the last D + hop frames of [history | new] (N >= hop: the buffer has them)
+                self.hist[b].copy_(buf[j, :, T - self.Th:])
+            if self._rows is not None:
+                self._rows.index_add_(1, sel, es["counts"])
+            return out, None
+        src = AdvanceSrc()
+        src.Bp, src.N, src.T = n, N, T
+        src.stft_ri = torch.view_as_real(buf).data_ptr()
+        for o, e, gi in [(src.fb, es["fb"], 0)] + [(src.sb[g], es["sb"], g) for g in range(ng)]:
+            for l in range(len(e["s8"])):
+                o.layer[l].spikes_i8, o.layer[l].c = e["s8"][l][gi].data_ptr(), e["states"][l][gi][1].data_ptr()
+        if es["cum"] is not None:
+            src.fb.cum = es["cum"][0].data_ptr()
+            for g in range(ng):
+                src.sb[g].cum = es["cum"][1 + g].data_ptr()
+        res = tail = None
+        if samples is not None:
+            enh = out["enh_stft"]  # (the new frames of the forward's [.., T] rows: the launch takes the rows)
+            src.enh_ri = enh.data_ptr() - D * enh.element_size()
+            tail = wbuf[:, -512:].contiguous()
+            res = torch.empty((n, spec.num_spks, 128 * N), dtype=torch.float32, device=dev)
+            src.wave_tail, src.wave_out = tail.data_ptr(), res.data_ptr()
+        for part in self._hop["parts"]:
+            pos = [j for j, b in enumerate(idx) if part["b0"] <= b < part["b0"] + part["nb"]]
+            if not pos:
+                continue
+            for j0 in range(0, len(pos), 256):
+                local = [idx[j] - part["b0"] for j in pos[j0:j0 + 256]]
+                src.b0 = pos[j0]
+                arr = (ctypes.c_int * len(local))(*local)
+                with torch.cuda.device(dev):
+                    rc = L.sfsn_hop_advance(part["ref"], arr, len(local), ctypes.byref(src), st)
+                if rc:
+                    check(rc, "sfsn_hop_advance")
+            # the clips' origins move back by the backlog's launches (32-bit wrap-around, as the launch's unsigned difference), behind
+            # the queued launches: the next launch continues N / hop frame indices further
+            for b0, m in self._runs([idx[j] - part["b0"] for j in pos]):
+                part["origin"][b0:b0 + m].sub_(N // hop)
+        return out, res
+
+    def _advance_checks(self, what: str, idx) -> None:
+        spec = self.eng.spec
+        if spec.cum_laplace:
+            ages = self.clip_frames[idx]
+            if (ages != ages[0]).any():
+                raise ValueError(f"{what}: with cumulative_laplace_norm the clips of one call must have seen the same number of frames, "
+                                 f"clips {list(idx)} have seen {ages.tolist()}: make one call per age")
+
+    def advance(self, stft: torch.Tensor, clips=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Run a BACKLOG of ``N`` frames on clips that are already running, at the speed of the offline forward: ``stft`` complex64
+        [len(clips), F, N] on the device, row i for ``clips[i]`` (``None``: every clip).  The clips continue from whatever state
+        they hold; the result ``(enh_stft [.., S, F, N], enh_mag)`` is what ``N / hop`` calls of ``step`` would have returned for
+        them, and the session is left where those calls would have left them -- last spikes, membranes, cumulative-norm sums,
+        deep-filter history, spike counts (``count_spikes=True``), ``clip_frames``.  The other clips are untouched.  A fresh clip
+        (never stepped, or just ``reset``) reads as zero state whatever memory holds: ``advance`` on it equals ``prime``.  Repeated
+        calls process a long recording in chunks.
+
+        The offline kernels run on the new frames behind ``D`` frames of the clip's history, from the carried state
+        (``Engine.forward_stft(..., _end_state=start)``).  The one-launch tier reads the state out in one launch
+        (``sfsn_hop_seed``) and takes the end state back in one (``sfsn_hop_advance``, csrc/sfsn_prime.hip), then moves the clips'
+        origins back by ``N / hop`` launches; the per-kernel tier uses row copies.  Exactness: bit for bit in the per-kernel tier;
+        in the one-launch tier ``prime``'s one reservation and no other -- the layer-0 membranes written back are the offline
+        kernels', which differ from the hop's in their low bits; where no layer-0 membrane lies within that rounding of the
+        threshold, every spike, higher-layer membrane, output and count is that of the ``step`` sequence, bit for bit.
+
+        ``N``: a positive multiple of ``hop``, the same for every listed clip (``ValueError``).  With the cumulative norm the listed
+        clips must share their frame count so far (``ValueError`` naming them: one call per age).  A frozen model with given
+        statistics uses the session's rows of those clips.  Ordered on torch's current stream, no synchronisation.  Not on resident
+        sessions (``NotImplementedError``), not across tiers, not for cIRM-GSN sessions."""
+        if self.resident:
+            raise NotImplementedError("advance: not on a resident session (resident=True): its launch holds the state while it runs")
+        if self.waveform:
+            raise RuntimeError("this session was opened with waveform=True: use advance_wave(samples)")
+        idx, order = self._prime_clips(clips, stft.shape[0] if isinstance(stft, torch.Tensor) and stft.dim() == 3 else -1, "advance")
+        if stft.device != self.dev or stft.dtype != torch.complex64 or stft.shape[1] != self.F:
+            raise RuntimeError(f"expected complex64 {(len(idx), self.F, 'N')} on {self.dev}, got {stft.dtype} {tuple(stft.shape)} on {stft.device}")
+        N = stft.shape[2]
+        if N < self.hop or N % self.hop != 0:
+            raise ValueError(f"advance: {N} frames is not a positive multiple of the session's hop ({self.hop})")
+        self._advance_checks("advance", idx)
+        perm = None
+        if order is not None:
+            perm = torch.tensor(order, dtype=torch.long).to(self.dev, non_blocking=True)
+            stft, idx = stft.index_select(0, perm), [idx[j] for j in order]
+        out, _ = self._advance_sorted(stft, idx)
+        self._clip_f0[idx] -= N
+        enh, mag = out["enh_stft"], out["enh_mag"]
+        if perm is not None:
+            inv = torch.empty_like(perm)
+            inv[perm] = torch.arange(len(order), device=self.dev)
+            return enh.index_select(0, inv), mag.index_select(0, inv)
+        return enh.contiguous(), mag.contiguous()
+
+    def advance_wave(self, samples: torch.Tensor, clips=None) -> torch.Tensor:
+        """``advance`` for waveform sessions (``host_io`` included; device tensors in and out): ``samples`` float32
+        [len(clips), 128 * c], ``c >= 1`` calls' worth.  Returns [.., S, 128 * c], the concatenation of what ``c`` calls of
+        ``step_wave`` would have returned.  The new frames come from the last 384 samples of the clip's STFT state followed by the
+        new samples (``spectral.stft``: the hop's transform, the same bits); the output blocks continue the clip's overlap-add
+        accumulator in the hop's order and with its envelope.  Every listed clip must have made at least one call in its current
+        utterance (``ValueError`` naming the clip; start such a clip with ``prime_wave``).  Exactness as for ``advance``."""
+        if self.resident:
+            raise NotImplementedError("advance_wave: not on a resident session (resident=True): its launch holds the state while it runs")
+        if not self.waveform:
+            raise RuntimeError("open the session with waveform=True")
+        idx, order = self._prime_clips(clips, samples.shape[0] if isinstance(samples, torch.Tensor) and samples.dim() == 2 else -1, "advance_wave")
+        if samples.device != self.dev or samples.dtype != torch.float32:
+            raise RuntimeError(f"expected float32 {(len(idx), '128 * c')} on {self.dev}, got {samples.dtype} {tuple(samples.shape)} on {samples.device}")
+        Ls = samples.shape[1]
+        if Ls < 128 or Ls % 128 != 0:
+            raise ValueError(f"advance_wave: {Ls} samples is not a positive multiple of 128")
+        calls = self.clip_calls
+        for b in idx:
+            if calls[b] < 1:
+                raise ValueError(f"advance_wave: clip {b} has made no call in its current utterance (no STFT state to continue from): "
+                                 "start it with prime_wave")
+        self._advance_checks("advance_wave", idx)
+        perm = None
+        if order is not None:
+            perm = torch.tensor(order, dtype=torch.long).to(self.dev, non_blocking=True)
+            samples, idx = samples.index_select(0, perm), [idx[j] for j in order]
+        _, res = self._advance_sorted(None, idx, samples=samples.contiguous())
+        self._clip_c0[idx] -= Ls // 128
+        self._primed = True  # the launch mutes each clip by its own frame index (see step_wave)
         if perm is not None:
             inv = torch.empty_like(perm)
             inv[perm] = torch.arange(len(order), device=self.dev)
