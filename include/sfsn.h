@@ -1061,6 +1061,74 @@ int sfsn_fullband_hop_state_import(const sfsn_fullband_hop_desc* desc, unsigned*
                                    float* ola_state /* nullable */, const int* clips /* host */, int n_clips,
                                    const void* blob /* device [..][bytes] */, int b0 /* first blob row */, void* stream);
 
+/* A backlog on a RUNNING clip of a cIRM-GSN session (csrc/sfsn_prime.hip): sfsn_hop_seed / sfsn_hop_advance for sfsn_fullband_hop_desc --
+ * the same two kernels from host-filled params (one sequence, one row per clip, H = Hp), the same rules: N new frames go through the
+ * OFFLINE kernels (sfsn_fullband_features -> sfsn_fullband_input_proj -> the GSN scans -> sfsn_fullband_proj_deepfilter), started from
+ * the state the session carries, and their end state is handed back.  One launch each, for the listed clips only (distinct indices,
+ * 1 <= n_clips <= B <= 16); every other clip's rows, scratch, z0, the tagged spikes buffers and launch_index are left as they are.
+ * Plain loads and stores, no atomics, nothing waits; ordered on `stream` like any launch.  k = desc->launch_index.  What lives
+ * outside the descriptor is handed over as for the state launches above: spike_slots (NULL: the session does not count), wave_state
+ * and ola_state of the sfsn_fullband_wave_desc whose `hop` is `desc` (waveform mode: wave_state != NULL).
+ *
+ * sfsn_fullband_hop_seed: the offline kernels' START tensors, rows b0 + i of tensors of Bp clips for clips[i]:
+ *   layer.h   <- h[k & 1] as fp32 0 / 1 [Bp][Hp] (the hop's row stride is pad64(Hp)), layer.c <- c;
+ *   stft_ri   <- frames [0, D) of every row [F][T][2] = hist_ri[k & 1], the half of the double buffer that launch k reads.  The
+ *                caller puts the N new frames at [T - N, T), T >= D + N, and runs the offline stages on those frames of the buffer;
+ *   wave_ctx  <- waveform mode: wave_state[128 .. 512) at the front of a row of wave_stride floats (the caller appends the new
+ *                samples: frame j of the backlog is the centred frame j + 2 of that row on sfsn_stft).
+ * desc->clip_start is read (required in waveform mode): a clip whose origin equals k (restarted or never stepped: the hop reads its
+ * state as zero in launch k, whatever memory holds) is written as zeros everywhere but wave_ctx.  Waveform mode: a clip whose origin
+ * equals k + 1 (no call yet: launch k is its first call, which has no frame and reads the old samples as zero) is written as zeros,
+ * wave_ctx included -- so [0 x 384 | its samples] holds its first call's STFT state, and its frame j is the centred frame j + 3.
+ *
+ * sfsn_fullband_hop_advance: `src` holds the offline kernels' results for the N new frames.
+ *   layer.h[k & 1], layer.c <- frame N - 1 of spikes_i8, and c (the end state of the backlog);
+ *   hist_ri[k & 1] <- the last D frames of stft_ri's rows of T frames, [history | new]: N < D keeps the tail of the old history;
+ *   spike_slots  <- ADDED to: slot (b, j) += the spikes of neurons 4j .. 4j + 3 over the N frames (a clip whose origin equals k:
+ *                   replaced, the hop reads its slot as zero);
+ *   wave_state   <- wave_tail, the last 512 input samples; ola_state <- continued in the hop's order: the carried partial sums first
+ *                   (zero for a clip whose origin equals k or k + 1), then frames T - N .. T - 1 of enh_ri's rows in ascending order
+ *                   (sfsn_hop_wave_dev.h's arithmetic and envelope); wave_out[b0 + i][s][128 j ..] <- the block the launch that
+ *                   computes the clip's new frame j would have written (zero while that frame's index is < 2).  For a clip that
+ *                   has made a call that is launch k + j; for a clip without a call launch k + 1 + j (launch k, its first call,
+ *                   writes a block of zeros, which the caller puts in front).
+ * N = 0 is legal in waveform mode only -- the clip without a call and one call's worth of samples: wave_state <- wave_tail, and h, c,
+ * hist_ri, ola_state are written as zero (which its frame 0 reads whatever memory holds).
+ * The caller then moves clip_start[clips[i]] back by the launches replaced -- N / hop; waveform mode: the calls replaced, N for a
+ * clip that had made a call, N + 1 for a clip that had not -- unsigned, wrap-safe, with a stream-ordered device operation behind the
+ * queued launches.
+ *
+ * Exactness: bit for bit what the launches would have left, layer 0 included -- sfsn_fullband_stream_hop is bit-identical to the
+ * offline sequence (above), so this pair carries no layer-0 reservation (sfsn_hop_advance has one).
+ * SFSN_EINVAL, before any launch: a NULL desc / clips / dst / src, n_clips < 1, an index outside [0, desc->B) or listed twice,
+ * b0 + n_clips > Bp, N % hop != 0, N < hop (waveform mode: N < 0), T < D + N (seed: T < D), wave_stride < 384, one of wave_state /
+ * ola_state NULL, a missing or misaligned pointer (h, c: 16 bytes; stft_ri, enh_ri, wave_out, ola_state: 8; the others: 4).
+ * SFSN_EUNSUPPORTED: a descriptor sfsn_fullband_hop_check (waveform mode: sfsn_fullband_wave_hop_check) refuses, spike_slots together
+ * with wave_state (the waveform launch has no counted form).  (Added without an ABI bump: no existing struct or signature changed.) */
+typedef struct sfsn_fullband_seed_dst {
+    int Bp, T, b0;
+    int wave_stride;         /* waveform mode: floats per row of wave_ctx (>= 384)                   */
+    float* stft_ri;          /* [Bp][F][T][2]: frames [0, D) are written (NULL if D == 0)            */
+    float* wave_ctx;         /* waveform mode: [Bp][wave_stride], samples [0, 384) are written       */
+    sfsn_seed_layer layer[SFSN_FULLBAND_HOP_MAX_LAYERS]; /* h, c: [Bp][Hp]                           */
+} sfsn_fullband_seed_dst;
+typedef struct sfsn_fullband_advance_src {
+    int Bp, N, b0;
+    int T;                   /* frames per row of stft_ri / enh_ri; the N new frames are the last ones  */
+    const float* stft_ri;    /* [Bp][F][T][2] [history | new] (NULL if D == 0 or N == 0)                */
+    const float* enh_ri;     /* waveform mode: [Bp][S][F][T][2] the enhanced frames (NULL if N == 0)    */
+    const float* wave_tail;  /* waveform mode: [Bp][512] the last 512 input samples                     */
+    float* wave_out;         /* waveform mode: [Bp][S][128 * N] out (NULL if N == 0)                    */
+    const float* window;     /* waveform mode: [512] the session's window (sfsn_fullband_wave_desc)     */
+    sfsn_prime_layer layer[SFSN_FULLBAND_HOP_MAX_LAYERS]; /* spikes_i8: the N new frames' [N][Bp][pad64(Hp)]; c [Bp][Hp]: after the last */
+} sfsn_fullband_advance_src;
+int sfsn_fullband_hop_seed(const sfsn_fullband_hop_desc* desc /* host */, const unsigned* spike_slots /* nullable */,
+                           const float* wave_state /* nullable */, const int* clips /* host */, int n_clips,
+                           const sfsn_fullband_seed_dst* dst /* host */, void* stream);
+int sfsn_fullband_hop_advance(const sfsn_fullband_hop_desc* desc /* host */, unsigned* spike_slots /* nullable */,
+                              float* wave_state /* nullable */, float* ola_state /* nullable */, const int* clips /* host */, int n_clips,
+                              const sfsn_fullband_advance_src* src /* host */, void* stream);
+
 /* ----------------------------------------------------------------------------------------------------
  * The intel_ndns recipe's training loss (recipes/intel_ndns/spiking_fullsubnet/trainer.py:24-48 on audiozen/loss.py) and its
  * gradient with respect to the estimate, in one call of two launches:

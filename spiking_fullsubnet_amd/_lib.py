@@ -159,6 +159,16 @@ class FullbandWaveDesc(ctypes.Structure):  # sfsn_fullband_wave_desc
                 ("spec_g", _P), ("enh_g", _P), ("done", _P)]
 
 
+class FullbandSeedDst(ctypes.Structure):  # sfsn_fullband_seed_dst
+    _fields_ = [("Bp", _I), ("T", _I), ("b0", _I), ("wave_stride", _I), ("stft_ri", _P), ("wave_ctx", _P),
+                ("layer", SeedLayer * FULLBAND_HOP_MAX_LAYERS)]
+
+
+class FullbandAdvanceSrc(ctypes.Structure):  # sfsn_fullband_advance_src
+    _fields_ = [("Bp", _I), ("N", _I), ("b0", _I), ("T", _I), ("stft_ri", _P), ("enh_ri", _P), ("wave_tail", _P), ("wave_out", _P),
+                ("window", _P), ("layer", PrimeLayer * FULLBAND_HOP_MAX_LAYERS)]
+
+
 def _sources():
     """The files the library is made of, in the order the Makefile hashes them (SRCS)."""
     return [os.path.join(_HERE, "..", "include", "sfsn.h")] + [
@@ -364,6 +374,11 @@ def lib() -> ctypes.CDLL:
     L.sfsn_fullband_hop_state_export.argtypes = [ctypes.POINTER(FullbandHopDesc), _P, _P, _P, ctypes.POINTER(_I), _I, _P, _P]
     L.sfsn_fullband_hop_state_import.restype = _I  # desc, spike_slots, wave_state, ola_state | clips, n_clips | blob, b0, stream
     L.sfsn_fullband_hop_state_import.argtypes = [ctypes.POINTER(FullbandHopDesc), _P, _P, _P, ctypes.POINTER(_I), _I, _P, _I, _P]
+    L.sfsn_fullband_hop_seed.restype = _I  # desc, spike_slots, wave_state | clips, n_clips | dst, stream
+    L.sfsn_fullband_hop_seed.argtypes = [ctypes.POINTER(FullbandHopDesc), _P, _P, ctypes.POINTER(_I), _I, ctypes.POINTER(FullbandSeedDst), _P]
+    L.sfsn_fullband_hop_advance.restype = _I  # desc, spike_slots, wave_state, ola_state | clips, n_clips | src, stream
+    L.sfsn_fullband_hop_advance.argtypes = [ctypes.POINTER(FullbandHopDesc), _P, _P, _P, ctypes.POINTER(_I), _I,
+                                            ctypes.POINTER(FullbandAdvanceSrc), _P]
     L.sfsn_recipe_loss_scratch_bytes.restype = ctypes.c_size_t  # rows, n_samples; 0: refused (host only)
     L.sfsn_recipe_loss_scratch_bytes.argtypes = [_I, _I]
     L.sfsn_recipe_loss.restype = _I  # est, tgt | rows, n_samples | c_freq, c_mag, c_sdr | flags | terms, grad_est, scratch, stream
@@ -417,7 +432,8 @@ EXPORTS = ("sfsn_abi_version", "sfsn_source_hash", "sfsn_strerror", "sfsn_device
            "sfsn_pit_sdr_ragged", "sfsn_gsn_layer_scan_l01", "sfsn_recipe_loss_ragged_scratch_bytes", "sfsn_recipe_loss_ragged",
            "sfsn_fullband_proj_deepfilter_ragged", "sfsn_hop_prime", "sfsn_gsn_layer_scan_l01_projdf",
            "sfsn_hop_state_bytes", "sfsn_hop_state_export", "sfsn_hop_state_import", "sfsn_fullband_hop_state_bytes",
-           "sfsn_fullband_hop_state_export", "sfsn_fullband_hop_state_import", "sfsn_hop_seed", "sfsn_hop_advance")
+           "sfsn_fullband_hop_state_export", "sfsn_fullband_hop_state_import", "sfsn_hop_seed", "sfsn_hop_advance",
+           "sfsn_fullband_hop_seed", "sfsn_fullband_hop_advance")
 
 
 def check(rc: int, what: str = "") -> None:

@@ -30,7 +30,10 @@
 #define PRIME_WAVES 4
 #define PRIME_MAX_SEQS (1 + SFSN_HOP_MAX_GROUPS)
 #define PRIME_MAX_CLIPS 256  // clip indices travel in the kernel arguments (16 bits each)
+// layers of a sequence: sfsn_hop_desc's, or the one sequence of a sfsn_fullband_hop_desc
+#define PRIME_MAX_LAYERS (SFSN_HOP_MAX_LAYERS > SFSN_FULLBAND_HOP_MAX_LAYERS ? SFSN_HOP_MAX_LAYERS : SFSN_FULLBAND_HOP_MAX_LAYERS)
 #define PRIME_MAX_SECS (PRIME_MAX_SEQS * SFSN_HOP_MAX_LAYERS + 3)
+static_assert(PRIME_MAX_SECS >= SFSN_FULLBAND_HOP_MAX_LAYERS + 3, "a cIRM-GSN descriptor's sections fit");
 
 enum { PRIME_ROWS = 0, PRIME_HIST = 1, PRIME_WAVE = 2, PRIME_OLA = 3 };
 
@@ -42,7 +45,7 @@ struct PrimeLayerDev {
     const float* csrc;  // [Bp * units][H]
 };
 struct PrimeSeqDev {
-    PrimeLayerDev layer[SFSN_HOP_MAX_LAYERS];
+    PrimeLayerDev layer[PRIME_MAX_LAYERS];
     float* cum;  // the half the next launch reads, or NULL
     const float* cum_src;
     int H, HP, units;
@@ -273,7 +276,7 @@ struct SeedLayerDev {
     float* cd;        // [Bp * units][H]
 };
 struct SeedSeqDev {
-    SeedLayerDev layer[SFSN_HOP_MAX_LAYERS];
+    SeedLayerDev layer[PRIME_MAX_LAYERS];
     const float* cum;  // the half the next launch reads, or NULL
     float* cum_d;
     int H, HP, units;
@@ -284,7 +287,7 @@ struct SeedParams {
     unsigned short clips[PRIME_MAX_CLIPS];
     int nsec, n_clips, b0, T;
     int F, D, fcov, ctx_stride;
-    unsigned k;
+    unsigned k, span;  // span: origins k .. k + span read as zero (0; the cIRM-GSN waveform hop: 1, the clip without a call)
     const unsigned* clip_start;
     const float* hist;
     const float* wave_state;
@@ -293,7 +296,9 @@ struct SeedParams {
 };
 static_assert(sizeof(SeedParams) <= 4096, "SeedParams travels as a kernel argument");
 
-__device__ __forceinline__ bool clip_fresh(const unsigned* clip_start, unsigned k, int clip) { return clip_start && clip_start[clip] == k; }
+__device__ __forceinline__ bool clip_fresh(const unsigned* clip_start, unsigned k, unsigned span, int clip) {
+    return clip_start && clip_start[clip] - k <= span;  // (unsigned, wrap-safe)
+}
 
 __device__ __forceinline__ void seed_rows(const SeedParams& p, const PrimeSecDev& sd, int item) {
     const SeedSeqDev& sq = p.seq[sd.seq];
@@ -302,7 +307,7 @@ __device__ __forceinline__ void seed_rows(const SeedParams& p, const PrimeSecDev
     const int j = item % W, rr = item / W;
     const int k = rr % sq.units, i = rr / sq.units;
     const size_t row_s = (size_t)p.clips[i] * sq.units + k, row_d = (size_t)(p.b0 + i) * sq.units + k;
-    const bool fresh = clip_fresh(p.clip_start, p.k, p.clips[i]);
+    const bool fresh = clip_fresh(p.clip_start, p.k, p.span, p.clips[i]);
     float4 h = make_float4(0.0f, 0.0f, 0.0f, 0.0f), c = h;
     float cum = 0.0f;
     if (!fresh) {
@@ -321,14 +326,16 @@ __device__ __forceinline__ void seed_hist(const SeedParams& p, int item) {
     const int d = item % D, r = item / D;
     const int f = r % p.F, i = r / p.F;
     float2 v = make_float2(0.0f, 0.0f);  // (the hop keeps no history of the bins no group covers: nobody reads theirs)
-    if (f < p.fcov && !clip_fresh(p.clip_start, p.k, p.clips[i]))
+    if (f < p.fcov && !clip_fresh(p.clip_start, p.k, p.span, p.clips[i]))
         v = *reinterpret_cast<const float2*>(p.hist + (((size_t)p.clips[i] * p.F + f) * D + d) * 2);
     *reinterpret_cast<float2*>(p.stft + (((size_t)(p.b0 + i) * p.F + f) * p.T + d) * 2) = v;
 }
 
 __device__ __forceinline__ void seed_wave(const SeedParams& p, int item) {
     const int n = item % SEED_CTX, i = item / SEED_CTX;
-    p.ctx[(size_t)(p.b0 + i) * p.ctx_stride + n] = p.wave_state[(size_t)p.clips[i] * FFT_NFFT + (FFT_NFFT - SEED_CTX) + n];
+    // (span: a clip whose origin is the launch after this one has made no call yet -- its old samples read as zero)
+    const bool nocall = p.span && p.clip_start[p.clips[i]] - p.k == 1u;
+    p.ctx[(size_t)(p.b0 + i) * p.ctx_stride + n] = nocall ? 0.0f : p.wave_state[(size_t)p.clips[i] * FFT_NFFT + (FFT_NFFT - SEED_CTX) + n];
 }
 
 __global__ __launch_bounds__(PRIME_THREADS) void hop_seed_kernel(const SeedParams p) {
@@ -349,7 +356,7 @@ __global__ __launch_bounds__(PRIME_THREADS) void hop_seed_kernel(const SeedParam
 struct AdvParams {
     PrimeParams base;  // (stft / enh: rows of T frames, the new ones last; s8 / csrc / cum_src: of the N new frames)
     int T, frame_index;
-    unsigned k;
+    unsigned k, span;  // span: as in SeedParams
     const unsigned* clip_start;
     float* wave_out;  // [Bp][S][128 * N]
 };
@@ -366,12 +373,17 @@ __device__ __forceinline__ void adv_rows(const AdvParams& a, const PrimeSecDev& 
     const size_t row_s = (size_t)(p.b0 + i) * sq.units + k, row_d = (size_t)p.clips[i] * sq.units + k;
     const int8_t* sp = L.s8 + row_s * sq.HP + 4 * j;  // my word of the first new frame; a frame further every Rs * HP bytes
     const size_t fs = Rs * sq.HP;
+    if (N == 0) {  // (the cIRM-GSN waveform clip whose one call has made no frame: zeros, which its frame 0 reads anyway)
+        *reinterpret_cast<unsigned*>(L.h + row_d * sq.HP + 4 * j) = 0u;
+        *reinterpret_cast<float4*>(L.c + row_d * sq.H + 4 * j) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        return;
+    }
     *reinterpret_cast<unsigned*>(L.h + row_d * sq.HP + 4 * j) = *reinterpret_cast<const unsigned*>(sp + (size_t)(N - 1) * fs) & 0x01010101u;
     *reinterpret_cast<float4*>(L.c + row_d * sq.H + 4 * j) = *reinterpret_cast<const float4*>(L.csrc + row_s * sq.H + 4 * j);
     if (sd.layer == 0 && j == 0 && sq.cum) sq.cum[row_d] = sq.cum_src[row_s];
     if (!L.slots) return;
     // (the clip's utterance goes on: its slot is added to -- unless it begins here, where the hop reads the slot as zero)
-    unsigned nspk = clip_fresh(a.clip_start, a.k, p.clips[i]) ? 0u : L.slots[row_d * W + j];
+    unsigned nspk = clip_fresh(a.clip_start, a.k, a.span, p.clips[i]) ? 0u : L.slots[row_d * W + j];
     for (int t0 = 0; t0 < N; t0 += 8) {  // eight independent loads in flight
         unsigned w[8];
 #pragma unroll
@@ -389,8 +401,9 @@ __device__ __forceinline__ void adv_hist(const AdvParams& a, int item) {
     const int d = item % D, r = item / D;
     const int f = r % p.fcov, i = r / p.fcov;
     // the last D frames of [history | new] (T >= D + N: N < D keeps the tail of the old history, which the seed launch wrote there)
-    *reinterpret_cast<float2*>(p.hist + (((size_t)p.clips[i] * p.F + f) * D + d) * 2) =
-        *reinterpret_cast<const float2*>(p.stft + (((size_t)(p.b0 + i) * p.F + f) * T + (T - D + d)) * 2);
+    float2 v = make_float2(0.0f, 0.0f);  // (N == 0: see adv_rows)
+    if (p.N > 0) v = *reinterpret_cast<const float2*>(p.stft + (((size_t)(p.b0 + i) * p.F + f) * T + (T - D + d)) * 2);
+    *reinterpret_cast<float2*>(p.hist + (((size_t)p.clips[i] * p.F + f) * D + d) * 2) = v;
 }
 
 // hop_wave_istft's arithmetic (sfsn_hop_wave_dev.h) over the N new frames, from the clip's carried accumulator: old partial sums
@@ -408,8 +421,11 @@ __device__ __forceinline__ void adv_ola(const AdvParams& a, int blk, char* smem)
     if (pair >= p.n_clips * p.S) return;
     const int i = pair / p.S, s = pair - i * p.S, N = p.N, F = p.F, T = a.T;
     const int clip = p.clips[i];
-    const int fi0 = a.clip_start ? (int)(a.k - a.clip_start[clip]) : a.frame_index;
-    const bool fresh = a.clip_start && fi0 == 0;
+    // the frame index of the first new frame; a clip that begins here carries no sums (span 1: also the clip whose first call, which
+    // has no frame, is launch k -- age -1 -- and whose frame 0 is the first new frame)
+    const int age = a.clip_start ? (int)(a.k - a.clip_start[clip]) : a.frame_index;
+    const bool fresh = a.clip_start && age <= 0 && age >= -(int)a.span;
+    const int fi0 = fresh ? 0 : age;
     const Twiddles tw = make_twiddles<true>(unit, lane);
     float* os = p.ola_state + ((size_t)clip * p.S + s) * FFT_NFFT;
     float2 win[4], wk[4], ola[4];
@@ -602,6 +618,121 @@ extern "C" int sfsn_hop_advance(const sfsn_hop_desc* desc, const int* clips, int
     if (wave) {
         add(PRIME_WAVE, 0, 0, n_clips * FFT_NFFT, PRIME_THREADS);
         add(PRIME_OLA, 0, 0, n_clips * desc->S, PRIME_WAVES);
+    }
+    p.nsec = nsec;
+    hipLaunchKernelGGL(hop_advance_kernel, dim3(blk), dim3(PRIME_THREADS), 0, static_cast<hipStream_t>(stream), a);
+    return hip_ok(hipGetLastError());
+}
+
+// =====================================================================================================================
+// The same two launches for the cIRM-GSN hop (sfsn_fullband_hop_seed / sfsn_fullband_hop_advance, include/sfsn.h): the kernels above
+// from host-filled params -- ONE sequence of one row per clip, H = Hp, every bin has history, and hist_ri is double-buffered by
+// launch parity like h (the half that launch k reads).  Waveform mode: span = 1, the clip whose first call is still to come (origin
+// k + 1) reads as zero like the clip whose frame 0 is launch k.
+// =====================================================================================================================
+static bool fullband_covered(const sfsn_fullband_hop_desc* d, bool wave) {
+    if (wave) return d->hop == 1 && d->D == d->df - 1 && sfsn_fullband_wave_hop_check(d->Hp, d->n_layers, d->F, d->S, d->df, d->B, d->unshared) == SFSN_OK;
+    return sfsn_fullband_hop_check(d->Hp, d->n_layers, d->F, d->S, d->df, d->B, d->hop, d->D, d->unshared) == SFSN_OK;
+}
+
+static int fullband_clip_list(const sfsn_fullband_hop_desc* desc, const int* clips, int n_clips, unsigned short* out) {
+    for (int i = 0; i < n_clips; ++i) {  // (distinct indices below B <= 16: n_clips <= 16)
+        if (clips[i] < 0 || clips[i] >= desc->B) return SFSN_EINVAL;
+        for (int j = 0; j < i; ++j)
+            if (clips[j] == clips[i]) return SFSN_EINVAL;  // (two lanes would own one row)
+        out[i] = (unsigned short)clips[i];
+    }
+    return SFSN_OK;
+}
+
+extern "C" int sfsn_fullband_hop_seed(const sfsn_fullband_hop_desc* desc, const unsigned* spike_slots, const float* wave_state, const int* clips,
+                                      int n_clips, const sfsn_fullband_seed_dst* dst, void* stream) {
+    if (!desc || !clips || !dst || n_clips < 1) return SFSN_EINVAL;
+    const bool wave = wave_state != nullptr;
+    if (!fullband_covered(desc, wave) || (spike_slots && wave)) return SFSN_EUNSUPPORTED;
+    SeedParams p;
+    memset(&p, 0, sizeof(p));
+    if (fullband_clip_list(desc, clips, n_clips, p.clips) != SFSN_OK) return SFSN_EINVAL;
+    const unsigned par = desc->launch_index & 1u;
+    const int D = desc->D, Hp = desc->Hp;
+    if (dst->Bp < 1 || dst->b0 < 0 || n_clips > dst->Bp - dst->b0) return SFSN_EINVAL;
+    if (D > 0 && (dst->T < D || !dst->stft_ri || !aligned8(dst->stft_ri) || !desc->hist_ri[par] || !aligned8(desc->hist_ri[par]))) return SFSN_EINVAL;
+    if (wave && (!desc->clip_start || !dst->wave_ctx || !aligned4(dst->wave_ctx) || dst->wave_stride < SEED_CTX || !aligned4(wave_state)))
+        return SFSN_EINVAL;
+    if (!aligned4(spike_slots) || !aligned4(desc->clip_start)) return SFSN_EINVAL;
+    p.n_clips = n_clips; p.b0 = dst->b0; p.T = dst->T; p.F = desc->F; p.D = D; p.fcov = desc->F; p.ctx_stride = dst->wave_stride;
+    p.k = desc->launch_index; p.span = wave ? 1u : 0u; p.clip_start = desc->clip_start;
+    p.hist = desc->hist_ri[par]; p.wave_state = wave_state; p.stft = dst->stft_ri; p.ctx = dst->wave_ctx;
+    int nsec = 0, blk = 0;
+    auto add = [&](int kind, int layer, int items) {
+        PrimeSecDev& s = p.sec[nsec++];
+        s.kind = kind; s.seq = 0; s.layer = layer; s.blk0 = blk; s.items = items;
+        blk += (items + PRIME_THREADS - 1) / PRIME_THREADS;
+    };
+    SeedSeqDev& d = p.seq[0];
+    d.H = Hp; d.HP = (Hp + 63) / 64 * 64; d.units = 1;
+    for (int l = 0; l < desc->n_layers; ++l) {
+        SeedLayerDev& o = d.layer[l];
+        const sfsn_fullband_hop_layer& hl = desc->layer[l];
+        if (!dst->layer[l].h || !dst->layer[l].c || !aligned16(dst->layer[l].h) || !aligned16(dst->layer[l].c)) return SFSN_EINVAL;
+        if (!hl.h[par] || !hl.c || !aligned4(hl.h[par]) || !aligned16(hl.c)) return SFSN_EINVAL;
+        o.h = hl.h[par]; o.c = hl.c; o.hd = dst->layer[l].h; o.cd = dst->layer[l].c;
+        add(SEED_ROWS, l, n_clips * (Hp / 4));
+    }
+    if (D > 0) add(SEED_HIST, 0, n_clips * desc->F * D);
+    if (wave) add(SEED_WAVE, 0, n_clips * SEED_CTX);
+    p.nsec = nsec;
+    hipLaunchKernelGGL(hop_seed_kernel, dim3(blk), dim3(PRIME_THREADS), 0, static_cast<hipStream_t>(stream), p);
+    return hip_ok(hipGetLastError());
+}
+
+extern "C" int sfsn_fullband_hop_advance(const sfsn_fullband_hop_desc* desc, unsigned* spike_slots, float* wave_state, float* ola_state,
+                                         const int* clips, int n_clips, const sfsn_fullband_advance_src* src, void* stream) {
+    if (!desc || !clips || !src || n_clips < 1) return SFSN_EINVAL;
+    if ((wave_state != nullptr) != (ola_state != nullptr)) return SFSN_EINVAL;
+    const bool wave = wave_state != nullptr;
+    if (!fullband_covered(desc, wave) || (spike_slots && wave)) return SFSN_EUNSUPPORTED;
+    AdvParams a;
+    memset(&a, 0, sizeof(a));
+    PrimeParams& p = a.base;
+    if (fullband_clip_list(desc, clips, n_clips, p.clips) != SFSN_OK) return SFSN_EINVAL;
+    const unsigned par = desc->launch_index & 1u;
+    const int N = src->N, T = src->T, B = desc->B, D = desc->D, Hp = desc->Hp;
+    // (N = 0, waveform mode: the clip without a call whose backlog is one call -- its samples enter wave_state and make no frame)
+    if (N < 0 || (!wave && N < desc->hop) || N % desc->hop != 0 || T < N + D) return SFSN_EINVAL;
+    if (src->Bp < 1 || src->b0 < 0 || n_clips > src->Bp - src->b0) return SFSN_EINVAL;
+    if (D > 0 && (!desc->hist_ri[par] || !aligned8(desc->hist_ri[par]) || (N > 0 && (!src->stft_ri || !aligned8(src->stft_ri))))) return SFSN_EINVAL;
+    if (wave && (!desc->clip_start || !src->wave_tail || !aligned4(src->wave_tail) || !src->window || !aligned4(src->window) ||
+                 !aligned4(wave_state) || !aligned8(ola_state) ||
+                 (N > 0 && (!src->enh_ri || !aligned8(src->enh_ri) || !src->wave_out || !aligned8(src->wave_out)))))
+        return SFSN_EINVAL;
+    if (!aligned4(spike_slots) || !aligned4(desc->clip_start)) return SFSN_EINVAL;
+    p.n_clips = n_clips; p.b0 = src->b0; p.Bp = src->Bp; p.N = N;
+    p.F = desc->F; p.S = desc->S; p.D = D; p.fcov = desc->F;
+    p.stft = src->stft_ri; p.enh = src->enh_ri; p.tail = src->wave_tail;
+    p.hist = desc->hist_ri[par]; p.wave_state = wave_state; p.ola_state = ola_state; p.window = src->window;
+    a.T = T; a.k = desc->launch_index; a.span = wave ? 1u : 0u; a.clip_start = desc->clip_start; a.wave_out = src->wave_out;
+    int nsec = 0, blk = 0;
+    auto add = [&](int kind, int layer, int items, int per_block) {
+        PrimeSecDev& s = p.sec[nsec++];
+        s.kind = kind; s.seq = 0; s.layer = layer; s.blk0 = blk; s.items = items;
+        blk += (items + per_block - 1) / per_block;
+    };
+    PrimeSeqDev& d = p.seq[0];
+    d.H = Hp; d.HP = (Hp + 63) / 64 * 64; d.units = 1;
+    for (int l = 0; l < desc->n_layers; ++l) {
+        PrimeLayerDev& o = d.layer[l];
+        const sfsn_fullband_hop_layer& hl = desc->layer[l];
+        if (N > 0 && (!src->layer[l].spikes_i8 || !src->layer[l].c || !aligned4(src->layer[l].spikes_i8) || !aligned16(src->layer[l].c))) return SFSN_EINVAL;
+        if (!hl.h[par] || !hl.c || !aligned4(hl.h[par]) || !aligned16(hl.c)) return SFSN_EINVAL;
+        o.h = hl.h[par]; o.c = hl.c; o.s8 = src->layer[l].spikes_i8; o.csrc = src->layer[l].c;
+        o.slots = spike_slots ? spike_slots + (size_t)l * B * (Hp / 4) : nullptr;
+        add(PRIME_ROWS, l, n_clips * (Hp / 4), PRIME_THREADS);
+    }
+    if (D > 0) add(PRIME_HIST, 0, n_clips * desc->F * D, PRIME_THREADS);
+    if (wave) {
+        add(PRIME_WAVE, 0, n_clips * FFT_NFFT, PRIME_THREADS);
+        add(PRIME_OLA, 0, n_clips * desc->S, PRIME_WAVES);
     }
     p.nsec = nsec;
     hipLaunchKernelGGL(hop_advance_kernel, dim3(blk), dim3(PRIME_THREADS), 0, static_cast<hipStream_t>(stream), a);

@@ -41,7 +41,15 @@ zero); the per-kernel sequence ends with one per-clip count launch (``sfsn_spike
 Moving a clip: ``export_state(clips)`` / ``import_state(state, clips)`` copy the clips' carried state out of the session (a
 ``clip_state.ClipState``) and into slots of this or another session of the same geometry and tier, where the clips continue bit for bit:
 one launch each way on the one-launch kernel (``sfsn_fullband_hop_state_export`` / ``_import``, csrc/sfsn_state.hip), row copies in the
-per-kernel sequence; stream-ordered, no synchronisation.  These sessions have no ``prime``: an import is their warm start.
+per-kernel sequence; stream-ordered, no synchronisation.
+
+A backlog: ``catch_up(stft, clips)`` / ``catch_up_wave(samples, clips)`` run recorded frames of some clips through the OFFLINE kernels
+(``FullbandEngine._launch_frames``) from the state the clips carry and hand the end state back: what ``N / hop`` calls of ``step``
+(``c`` calls of ``step_wave``) would have returned and left, bit for bit, at offline speed -- a clip that joins mid-call, reconnects
+after a stall or switches from a file to live input.  One launch each way on the one-launch kernel (``sfsn_fullband_hop_seed`` /
+``sfsn_fullband_hop_advance``, csrc/sfsn_prime.hip), row copies in the per-kernel sequence; stream-ordered, no synchronisation.  A
+fresh clip reads as zero state, so ``reset(clips); catch_up(prefix, clips)`` is the warm start from a recorded prefix (the sibling's
+``prime``; its four method names are not defined here).
 
 Not covered here: ``resident`` sessions, ``count_spikes`` together with ``waveform``, waveform sessions beyond 16 clips or with
 separate gate weights, and LSTM models.
@@ -142,6 +150,7 @@ class FullbandStreamingSession:
         self._clip_c0 = np.zeros(batch, dtype=np.int64)
         self._graph: Optional[torch.cuda.CUDAGraph] = None
         self._hop = None
+        self._catch_up_ws: Dict[tuple, dict] = {}  # the offline launches' scratch of the last few backlog sizes (catch_up)
         covered = hop_covers(engine, batch, hop)
         if one_launch is True and not covered:
             raise NotImplementedError(
@@ -469,6 +478,194 @@ class FullbandStreamingSession:
             if self._rows is not None:
                 self._rows[:, b].zero_()
 
+    # ---- a backlog on running clips: the offline kernels from the carried state, their end state back into the session -----------
+    def _catch_up_workspace(self, n: int, N: int, T: int, stack: bool) -> dict:
+        """The offline launches' scratch for a backlog of N frames of n clips (kept for the next backlog of that size: the int8
+        spikes' pad columns stay zero, every stack launch leaves its counters zeroed)."""
+        cache = self._catch_up_ws
+        key = (n, N, stack, torch.cuda.current_stream(self.dev).cuda_stream)
+        ws = cache.get(key)
+        if ws is None:
+            if len(cache) >= 4:
+                cache.clear()
+            ws = cache[key] = self.eng._make_workspace(n, max(N, 1), T, stack)
+        return ws
+
+    def _catch_up_run(self, idx, stft=None, samples=None, nocall: bool = False):
+        """``idx``: distinct clip indices in the caller's order; ``stft`` complex64 [len(idx), F, N], or (waveform mode) ``samples``
+        float32 [len(idx), 128 c] contiguous, ``nocall``: the clips have made no call in their utterance.  Returns (enh [n, S, F, N],
+        mag or None) or the waveform blocks [n, S, 128 c].  Everything on torch's current stream."""
+        eng, spec, dev, L = self.eng, self.eng.spec, self.dev, self.eng.lib
+        n, hop, D, F, S, nl, Hp, HP8 = len(idx), self.hop, self.D, self.F, self.S, spec.layers, eng.Hp, eng.HP8
+        f32 = dict(dtype=torch.float32, device=dev)
+        c = samples.shape[1] // 128 if samples is not None else 0
+        N = stft.shape[-1] if samples is None else c - int(nocall)  # (a clip's first call makes no frame)
+        T = D + N
+        arr = (ctypes.c_int * n)(*idx)
+        h = self._hop
+        with torch.cuda.device(dev):
+            st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            flat = torch.empty((nl, 2, n, Hp), **f32)  # the offline kernels' (h, c) of the listed clips
+            buf = torch.empty((n, F, max(T, 1)), dtype=torch.complex64, device=dev)  # [history | new]
+            ri = torch.view_as_real(buf)
+            wbuf = None
+            if samples is not None:  # [384 samples of context | the new samples]
+                wbuf = (torch.empty if N else torch.zeros)((n, 384 + 128 * c), **f32)
+            if h is not None:
+                slots, wstate, ola = self._state_pointers()
+            if N and h is None:
+                # the per-kernel sequence: the clips' rows of its states and the last D frames of its history window
+                sel = torch.tensor(idx, dtype=torch.long).to(dev, non_blocking=True)
+                flat.copy_(self._flat.index_select(2, sel))
+                if D:
+                    buf[:, :, :D].copy_(self.hist.index_select(0, sel)[:, :, hop:])
+            elif N:
+                dst = _lib.FullbandSeedDst()
+                dst.Bp, dst.T, dst.b0 = n, T, 0
+                if D:
+                    dst.stft_ri = ri.data_ptr()
+                if wbuf is not None:
+                    dst.wave_ctx, dst.wave_stride = wbuf.data_ptr(), wbuf.shape[1]
+                for l in range(nl):
+                    dst.layer[l].h, dst.layer[l].c = flat[l, 0].data_ptr(), flat[l, 1].data_ptr()
+                rc = L.sfsn_fullband_hop_seed(h["ref"], slots, wstate, arr, n, ctypes.byref(dst), st)
+                if rc:
+                    check(rc, "sfsn_fullband_hop_seed")
+                self._count("seed")
+            ws = enh = mag = None
+            if samples is not None:
+                wbuf[:, 384:].copy_(samples)
+            if N:
+                if samples is not None:
+                    from . import spectral
+                    # frame j of the backlog covers samples [128 j, 128 j + 512) of the buffer, the centred frame j + 2 -- behind a
+                    # first call, whose samples make no frame, [128 (j + 1), ..): the centred frame j + 3
+                    lead = 3 if nocall else 2
+                    stft = spectral.stft(wbuf, 512, 128)[:, :, lead:lead + N]
+                buf[:, :, D:].copy_(stft)
+                stack = eng._use_stack(n)
+                ws = self._catch_up_workspace(n, N, T, stack)
+                x = torch.empty((T, n, F), **f32)
+                states = [(flat[l, 0], flat[l, 1]) for l in range(nl)]
+                enh = torch.empty((n, S, F, T, 2), **f32)
+                mag = torch.empty((n, S, F, T), **f32) if S == 1 else None
+                if not torch.cuda.is_current_stream_capturing():
+                    eng._errors.poll()
+                eng._launch_frames(ri, n, T, D, N, stack, ws, x, states, [None] * nl, None, enh, mag)
+            if h is None:
+                self._flat.index_copy_(2, sel, flat)
+                self.hist.index_copy_(0, sel, buf[:, :, T - self.Th:])  # the last D + hop frames of [history | new] (N >= hop)
+                if self._rows is not None:  # the new frames' spikes per clip, added to the clips' counts
+                    tmp = torch.zeros((nl, n), dtype=torch.int64, device=dev)
+                    for l0 in range(0, nl, MAX_COUNT_TENSORS):
+                        jobs = (RowCount * min(MAX_COUNT_TENSORS, nl - l0))()
+                        for j in range(len(jobs)):
+                            t = ws["s8"][l0 + j]
+                            jobs[j].spikes_i8, jobs[j].T, jobs[j].R, jobs[j].HP, jobs[j].rows_per_clip = _ptr(t), T, n, HP8, 1
+                            jobs[j].counts = _ptr(tmp[l0 + j])
+                        check(L.sfsn_spike_count_rows(jobs, len(jobs), D, N, st), "sfsn_spike_count_rows")
+                        eng._count("spike_count")
+                    self._rows.index_add_(1, sel, tmp)
+                return torch.view_as_complex(enh)[..., D:].contiguous(), (mag[..., D:].contiguous() if mag is not None else None)
+            src = _lib.FullbandAdvanceSrc()
+            src.Bp, src.N, src.b0, src.T = n, N, 0, T
+            if N:
+                src.stft_ri = ri.data_ptr()
+                for l in range(nl):  # (the new frames of the workspace's [T][n][HP8] spikes)
+                    src.layer[l].spikes_i8, src.layer[l].c = ws["s8"][l].data_ptr() + D * n * HP8, flat[l, 1].data_ptr()
+            wo = None
+            if samples is not None:
+                tail = wbuf[:, -512:].contiguous()
+                src.wave_tail, src.window = tail.data_ptr(), h["wave"]["window"].data_ptr()
+                if N:
+                    wo = torch.empty((n, S, 128 * N), **f32)
+                    src.enh_ri, src.wave_out = enh.data_ptr(), wo.data_ptr()
+            rc = L.sfsn_fullband_hop_advance(h["ref"], slots, wstate, ola, arr, n, ctypes.byref(src), st)
+            if rc:
+                check(rc, "sfsn_fullband_hop_advance")
+            self._count("advance")
+            # the clips' origins move back by the launches replaced (32-bit wrap-around, as the launch's unsigned difference), behind
+            # the queued launches: the next launch continues that many frame indices further
+            back = c if samples is not None else N // hop
+            b = sorted(idx)
+            j = 0
+            while j < n:  # (one op per run of consecutive clips)
+                m = 1
+                while j + m < n and b[j + m] == b[j] + m:
+                    m += 1
+                h["origin"][b[j]:b[j] + m].sub_(back)
+                j += m
+            if samples is None:
+                return torch.view_as_complex(enh)[..., D:].contiguous(), (mag[..., D:].contiguous() if mag is not None else None)
+            if not nocall:
+                return wo
+            lead0 = torch.zeros((n, S, 128), **f32)  # (the first call's block)
+            return torch.cat([lead0, wo], -1) if wo is not None else lead0
+
+    def _catch_up_clips(self, what: str, clips, given) -> list:
+        from .clip_state import clip_list
+        idx = clip_list(clips, self.B, what)
+        if given != len(idx):
+            raise RuntimeError(f"{what}: a backlog of {given} clips for {len(idx)} clip indices")
+        return idx
+
+    def catch_up(self, stft: torch.Tensor, clips=None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """Run a BACKLOG of ``N`` frames on clips of a running session at the speed of the offline kernels: ``stft`` complex64
+        [len(clips), F, N] on the device, row i for ``clips[i]`` (``None``: every clip; any order).  Returns what ``N / hop`` calls
+        of ``step`` would have returned for those clips -- ``(enh_stft [.., S, F, N], enh_mag`` or None when S > 1``)`` -- and leaves
+        the session where those calls would have left it: last spikes, membranes, deep-filter history, spike counts
+        (``count_spikes=True``), ``clip_frames()``.  The other clips are untouched.  A fresh clip (never stepped, or just
+        ``reset(clips=[b])``) reads as zero state whatever memory holds, so ``reset(clips); catch_up(prefix, clips)`` is the warm
+        start from a recorded prefix; repeated calls process a long recording in chunks.
+
+        The new frames run through ``FullbandEngine._launch_frames`` behind ``D`` frames of the clips' history, from the carried
+        state.  The one-launch tier reads the state out in one launch (``sfsn_fullband_hop_seed``) and takes the end state back in
+        one (``sfsn_fullband_hop_advance``, csrc/sfsn_prime.hip), then moves the clips' origins back by ``N / hop`` launches; the
+        per-kernel tier uses row copies, which the captured graph's next replay sees.  Bit for bit in both tiers, layer 0 included:
+        the hop is bit-identical to the offline sequence (include/sfsn.h).
+
+        ``N``: a positive multiple of ``hop``, the same for every listed clip (``ValueError``).  Ordered on torch's current stream,
+        no synchronisation, like ``reset(clips=...)``."""
+        if self.waveform:
+            raise RuntimeError("this session was opened with waveform=True: use catch_up_wave(samples)")
+        idx = self._catch_up_clips("catch_up", clips, stft.shape[0] if isinstance(stft, torch.Tensor) and stft.dim() == 3 else -1)
+        if stft.device != self.dev or stft.dtype != torch.complex64 or stft.shape[1] != self.F:
+            raise RuntimeError(f"expected complex64 {(len(idx), self.F, 'N')} on {self.dev}, got {stft.dtype} {tuple(stft.shape)} on {stft.device}")
+        N = stft.shape[2]
+        if N < self.hop or N % self.hop != 0:
+            raise ValueError(f"catch_up: {N} frames is not a positive multiple of the session's hop ({self.hop})")
+        out = self._catch_up_run(idx, stft=stft)
+        self._clip_f0[idx] -= N
+        return out
+
+    def catch_up_wave(self, samples: torch.Tensor, clips=None) -> torch.Tensor:
+        """``catch_up`` for waveform sessions (``host_io`` included; device tensors in and out): ``samples`` float32
+        [len(clips), 128 c], ``c >= 1`` calls' worth.  Returns [.., S, 128 c], the concatenation of what ``c`` calls of ``step_wave``
+        would have returned (zero blocks while the clip's frame index is below 2).  A clip that has made a call in its utterance
+        continues: its frames come from the last 384 samples of its STFT state followed by the new samples (``spectral.stft``: the
+        hop's transform, the same bits), ``c`` frames.  A clip that has made no call yet takes its first 128 samples into the STFT
+        state, which makes no frame: ``c - 1`` frames (``c = 1`` writes only the STFT state).  The two kinds have different frame
+        counts: all clips of one call must be of one kind (``ValueError`` naming the first clip of each).  The output blocks continue
+        the clip's overlap-add accumulator in the hop's order and with its envelope; ``clip_calls()`` and ``clip_frames()`` advance
+        by ``c`` calls.  Bit for bit, as ``catch_up``."""
+        if not self.waveform:
+            raise RuntimeError("open the session with waveform=True")
+        idx = self._catch_up_clips("catch_up_wave", clips, samples.shape[0] if isinstance(samples, torch.Tensor) and samples.dim() == 2 else -1)
+        if samples.device != self.dev or samples.dtype != torch.float32:
+            raise RuntimeError(f"expected float32 {(len(idx), '128 * c')} on {self.dev}, got {samples.dtype} {tuple(samples.shape)} on {samples.device}")
+        Ls = samples.shape[1]
+        if Ls < 128 or Ls % 128 != 0:
+            raise ValueError(f"catch_up_wave: {Ls} samples is not a positive multiple of 128")
+        calls = self.clip_calls()
+        none = [b for b in idx if calls[b] < 1]
+        some = [b for b in idx if calls[b] >= 1]
+        if none and some:
+            raise ValueError(f"catch_up_wave: clip {none[0]} has made no call in its current utterance and clip {some[0]} has: they get "
+                             "different frame counts -- make one call per kind")
+        res = self._catch_up_run(idx, samples=samples.contiguous(), nocall=bool(none))
+        self._clip_c0[idx] -= Ls // 128
+        return res
+
     # ---- moving a clip: its state out of its slot, and into a slot of this or another session ------------------------------------
     def _state_signature(self) -> tuple:
         """What two sessions must share for a clip to move between them (clip_state.py): tier, call geometry, model geometry."""
@@ -523,7 +720,7 @@ class FullbandStreamingSession:
     def export_state(self, clips=None):
         """The carried state of ``clips`` (``None``: every clip) as a ``ClipState`` of ``len(clips)`` rows, row i = ``clips[i]``: what
         ``import_state`` needs to continue those clips, bit for bit, in other slots of this session or in another session of equal
-        signature (``clip_state.py``).  cIRM-GSN sessions have no ``prime``: this is their warm start.  The one-launch hop copies
+        signature (``clip_state.py``).  (The warm start from a recorded prefix is ``reset(clips); catch_up(prefix, clips)``.)  The one-launch hop copies
         the state in one launch (``sfsn_fullband_hop_state_export``), the per-kernel sequence with stream-ordered row copies.  The
         session is not changed.  Ordered on torch's current stream, no synchronisation; may return before the copy has run."""
         from .clip_state import ClipState, clip_list, gather_rows
