@@ -553,8 +553,10 @@ __device__ __forceinline__ void scan3j_role(const Scan3jRole& rl, char* smem, in
 // =====================================================================================================================
 #ifndef SFSN_S3Y_LSPLIT
 // fp32 store instructions per frame issued by the loader wave (it also converts the features).  Measured (B = 64, T = 1000, 32 workgroups,
-// ms per launch): 0 / 1-3 / 4 / 7 -> 1.49 / 1.47 / 1.52 / 1.66 (round 2's body 1.64); without fp32 spikes 1.37 (1.64)
-#define SFSN_S3Y_LSPLIT 2
+// ms per launch): 0 / 1-3 / 4 / 7 -> 1.49 / 1.47 / 1.52 / 1.66 (round 2's body 1.64); without fp32 spikes 1.37 (1.64).  Swept again
+// behind the step trim and the stagger (profiles/scan_cell_unpacked.md), 1 / 2 / 3: this role alone 1.32 (2) -> 1.29 (3), the layers
+// 0 + 1 + epilogue launch 1.55 / 1.51 / 1.47, the same at every SFSN_S3J_LSPLIT from 4 to 8.  Values above 3 were not candidates.
+#define SFSN_S3Y_LSPLIT 3
 #endif
 
 template <int KS, int KSB>
