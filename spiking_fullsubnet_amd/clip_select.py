@@ -1,0 +1,123 @@
+"""Host-side bookkeeping the streaming sessions share: which clips a call names, in which order its launches take them, which
+stream-ordered fills / copies and which launch chunks that makes, and the argument checks of the calls that take recorded input.
+
+Pure functions of lists and integers (torch only for ``isinstance`` and tensor attributes): no device work, no session object.
+``streaming.StreamingSession`` and ``fullband_streaming.FullbandStreamingSession`` call them; tests/test_clip_select_host.py runs
+them on the CPU.
+"""
+from __future__ import annotations
+
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+
+def clip_indices(clips, B: int, what: str, *, duplicates: str, empty: str) -> List[int]:
+    """The clip indices a call names, checked: ``clips`` is a sequence, a 1-D numpy array or a 1-D tensor of integers (no bools) in
+    ``[0, B)``; ``None`` is every clip, ``list(range(B))``.
+
+    ``duplicates``: ``"refuse"`` raises ``ValueError(f"{what}: clip indices must be distinct")`` and keeps the caller's order;
+    ``"merge"`` returns ``sorted(set(...))``, and the range check sees the sorted indices; ``"merge_late"`` is ``"merge"`` with the
+    range check on the caller's order (the ``IndexError`` names the first index out of range that the check meets).
+    ``empty``: ``"ok"`` returns ``[]``; ``"refuse"`` raises ``ValueError(f"{what}: no clip selected")``.
+
+    ==========================================  ==========  =============================  ============
+    Call                                        Duplicates  Empty list                     Order
+    ==========================================  ==========  =============================  ============
+    ``reset(clips)``                            merge [1]_  no-op                          sorted
+    ``set_norm_stats``                          refuse      return                         caller order
+    ``prime*``, ``advance*``, ``catch_up*``,    refuse      ``"{what}: no clip selected"``  caller order
+    ``export_state``, ``import_state``
+    ``spike_summary`` (``what="clips"``)        merge       ``"clips: no clip selected"``   sorted
+    ==========================================  ==========  =============================  ============
+
+    .. [1] ``StreamingSession.reset``: ``merge_late``; ``FullbandStreamingSession.reset``: ``merge``.
+    """
+    assert duplicates in ("refuse", "merge", "merge_late") and empty in ("ok", "refuse")
+    if clips is None:
+        return list(range(B))
+    array = isinstance(clips, (torch.Tensor, np.ndarray))
+    if (array and clips.ndim != 1) or isinstance(clips, (str, bytes)) or not hasattr(clips, "__iter__"):
+        raise TypeError("clips: a 1-D tensor or a sequence of clip indices")
+    items = clips.tolist() if array else list(clips)
+    if any(isinstance(i, bool) or not isinstance(i, (int, np.integer)) for i in items):
+        raise TypeError("clips: integer clip indices")
+    idx = [int(i) for i in items]
+    if duplicates == "merge":
+        idx = sorted(set(idx))
+    bad = [i for i in idx if not 0 <= i < B]
+    if bad:
+        raise IndexError(f"clip index {bad[0]} out of range for a session of {B} clips")
+    if duplicates == "merge_late":
+        idx = sorted(set(idx))
+    elif len(set(idx)) != len(idx):
+        raise ValueError(f"{what}: clip indices must be distinct")
+    if not idx and empty == "refuse":
+        raise ValueError(f"{what}: no clip selected")
+    return idx
+
+
+def slot_order(idx: Sequence[int]) -> Tuple[List[int], Optional[List[int]]]:
+    """``(idx sorted, order)`` with ``sorted[j] == idx[order[j]]``; ``order`` is None where ``idx`` ascends already (the launches
+    take clips in slot order: the caller's rows go through ``order`` first, the results through its inverse)."""
+    order = sorted(range(len(idx)), key=idx.__getitem__)
+    return [idx[j] for j in order], (None if order == list(range(len(idx))) else order)
+
+
+def runs_by(indices: Sequence[int], keys: Sequence) -> List[tuple]:
+    """``[(first, count, key), ...]``: ``indices`` cut into runs of consecutive ones (each its predecessor plus one) with equal
+    ``keys`` -- one stream-ordered fill per run (clips that moved together share an age)."""
+    out: List[list] = []
+    for i, k in zip(indices, keys):
+        if out and out[-1][0] + out[-1][1] == i and out[-1][2] == k:
+            out[-1][1] += 1
+        else:
+            out.append([i, 1, k])
+    return [tuple(r) for r in out]
+
+
+def runs(ascending: Sequence[int]) -> List[Tuple[int, int]]:
+    """``[(first, count), ...]``: runs of consecutive indices (one stream-ordered fill / copy per run)."""
+    return [(first, count) for first, count, _ in runs_by(ascending, [None] * len(ascending))]
+
+
+def part_runs(idx: Sequence[int], bounds: Sequence[Tuple[int, int]], limit: int = 256) -> List[Tuple[int, int, List[int]]]:
+    """``[(part number, first position, local clip indices), ...]``: ``idx`` cut into runs of consecutive POSITIONS whose clips
+    lie in one part (``bounds[p] = (b0, nb)``: part p holds the clips ``[b0, b0 + nb)``; local index = clip - b0), ``limit`` clips at
+    most -- what one launch with clip indices in its arguments takes: consecutive rows of the caller's tensor, one part.  Every
+    change of part starts a run; where ``idx`` ascends, a part's runs follow each other."""
+    out: List[Tuple[int, int, List[int]]] = []
+    for j, b in enumerate(idx):
+        p = next(p for p, (b0, nb) in enumerate(bounds) if b0 <= b < b0 + nb)
+        if out and out[-1][0] == p and len(out[-1][2]) < limit:
+            out[-1][2].append(b - bounds[p][0])
+        else:
+            out.append((p, j, [b - bounds[p][0]]))
+    return out
+
+
+def as_i32(v: int) -> int:
+    """A launch index (uint32, wrapping) as the int32 a fill writes."""
+    v &= 0xFFFFFFFF
+    return v - (1 << 32) if v >= 1 << 31 else v
+
+
+def check_frames(what: str, stft: torch.Tensor, n: int, F: int, dev, hop: int) -> int:
+    """``stft``: recorded frames of ``n`` clips, complex64 [n, F, N] on ``dev`` with ``N`` a positive multiple of ``hop``; returns N."""
+    if stft.device != dev or stft.dtype != torch.complex64 or stft.shape[1] != F:
+        raise RuntimeError(f"expected complex64 {(n, F, 'N')} on {dev}, got {stft.dtype} {tuple(stft.shape)} on {stft.device}")
+    N = stft.shape[2]
+    if N < hop or N % hop != 0:
+        raise ValueError(f"{what}: {N} frames is not a positive multiple of the session's hop ({hop})")
+    return N
+
+
+def check_samples(what: str, samples: torch.Tensor, n: int, dev) -> int:
+    """``samples``: recorded samples of ``n`` clips, float32 [n, Ls] on ``dev`` with ``Ls`` a positive multiple of 128; returns Ls."""
+    if samples.device != dev or samples.dtype != torch.float32:
+        raise RuntimeError(f"expected float32 {(n, '128 * c')} on {dev}, got {samples.dtype} {tuple(samples.shape)} on {samples.device}")
+    Ls = samples.shape[1]
+    if Ls < 128 or Ls % 128 != 0:
+        raise ValueError(f"{what}: {Ls} samples is not a positive multiple of 128")
+    return Ls

@@ -33,6 +33,8 @@ from typing import Dict, Sequence, Tuple
 import numpy as np
 import torch
 
+from .clip_select import clip_indices
+
 
 def _pad16(n: int) -> int:
     return (n + 15) // 16 * 16
@@ -97,25 +99,15 @@ def scatter_rows(parts, sel: torch.Tensor, blob: torch.Tensor, layout) -> None:
 
 
 def clip_list(clips, B: int, what: str):
-    """Clip indices of an export / import call, checked with the wording of ``StreamingSession._prime_clips``."""
-    if clips is None:
-        return list(range(B))
-    if isinstance(clips, (torch.Tensor, np.ndarray)) and clips.ndim != 1:
-        raise TypeError("clips: a 1-D tensor or a sequence of clip indices")
-    if isinstance(clips, (str, bytes)) or not hasattr(clips, "__iter__"):
-        raise TypeError("clips: a 1-D tensor or a sequence of clip indices")
-    items = clips.tolist() if isinstance(clips, (torch.Tensor, np.ndarray)) else list(clips)
-    if any(isinstance(i, bool) or not isinstance(i, (int, np.integer)) for i in items):
-        raise TypeError("clips: integer clip indices")
-    idx = [int(i) for i in items]
-    bad = [i for i in idx if not 0 <= i < B]
-    if bad:
-        raise IndexError(f"clip index {bad[0]} out of range for a session of {B} clips")
-    if len(set(idx)) != len(idx):
-        raise ValueError(f"{what}: clip indices must be distinct")
-    if not idx:
-        raise ValueError(f"{what}: no clip selected")
-    return idx
+    """Clip indices of an export / import / backlog call: ``clip_select.clip_indices``, distinct, at least one, caller's order."""
+    return clip_indices(clips, B, what, duplicates="refuse", empty="refuse")
+
+
+def new_blob(n: int, nbytes: int, layout, device) -> torch.Tensor:
+    """The ``[n, nbytes]`` blob an export launch writes: no fill launch in front of it where the sections tile the row; the padding
+    between sections reads as zero."""
+    alloc = torch.empty if sum(b - a for _, a, b in layout) == nbytes else torch.zeros
+    return alloc((n, nbytes), dtype=torch.uint8, device=device)
 
 
 class ClipState:
@@ -195,3 +187,14 @@ def check_import(state, idx, dev, what: str = "import_state") -> None:
         raise RuntimeError(f"{what}: the state is on {state.device}, the session on {dev}: call state.to({str(dev)!r}) first")
     if len(state) != len(idx):
         raise RuntimeError(f"{what}: a state of {len(state)} clips for {len(idx)} clip indices")
+
+
+def import_clips(state, clips, B: int, dev, signature, layout, nbytes: int) -> list:
+    """What every session's ``import_state`` does first: the clip indices (``clip_list``), then the refusals in their order -- the
+    state's type, device and row count, its signature against the session's, its blob layout against the session's."""
+    idx = clip_list(clips, B, "import_state")
+    check_import(state, idx, dev)
+    state.check_signature(signature)
+    if state.layout != layout or state.blob.shape[1] != nbytes:
+        raise ValueError("import_state: the state's blob layout is not this session's")
+    return idx

@@ -66,6 +66,7 @@ import torch
 
 from . import _lib
 from ._lib import MAX_COUNT_TENSORS, FullbandHopDesc, FullbandWaveDesc, RowCount, check
+from .clip_select import as_i32, check_frames, check_samples, clip_indices, runs, runs_by
 from .engine import SpikeSummary, _ptr
 from .fullband_engine import FullbandEngine
 
@@ -442,25 +443,10 @@ class FullbandStreamingSession:
         self._calls = 0
         self._clip_c0[:] = 0
 
-    @staticmethod
-    def _as_i32(v: int) -> int:  # a launch index (uint32) as the int32 a fill writes
-        v &= 0xFFFFFFFF
-        return v - (1 << 32) if v >= 1 << 31 else v
-
-    def _clip_indices(self, clips) -> list:
-        if isinstance(clips, (torch.Tensor, np.ndarray)) and clips.ndim != 1:
-            raise TypeError("clips: a 1-D tensor or a sequence of clip indices")
-        items = clips.tolist() if isinstance(clips, (torch.Tensor, np.ndarray)) else list(clips)
-        if any(isinstance(i, bool) or not isinstance(i, (int, np.integer)) for i in items):
-            raise TypeError("clips: integer clip indices")
-        idx = sorted(set(int(i) for i in items))
-        bad = [i for i in idx if not 0 <= i < self.B]
-        if bad:
-            raise IndexError(f"clip index {bad[0]} out of range for a session of {self.B} clips")
-        return idx
+    _as_i32 = staticmethod(as_i32)  # a launch index (uint32) as the int32 a fill writes
 
     def _reset_clips(self, clips) -> None:
-        idx = self._clip_indices(clips)
+        idx = clip_indices(clips, self.B, "reset", duplicates="merge", empty="ok")
         if not idx:
             return
         self._clip_f0[idx] = self.frames_done
@@ -587,14 +573,8 @@ class FullbandStreamingSession:
             # the clips' origins move back by the launches replaced (32-bit wrap-around, as the launch's unsigned difference), behind
             # the queued launches: the next launch continues that many frame indices further
             back = c if samples is not None else N // hop
-            b = sorted(idx)
-            j = 0
-            while j < n:  # (one op per run of consecutive clips)
-                m = 1
-                while j + m < n and b[j + m] == b[j] + m:
-                    m += 1
-                h["origin"][b[j]:b[j] + m].sub_(back)
-                j += m
+            for b0, m in runs(sorted(idx)):  # (one op per run of consecutive clips)
+                h["origin"][b0:b0 + m].sub_(back)
             if samples is None:
                 return torch.view_as_complex(enh)[..., D:].contiguous(), (mag[..., D:].contiguous() if mag is not None else None)
             if not nocall:
@@ -603,8 +583,7 @@ class FullbandStreamingSession:
             return torch.cat([lead0, wo], -1) if wo is not None else lead0
 
     def _catch_up_clips(self, what: str, clips, given) -> list:
-        from .clip_state import clip_list
-        idx = clip_list(clips, self.B, what)
+        idx = clip_indices(clips, self.B, what, duplicates="refuse", empty="refuse")
         if given != len(idx):
             raise RuntimeError(f"{what}: a backlog of {given} clips for {len(idx)} clip indices")
         return idx
@@ -629,11 +608,7 @@ class FullbandStreamingSession:
         if self.waveform:
             raise RuntimeError("this session was opened with waveform=True: use catch_up_wave(samples)")
         idx = self._catch_up_clips("catch_up", clips, stft.shape[0] if isinstance(stft, torch.Tensor) and stft.dim() == 3 else -1)
-        if stft.device != self.dev or stft.dtype != torch.complex64 or stft.shape[1] != self.F:
-            raise RuntimeError(f"expected complex64 {(len(idx), self.F, 'N')} on {self.dev}, got {stft.dtype} {tuple(stft.shape)} on {stft.device}")
-        N = stft.shape[2]
-        if N < self.hop or N % self.hop != 0:
-            raise ValueError(f"catch_up: {N} frames is not a positive multiple of the session's hop ({self.hop})")
+        N = check_frames("catch_up", stft, len(idx), self.F, self.dev, self.hop)
         out = self._catch_up_run(idx, stft=stft)
         self._clip_f0[idx] -= N
         return out
@@ -651,11 +626,7 @@ class FullbandStreamingSession:
         if not self.waveform:
             raise RuntimeError("open the session with waveform=True")
         idx = self._catch_up_clips("catch_up_wave", clips, samples.shape[0] if isinstance(samples, torch.Tensor) and samples.dim() == 2 else -1)
-        if samples.device != self.dev or samples.dtype != torch.float32:
-            raise RuntimeError(f"expected float32 {(len(idx), '128 * c')} on {self.dev}, got {samples.dtype} {tuple(samples.shape)} on {samples.device}")
-        Ls = samples.shape[1]
-        if Ls < 128 or Ls % 128 != 0:
-            raise ValueError(f"catch_up_wave: {Ls} samples is not a positive multiple of 128")
+        Ls = check_samples("catch_up_wave", samples, len(idx), self.dev)
         calls = self.clip_calls()
         none = [b for b in idx if calls[b] < 1]
         some = [b for b in idx if calls[b] >= 1]
@@ -723,16 +694,14 @@ class FullbandStreamingSession:
         signature (``clip_state.py``).  (The warm start from a recorded prefix is ``reset(clips); catch_up(prefix, clips)``.)  The one-launch hop copies
         the state in one launch (``sfsn_fullband_hop_state_export``), the per-kernel sequence with stream-ordered row copies.  The
         session is not changed.  Ordered on torch's current stream, no synchronisation; may return before the copy has run."""
-        from .clip_state import ClipState, clip_list, gather_rows
+        from .clip_state import ClipState, clip_list, gather_rows, new_blob
         idx = clip_list(clips, self.B, "export_state")
         layout, nbytes = self._state_layout()
         if self._hop is None:
             sel = torch.tensor(idx, dtype=torch.long).to(self.dev, non_blocking=True)
             blob = gather_rows(self._state_parts(), sel, nbytes, layout)
         else:
-            # (no fill launch in front of the copy where the sections tile the row; the padding between sections reads as zero)
-            alloc = torch.empty if sum(b - a for _, a, b in layout) == nbytes else torch.zeros
-            blob = alloc((len(idx), nbytes), dtype=torch.uint8, device=self.dev)
+            blob = new_blob(len(idx), nbytes, layout, self.dev)
             slots, wstate, ola = self._state_pointers()
             arr = (ctypes.c_int * len(idx))(*idx)  # (B <= 16: one launch)
             with torch.cuda.device(self.dev):
@@ -749,13 +718,9 @@ class FullbandStreamingSession:
         clips go on untouched.  Ordered on torch's current stream, no synchronisation.  The weights are NOT compared: importing
         into a session of another model of the same geometry is the caller's decision.  Refusals as for
         ``StreamingSession.import_state``."""
-        from .clip_state import check_import, clip_list, scatter_rows
-        idx = clip_list(clips, self.B, "import_state")
-        check_import(state, idx, self.dev)
-        state.check_signature(self._state_signature())
+        from .clip_state import import_clips, scatter_rows
         layout, nbytes = self._state_layout()
-        if state.layout != layout or state.blob.shape[1] != nbytes:
-            raise ValueError("import_state: the state's blob layout is not this session's")
+        idx = import_clips(state, clips, self.B, self.dev, self._state_signature(), layout, nbytes)
         blob = state.blob.contiguous()
         if self._hop is None:
             sel = torch.tensor(idx, dtype=torch.long).to(self.dev, non_blocking=True)
@@ -773,13 +738,8 @@ class FullbandStreamingSession:
         # the clips' origins (include/sfsn.h): the next launch gives each the frame index it had at export -- a waveform clip's is its
         # calls minus one (-1: its first call is still to come).  Fills behind the queued launches, as in _reset_clips
         ages = [int(state.calls[j]) - 1 if self.waveform else int(state.frames[j]) // self.hop for j in range(len(idx))]
-        j = 0
-        while j < len(idx):  # (one fill per run of consecutive clips of one age: clips that moved together)
-            m = 1
-            while j + m < len(idx) and idx[j + m] == idx[j] + m and ages[j + m] == ages[j]:
-                m += 1
-            h["origin"][idx[j]:idx[j] + m].fill_(self._as_i32(h["desc"].launch_index - ages[j]))
-            j += m
+        for b0, m, age in runs_by(idx, ages):  # (one fill per run of consecutive clips of one age: clips that moved together)
+            h["origin"][b0:b0 + m].fill_(self._as_i32(h["desc"].launch_index - age))
         if self.waveform:
             self._clip_c0[idx] = self._calls - state.calls
         else:
@@ -803,12 +763,7 @@ class FullbandStreamingSession:
         (``RuntimeError``)."""
         if not self.count_spikes:
             raise RuntimeError("open the session with count_spikes=True to count spikes")
-        if clips is None:
-            idx = list(range(self.B))
-        else:
-            idx = self._clip_indices(clips)
-            if not idx:
-                raise ValueError("clips: no clip selected")
+        idx = clip_indices(clips, self.B, "clips", duplicates="merge", empty="refuse")
         frames = self.clip_frames()[idx]
         if (frames != frames[0]).any():
             raise ValueError(f"spike_summary: the selected clips have seen different numbers of frames {frames.tolist()}; select "

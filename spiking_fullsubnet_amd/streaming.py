@@ -68,6 +68,7 @@ import torch
 
 from ._lib import (AdvanceSrc, DfGroup, HopDesc, HOP_MAX_GROUPS, HOP_MAX_LAYERS, MAX_COUNT_TENSORS, NORM_CUMLAPLACE, PrimeSrc, RowCount,
                    SeedDst, check)
+from .clip_select import as_i32, check_frames, check_samples, clip_indices, part_runs, runs, runs_by, slot_order
 from .engine import Engine, NormStats, SpikeSummary, _ptr
 
 
@@ -461,17 +462,7 @@ class StreamingSession:
             idx = None
             n = self.B
         else:
-            if isinstance(clips, (torch.Tensor, np.ndarray)) and clips.ndim != 1:
-                raise TypeError("clips: a 1-D tensor or a sequence of clip indices")
-            items = clips.tolist() if isinstance(clips, (torch.Tensor, np.ndarray)) else list(clips)
-            if any(isinstance(i, bool) or not isinstance(i, (int, np.integer)) for i in items):
-                raise TypeError("clips: integer clip indices")
-            idx = [int(i) for i in items]
-            bad = [i for i in idx if not 0 <= i < self.B]
-            if bad:
-                raise IndexError(f"clip index {bad[0]} out of range for a session of {self.B} clips")
-            if len(set(idx)) != len(idx):
-                raise ValueError("set_norm_stats: clip indices must be distinct")
+            idx = clip_indices(clips, self.B, "set_norm_stats", duplicates="refuse", empty="ok")
             if not idx:
                 return
             n = len(idx)
@@ -487,22 +478,14 @@ class StreamingSession:
             else:
                 mine.index_copy_(-1, sel, new)
 
-    @staticmethod
-    def _as_i32(v: int) -> int:  # a launch index (uint32) as the int32 a fill writes
-        v &= 0xFFFFFFFF
-        return v - (1 << 32) if v >= 1 << 31 else v
+    _as_i32 = staticmethod(as_i32)  # a launch index (uint32) as the int32 a fill writes
+
+    def _refuse_resident(self, what: str) -> None:
+        if self.resident:
+            raise NotImplementedError(f"{what}: not on a resident session (resident=True): its launch holds the state while it runs")
 
     def _reset_clips(self, clips) -> None:
-        if isinstance(clips, (torch.Tensor, np.ndarray)) and clips.ndim != 1:
-            raise TypeError("clips: a 1-D tensor or a sequence of clip indices")
-        items = clips.tolist() if isinstance(clips, (torch.Tensor, np.ndarray)) else list(clips)
-        if any(isinstance(i, bool) or not isinstance(i, (int, np.integer)) for i in items):
-            raise TypeError("clips: integer clip indices")
-        idx = [int(i) for i in items]
-        bad = [i for i in idx if not 0 <= i < self.B]
-        if bad:
-            raise IndexError(f"clip index {bad[0]} out of range for a session of {self.B} clips")
-        idx = sorted(set(idx))
+        idx = clip_indices(clips, self.B, "reset", duplicates="merge_late", empty="ok")
         if not idx:
             return
         self._clip_f0[idx] = self.frames_done
@@ -537,39 +520,68 @@ class StreamingSession:
 
     # ---- priming: a recorded prefix through the offline kernels, its end state into the session ---------------------------------
     def _prime_clips(self, clips, n_given: int, what: str = "prime"):
-        """(clip indices in the caller's order, the permutation that sorts them or None) of a prime / advance call; checked like
-        set_norm_stats' clips."""
-        if clips is None:
-            idx = list(range(self.B))
-        else:
-            if isinstance(clips, (torch.Tensor, np.ndarray)) and clips.ndim != 1:
-                raise TypeError("clips: a 1-D tensor or a sequence of clip indices")
-            items = clips.tolist() if isinstance(clips, (torch.Tensor, np.ndarray)) else list(clips)
-            if any(isinstance(i, bool) or not isinstance(i, (int, np.integer)) for i in items):
-                raise TypeError("clips: integer clip indices")
-            idx = [int(i) for i in items]
-            bad = [i for i in idx if not 0 <= i < self.B]
-            if bad:
-                raise IndexError(f"clip index {bad[0]} out of range for a session of {self.B} clips")
-            if len(set(idx)) != len(idx):
-                raise ValueError(f"{what}: clip indices must be distinct")
-            if not idx:
-                raise ValueError(f"{what}: no clip selected")
+        """(clip indices in the caller's order, the permutation that sorts them or None) of a prime / advance call."""
+        idx = clip_indices(clips, self.B, what, duplicates="refuse", empty="refuse")
         if n_given != len(idx):
             raise RuntimeError(f"{what}: {'a prefix' if what.startswith('prime') else 'a backlog'} of {n_given} clips for {len(idx)} clip indices")
-        order = sorted(range(len(idx)), key=idx.__getitem__)
-        return idx, (None if order == list(range(len(idx))) else order)
+        return idx, slot_order(idx)[1]
 
-    @staticmethod
-    def _runs(local):
-        """Ascending indices as (first, count) runs of consecutive ones (one stream-ordered fill / copy per run)."""
-        runs = []
-        for i in local:
-            if runs and runs[-1][0] + runs[-1][1] == i:
-                runs[-1][1] += 1
-            else:
-                runs.append([i, 1])
-        return runs
+    def _slot_ordered(self, rows, idx, order, run):
+        """``run(rows, idx)`` -> a tuple of tensors with one row per clip, called with the rows and the clip indices in slot order
+        (``order``: ``_prime_clips``'; None: they are) and its results put back into the caller's order."""
+        if order is None:
+            return run(rows, idx)
+        perm = torch.tensor(order, dtype=torch.long).to(self.dev, non_blocking=True)
+        res = run(rows.index_select(0, perm), [idx[j] for j in order])
+        inv = torch.empty_like(perm)
+        inv[perm] = torch.arange(len(order), device=self.dev)
+        return tuple(t.index_select(0, inv) for t in res)
+
+    def _put_states(self, es, idx) -> None:
+        """The per-kernel sequence: rows of an offline forward's end state ``es`` into the (h, c) of the clips ``idx`` (ascending)."""
+        spec = self.eng.spec
+        units = [1] + [spec.units(g) for g in range(spec.n_groups)]
+        for d, e, us in ((self.fb, es["fb"], units[:1]), (self.sb, es["sb"], units[1:])):
+            for mine, theirs in zip(d["states"], e["states"]):
+                for (h, c), (hs, cs), u in zip(mine, theirs, us):
+                    j0 = 0  # (idx ascends: a run of consecutive clips is a run of consecutive rows on both sides)
+                    for b0, m in runs(idx):
+                        h[b0 * u:(b0 + m) * u].copy_(hs[j0 * u:(j0 + m) * u])
+                        c[b0 * u:(b0 + m) * u].copy_(cs[j0 * u:(j0 + m) * u])
+                        j0 += m
+
+    def _part_chunks(self, idx) -> list:
+        """``idx`` ascending: [(part, [(first position, local clip indices), ...])] for the parts that hold some of the clips, each
+        part's clips in chunks of 256 at most (a launch takes 256 clip indices in its arguments)."""
+        out = []
+        for part, j0, local in self._part_runs(idx):
+            if not out or out[-1][0] is not part:
+                out.append((part, []))
+            out[-1][1].append((j0, local))
+        return out
+
+    def _part_launch(self, name: str, part, local, arg, st) -> None:
+        """One ``sfsn_hop_prime`` / ``_seed`` / ``_advance`` launch: clips ``local`` of ``part``, ``arg`` the launch's source / sink."""
+        arr = (ctypes.c_int * len(local))(*local)
+        with torch.cuda.device(self.dev):
+            rc = getattr(self.eng.lib, name)(part["ref"], arr, len(local), ctypes.byref(arg), st)
+        if rc:
+            check(rc, name)
+
+    def _first_call_made(self, idx) -> None:
+        """Waveform sessions, before clips ``idx`` take a state from outside: when nobody has called yet -- the session's first call
+        launches nothing -- count that call as made, with every other clip's utterance beginning at the next call (origin = the
+        launch after the next: that launch is their first call)."""
+        if not self.waveform or self._wave_calls != 0:
+            return
+        self._wave_calls = 1
+        self._clip_c0[:] = 1
+        listed = set(idx)
+        for part in self._hop["parts"]:
+            others = [b - part["b0"] for b in range(part["b0"], part["b0"] + part["nb"]) if b not in listed]
+            for b0, m in runs(others):
+                part["origin"][b0:b0 + m].fill_(self._as_i32(part["desc"].launch_index + 1))
+            part["desc"].clip_start = part["origin"].data_ptr()
 
     def _prime_sorted(self, stft, idx, tail=None):
         """The transplant.  ``stft``: complex64 [len(idx), F, N] contiguous, or None (waveform mode, no frame yet); ``idx`` ascending;
@@ -587,17 +599,9 @@ class StreamingSession:
             finally:
                 eng._l0_hop = None
             es = out["end_state"]
-        units = [1] + [spec.units(g) for g in range(ng)]
         if self._hop is None:
             # the per-kernel sequence: row copies into the states, the history and the counts the (captured) launches read and write
-            for d, e, us in ((self.fb, es["fb"], units[:1]), (self.sb, es["sb"], units[1:])):
-                for mine, theirs in zip(d["states"], e["states"]):
-                    for (h, c), (hs, cs), u in zip(mine, theirs, us):
-                        j0 = 0  # (idx ascends: a run of consecutive clips is a run of consecutive rows on both sides)
-                        for b0, m in self._runs(idx):
-                            h[b0 * u:(b0 + m) * u].copy_(hs[j0 * u:(j0 + m) * u])
-                            c[b0 * u:(b0 + m) * u].copy_(cs[j0 * u:(j0 + m) * u])
-                            j0 += m
+            self._put_states(es, idx)
             Th = self.Th
             for j, b in enumerate(idx):  # the last D + hop frames, zeros in front of a shorter prefix
                 if N >= Th:
@@ -608,7 +612,6 @@ class StreamingSession:
                 if self._rows is not None:
                     self._rows[:, b].copy_(es["counts"][:, j])
             return out
-        L = eng.lib
         st = ctypes.c_void_p(_raw_stream(self._dev_index))
         src = PrimeSrc()
         src.Bp, src.N = n, N
@@ -624,24 +627,16 @@ class StreamingSession:
                     src.sb[g].cum = es["cum"][1 + g].data_ptr()
         if tail is not None:
             src.wave_tail = tail.data_ptr()
-        for part in self._hop["parts"]:
-            pos = [j for j, b in enumerate(idx) if part["b0"] <= b < part["b0"] + part["nb"]]
-            if not pos:
-                continue
+        for part, chunks in self._part_chunks(idx):
             d = part["desc"]
             # the clips' origin: launch_index is the next launch, which gives them frame index N / hop.  (N = 0, a waveform clip
             # whose first call has made no frame: the origin IS the next launch, which reads the state as zero -- as it must -- and
             # the samples from wave_state, which no origin makes it skip)
             org = self._as_i32(d.launch_index - N // hop)
-            for j0 in range(0, len(pos), 256):  # (the launch takes 256 clip indices in its arguments)
-                local = [idx[j] - part["b0"] for j in pos[j0:j0 + 256]]
-                src.b0 = pos[j0]
-                arr = (ctypes.c_int * len(local))(*local)
-                with torch.cuda.device(self.dev):
-                    rc = L.sfsn_hop_prime(part["ref"], arr, len(local), ctypes.byref(src), st)
-                if rc:
-                    check(rc, "sfsn_hop_prime")
-            for b0, m in self._runs([idx[j] - part["b0"] for j in pos]):  # (fills behind the queued launches, as in _reset_clips)
+            for j0, local in chunks:
+                src.b0 = j0
+                self._part_launch("sfsn_hop_prime", part, local, src, st)
+            for b0, m in runs([b for _, local in chunks for b in local]):  # (fills behind the queued launches, as in _reset_clips)
                 part["origin"][b0:b0 + m].fill_(org)
             d.clip_start = part["origin"].data_ptr()
         return out
@@ -656,31 +651,22 @@ class StreamingSession:
         ``hop`` (``ValueError``): a clip's origin is a launch index.  A frozen model with an offline norm runs the prefix with the
         session's current statistics of those clips.  Ordered on torch's current stream, no synchronisation, like
         ``reset(clips=...)``.  Not on resident sessions (``NotImplementedError``); every listed clip gets the same ``N``."""
-        if self.resident:
-            raise NotImplementedError("prime: not on a resident session (resident=True): its launch holds the state while it runs")
+        self._refuse_resident("prime")
         if self.waveform:
             raise RuntimeError("this session was opened with waveform=True: use prime_wave(samples)")
         idx, order = self._prime_clips(clips, stft.shape[0] if isinstance(stft, torch.Tensor) and stft.dim() == 3 else -1)
-        if stft.device != self.dev or stft.dtype != torch.complex64 or stft.shape[1] != self.F:
-            raise RuntimeError(f"expected complex64 {(len(idx), self.F, 'N')} on {self.dev}, got {stft.dtype} {tuple(stft.shape)} on {stft.device}")
-        N = stft.shape[2]
-        if N < self.hop or N % self.hop != 0:
-            raise ValueError(f"prime: {N} frames is not a positive multiple of the session's hop ({self.hop})")
-        perm = None
-        if order is not None:
-            perm = torch.tensor(order, dtype=torch.long).to(self.dev, non_blocking=True)
-            stft, idx = stft.index_select(0, perm), [idx[j] for j in order]
-        out = self._prime_sorted(stft.contiguous(), idx)
+        N = check_frames("prime", stft, len(idx), self.F, self.dev, self.hop)
+
+        def run(rows, slots):
+            out = self._prime_sorted(rows.contiguous(), slots)
+            return out["enh_stft"], out["enh_mag"]
+
+        enh, mag = self._slot_ordered(stft, idx, order, run)
         if clips is None:  # the whole session: as after reset() and N frames of step()
             self.frames_done = N
             self._clip_f0[:] = 0
         else:
             self._clip_f0[idx] = self.frames_done - N
-        enh, mag = out["enh_stft"], out["enh_mag"]
-        if perm is not None:
-            inv = torch.empty_like(perm)
-            inv[perm] = torch.arange(len(order), device=self.dev)
-            enh, mag = enh.index_select(0, inv), mag.index_select(0, inv)
         return enh, mag
 
     def prime_wave(self, samples: torch.Tensor, clips=None) -> torch.Tensor:
@@ -689,50 +675,33 @@ class StreamingSession:
         ``step_wave`` would have returned (the first three blocks are zero).  The prefix has the frames ``0 .. c - 2``: the two
         further frames torch.stft(center=True) makes of these samples look into samples not yet heard and are not used; ``c = 1``
         has no frame, its samples only enter the STFT state."""
-        if self.resident:
-            raise NotImplementedError("prime_wave: not on a resident session (resident=True): its launch holds the state while it runs")
+        self._refuse_resident("prime_wave")
         if not self.waveform:
             raise RuntimeError("open the session with waveform=True")
         idx, order = self._prime_clips(clips, samples.shape[0] if isinstance(samples, torch.Tensor) and samples.dim() == 2 else -1)
-        if samples.device != self.dev or samples.dtype != torch.float32:
-            raise RuntimeError(f"expected float32 {(len(idx), '128 * c')} on {self.dev}, got {samples.dtype} {tuple(samples.shape)} on {samples.device}")
-        Ls = samples.shape[1]
-        if Ls < 128 or Ls % 128 != 0:
-            raise ValueError(f"prime_wave: {Ls} samples is not a positive multiple of 128")
+        Ls = check_samples("prime_wave", samples, len(idx), self.dev)
         from . import spectral
         c, n, S = Ls // 128, len(idx), self.eng.spec.num_spks
-        perm = None
-        if order is not None:
-            perm = torch.tensor(order, dtype=torch.long).to(self.dev, non_blocking=True)
-            samples, idx = samples.index_select(0, perm), [idx[j] for j in order]
-        samples = samples.contiguous()
-        tail = samples[:, -512:].contiguous() if Ls >= 512 else torch.nn.functional.pad(samples, (512 - Ls, 0))
-        stft = spectral.stft(samples, 512, 128)[:, :, :c - 1].contiguous() if c > 1 else None  # frames 0 .. c - 2 (see above)
-        out = self._prime_sorted(stft, idx, tail=tail)
-        res = torch.zeros((n, S, Ls), dtype=torch.float32, device=self.dev)
-        if c > 3:  # calls 3 .. c - 1 return samples [0, 128 (c - 3)): complete with frame c - 2, the last one the prefix has
-            res[:, :, 384:] = spectral.istft(out["enh_stft"].reshape(n * S, self.F, c - 1), 512, 128, length=128 * (c - 3)).view(n, S, -1)
+
+        def run(rows, slots):
+            rows = rows.contiguous()
+            tail = rows[:, -512:].contiguous() if Ls >= 512 else torch.nn.functional.pad(rows, (512 - Ls, 0))
+            stft = spectral.stft(rows, 512, 128)[:, :, :c - 1].contiguous() if c > 1 else None  # frames 0 .. c - 2 (see above)
+            out = self._prime_sorted(stft, slots, tail=tail)
+            res = torch.zeros((n, S, Ls), dtype=torch.float32, device=self.dev)
+            if c > 3:  # calls 3 .. c - 1 return samples [0, 128 (c - 3)): complete with frame c - 2, the last one the prefix has
+                res[:, :, 384:] = spectral.istft(out["enh_stft"].reshape(n * S, self.F, c - 1), 512, 128, length=128 * (c - 3)).view(n, S, -1)
+            if clips is not None:
+                self._first_call_made(slots)
+            return (res,)
+
+        res, = self._slot_ordered(samples, idx, order, run)
         if clips is None:  # the whole session: as after reset() and c calls of step_wave()
             self._wave_calls, self.frames_done = c, c - 1
             self._clip_c0[:] = 0
         else:
-            if self._wave_calls == 0:
-                # nobody has called yet, and the session's first call launches nothing: count it as made, with every other clip's
-                # utterance beginning at the next call (origin = the launch after the next: that launch is their first call)
-                self._wave_calls = 1
-                self._clip_c0[:] = 1
-                listed = set(idx)
-                for part in self._hop["parts"]:
-                    others = [b - part["b0"] for b in range(part["b0"], part["b0"] + part["nb"]) if b not in listed]
-                    for b0, m in self._runs(others):
-                        part["origin"][b0:b0 + m].fill_(self._as_i32(part["desc"].launch_index + 1))
-                    part["desc"].clip_start = part["origin"].data_ptr()
             self._clip_c0[idx] = self._wave_calls - c
         self._primed = True
-        if perm is not None:
-            inv = torch.empty_like(perm)
-            inv[perm] = torch.arange(len(order), device=self.dev)
-            res = res.index_select(0, inv)
         return res
 
     # ---- a backlog on running clips: the offline kernels from the carried state, their end state back into the session -----------
@@ -740,7 +709,7 @@ class StreamingSession:
         """``stft``: complex64 [len(idx), F, N], or None in waveform mode, where ``samples`` float32 [len(idx), 128 * N] contiguous
         give the frames; ``idx`` ascending.  Returns (the forward of the N new frames, the waveform blocks or None).  Everything on
         torch's current stream."""
-        eng, spec, L = self.eng, self.eng.spec, self.eng.lib
+        eng, spec = self.eng, self.eng.spec
         n, hop, D, ng, dev = len(idx), self.hop, self.D, spec.n_groups, self.dev
         N = stft.shape[-1] if samples is None else samples.shape[1] // 128
         T = D + N
@@ -774,19 +743,11 @@ class StreamingSession:
                 dst.fb.cum = start["cum"][0].data_ptr()
                 for g in range(ng):
                     dst.sb[g].cum = start["cum"][1 + g].data_ptr()
-            for part in self._hop["parts"]:
-                pos = [j for j, b in enumerate(idx) if part["b0"] <= b < part["b0"] + part["nb"]]
-                if not pos:
-                    continue
+            for part, chunks in self._part_chunks(idx):
                 part["desc"].clip_start = part["origin"].data_ptr()  # the clips' own origins from now on (they say which clip is fresh)
-                for j0 in range(0, len(pos), 256):  # (a launch takes 256 clip indices in its arguments)
-                    local = [idx[j] - part["b0"] for j in pos[j0:j0 + 256]]
-                    dst.b0 = pos[j0]
-                    arr = (ctypes.c_int * len(local))(*local)
-                    with torch.cuda.device(dev):
-                        rc = L.sfsn_hop_seed(part["ref"], arr, len(local), ctypes.byref(dst), st)
-                    if rc:
-                        check(rc, "sfsn_hop_seed")
+                for j0, local in chunks:
+                    dst.b0 = j0
+                    self._part_launch("sfsn_hop_seed", part, local, dst, st)
         if samples is not None:
             from . import spectral
             wbuf[:, 384:].copy_(samples)
@@ -802,14 +763,7 @@ class StreamingSession:
             eng._l0_hop = None
         es = out["end_state"]
         if self._hop is None:
-            for d, e, us in ((self.fb, es["fb"], units[:1]), (self.sb, es["sb"], units[1:])):
-                for mine, theirs in zip(d["states"], e["states"]):
-                    for (h, c), (hs, cs), u in zip(mine, theirs, us):
-                        j0 = 0  # (idx ascends: a run of consecutive clips is a run of consecutive rows on both sides)
-                        for b0, m in self._runs(idx):
-                            h[b0 * u:(b0 + m) * u].copy_(hs[j0 * u:(j0 + m) * u])
-                            c[b0 * u:(b0 + m) * u].copy_(cs[j0 * u:(j0 + m) * u])
-                            j0 += m
+            self._put_states(es, idx)
             for j, b in enumerate(idx):  # the last D + hop frames of [history | new] (N >= hop: the buffer has them)
                 self.hist[b].copy_(buf[j, :, T - self.Th:])
             if self._rows is not None:
@@ -832,21 +786,13 @@ class StreamingSession:
             tail = wbuf[:, -512:].contiguous()
             res = torch.empty((n, spec.num_spks, 128 * N), dtype=torch.float32, device=dev)
             src.wave_tail, src.wave_out = tail.data_ptr(), res.data_ptr()
-        for part in self._hop["parts"]:
-            pos = [j for j, b in enumerate(idx) if part["b0"] <= b < part["b0"] + part["nb"]]
-            if not pos:
-                continue
-            for j0 in range(0, len(pos), 256):
-                local = [idx[j] - part["b0"] for j in pos[j0:j0 + 256]]
-                src.b0 = pos[j0]
-                arr = (ctypes.c_int * len(local))(*local)
-                with torch.cuda.device(dev):
-                    rc = L.sfsn_hop_advance(part["ref"], arr, len(local), ctypes.byref(src), st)
-                if rc:
-                    check(rc, "sfsn_hop_advance")
+        for part, chunks in self._part_chunks(idx):
+            for j0, local in chunks:
+                src.b0 = j0
+                self._part_launch("sfsn_hop_advance", part, local, src, st)
             # the clips' origins move back by the backlog's launches (32-bit wrap-around, as the launch's unsigned difference), behind
             # the queued launches: the next launch continues N / hop frame indices further
-            for b0, m in self._runs([idx[j] - part["b0"] for j in pos]):
+            for b0, m in runs([b for _, local in chunks for b in local]):
                 part["origin"][b0:b0 + m].sub_(N // hop)
         return out, res
 
@@ -879,29 +825,21 @@ class StreamingSession:
         clips must share their frame count so far (``ValueError`` naming them: one call per age).  A frozen model with given
         statistics uses the session's rows of those clips.  Ordered on torch's current stream, no synchronisation.  Not on resident
         sessions (``NotImplementedError``), not across tiers, not for cIRM-GSN sessions."""
-        if self.resident:
-            raise NotImplementedError("advance: not on a resident session (resident=True): its launch holds the state while it runs")
+        self._refuse_resident("advance")
         if self.waveform:
             raise RuntimeError("this session was opened with waveform=True: use advance_wave(samples)")
         idx, order = self._prime_clips(clips, stft.shape[0] if isinstance(stft, torch.Tensor) and stft.dim() == 3 else -1, "advance")
-        if stft.device != self.dev or stft.dtype != torch.complex64 or stft.shape[1] != self.F:
-            raise RuntimeError(f"expected complex64 {(len(idx), self.F, 'N')} on {self.dev}, got {stft.dtype} {tuple(stft.shape)} on {stft.device}")
-        N = stft.shape[2]
-        if N < self.hop or N % self.hop != 0:
-            raise ValueError(f"advance: {N} frames is not a positive multiple of the session's hop ({self.hop})")
+        N = check_frames("advance", stft, len(idx), self.F, self.dev, self.hop)
         self._advance_checks("advance", idx)
-        perm = None
-        if order is not None:
-            perm = torch.tensor(order, dtype=torch.long).to(self.dev, non_blocking=True)
-            stft, idx = stft.index_select(0, perm), [idx[j] for j in order]
-        out, _ = self._advance_sorted(stft, idx)
+
+        def run(rows, slots):
+            out, _ = self._advance_sorted(rows, slots)
+            return out["enh_stft"], out["enh_mag"]
+
+        enh, mag = self._slot_ordered(stft, idx, order, run)
         self._clip_f0[idx] -= N
-        enh, mag = out["enh_stft"], out["enh_mag"]
-        if perm is not None:
-            inv = torch.empty_like(perm)
-            inv[perm] = torch.arange(len(order), device=self.dev)
-            return enh.index_select(0, inv), mag.index_select(0, inv)
-        return enh.contiguous(), mag.contiguous()
+        # (reordered results are copies already; otherwise the new frames of the forward's [.., T] rows are made contiguous here)
+        return (enh, mag) if order is not None else (enh.contiguous(), mag.contiguous())
 
     def advance_wave(self, samples: torch.Tensor, clips=None) -> torch.Tensor:
         """``advance`` for waveform sessions (``host_io`` included; device tensors in and out): ``samples`` float32
@@ -910,33 +848,20 @@ class StreamingSession:
         new samples (``spectral.stft``: the hop's transform, the same bits); the output blocks continue the clip's overlap-add
         accumulator in the hop's order and with its envelope.  Every listed clip must have made at least one call in its current
         utterance (``ValueError`` naming the clip; start such a clip with ``prime_wave``).  Exactness as for ``advance``."""
-        if self.resident:
-            raise NotImplementedError("advance_wave: not on a resident session (resident=True): its launch holds the state while it runs")
+        self._refuse_resident("advance_wave")
         if not self.waveform:
             raise RuntimeError("open the session with waveform=True")
         idx, order = self._prime_clips(clips, samples.shape[0] if isinstance(samples, torch.Tensor) and samples.dim() == 2 else -1, "advance_wave")
-        if samples.device != self.dev or samples.dtype != torch.float32:
-            raise RuntimeError(f"expected float32 {(len(idx), '128 * c')} on {self.dev}, got {samples.dtype} {tuple(samples.shape)} on {samples.device}")
-        Ls = samples.shape[1]
-        if Ls < 128 or Ls % 128 != 0:
-            raise ValueError(f"advance_wave: {Ls} samples is not a positive multiple of 128")
+        Ls = check_samples("advance_wave", samples, len(idx), self.dev)
         calls = self.clip_calls
         for b in idx:
             if calls[b] < 1:
                 raise ValueError(f"advance_wave: clip {b} has made no call in its current utterance (no STFT state to continue from): "
                                  "start it with prime_wave")
         self._advance_checks("advance_wave", idx)
-        perm = None
-        if order is not None:
-            perm = torch.tensor(order, dtype=torch.long).to(self.dev, non_blocking=True)
-            samples, idx = samples.index_select(0, perm), [idx[j] for j in order]
-        _, res = self._advance_sorted(None, idx, samples=samples.contiguous())
+        res, = self._slot_ordered(samples, idx, order, lambda rows, slots: self._advance_sorted(None, slots, samples=rows.contiguous())[1:])
         self._clip_c0[idx] -= Ls // 128
         self._primed = True  # the launch mutes each clip by its own frame index (see step_wave)
-        if perm is not None:
-            inv = torch.empty_like(perm)
-            inv[perm] = torch.arange(len(order), device=self.dev)
-            res = res.index_select(0, inv)
         return res
 
     # ---- moving a clip: its state out of its slot, and into a slot of this or another session ------------------------------------
@@ -990,14 +915,8 @@ class StreamingSession:
     def _part_runs(self, idx) -> list:
         """[part, first position, local clip indices] for runs of consecutive positions of ``idx`` that lie in one part, 256 at most
         (what one sfsn_hop_state_export / _import launch takes: consecutive blob rows, clip indices in its arguments)."""
-        runs = []
-        for j, b in enumerate(idx):
-            part = next(p for p in self._hop["parts"] if p["b0"] <= b < p["b0"] + p["nb"])
-            if runs and runs[-1][0] is part and len(runs[-1][2]) < 256:
-                runs[-1][2].append(b - part["b0"])
-            else:
-                runs.append([part, j, [b - part["b0"]]])
-        return runs
+        parts = self._hop["parts"]
+        return [(parts[p], j0, local) for p, j0, local in part_runs(idx, [(part["b0"], part["nb"]) for part in parts])]
 
     def export_state(self, clips=None):
         """The carried state of ``clips`` (``None``: every clip) as a ``ClipState`` of ``len(clips)`` rows, row i = ``clips[i]``: what
@@ -1008,18 +927,15 @@ class StreamingSession:
         stream-ordered copies.  The session is not changed: the clips go on here as well unless the caller resets them.  Ordered on
         torch's current stream with no synchronisation, like ``reset(clips=...)``: the state is that behind every step queued so
         far, and the call may return before the copy has run.  Not on resident sessions (``NotImplementedError``)."""
-        from .clip_state import ClipState, clip_list, gather_rows
-        if self.resident:
-            raise NotImplementedError("export_state: not on a resident session (resident=True): its launch holds the state while it runs")
+        from .clip_state import ClipState, clip_list, gather_rows, new_blob
+        self._refuse_resident("export_state")
         idx = clip_list(clips, self.B, "export_state")
         layout, nbytes = self._state_layout()
         if self._hop is None:
             sel = torch.tensor(idx, dtype=torch.long).to(self.dev, non_blocking=True)
             blob = gather_rows(self._state_parts(), sel, nbytes, layout)
         else:
-            # (no fill launch in front of the copy where the sections tile the row; the padding between sections reads as zero)
-            alloc = torch.empty if sum(b - a for _, a, b in layout) == nbytes else torch.zeros
-            blob = alloc((len(idx), nbytes), dtype=torch.uint8, device=self.dev)
+            blob = new_blob(len(idx), nbytes, layout, self.dev)
             st = ctypes.c_void_p(_raw_stream(self._dev_index))
             for part, j0, local in self._part_runs(idx):
                 arr = (ctypes.c_int * len(local))(*local)
@@ -1044,15 +960,10 @@ class StreamingSession:
         ``ValueError``: a signature mismatch (named), duplicate indices; ``IndexError``: an index out of range; ``TypeError``: wrong
         types; ``RuntimeError``: a state on another device (``state.to(...)`` first), a row count other than ``len(clips)``;
         ``NotImplementedError``: a resident session."""
-        from .clip_state import check_import, clip_list, scatter_rows
-        if self.resident:
-            raise NotImplementedError("import_state: not on a resident session (resident=True): its launch holds the state while it runs")
-        idx = clip_list(clips, self.B, "import_state")
-        check_import(state, idx, self.dev)
-        state.check_signature(self._state_signature())
+        from .clip_state import import_clips, scatter_rows
+        self._refuse_resident("import_state")
         layout, nbytes = self._state_layout()
-        if state.layout != layout or state.blob.shape[1] != nbytes:
-            raise ValueError("import_state: the state's blob layout is not this session's")
+        idx = import_clips(state, clips, self.B, self.dev, self._state_signature(), layout, nbytes)
         blob = state.blob.contiguous()
         if self._stats is not None:
             self.set_norm_stats(NormStats(*state.stats), clips=idx)
@@ -1061,17 +972,7 @@ class StreamingSession:
             scatter_rows(self._state_parts(), sel, blob, layout)
             self._clip_f0[idx] = self.frames_done - state.frames
             return
-        if self.waveform and self._wave_calls == 0:
-            # nobody has called yet, and the session's first call launches nothing: count it as made, with every other clip's
-            # utterance beginning at the next call (as prime_wave does)
-            self._wave_calls = 1
-            self._clip_c0[:] = 1
-            listed = set(idx)
-            for part in self._hop["parts"]:
-                others = [b - part["b0"] for b in range(part["b0"], part["b0"] + part["nb"]) if b not in listed]
-                for b0, m in self._runs(others):
-                    part["origin"][b0:b0 + m].fill_(self._as_i32(part["desc"].launch_index + 1))
-                part["desc"].clip_start = part["origin"].data_ptr()
+        self._first_call_made(idx)
         st = ctypes.c_void_p(_raw_stream(self._dev_index))
         for part, j0, local in self._part_runs(idx):
             arr = (ctypes.c_int * len(local))(*local)
@@ -1082,13 +983,8 @@ class StreamingSession:
             # the clips' origins (include/sfsn.h): the next launch gives each the frame index it had at export.  Fills behind the
             # queued launches, as in _reset_clips
             ages = [int(state.calls[j0 + i]) - 1 if self.waveform else int(state.frames[j0 + i]) // self.hop for i in range(len(local))]
-            i = 0
-            while i < len(local):  # (one fill per run of consecutive clips of one age: clips that moved together)
-                m = 1
-                while i + m < len(local) and local[i + m] == local[i] + m and ages[i + m] == ages[i]:
-                    m += 1
-                part["origin"][local[i]:local[i] + m].fill_(self._as_i32(part["desc"].launch_index - ages[i]))
-                i += m
+            for b0, m, age in runs_by(local, ages):  # (one fill per run of consecutive clips of one age: clips that moved together)
+                part["origin"][b0:b0 + m].fill_(self._as_i32(part["desc"].launch_index - age))
             part["desc"].clip_start = part["origin"].data_ptr()
         if self.waveform:
             self._clip_c0[idx] = self._wave_calls - state.calls
@@ -1123,20 +1019,7 @@ class StreamingSession:
         ``count_spikes=True`` (``RuntimeError``)."""
         if not self.count_spikes:
             raise RuntimeError("open the session with count_spikes=True to count spikes")
-        if clips is None:
-            idx = list(range(self.B))
-        else:
-            if isinstance(clips, (torch.Tensor, np.ndarray)) and clips.ndim != 1:
-                raise TypeError("clips: a 1-D tensor or a sequence of clip indices")
-            items = clips.tolist() if isinstance(clips, (torch.Tensor, np.ndarray)) else list(clips)
-            if any(isinstance(i, bool) or not isinstance(i, (int, np.integer)) for i in items):
-                raise TypeError("clips: integer clip indices")
-            idx = sorted(set(int(i) for i in items))
-            bad = [i for i in idx if not 0 <= i < self.B]
-            if bad:
-                raise IndexError(f"clip index {bad[0]} out of range for a session of {self.B} clips")
-            if not idx:
-                raise ValueError("clips: no clip selected")
+        idx = clip_indices(clips, self.B, "clips", duplicates="merge", empty="refuse")
         frames = self.clip_frames[idx]
         if (frames != frames[0]).any():
             raise ValueError(f"spike_summary: the selected clips have seen different numbers of frames {frames.tolist()}; select "

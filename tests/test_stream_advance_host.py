@@ -74,6 +74,7 @@ def as_i32(v):
 @pytest.mark.parametrize("hop", [1, 2, 3])
 @pytest.mark.parametrize("k", [0, 1, 5, 2 ** 31 - 1, 2 ** 31, 2 ** 31 + 3, 2 ** 32 - 3, 2 ** 32 - 1])
 def test_origin_arithmetic_wraps(k, hop):
+    from spiking_fullsubnet_amd import clip_select
     from spiking_fullsubnet_amd.streaming import StreamingSession
     for age in (0, 1, 7, 40, 2 ** 31 - 5):  # launches the clip has made when launch k is next
         org = (k - age) % (1 << 32)
@@ -91,6 +92,7 @@ def test_origin_arithmetic_wraps(k, hop):
             with np.errstate(over="ignore"):
                 i32 -= np.int32(n_launches)
             assert int(i32[0]) % 2 ** 32 == new and as_i32(new) == int(i32[0])
+            assert clip_select.as_i32(new) == as_i32(new) and StreamingSession._as_i32 is clip_select.as_i32  # (the sessions' own)
             if age == 0:
                 assert new == pr.origin(k, N, hop)  # a fresh clip: prime's formula
 
