@@ -654,6 +654,34 @@ size_t sfsn_hop_scratch_bytes(const sfsn_hop_desc* desc /* host */);
 size_t sfsn_hop_spike_slots(const sfsn_hop_desc* desc /* host */);
 int sfsn_stream_hop(const sfsn_hop_desc* desc /* host */, void* stream);
 
+/* sfsn_stream_hop with HELD clips: bit b of held_bits (ceil(B / 64) words, host memory, read before the call returns) = clip b has
+ * no frame this tick and sits launch k = desc->launch_index out.  ONE launch and nothing else on the stream: the mask travels by value
+ * in the kernel arguments (no device buffer a queued launch could find overwritten, no copy enqueued).  held_bits == NULL or all bits
+ * zero IS sfsn_stream_hop: the same kernels, which do not carry the predicate (the held form is a template instantiation of its own).
+ * Every stage, hand-off and tag runs as in sfsn_stream_hop -- rows are independent in every product, LayerNorm and filter, so a held
+ * clip's rows compute on whatever inp_ri / wave_in hold for them (anything, NaN included; nothing of it reaches another clip or any
+ * carried state) and no wait is added.  For a row of a held clip b:
+ *   h          h[(k + 1) & 1] <- the bytes of h[k & 1] (instead of the new spikes);
+ *   c          not written;          spike_slots   not added to (nor zeroed);
+ *   cum        cum[(k + 1) & 1] <- cum[k & 1], no row sum added;
+ *   hist_ri    not shifted;
+ *   wave_state not shifted, and a first call (k == clip_start[b] - 1) does not take the samples;   ola_state not touched;
+ *   enh_ri, enh_mag, wave_out   written as zero;      done   written (launch_index + 1), so a host that waits on the words returns;
+ *   clip_start[b] += 1 (unsigned): the clip's origin moves on by one launch, so that launch k + 1 -- and sfsn_hop_prime / _seed /
+ *              _advance / _state_export, which all read clip b through its origin -- see it exactly as if launch k had never happened
+ *              for it: same frame index, same frames_before, and a restart or first call that was due in launch k is due in k + 1.
+ * The origin rule: the + 1 is ordered after every read of clip_start in this launch and before the next launch on the stream.  It is
+ * done in the launch: each workgroup, its role finished, adds 1 to word 3 of `scratch` (vector atomic) as its last act, and the
+ * workgroup that finds itself last applies the + 1s and clears the word.  Nobody waits on that word: no spin is added.  clip_start
+ * must therefore be device-writable memory the caller hands over for the launch (the caller still numbers the launches itself and
+ * adds 1 to launch_index after this one too).  The caller's own bookkeeping of a held clip's frames / calls does not advance.
+ * Returns what sfsn_stream_hop returns for the descriptor (a descriptor it refuses: the same code); with some bit set:
+ *   a bit at or beyond desc->B                          SFSN_EINVAL
+ *   desc->clip_start == NULL                            SFSN_EINVAL   (a held clip needs an origin of its own)
+ *   desc->B > 256 (what the argument block carries)     SFSN_EUNSUPPORTED
+ * Not for the resident form, nor for the cIRM-GSN hop. */
+int sfsn_stream_hop_held(const sfsn_hop_desc* desc /* host */, const uint64_t* held_bits /* host, ceil(B/64) words, bit b = clip b is held */, void* stream);
+
 /* The RESIDENT form of the waveform hop (BASELINE.json configs[4] names a "persistent kernel"; round 3).  One launch serves hop
  * after hop of a waveform session with host completion words (wave_in, wave_out and done in pinned host memory, hop == 1):
  * for hop k = 0, 1, ... the host writes the 128 samples per clip into wave_in, then stores k + 1 into the 32-bit `doorbell`

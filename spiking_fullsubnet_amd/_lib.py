@@ -322,6 +322,8 @@ def lib() -> ctypes.CDLL:
     L.sfsn_hop_stages.argtypes = [ctypes.POINTER(HopDesc), ctypes.POINTER(_I), _I]
     L.sfsn_stream_hop.restype = _I
     L.sfsn_stream_hop.argtypes = [ctypes.POINTER(HopDesc), _P]
+    L.sfsn_stream_hop_held.restype = _I  # desc, held_bits (ceil(B / 64) words, bit b = clip b is held), stream
+    L.sfsn_stream_hop_held.argtypes = [ctypes.POINTER(HopDesc), ctypes.POINTER(ctypes.c_uint64), _P]
     L.sfsn_hop_prime.restype = _I
     L.sfsn_hop_prime.argtypes = [ctypes.POINTER(HopDesc), ctypes.POINTER(_I), _I, ctypes.POINTER(PrimeSrc), _P]
     L.sfsn_hop_seed.restype = _I  # desc, clips, n_clips, dst, stream
@@ -433,7 +435,7 @@ EXPORTS = ("sfsn_abi_version", "sfsn_source_hash", "sfsn_strerror", "sfsn_device
            "sfsn_fullband_proj_deepfilter_ragged", "sfsn_hop_prime", "sfsn_gsn_layer_scan_l01_projdf",
            "sfsn_hop_state_bytes", "sfsn_hop_state_export", "sfsn_hop_state_import", "sfsn_fullband_hop_state_bytes",
            "sfsn_fullband_hop_state_export", "sfsn_fullband_hop_state_import", "sfsn_hop_seed", "sfsn_hop_advance",
-           "sfsn_fullband_hop_seed", "sfsn_fullband_hop_advance")
+           "sfsn_fullband_hop_seed", "sfsn_fullband_hop_advance", "sfsn_stream_hop_held")
 
 
 def check(rc: int, what: str = "") -> None:

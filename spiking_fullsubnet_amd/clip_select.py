@@ -30,9 +30,11 @@ def clip_indices(clips, B: int, what: str, *, duplicates: str, empty: str) -> Li
     ``prime*``, ``advance*``, ``catch_up*``,    refuse      ``"{what}: no clip selected"``  caller order
     ``export_state``, ``import_state``
     ``spike_summary`` (``what="clips"``)        merge       ``"clips: no clip selected"``   sorted
+    ``step*(clips=)`` (``held_masks``) [2]_     merge       every clip is held             sorted
     ==========================================  ==========  =============================  ============
 
     .. [1] ``StreamingSession.reset``: ``merge_late``; ``FullbandStreamingSession.reset``: ``merge``.
+    .. [2] ``merge_late``; an index out of range is re-raised as a ``ValueError`` with the same wording.
     """
     assert duplicates in ("refuse", "merge", "merge_late") and empty in ("ok", "refuse")
     if clips is None:
@@ -95,6 +97,26 @@ def part_runs(idx: Sequence[int], bounds: Sequence[Tuple[int, int]], limit: int 
         else:
             out.append((p, j, [b - bounds[p][0]]))
     return out
+
+
+def held_masks(clips, B: int, bounds: Sequence[Tuple[int, int]], what: str) -> Tuple[List[int], List[int], List[List[int]]]:
+    """``step(..., clips=)``: the clips that take this hop and the ones that are HELD, as ``(active, held, words)`` -- ``active`` =
+    ``clips`` checked like ``reset(clips)``'s (duplicates merged, sorted), ``held`` = every other clip of the batch, ``words[p]`` = the
+    mask ``sfsn_stream_hop_held`` takes for part p (``bounds[p] = (b0, nb)``, as for ``part_runs``): ``ceil(nb / 64)`` 64-bit words, bit
+    ``b - b0`` of the part's mask set for a held clip b.  An empty list holds everybody (all-held masks).  An index out of range is a
+    ``ValueError`` that names it (``clip_indices``' wording); a wrong type is ``clip_indices``' ``TypeError``."""
+    # this runs in front of every tick's launch: a plain list of ints inside the batch -- the everyday call -- is taken without the
+    # per-item checks (anything else goes through clip_indices, which raises what it always raises)
+    active = sorted(set(clips)) if type(clips) is list and set(map(type, clips)) <= {int} else None
+    if active is None or (active and not 0 <= active[0] <= active[-1] < B):
+        try:
+            active = clip_indices(clips, B, what, duplicates="merge_late", empty="ok")
+        except IndexError as e:
+            raise ValueError(f"{what}: {e}") from None
+    held = sorted(set(range(B)).difference(active))
+    mask = sum(1 << b for b in held)  # bit b = clip b is held
+    words = [[((mask >> b0) & ((1 << nb) - 1)) >> (64 * i) & 0xFFFFFFFFFFFFFFFF for i in range((nb + 63) // 64)] for b0, nb in bounds]
+    return active, held, words
 
 
 def as_i32(v: int) -> int:

@@ -130,6 +130,25 @@ struct HopStep {
     int wait_fin;
 };
 
+// ---- held clips (sfsn_stream_hop_held) ---------------------------------------------------------------------------------------
+// Bit b of the mask = clip b sits this launch out.  The mask travels by value in the kernel arguments (nothing a queued launch reads
+// can be overwritten under it, and no copy is enqueued).  Every stage runs as it always does -- rows are independent in every
+// product, LayerNorm and filter, so a held row computes on whatever its input holds and the hand-off protocol is untouched -- but a
+// held row's stores of carried state are suppressed, h and cum cross the launch parity unchanged, its outputs are zero, and the last
+// workgroup to finish moves the clip's origin on by one launch: to every later launch, and to every other entry point, this launch
+// never happened for the clip.  Every held-only statement sits under `if constexpr (HELD)`: sfsn_stream_hop's and the resident
+// kernels (HELD = false) do not carry the predicate, and compile to the code they were before it existed.
+#define HOP_HELD_WORDS 4  // 256 clips per launch
+#define HOP_HELD_CNT 3    // scratch word: workgroups of a held launch that have finished (cleared by the last one)
+struct HopHeld {
+    unsigned long long w[HOP_HELD_WORDS];
+};
+template <bool HELD>
+__device__ __forceinline__ bool hop_held(const HopHeld& hm, int b) {
+    if constexpr (HELD) return (hm.w[b >> 6] >> (b & 63)) & 1ull;
+    return false;
+}
+
 #ifdef SFSN_HOP_STAMPS
 // (every lane stores the same value to the same word: no branch, so the compiler's wait-count bookkeeping is not disturbed;
 // a stamps build always has a valid dbg pointer)
@@ -171,8 +190,11 @@ __device__ __forceinline__ float2 hop_in_bin(const HopParams& p, int b, int f, i
 // GIVEN (layer 0 only): the offline Laplace / Gaussian norm with the clips' statistics given (sfsn_hop_seq.feat) -- a kernel of its
 // own, so that the kernels of the other norms keep their register allocation (these kernels have no register to spare; the two
 // branches compiled into them cost the multi-frame and the resident kernels 4 to 48 bytes of scratch per lane).
-template <bool L0, bool ONE, int G, bool GIVEN>
-__device__ __forceinline__ void hop_layer_role(const HopParams& p, const HopStep& hs, const HopStageDev& sd, const HopSeqDev& sq, char* smem) {
+// HELD: some clips sit this launch out (HopHeld): their rows run like every row, but at the end h[k & 1] goes to h[(k + 1) & 1] in
+// place of the new spikes, c and the spike slot stay, and cum[k & 1] goes to cum[(k + 1) & 1] with no row sum added.
+template <bool L0, bool ONE, int G, bool GIVEN, bool HELD>
+__device__ __forceinline__ void hop_layer_role(const HopParams& p, const HopStep& hs, const HopStageDev& sd, const HopSeqDev& sq, const HopHeld& hm,
+                                               char* smem) {
     const int l = sd.layer;
     const HopLayerDev& L = sq.layer[l];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -550,7 +572,14 @@ __device__ __forceinline__ void hop_layer_role(const HopParams& p, const HopStep
         if (active && row < R) st_agent(L.spikes + ((size_t)t * R + row) * HP + cc, pk | tagw);  // data + tag: published
         if (t == 0) HOP_STAMP(5);
     }
-    if (active && row < R) {
+    // (the mask is asked here, not at the top: nothing more stays live across the frame.  The plain form keeps its condition word for
+    //  word: with `&& live` in it the multi-frame kernels came out with other spill counts than before)
+    bool live = true;
+    if constexpr (HELD) {
+        live = !hop_held<HELD>(hm, rowc / sq.N);
+        if (active && row < R && !live) st_agent(hnext + (size_t)row * HP + cc, *reinterpret_cast<const unsigned*>(hprev + (size_t)row * HP + cc));
+    }
+    if (HELD ? (live && active && row < R) : (active && row < R)) {
         *reinterpret_cast<v4f*>(L.c + (size_t)row * H + cc) = c;
         st_agent(hnext + (size_t)row * HP + cc, pk);  // (write-through: the resident form has no launch boundary to write L2 back)
         if (p.slots) {
@@ -568,7 +597,13 @@ __device__ __forceinline__ void hop_layer_role(const HopParams& p, const HopStep
 #pragma unroll
         for (int ri = 0; ri < HOP_ROWS_PER_WAVE; ++ri) {
             const int frow = 16 * rt + wave + HOP_WAVES * ri;
-            if (frow < R) st_agent(&sq.cum[(hs.launch + 1u) & 1u][frow], __float_as_uint(cumr[ri]));  // (write-through, as the last spikes are)
+            if (frow < R) {
+                unsigned sum = __float_as_uint(cumr[ri]);
+                if constexpr (HELD) {
+                    if (hop_held<HELD>(hm, frow / sq.N)) sum = ld_agent(&sq.cum[hs.launch & 1u][frow]);
+                }
+                st_agent(&sq.cum[(hs.launch + 1u) & 1u][frow], sum);  // (write-through, as the last spikes are)
+            }
         }
     }
 }
@@ -578,8 +613,10 @@ __device__ __forceinline__ void hop_layer_role(const HopParams& p, const HopStep
 // P (weight fragments in registers).  Rows to LDS, then the deep filter of the tile's bins for this frame, then (after the
 // last frame) the history shift of those bins.  LDS: [64 B][hb: KS_MAX KB][16 x (P + 4) floats].
 // ---------------------------------------------------------------------------------------------------------------------
-template <bool ONE>
-__device__ __forceinline__ void hop_proj_role(const HopParams& p, const HopStep& hs, const HopStageDev& sd, const HopSeqDev& sq, char* smem) {
+// HELD: a held clip's bins leave as zeros (the enhanced granules too: the inverse STFT still polls them) and its history stays.
+template <bool ONE, bool HELD>
+__device__ __forceinline__ void hop_proj_role(const HopParams& p, const HopStep& hs, const HopStageDev& sd, const HopSeqDev& sq, const HopHeld& hm,
+                                              char* smem) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n = lane & 15, q = lane >> 4;
@@ -620,7 +657,10 @@ __device__ __forceinline__ void hop_proj_role(const HopParams& p, const HopStep&
         for (int idx = tid; idx < p.B * (F - p.fcov) * hop; idx += HOP_THREADS) {
             const int t = idx % hop, r_ = idx / hop;
             const int b_ = r_ / (F - p.fcov), f = p.fcov + r_ - b_ * (F - p.fcov);
-            const float2 xv = hop_in_bin(p, b_, f, t, hop, tagw, ok);
+            float2 xv = hop_in_bin(p, b_, f, t, hop, tagw, ok);
+            if constexpr (HELD) {
+                if (hop_held<HELD>(hm, b_)) xv = make_float2(0.0f, 0.0f);
+            }
             for (int s = 0; s < S; ++s) {
                 const size_t o = (((size_t)b_ * S + s) * F + f) * hop + t;
                 *reinterpret_cast<float2*>(p.enh + 2 * o) = xv;
@@ -682,6 +722,8 @@ __device__ __forceinline__ void hop_proj_role(const HopParams& p, const HopStep&
                 const int frow = 16 * rt + rl, b_ = frow / sq.N, k = frow - b_ * sq.N;
                 const int f = sq.lo + k * fc + fci;
                 const float* pr = pbuf + rl * LDP;
+                bool held = false;
+                if constexpr (HELD) held = hop_held<HELD>(hm, b_);
                 for (int s = 0; s < S; ++s) {
                     float yr = 0.0f, yi = 0.0f;
 #pragma unroll
@@ -694,10 +736,16 @@ __device__ __forceinline__ void hop_proj_role(const HopParams& p, const HopStep&
                             yi += tap[it][i].x * ci + tap[it][i].y * cr;
                         }
                     }
+                    if constexpr (HELD) {
+                        if (held) yr = yi = 0.0f;
+                    }
                     const size_t o = ((size_t)b_ * S + s) * F + f;
                     *reinterpret_cast<float2*>(p.enh + 2 * o) = make_float2(yr, yi);
                     if (p.mag) p.mag[o] = fast_abs2(yr, yi);
                     if (p.enh_g) hop_put_cplx(p.enh_g + 4 * o, make_float2(yr, yi), tagw);
+                }
+                if constexpr (HELD) {
+                    if (held) continue;  // (the history stays; nothing follows in this bin's turn)
                 }
                 float* hrow = p.hist + ((size_t)b_ * F + f) * D * 2;  // history: drop the oldest frame, append the new one
 #pragma unroll
@@ -715,6 +763,8 @@ __device__ __forceinline__ void hop_proj_role(const HopParams& p, const HopStep&
             const float* hrow = p.hist + ((size_t)b_ * F + f) * D * 2;
             const float* irow = p.inp + ((size_t)b_ * F + f) * hop * 2;
             const bool fresh = p.clip_start && hop_clip_k(p, hs, b_) == 0;
+            bool held = false;
+            if constexpr (HELD) held = hop_held<HELD>(hm, b_);
             for (int s = 0; s < S; ++s) {
                 float yr = 0.0f, yi = 0.0f;
                 for (int d = 0; d < df; ++d) {
@@ -725,6 +775,9 @@ __device__ __forceinline__ void hop_proj_role(const HopParams& p, const HopStep&
                     const float ci = pr[((1 * fc + fci) * df + d) * S + s];
                     yr += xv.x * cr - xv.y * ci;
                     yi += xv.x * ci + xv.y * cr;
+                }
+                if constexpr (HELD) {
+                    if (held) yr = yi = 0.0f;
                 }
                 const size_t o = (((size_t)b_ * S + s) * F + f) * hop + t;
                 *reinterpret_cast<float2*>(p.enh + 2 * o) = make_float2(yr, yi);
@@ -743,6 +796,9 @@ __device__ __forceinline__ void hop_proj_role(const HopParams& p, const HopStep&
         float* hrow = p.hist + ((size_t)b_ * F + f) * D * 2;
         const float* irow = p.inp + ((size_t)b_ * F + f) * hop * 2;
         const bool fresh = p.clip_start && hop_clip_k(p, hs, b_) == 0;
+        if constexpr (HELD) {
+            if (hop_held<HELD>(hm, b_)) continue;
+        }
         for (int i = 0; i < D; ++i) {
             const int src = i + hop;
             const float2 v = src < D ? (fresh ? make_float2(0.0f, 0.0f) : *reinterpret_cast<const float2*>(hrow + 2 * src))
@@ -756,17 +812,20 @@ __device__ __forceinline__ void hop_proj_role(const HopParams& p, const HopStep&
 // waveform mode (hop == 1), first and last stage: the new frame's spectrum (one workgroup per 16 clips, a wave per clip) and the
 // enhanced frame back to samples (a wave per (clip, speaker)).  The bodies are sfsn_hop_wave_dev.h's, shared with the cIRM-GSN hop.
 // ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void hop_stft_role(const HopParams& p, const HopStep& hs, const HopStageDev& sd, char* smem) {
+template <bool HELD>
+__device__ __forceinline__ void hop_stft_role(const HopParams& p, const HopStep& hs, const HopStageDev& sd, const HopHeld& hm, char* smem) {
     const int rt = (int)blockIdx.x - sd.wg0;
     const int nclip = (p.B - 16 * rt) < 16 ? (p.B - 16 * rt) : 16;
     // (the origins are read once, before anything leaves this workgroup: the resident kernel's host may write the origins of the
     //  next hop as soon as this hop's samples are out)
-    hop_wave_stft(p.wave_in, p.wave_state, p.window, p.spec_g, p.F, 16 * rt, nclip, hop_tag(hs.launch) * 0x02020202u, smem,
-                  [&](int ln, int n) { return p.clip_start ? __ballot(ln < n && hop_clip_k(p, hs, 16 * rt + ln) == -1) : 0ull; });
+    hop_wave_stft_held<HELD>(p.wave_in, p.wave_state, p.window, p.spec_g, p.F, 16 * rt, nclip, hop_tag(hs.launch) * 0x02020202u, smem,
+                             [&](int ln, int n) { return p.clip_start ? __ballot(ln < n && hop_clip_k(p, hs, 16 * rt + ln) == -1) : 0ull; },
+                             [&](int ci) { return hop_held<HELD>(hm, 16 * rt + ci); });
 }
 
-__device__ __forceinline__ void hop_istft_role(const HopParams& p, const HopStep& hs, const HopStageDev& sd, char* smem) {
-    hop_wave_istft(
+template <bool HELD>
+__device__ __forceinline__ void hop_istft_role(const HopParams& p, const HopStep& hs, const HopStageDev& sd, const HopHeld& hm, char* smem) {
+    hop_wave_istft_held<HELD>(
         p.ola_state, p.wave_out, p.window, p.enh_g, p.done, p.cnt, p.F, (int)blockIdx.x - sd.wg0, p.B * p.S, hop_tag(hs.launch) * 0x02020202u,
         hs.launch + 1u, smem,
         [&](int pair, int& fi, bool& fresh, bool& mute) {
@@ -787,16 +846,17 @@ __device__ __forceinline__ void hop_istft_role(const HopParams& p, const HopStep
                     __builtin_amdgcn_s_sleep(1);
                 }
             }
-        });
+        },
+        [&](int pair) { return hop_held<HELD>(hm, pair / p.S); });
 }
 
 // one hop of one workgroup: the role its block index selects
-template <bool ONE, int G, bool GIVEN>
-__device__ __forceinline__ void hop_dispatch(const HopParams& p, const HopStep& hs, char* smem) {
+template <bool ONE, int G, bool GIVEN, bool HELD>
+__device__ __forceinline__ void hop_dispatch(const HopParams& p, const HopStep& hs, const HopHeld& hm, char* smem) {
     if ((int)blockIdx.x < p.st[0].nwg) {
         // layer 0 of the full-band model is the head of the frame's critical path: its descriptors sit at fixed kernarg
         // offsets, so every scalar load is issued at once instead of table -> stage -> sequence
-        hop_layer_role<true, ONE, G, GIVEN>(p, hs, p.st[0], p.seq[0], smem);
+        hop_layer_role<true, ONE, G, GIVEN, HELD>(p, hs, p.st[0], p.seq[0], hm, smem);
         return;
     }
     const int si = (int)((p.stage_of_block[blockIdx.x >> 2] >> (8 * (blockIdx.x & 3))) & 0xffu);
@@ -804,15 +864,15 @@ __device__ __forceinline__ void hop_dispatch(const HopParams& p, const HopStep& 
     const HopSeqDev& sq = p.seq[sd.seq];
     if (sd.layer >= 0) {
         if (sd.layer == 0)
-            hop_layer_role<true, ONE, G, GIVEN>(p, hs, sd, sq, smem);
+            hop_layer_role<true, ONE, G, GIVEN, HELD>(p, hs, sd, sq, hm, smem);
         else
-            hop_layer_role<false, ONE, G, false>(p, hs, sd, sq, smem);
+            hop_layer_role<false, ONE, G, false, HELD>(p, hs, sd, sq, hm, smem);
     } else if (sd.layer == -1) {
-        hop_proj_role<ONE>(p, hs, sd, sq, smem);
+        hop_proj_role<ONE, HELD>(p, hs, sd, sq, hm, smem);
     } else if (ONE && sd.layer == -2) {
-        hop_stft_role(p, hs, sd, smem);
+        hop_stft_role<HELD>(p, hs, sd, hm, smem);
     } else if (ONE) {
-        hop_istft_role(p, hs, sd, smem);
+        hop_istft_role<HELD>(p, hs, sd, hm, smem);
     }
 }
 
@@ -827,8 +887,36 @@ __global__ __launch_bounds__(HOP_THREADS) void stream_hop_kernel(const HopParams
     HopStep hs;
     hs.launch = p.launch; hs.frame_index = p.frame_index; hs.frames_before = p.frames_before;
     hs.wait_fin = 0;
-    hop_dispatch<ONE, G, GIVEN>(p, hs, smem);
+    const HopHeld none = {};
+    hop_dispatch<ONE, G, GIVEN, false>(p, hs, none, smem);
     HOP_STAMP(7);
+}
+
+// The launch with held clips (sfsn_stream_hop_held): the same roles with the predicate compiled in, then the origins.  clip_start[b]
+// += 1 must come after every read of clip_start in this launch: each workgroup, its role done (every origin it asked for has
+// arrived: the role's stores depend on them), counts itself in a scratch word as its last act; the workgroup that finds itself
+// last applies the + 1s and clears the word for the next held launch.  Nobody waits on that word.  The launch boundary orders the
+// new origins before the next launch on the stream.
+template <bool ONE, int G, bool GIVEN>
+__global__ __launch_bounds__(HOP_THREADS) void stream_hop_held_kernel(const HopParams p, const HopHeld hm) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    HOP_STAMP(0);
+    HopStep hs;
+    hs.launch = p.launch; hs.frame_index = p.frame_index; hs.frames_before = p.frames_before;
+    hs.wait_fin = 0;
+    hop_dispatch<ONE, G, GIVEN, true>(p, hs, hm, smem);
+    HOP_STAMP(7);
+    __builtin_amdgcn_s_waitcnt(0);  // vmcnt(0) expcnt(0) lgkmcnt(0): nothing of this wave's role is still in flight
+    __syncthreads();
+    unsigned* fin = p.cnt + HOP_HELD_CNT;
+    if (threadIdx.x == 0)
+        *reinterpret_cast<unsigned*>(smem) = __hip_atomic_fetch_add(fin, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    if (*reinterpret_cast<const unsigned*>(smem) != gridDim.x - 1u) return;
+    for (int b = threadIdx.x; b < p.B; b += HOP_THREADS)
+        if (hop_held<true>(hm, b)) __hip_atomic_fetch_add(const_cast<unsigned*>(p.clip_start) + b, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (threadIdx.x == 0) st_agent(fin, 0u);
 }
 
 // ---- the RESIDENT form (BASELINE configs[4]: "persistent kernel", round 3): one launch serves hop after hop.  The host rings a
@@ -880,7 +968,8 @@ __global__ __launch_bounds__(HOP_THREADS) void stream_hop_resident_kernel(const 
         HopStep hs;
         hs.launch = p.launch + k; hs.frame_index = p.frame_index + (int)k; hs.frames_before = p.frames_before + (int)k * p.hop;
         hs.wait_fin = p.slots != nullptr;
-        hop_dispatch<true, G, GIVEN>(p, hs, smem);
+        const HopHeld none = {};
+        hop_dispatch<true, G, GIVEN, false>(p, hs, none, smem);
 #ifdef SFSN_HOP_STAMPS
         HOP_STAMP(7);
 #endif
@@ -1078,7 +1167,22 @@ extern "C" int sfsn_hop_stages(const sfsn_hop_desc* desc, int* out, int cap) {
     return p.nstage;
 }
 
-extern "C" int sfsn_stream_hop(const sfsn_hop_desc* desc, void* stream) {
+// the mask of a held launch, checked: SFSN_OK with `any` = some clip is held
+static int hop_held_mask(HopHeld& hm, bool& any, const sfsn_hop_desc* desc, const uint64_t* held_bits) {
+    memset(&hm, 0, sizeof(hm));
+    any = false;
+    if (!held_bits) return SFSN_OK;
+    const int nw = (desc->B + 63) / 64;
+    for (int i = 0; i < nw; ++i) any = any || held_bits[i] != 0;
+    if (!any) return SFSN_OK;
+    if (desc->B > 64 * HOP_HELD_WORDS) return SFSN_EUNSUPPORTED;  // more clips than the argument block carries: the caller splits
+    if ((desc->B & 63) && (held_bits[nw - 1] >> (desc->B & 63)) != 0) return SFSN_EINVAL;  // a bit at or beyond B
+    if (!desc->clip_start) return SFSN_EINVAL;  // a held clip needs an origin of its own
+    for (int i = 0; i < nw; ++i) hm.w[i] = held_bits[i];
+    return SFSN_OK;
+}
+
+static int hop_launch(const sfsn_hop_desc* desc, const uint64_t* held_bits, void* stream) {
     HopParams local;
     size_t lds;
     const int rc = hop_plan(local, lds, desc);
@@ -1089,18 +1193,36 @@ extern "C" int sfsn_stream_hop(const sfsn_hop_desc* desc, void* stream) {
     local.frames_before = desc->frames_before;
     // per-wave time stamps behind the control words (written by -DSFSN_HOP_STAMPS builds only; scripts/exp_hop.py reads them)
     local.dbg = reinterpret_cast<unsigned long long*>(static_cast<char*>(desc->scratch) + hop_counter_bytes(local));
+    HopHeld hm;
+    bool any_held = false;
+    const int hrc = hop_held_mask(hm, any_held, desc, held_bits);
+    if (hrc != SFSN_OK) return hrc;
     const int fit = hop_fits_device(local.nblocks);
     if (fit != SFSN_OK) return fit;
     if (lds > 160 * 1024) return SFSN_EUNSUPPORTED;
     const bool one = local.hop == 1, g2 = local.G == 2;
     const dim3 grid(local.nblocks), block(HOP_THREADS);
     hipStream_t st = static_cast<hipStream_t>(stream);
+    if (any_held) {
+        if (local.given) {
+            if (one) return g2 ? launch_lds<stream_hop_held_kernel<true, 2, true>>(grid, block, lds, st, local, hm) : launch_lds<stream_hop_held_kernel<true, 1, true>>(grid, block, lds, st, local, hm);
+            return g2 ? launch_lds<stream_hop_held_kernel<false, 2, true>>(grid, block, lds, st, local, hm) : launch_lds<stream_hop_held_kernel<false, 1, true>>(grid, block, lds, st, local, hm);
+        }
+        if (one) return g2 ? launch_lds<stream_hop_held_kernel<true, 2, false>>(grid, block, lds, st, local, hm) : launch_lds<stream_hop_held_kernel<true, 1, false>>(grid, block, lds, st, local, hm);
+        return g2 ? launch_lds<stream_hop_held_kernel<false, 2, false>>(grid, block, lds, st, local, hm) : launch_lds<stream_hop_held_kernel<false, 1, false>>(grid, block, lds, st, local, hm);
+    }
     if (local.given) {
         if (one) return g2 ? launch_lds<stream_hop_kernel<true, 2, true>>(grid, block, lds, st, local) : launch_lds<stream_hop_kernel<true, 1, true>>(grid, block, lds, st, local);
         return g2 ? launch_lds<stream_hop_kernel<false, 2, true>>(grid, block, lds, st, local) : launch_lds<stream_hop_kernel<false, 1, true>>(grid, block, lds, st, local);
     }
     if (one) return g2 ? launch_lds<stream_hop_kernel<true, 2, false>>(grid, block, lds, st, local) : launch_lds<stream_hop_kernel<true, 1, false>>(grid, block, lds, st, local);
     return g2 ? launch_lds<stream_hop_kernel<false, 2, false>>(grid, block, lds, st, local) : launch_lds<stream_hop_kernel<false, 1, false>>(grid, block, lds, st, local);
+}
+
+extern "C" int sfsn_stream_hop(const sfsn_hop_desc* desc, void* stream) { return hop_launch(desc, nullptr, stream); }
+
+extern "C" int sfsn_stream_hop_held(const sfsn_hop_desc* desc, const uint64_t* held_bits, void* stream) {
+    return hop_launch(desc, held_bits, stream);
 }
 
 extern "C" int sfsn_stream_hop_resident(const sfsn_hop_desc* desc, void* doorbell, unsigned idle_ms, void* stream) {

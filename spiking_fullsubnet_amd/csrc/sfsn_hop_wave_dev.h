@@ -37,10 +37,12 @@ __device__ __forceinline__ float2 hop_take_cplx(const float* g, unsigned tagw, b
 // 384 samples of the state followed by the 128 new ones; sfsn_fft.hip's transform (same code, same bits); the bins leave as
 // granules; then the state moves on by one hop.  first_calls(lane, nclip): the wave's mask of clips that make their first call in this
 // launch (bit ci: clip b0 + ci; their state reads as zero) -- asked once, before anything leaves this workgroup.  LDS: [64 B][unit table 4 KB][8 x 2 KB exchange].
+// HELD (sfsn_stream_hop_held): held_clip(ci) = clip b0 + ci sits this launch out -- its granules leave like everyone's (the stages
+// downstream poll them; what they hold is never used), its state does not move and a first call does not take the samples.
 // ---------------------------------------------------------------------------------------------------------------------
-template <class FirstCalls>
-__device__ __forceinline__ void hop_wave_stft(const float* wave_in, float* wave_state, const float* window, float* spec_g, int F, int b0,
-                                              int nclip, unsigned tagw, char* smem, FirstCalls first_calls) {
+template <bool HELD, class FirstCalls, class HeldClip>
+__device__ __forceinline__ void hop_wave_stft_held(const float* wave_in, float* wave_state, const float* window, float* spec_g, int F, int b0,
+                                                   int nclip, unsigned tagw, char* smem, FirstCalls first_calls, HeldClip held_clip) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     float2* unit = reinterpret_cast<float2*>(smem + 64);
@@ -90,7 +92,17 @@ __device__ __forceinline__ void hop_wave_stft(const float* wave_in, float* wave_
     __syncthreads();
 #pragma unroll
     for (int ci = 0; ci < 16; ++ci)
-        if (ci < nclip) wave_state[(size_t)(b0 + ci) * FFT_NFFT + tid] = keep[ci];
+        if (ci < nclip) {
+            if constexpr (HELD) {
+                if (held_clip(ci)) continue;
+            }
+            wave_state[(size_t)(b0 + ci) * FFT_NFFT + tid] = keep[ci];
+        }
+}
+template <class FirstCalls>
+__device__ __forceinline__ void hop_wave_stft(const float* wave_in, float* wave_state, const float* window, float* spec_g, int F, int b0,
+                                              int nclip, unsigned tagw, char* smem, FirstCalls first_calls) {
+    hop_wave_stft_held<false>(wave_in, wave_state, window, spec_g, F, b0, nclip, tagw, smem, first_calls, [](int) { return false; });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -101,11 +113,13 @@ __device__ __forceinline__ void hop_wave_stft(const float* wave_in, float* wave_
 // frame_of(pair, fi, fresh, mute): the pair's frame index; fresh = its accumulator reads as zero; mute = its output is zero.
 // before_done(ok): runs between the samples' store and the completion word.
 // LDS: [64 B][unit table 4 KB][8 x 2 KB exchange][8 x 264 float2 spectrum rows].
+// HELD (sfsn_stream_hop_held): held_pair(pair) = the pair's clip sits this launch out -- its samples are zero, its completion word is
+// written all the same, its accumulator is not touched.
 // ---------------------------------------------------------------------------------------------------------------------
-template <class FrameOf, class BeforeDone>
-__device__ __forceinline__ void hop_wave_istft(float* ola_state, float* wave_out, const float* window, const float* enh_g, unsigned* done,
-                                               unsigned* err, int F, int wg, int npair, unsigned tagw, unsigned done_value, char* smem,
-                                               FrameOf frame_of, BeforeDone before_done) {
+template <bool HELD, class FrameOf, class BeforeDone, class HeldPair>
+__device__ __forceinline__ void hop_wave_istft_held(float* ola_state, float* wave_out, const float* window, const float* enh_g, unsigned* done,
+                                                    unsigned* err, int F, int wg, int npair, unsigned tagw, unsigned done_value, char* smem,
+                                                    FrameOf frame_of, BeforeDone before_done, HeldPair held_pair) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int pair = wg * HOP_WAVES + wave;  // clip * S + speaker
@@ -121,6 +135,11 @@ __device__ __forceinline__ void hop_wave_istft(float* ola_state, float* wave_out
     int fi;
     bool fresh, mute;
     frame_of(pair, fi, fresh, mute);
+    bool held = false;
+    if constexpr (HELD) {
+        held = held_pair(pair);
+        mute = mute || held;
+    }
     float2 win[4], wk[4], ola[4];
     float* os = ola_state + (size_t)pair * FFT_NFFT;
 #pragma unroll
@@ -169,11 +188,21 @@ __device__ __forceinline__ void hop_wave_istft(float* ola_state, float* wave_out
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (lane == 0) __hip_atomic_store(done + pair, done_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
+    if constexpr (HELD) {
+        if (held) return;
+    }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int n = 2 * (lane + 64 * r);
         *reinterpret_cast<float2*>(os + n) = r < 3 ? acc[r + 1] : make_float2(0.0f, 0.0f);
     }
+}
+template <class FrameOf, class BeforeDone>
+__device__ __forceinline__ void hop_wave_istft(float* ola_state, float* wave_out, const float* window, const float* enh_g, unsigned* done,
+                                               unsigned* err, int F, int wg, int npair, unsigned tagw, unsigned done_value, char* smem,
+                                               FrameOf frame_of, BeforeDone before_done) {
+    hop_wave_istft_held<false>(ola_state, wave_out, window, enh_g, done, err, F, wg, npair, tagw, done_value, smem, frame_of, before_done,
+                               [](int) { return false; });
 }
 
 #endif

@@ -49,6 +49,18 @@ the clips continue bit for bit, layer 0 included -- compaction, rebalancing, pau
 one-launch tier (``sfsn_hop_state_export`` / ``sfsn_hop_state_import``, csrc/sfsn_state.hip; the clips' origins move with them), row
 copies in the per-kernel tier; stream-ordered, no synchronisation.  Not for resident sessions.
 
+Holding clips: live frames arrive with jitter, and at a tick some calls of a batched session have a frame and some do not.
+``step(frames, clips=[...])`` / ``step_wave(samples, clips=[...])`` / ``step_wave_host(samples, clips=[...])`` advance only the listed
+clips; every other clip is HELD: whatever its input row holds (NaN included) reaches nothing, its output rows are zero, and its carried
+state, spike counts, ``clip_frames`` and ``clip_calls`` are afterwards what they were -- its next active call continues the utterance
+with the next frame (waveform: with the next call's delay line), and ``reset`` / ``prime`` / ``advance`` / ``export_state`` /
+``spike_summary`` see it as if the call had not happened for it.  The one-launch hop does it in the launch it makes anyway
+(``sfsn_stream_hop_held``: the mask travels in the kernel arguments, held rows' state stores are suppressed, ``h`` and ``cum`` cross
+the launch parity unchanged and the clip's origin moves on by one launch -- no fill, no copy, no second kernel); the per-kernel
+sequence saves the held clips' rows of its states, history and counts before the graph replay and puts them back after it
+(stream-ordered row copies).  ``clips=None`` is the call without the keyword: same code path, same launches.  An empty list holds
+everybody: nothing is launched and zeros come back.  Not for resident sessions.
+
 Spike counts: a session opened with ``count_spikes=True`` counts every layer's spikes per clip as it runs, and
 ``spike_summary(clips)`` returns them in the form of the offline forward's ``layer_outputs="counts"`` lists, so that
 ``metric.compute_synops`` / ``compute_neuronops`` give each clip's current utterance's SynOPs and NeuronOPs.  The one-launch hop
@@ -68,7 +80,7 @@ import torch
 
 from ._lib import (AdvanceSrc, DfGroup, HopDesc, HOP_MAX_GROUPS, HOP_MAX_LAYERS, MAX_COUNT_TENSORS, NORM_CUMLAPLACE, PrimeSrc, RowCount,
                    SeedDst, check)
-from .clip_select import as_i32, check_frames, check_samples, clip_indices, part_runs, runs, runs_by, slot_order
+from .clip_select import as_i32, check_frames, check_samples, clip_indices, held_masks, part_runs, runs, runs_by, slot_order
 from .engine import Engine, NormStats, SpikeSummary, _ptr
 
 
@@ -379,15 +391,18 @@ class StreamingSession:
             parts.append(dict(desc=desc, ref=ctypes.byref(desc), b0=b0, nb=nb, st=st, spool=spool.buf, scratch=scratch, origin=origin, slots=slots,
                               err=torch.zeros((1,), dtype=torch.int32).pin_memory(), err_pending=False))
         return dict(parts=parts, desc=parts[0]["desc"], scratch=parts[0]["scratch"], wpool=wpool.buf, enh=torch.view_as_complex(enh),
-                    mag=mag, wave_out=wave_out, host=host)
+                    mag=mag, wave_out=wave_out, host=host, bounds=[(part["b0"], part["nb"]) for part in parts], held_before=False)
 
-    def _launch_hops(self, base_ptr: int, stride_bytes: int, field: str, frame_index=None) -> None:
+    def _launch_hops(self, base_ptr: int, stride_bytes: int, field: str, frame_index=None, held=None) -> None:
         """One sfsn_stream_hop launch per part, back to back on torch's current stream; `field` of each descriptor is pointed at
-        the part's slice of the caller's input (clips are the slowest axis: a part is a contiguous range)."""
+        the part's slice of the caller's input (clips are the slowest axis: a part is a contiguous range).  `held`: per part the mask
+        words of the clips that sit this hop out (clip_select.held_masks); a part with a held clip is launched through
+        sfsn_stream_hop_held (still one launch; a part held as a whole is launched too: every part carries the same launch index),
+        a part without one through sfsn_stream_hop."""
         idx = self._dev_index
         st = ctypes.c_void_p(_raw_stream(idx))
         same = torch.cuda.current_device() == idx  # the C ABI launches on the calling thread's current device
-        for part in self._hop["parts"]:
+        for pi, part in enumerate(self._hop["parts"]):
             if part["err_pending"] and int(part["err"][0]) != 0:  # written behind an earlier launch; no blocking here
                 self.check_errors()  # (synchronises, clears the sticky words and raises)
             d = part["desc"]
@@ -395,13 +410,23 @@ class StreamingSession:
             setattr(d, field, base_ptr + part["b0"] * stride_bytes)
             if frame_index is not None:
                 d.frame_index = frame_index
-            if same:
-                rc = self.eng.lib.sfsn_stream_hop(part["ref"], st)
+            if held is not None and any(held[pi]):
+                bits = (ctypes.c_uint64 * len(held[pi]))(*held[pi])
+                if same:
+                    rc = self.eng.lib.sfsn_stream_hop_held(part["ref"], bits, st)
+                else:
+                    with torch.cuda.device(self.dev):
+                        rc = self.eng.lib.sfsn_stream_hop_held(part["ref"], bits, st)
+                if rc:
+                    check(rc, "sfsn_stream_hop_held")
             else:
-                with torch.cuda.device(self.dev):
+                if same:
                     rc = self.eng.lib.sfsn_stream_hop(part["ref"], st)
-            if rc:
-                check(rc, "sfsn_stream_hop")
+                else:
+                    with torch.cuda.device(self.dev):
+                        rc = self.eng.lib.sfsn_stream_hop(part["ref"], st)
+                if rc:
+                    check(rc, "sfsn_stream_hop")
             d.launch_index += 1
         self.frames_done += self.hop
         if self.frames_done % 256 < self.hop:  # every ~256 frames the error words follow the launches into pinned memory
@@ -483,6 +508,45 @@ class StreamingSession:
     def _refuse_resident(self, what: str) -> None:
         if self.resident:
             raise NotImplementedError(f"{what}: not on a resident session (resident=True): its launch holds the state while it runs")
+
+    # ---- holding clips: a hop that advances only some clips of the batch ----------------------------------------------------------
+    def _hold(self, clips, what: str):
+        """``clips=`` (not None) of a step: None where every clip is listed; otherwise
+        ``(active, held, per-part mask words)`` (clip_select.held_masks).  The one-launch tier's parts take the clips' own origins
+        from now on, the way ``_reset_clips`` switches them at the first per-clip reset."""
+        self._refuse_resident(f"{what}(clips=...)")
+        h = self._hop
+        active, held, words = held_masks(clips, self.B, [(0, self.B)] if h is None else h["bounds"], what)
+        if not held:
+            return None
+        if h is not None and not h["held_before"]:  # (once: nothing ever takes a part back to the session-wide counters)
+            h["held_before"] = True
+            for part in h["parts"]:
+                part["desc"].clip_start = part["origin"].data_ptr()
+        # (waveform: no clip is older than the session's call count, so step_wave's zeros for the first three calls stay right, and
+        #  from then on the launch mutes each clip by its own frame index)
+        return active, held, words
+
+    def _held_bookkeeping(self, held) -> None:
+        """After a hop that held ``held``: their utterances began one hop (waveform: one call) later, so that ``clip_frames`` /
+        ``clip_calls`` stay what they were."""
+        self._clip_f0[held] += self.hop
+        if self.waveform:
+            self._clip_c0[held] += 1
+
+    def _first_wave_call(self, src: torch.Tensor, hold) -> None:
+        """A waveform session's first call launches nothing: the samples of the clips that make it enter the STFT state (``src``:
+        [B, 128] on the device or pinned).  A held clip does not make it: its origin moves on by one launch (a stream-ordered add
+        behind the queued launches), so that the next launch is ITS first call."""
+        held = set() if hold is None else set(hold[1])
+        for part in self._hop["parts"]:
+            b0, nb = part["b0"], part["nb"]
+            for i0, m in runs([b - b0 for b in range(b0, b0 + nb) if b not in held]):
+                part["st"]["state"][i0:i0 + m, 384:].copy_(src[b0 + i0:b0 + i0 + m])
+            for i0, m in runs([b - b0 for b in range(b0, b0 + nb) if b in held]):
+                part["origin"][i0:i0 + m].add_(1)
+        if hold is not None:
+            self._clip_c0[hold[1]] += 1
 
     def _reset_clips(self, clips) -> None:
         idx = clip_indices(clips, self.B, "reset", duplicates="merge_late", empty="ok")
@@ -1143,49 +1207,85 @@ class StreamingSession:
         self._graph = g
         self.reset()
 
-    def step(self, frames: torch.Tensor, copy: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    def step(self, frames: torch.Tensor, copy: bool = True, clips=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """``frames``: complex64 [B, F, hop] on the device.  Returns the enhanced frames and their magnitudes; with
-        ``copy=False`` the returned tensors are views of the session's buffers, valid until the next ``step``."""
+        ``copy=False`` the returned tensors are views of the session's buffers, valid until the next ``step``.
+
+        ``clips`` (a sequence or 1-D tensor of clip indices, checked like ``reset(clips)``'s; duplicates merged): only these clips
+        take the hop, every other clip is HELD -- its rows of ``frames`` may hold anything (NaN included), its output rows are
+        zero, and its state, counts and ``clip_frames`` are what they were: its next active call continues its utterance with the
+        next frame.  Shapes do not change and the call stays zero-copy.  The one-launch tier holds clips inside the one launch per
+        part it makes anyway (``sfsn_stream_hop_held``); the per-kernel tier saves and restores the held clips' rows around the
+        replay.  An empty list advances nobody: nothing is launched, zeros are returned.  ``clips=None``: today's call.
+        ``ValueError``: an index out of range (named); ``TypeError``: wrong types; ``NotImplementedError``: a resident session."""
         if frames.device != self.dev or frames.dtype != torch.complex64 or tuple(frames.shape) != (self.B, self.F, self.hop):
             raise RuntimeError(f"expected complex64 {(self.B, self.F, self.hop)} on {self.dev}, got {frames.dtype} {tuple(frames.shape)} "
                                f"on {frames.device}")
         if self.waveform:
             raise RuntimeError("this session was opened with waveform=True: use step_wave(samples)")
+        hold = None if clips is None else self._hold(clips, "step")
         if self._hop is not None:
             h = self._hop
+            if hold is not None and not hold[0]:  # nobody advances
+                return torch.zeros_like(h["enh"]), torch.zeros_like(h["mag"])
             if not (frames.is_contiguous() and frames.data_ptr() % 8 == 0):
                 self.inp.copy_(frames)
                 frames = self.inp
-            self._launch_hops(frames.data_ptr(), self.F * self.hop * 8, "inp_ri")  # read in place: no staging copy in front
+            # read in place: no staging copy in front
+            self._launch_hops(frames.data_ptr(), self.F * self.hop * 8, "inp_ri", held=None if hold is None else hold[2])
+            if hold is not None:
+                self._held_bookkeeping(hold[1])
             return (h["enh"].clone(), h["mag"].clone()) if copy else (h["enh"], h["mag"])
+        e, m = self.enh[..., self.D:], self.enh_mag[..., self.D:]
+        if hold is not None and not hold[0]:
+            return torch.zeros_like(e), torch.zeros_like(m)
+        if hold is not None:
+            # the held clips' rows of everything a step reads before it writes (export_state's sections) are put aside and put back
+            # behind the replay: stream-ordered row copies, the ones export_state / import_state of this tier make
+            sel = torch.tensor(hold[1], dtype=torch.long).to(self.dev, non_blocking=True)
+            parts = self._state_parts()
+            saved = [t.index_select(0, sel) for _, t in parts]
         self.inp.copy_(frames)
         if self._graph is not None:
             self._graph.replay()
         else:
             self._enqueue()
         self.frames_done += self.hop
-        e, m = self.enh[..., self.D:], self.enh_mag[..., self.D:]
+        if hold is not None:
+            for (_, t), rows in zip(parts, saved):
+                t.index_copy_(0, sel, rows)
+            e.index_fill_(0, sel, 0)
+            m.index_fill_(0, sel, 0)
+            self._held_bookkeeping(hold[1])
         return (e.clone(), m.clone()) if copy else (e, m)
 
-    def step_wave(self, samples: torch.Tensor, copy: bool = True) -> torch.Tensor:
+    def step_wave(self, samples: torch.Tensor, copy: bool = True, clips=None) -> torch.Tensor:
         """Waveform streaming (``waveform=True``): ``samples`` float32 [B, 128] on the device -- the next 8 ms of every clip.
         Returns enhanced samples [B, S, 128]: call c returns the samples that entered with call c - 3 (the framing of
         torch.stft(center=True) needs 256 samples of look-ahead, the overlap-add another hop: 24 ms of algorithmic delay, as for
         any causal use of the reference's 32 ms / 8 ms analysis); the first three calls of an utterance return zeros.
-        One launch per call: the frame's STFT, the whole model, the inverse STFT with its overlap-add state."""
+        One launch per call: the frame's STFT, the whole model, the inverse STFT with its overlap-add state.
+
+        ``clips``: as for ``step`` -- only the listed clips make this call; a held clip's row of ``samples`` is ignored, it gets
+        zeros, its ``clip_calls`` stays, and its next active call returns what that call would have returned (the three-call delay
+        line of its OWN calls).  A clip may be held at the session's first call, and before it has ever run."""
         if not self.waveform:
             raise RuntimeError("open the session with waveform=True")
         if samples.device != self.dev or samples.dtype != torch.float32 or tuple(samples.shape) != (self.B, 128) or not samples.is_contiguous():
             raise RuntimeError(f"expected contiguous float32 {(self.B, 128)} on {self.dev}, got {samples.dtype} {tuple(samples.shape)}")
         h = self._hop
+        out = h["wave_out"]
+        hold = None if clips is None else self._hold(clips, "step_wave")
+        if hold is not None and not hold[0]:  # nobody makes this call
+            return torch.zeros_like(out)
         c = self._wave_calls
         self._wave_calls += 1
-        out = h["wave_out"]
         if c == 0:  # no frame ends here yet (frame 0 covers samples [-256, 256)): the samples only enter the state
-            for part in h["parts"]:
-                part["st"]["state"][:, 384:].copy_(samples[part["b0"]:part["b0"] + part["nb"]])
+            self._first_wave_call(samples, hold)
             return torch.zeros_like(out)
-        self._launch_hops(samples.data_ptr(), 128 * 4, "wave_in", frame_index=c - 1)
+        self._launch_hops(samples.data_ptr(), 128 * 4, "wave_in", frame_index=c - 1, held=None if hold is None else hold[2])
+        if hold is not None:
+            self._held_bookkeeping(hold[1])
         if c < 3 and not self._primed:  # padded positions torch.istft trims (primed clips: the launch mutes each clip by its own index)
             return torch.zeros_like(out)
         return out.clone() if copy else out
@@ -1242,30 +1342,34 @@ class StreamingSession:
         except Exception:
             pass
 
-    def step_wave_host(self, samples, timeout_s: float = 2.0) -> torch.Tensor:
+    def step_wave_host(self, samples, timeout_s: float = 2.0, clips=None) -> torch.Tensor:
         """Waveform streaming with the samples on the HOST (``waveform=True, host_io=True``): ``samples`` = float32 [B, 128] CPU
         tensor (or anything ``torch.as_tensor`` takes).  The launch reads them from pinned host memory and writes the enhanced
         samples and a completion word per (clip, speaker) back into pinned host memory; the caller's thread spins on the words --
         no copy launch, no stream synchronisation.  Returns a CPU tensor [B, S, 128] (a view of the session's pinned buffer, valid
-        until the next call); same three-hop delay as ``step_wave``."""
+        until the next call); same three-hop delay as ``step_wave``.  ``clips``: as for ``step_wave`` (non-resident sessions); the
+        held clips' completion words are written too, so the wait ends as it always does."""
         h = self._hop
         if not self.host_io or h is None:
             raise RuntimeError("open the session with waveform=True, host_io=True")
         host = h["host"]
+        hold = None if clips is None else self._hold(clips, "step_wave_host")
+        if hold is not None and not hold[0]:  # nobody makes this call
+            return torch.zeros_like(host["out"])
         host["inp"].copy_(torch.as_tensor(samples, dtype=torch.float32).reshape(self.B, 128))
         c = self._wave_calls
         self._wave_calls += 1
         if c == 0:
-            for part in h["parts"]:
-                # (blocking: the next call overwrites the pinned buffer right away)
-                part["st"]["state"][:, 384:].copy_(host["inp"][part["b0"]:part["b0"] + part["nb"]])
+            self._first_wave_call(host["inp"], hold)  # (blocking: the next call overwrites the pinned buffer right away)
             torch.cuda.current_stream(self.dev).synchronize()
             return torch.zeros_like(host["out"])
         if self.resident:
             target = self._ring_resident(c)
         else:
             target = h["parts"][0]["desc"].launch_index + 1
-            self._launch_hops(host["inp"].data_ptr(), 128 * 4, "wave_in", frame_index=c - 1)
+            self._launch_hops(host["inp"].data_ptr(), 128 * 4, "wave_in", frame_index=c - 1, held=None if hold is None else hold[2])
+            if hold is not None:
+                self._held_bookkeeping(hold[1])
         done, t_end, t_soft = host["done_np"], None, None
         target &= 0xFFFFFFFF
         while (int(done.min()) & 0xFFFFFFFF) != target or (int(done.max()) & 0xFFFFFFFF) != target:  # (all parts carry the same launch index; uint32 compare: the index wraps)
