@@ -8,7 +8,7 @@
 //
 // The blob is free of launch parity (include/sfsn.h states it byte for byte): a list of sections, each a clip's rows of one array.
 // One kernel serves both directions and both hops: the host turns a descriptor into sections {array, clip stride, row stride, row
-// bytes, rows per clip, offset in the blob}; sections lie in block order, as in hop_prime_kernel; a lane copies one vector of a row --
+// bytes, rows per clip, offset in the blob}; sections lie in block order, as in hop_take_kernel; a lane copies one vector of a row --
 // 16 bytes where the array's address and strides allow (one lane per 4 neurons of a membrane row), else 8 or 4 (a lane per 4 neurons
 // of a spike row whose pitch is not a multiple of 16).  Plain stores only: the launch boundary publishes them.  Nothing waits inside
 // the launch; the tagged scratch of the hop (spikes, spec_g, enh_g, z0) is not touched and launch_index does not move.

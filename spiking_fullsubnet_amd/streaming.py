@@ -632,6 +632,37 @@ class StreamingSession:
         if rc:
             check(rc, name)
 
+    def _chunk_launches(self, name: str, part, chunks, arg, st):
+        """``_part_launch`` for every chunk of ``part`` (``_part_chunks``'); returns the runs of the part's clips launched for."""
+        for j0, local in chunks:
+            arg.b0 = j0
+            self._part_launch(name, part, local, arg, st)
+        return runs([b for _, local in chunks for b in local])
+
+    def _end_state_ptrs(self, src, es) -> None:
+        """The ``fb`` / ``sb[g]`` of a ``PrimeSrc`` / ``AdvanceSrc``: the spikes, membranes and running sums of an offline forward's
+        end state ``es``."""
+        ng = self.eng.spec.n_groups
+        for o, e, gi in [(src.fb, es["fb"], 0)] + [(src.sb[g], es["sb"], g) for g in range(ng)]:
+            for l in range(len(e["s8"])):
+                o.layer[l].spikes_i8, o.layer[l].c = e["s8"][l][gi].data_ptr(), e["states"][l][gi][1].data_ptr()
+        if es["cum"] is not None:
+            src.fb.cum = es["cum"][0].data_ptr()
+            for g in range(ng):
+                src.sb[g].cum = es["cum"][1 + g].data_ptr()
+
+    def _offline_forward(self, stft, idx, end_state):
+        """The offline forward of the clips ``idx``' frames ``stft`` with the session's statistics of those clips; ``end_state``:
+        True (from zero) or the start buffers it continues from."""
+        eng = self.eng
+        ns = None if self._stats is None else (self._stats if len(idx) == self.B else self._stats.select(idx))
+        # (the per-kernel sequence's layer-0 membranes are those of ITS input product, the form below 64 rows: these frames take it too)
+        eng._l0_hop = self.hop if self._hop is None else None
+        try:
+            return eng.forward_stft(stft, want_layers=False, want_counts=self._rows is not None, norm_stats=ns, _end_state=end_state)
+        finally:
+            eng._l0_hop = None
+
     def _first_call_made(self, idx) -> None:
         """Waveform sessions, before clips ``idx`` take a state from outside: when nobody has called yet -- the session's first call
         launches nothing -- count that call as made, with every other clip's utterance beginning at the next call (origin = the
@@ -651,17 +682,10 @@ class StreamingSession:
         """The transplant.  ``stft``: complex64 [len(idx), F, N] contiguous, or None (waveform mode, no frame yet); ``idx`` ascending;
         ``tail``: waveform mode, float32 [len(idx), 512].  Returns the prefix's forward (None without frames).  Everything on torch's
         current stream."""
-        eng, spec = self.eng, self.eng.spec
-        n, N, hop, ng = len(idx), (0 if stft is None else stft.shape[-1]), self.hop, spec.n_groups
+        n, N, hop = len(idx), (0 if stft is None else stft.shape[-1]), self.hop
         out = es = None
         if N:
-            ns = None if self._stats is None else (self._stats if n == self.B else self._stats.select(idx))
-            # (the per-kernel sequence's layer-0 membranes are those of ITS input product, the form below 64 rows: the prefix takes it too)
-            eng._l0_hop = hop if self._hop is None else None
-            try:
-                out = eng.forward_stft(stft, want_layers=False, want_counts=self._rows is not None, norm_stats=ns, _end_state=True)
-            finally:
-                eng._l0_hop = None
+            out = self._offline_forward(stft, idx, True)
             es = out["end_state"]
         if self._hop is None:
             # the per-kernel sequence: row copies into the states, the history and the counts the (captured) launches read and write
@@ -682,13 +706,7 @@ class StreamingSession:
         if N:
             src.stft_ri = torch.view_as_real(stft).data_ptr()
             src.enh_ri = torch.view_as_real(out["enh_stft"]).data_ptr()
-            for dst, e, gi in [(src.fb, es["fb"], 0)] + [(src.sb[g], es["sb"], g) for g in range(ng)]:
-                for l in range(len(e["s8"])):
-                    dst.layer[l].spikes_i8, dst.layer[l].c = e["s8"][l][gi].data_ptr(), e["states"][l][gi][1].data_ptr()
-            if es["cum"] is not None:
-                src.fb.cum = es["cum"][0].data_ptr()
-                for g in range(ng):
-                    src.sb[g].cum = es["cum"][1 + g].data_ptr()
+            self._end_state_ptrs(src, es)
         if tail is not None:
             src.wave_tail = tail.data_ptr()
         for part, chunks in self._part_chunks(idx):
@@ -697,11 +715,8 @@ class StreamingSession:
             # whose first call has made no frame: the origin IS the next launch, which reads the state as zero -- as it must -- and
             # the samples from wave_state, which no origin makes it skip)
             org = self._as_i32(d.launch_index - N // hop)
-            for j0, local in chunks:
-                src.b0 = j0
-                self._part_launch("sfsn_hop_prime", part, local, src, st)
-            for b0, m in runs([b for _, local in chunks for b in local]):  # (fills behind the queued launches, as in _reset_clips)
-                part["origin"][b0:b0 + m].fill_(org)
+            for b0, m in self._chunk_launches("sfsn_hop_prime", part, chunks, src, st):
+                part["origin"][b0:b0 + m].fill_(org)  # (fills behind the queued launches, as in _reset_clips)
             d.clip_start = part["origin"].data_ptr()
         return out
 
@@ -809,22 +824,14 @@ class StreamingSession:
                     dst.sb[g].cum = start["cum"][1 + g].data_ptr()
             for part, chunks in self._part_chunks(idx):
                 part["desc"].clip_start = part["origin"].data_ptr()  # the clips' own origins from now on (they say which clip is fresh)
-                for j0, local in chunks:
-                    dst.b0 = j0
-                    self._part_launch("sfsn_hop_seed", part, local, dst, st)
+                self._chunk_launches("sfsn_hop_seed", part, chunks, dst, st)
         if samples is not None:
             from . import spectral
             wbuf[:, 384:].copy_(samples)
             # frame j of the backlog covers samples [128 j, 128 j + 512) of the buffer: the centred frame j + 2
             stft = spectral.stft(wbuf, 512, 128)[:, :, 2:2 + N]
         buf[:, :, D:].copy_(stft)
-        ns = None if self._stats is None else (self._stats if n == self.B else self._stats.select(idx))
-        # (the per-kernel sequence's layer-0 membranes are those of ITS input product, the form below 64 rows: the backlog takes it too)
-        eng._l0_hop = hop if self._hop is None else None
-        try:
-            out = eng.forward_stft(buf, want_layers=False, want_counts=self._rows is not None, norm_stats=ns, _end_state=start)
-        finally:
-            eng._l0_hop = None
+        out = self._offline_forward(buf, idx, start)
         es = out["end_state"]
         if self._hop is None:
             self._put_states(es, idx)
@@ -836,13 +843,7 @@ class StreamingSession:
         src = AdvanceSrc()
         src.Bp, src.N, src.T = n, N, T
         src.stft_ri = torch.view_as_real(buf).data_ptr()
-        for o, e, gi in [(src.fb, es["fb"], 0)] + [(src.sb[g], es["sb"], g) for g in range(ng)]:
-            for l in range(len(e["s8"])):
-                o.layer[l].spikes_i8, o.layer[l].c = e["s8"][l][gi].data_ptr(), e["states"][l][gi][1].data_ptr()
-        if es["cum"] is not None:
-            src.fb.cum = es["cum"][0].data_ptr()
-            for g in range(ng):
-                src.sb[g].cum = es["cum"][1 + g].data_ptr()
+        self._end_state_ptrs(src, es)
         res = tail = None
         if samples is not None:
             enh = out["enh_stft"]  # (the new frames of the forward's [.., T] rows: the launch takes the rows)
@@ -851,12 +852,9 @@ class StreamingSession:
             res = torch.empty((n, spec.num_spks, 128 * N), dtype=torch.float32, device=dev)
             src.wave_tail, src.wave_out = tail.data_ptr(), res.data_ptr()
         for part, chunks in self._part_chunks(idx):
-            for j0, local in chunks:
-                src.b0 = j0
-                self._part_launch("sfsn_hop_advance", part, local, src, st)
             # the clips' origins move back by the backlog's launches (32-bit wrap-around, as the launch's unsigned difference), behind
             # the queued launches: the next launch continues N / hop frame indices further
-            for b0, m in runs([b for _, local in chunks for b in local]):
+            for b0, m in self._chunk_launches("sfsn_hop_advance", part, chunks, src, st):
                 part["origin"][b0:b0 + m].sub_(N // hop)
         return out, res
 
