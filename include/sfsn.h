@@ -679,7 +679,7 @@ int sfsn_stream_hop(const sfsn_hop_desc* desc /* host */, void* stream);
  *   a bit at or beyond desc->B                          SFSN_EINVAL
  *   desc->clip_start == NULL                            SFSN_EINVAL   (a held clip needs an origin of its own)
  *   desc->B > 256 (what the argument block carries)     SFSN_EUNSUPPORTED
- * Not for the resident form, nor for the cIRM-GSN hop. */
+ * Not for the resident form.  The cIRM-GSN hop has its own held entries: sfsn_fullband_stream_hop_held / _wave_held. */
 int sfsn_stream_hop_held(const sfsn_hop_desc* desc /* host */, const uint64_t* held_bits /* host, ceil(B/64) words, bit b = clip b is held */, void* stream);
 
 /* The RESIDENT form of the waveform hop (BASELINE.json configs[4] names a "persistent kernel"; round 3).  One launch serves hop
@@ -1064,6 +1064,56 @@ typedef struct {
 
 int sfsn_fullband_wave_hop_check(int Hp, int n_layers, int F, int S, int df, int B, int unshared);
 int sfsn_fullband_stream_hop_wave(const sfsn_fullband_wave_desc* desc, void* stream);
+
+/* ----------------------------------------------------------------------------------------------------
+ * The cIRM-GSN hop with HELD clips: bit b of held_mask = clip b has no frame (no samples) this tick and sits launch
+ * k = desc->launch_index out.  ONE launch and nothing else on the stream: B <= 16 for this kernel, so the mask is one word by value in
+ * the kernel arguments -- no device buffer exists that a queued launch could find overwritten, and no copy is enqueued.
+ * held_mask == 0 IS the existing launch: sfsn_fullband_stream_hop (spike_slots == NULL), sfsn_fullband_stream_hop_counted or
+ * sfsn_fullband_stream_hop_wave, the same kernels, which do not carry the mask (the held forms are three kernels of their own: held,
+ * held + counted, held waveform).
+ *
+ * Every stage, hand-off, granule and tag runs for every row as in the plain launch.  Rows are independent in the LayerNorm, the
+ * layer-0 fmaf chains, the MFMA products (a clip is a column) and the deep filter, so a held clip's rows compute on whatever inp_ri /
+ * wave_in hold for them (anything, NaN included; nothing of it reaches another clip or any carried state) and no wait is added.  For a
+ * held clip b in launch k:
+ *   h                      h[(k + 1) & 1] row <- the bytes of h[k & 1] row, instead of the last frame's spikes
+ *   c                      not written
+ *   spike_slots            not added to, nor zeroed
+ *   layer.spikes           (work buffer) published with its tag as always: every tile gathers all rows
+ *   hist_ri                hist_ri[(k + 1) & 1] rows <- hist_ri[k & 1] rows, no shift, none of the new frames.  (The sibling's history is
+ *                          one buffer and simply stays; this one is double-buffered by launch parity, so it must cross.)  Written by
+ *                          the speaker-0 workgroups only, as always; with D == 0 nothing is written
+ *   enh_ri, enh_mag        written as zero for all S speakers and all `hop` frames
+ *   enh_g granules         leave (zeros) with their tag: the inverse-STFT waves poll them
+ *   wave_state             not shifted; a first call (k == clip_start[b] - 1) does not take the samples
+ *   ola_state              not touched
+ *   wave_out               zero
+ *   done                   written as always (launch_index + 1): a host that spins on the words returns
+ *   clip_start[b] += 1     (unsigned): the clip's origin moves on by one launch, so that launch k + 1 -- and
+ *                          sfsn_fullband_hop_state_export / _import and sfsn_fullband_hop_seed / _advance, which all read clip b
+ *                          through its origin -- see it exactly as if launch k had never happened for it: a restart or first call
+ *                          that was due in launch k is due in k + 1
+ * The origin rule (sfsn_stream_hop_held's): the + 1 is ordered after every read of clip_start in this launch and before the next launch
+ * on the stream.  Each workgroup, its role done and nothing of it in flight, adds 1 (vector atomic) to word 3 of `scratch` as its last
+ * act -- also a workgroup whose bounded wait expired, and the inverse-STFT waves that have no pair -- and the workgroup that finds
+ * itself last applies the + 1s and clears the word.  Nobody waits on that word: no spin is added.  Word 0 stays the error word, words
+ * 1 and 2 are unused, sfsn_fullband_hop_scratch_bytes stays 64.  clip_start must therefore be device-writable memory the caller hands
+ * over for the launch; the caller still numbers the launches itself (launch_index + 1 after this one too) and does not advance its own
+ * count of a held clip's frames / calls.
+ *
+ * Returns, with held_mask == 0, what the plain launch returns.  With a bit set, in this order -- the mask checks come before any
+ * device query, so they are answered without a device:
+ *   desc == NULL                                        SFSN_EINVAL
+ *   a bit at or beyond desc->B                          SFSN_EINVAL
+ *   desc->clip_start == NULL                            SFSN_EINVAL   (a held clip needs an origin of its own)
+ *   a descriptor the plain launch refuses               the plain launch's code
+ *   spike_slots misaligned (4 bytes)                    SFSN_EINVAL
+ * spike_slots == NULL: the uncounted launch.  (Added without an ABI bump: no existing struct or signature changed.)
+ * ---------------------------------------------------------------------------------------------------- */
+int sfsn_fullband_stream_hop_held(const sfsn_fullband_hop_desc* desc, unsigned* spike_slots /* nullable: the uncounted launch */,
+                                  unsigned held_mask /* bit b = clip b sits launch desc->launch_index out */, void* stream);
+int sfsn_fullband_stream_hop_wave_held(const sfsn_fullband_wave_desc* desc, unsigned held_mask, void* stream);
 
 /* Moving a clip of a cIRM-GSN session (csrc/sfsn_state.hip): sfsn_hop_state_export / sfsn_hop_state_import for sfsn_fullband_hop_desc --
  * the same launch, the same rules (one launch, plain stores, the half of h and hist_ri that launch launch_index reads, scratch and z0

@@ -370,6 +370,10 @@ def lib() -> ctypes.CDLL:
     L.sfsn_fullband_wave_hop_check.argtypes = [_I] * 7
     L.sfsn_fullband_stream_hop_wave.restype = _I
     L.sfsn_fullband_stream_hop_wave.argtypes = [ctypes.POINTER(FullbandWaveDesc), _P]
+    L.sfsn_fullband_stream_hop_held.restype = _I  # desc, spike_slots (nullable), held_mask (bit b = clip b is held), stream
+    L.sfsn_fullband_stream_hop_held.argtypes = [ctypes.POINTER(FullbandHopDesc), _P, ctypes.c_uint, _P]
+    L.sfsn_fullband_stream_hop_wave_held.restype = _I  # desc, held_mask, stream
+    L.sfsn_fullband_stream_hop_wave_held.argtypes = [ctypes.POINTER(FullbandWaveDesc), ctypes.c_uint, _P]
     L.sfsn_fullband_hop_state_bytes.restype = ctypes.c_size_t  # desc, counted, wave; 0: not covered (host only)
     L.sfsn_fullband_hop_state_bytes.argtypes = [ctypes.POINTER(FullbandHopDesc), _I, _I]
     L.sfsn_fullband_hop_state_export.restype = _I  # desc, spike_slots, wave_state, ola_state | clips, n_clips | blob, stream
@@ -435,7 +439,8 @@ EXPORTS = ("sfsn_abi_version", "sfsn_source_hash", "sfsn_strerror", "sfsn_device
            "sfsn_fullband_proj_deepfilter_ragged", "sfsn_hop_prime", "sfsn_gsn_layer_scan_l01_projdf",
            "sfsn_hop_state_bytes", "sfsn_hop_state_export", "sfsn_hop_state_import", "sfsn_fullband_hop_state_bytes",
            "sfsn_fullband_hop_state_export", "sfsn_fullband_hop_state_import", "sfsn_hop_seed", "sfsn_hop_advance",
-           "sfsn_fullband_hop_seed", "sfsn_fullband_hop_advance", "sfsn_stream_hop_held")
+           "sfsn_fullband_hop_seed", "sfsn_fullband_hop_advance", "sfsn_stream_hop_held",
+           "sfsn_fullband_stream_hop_held", "sfsn_fullband_stream_hop_wave_held")
 
 
 def check(rc: int, what: str = "") -> None:

@@ -33,6 +33,13 @@
 // stores spikes adds the set bytes of its words over the launch's frames into a slot of its own (include/sfsn.h).  The other two
 // kernels are compiled without it.
 //
+// Held clips (sfsn_fullband_stream_hop_held / _wave_held; include/sfsn.h has the per-row contract): three more kernels -- held, held +
+// counted, held waveform -- whose roles carry the mask (one word by value in the kernel arguments, bit b = clip b sits this launch out)
+// under `if constexpr (HELD)`.  Every stage, hand-off, granule and tag runs for every row as always; a held row's carried state is not
+// written, its h and history cross the launch parity unchanged, its outputs are zero, and the last workgroup to finish moves its origin
+// on by one launch (scratch word 3 counts the finished workgroups; nobody waits on it).  The input role keeps no state and has no held
+// form.  The three kernels above are compiled without any of this (profiles/device_code_digest.txt).
+//
 // Arithmetic: sfsn_fullband_dev.h's expressions (shared with the offline kernels) and scan_body's cell: bit-identical to
 // FullbandEngine.forward_stft on the concatenated input (tests/test_cirm_streaming.py).
 #include <hip/hip_runtime.h>
@@ -53,6 +60,7 @@
 #define FBH_NU 5        // feature slots per lane: F <= 320
 #define FBH_TPW 2       // coefficient tiles per projection wave: 2 df <= 16
 #define FBH_DF_MAX 5
+#define FBH_HELD_CNT 3  // scratch word: workgroups of a held launch that have finished (cleared by the last one), as sfsn_hop.hip's
 
 struct FbhLayerDev {
     const int8_t* w_ih;
@@ -79,7 +87,7 @@ struct FbhParams {
     float* enh;
     float* mag;
     float* z0;
-    unsigned* cnt;  // [0] error word
+    unsigned* cnt;  // [0] error word; [3] held launches: workgroups that have finished (FBH_HELD_CNT)
     const unsigned* clip_start;
     int nl, Hp, KS, NT, B, F, S, df, hop, D, act, NCT, NTT;
     int nwg_in, wpl, nwg_proj, nblocks;
@@ -196,8 +204,11 @@ __device__ __forceinline__ void fbh_input_role(const FbhParams& p, char* smem) {
 // COUNT (sfsn_fullband_stream_hop_counted): the lane also keeps the running spike count of its four neurons of its clip row in the slot
 // it alone owns, slots[(l B + row) Hp / 4 + cc / 4] -- requested with the carried state, read as zero where the clip restarts, written
 // back once per launch (plain load + store).  Without COUNT nothing of this is compiled: the role is the uncounted launches' code.
-template <bool L0, bool COUNT = false>
-__device__ __forceinline__ void fbh_layer_role(const FbhParams& p, int l, int part, char* smem, [[maybe_unused]] unsigned* slots = nullptr) {
+// HELD: bit b of `held` = clip b sits this launch out -- its row runs like every row (its spikes are published: every tile gathers all
+// rows), but at the end the bytes of h[k & 1] go to h[(k + 1) & 1] instead of the last frame's spikes, and c and the slot stay.
+template <bool L0, bool COUNT = false, bool HELD = false>
+__device__ __forceinline__ void fbh_layer_role(const FbhParams& p, int l, int part, char* smem, [[maybe_unused]] unsigned* slots = nullptr,
+                                               [[maybe_unused]] unsigned held = 0u) {
     const FbhLayerDev& L = p.layer[l];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -324,7 +335,13 @@ __device__ __forceinline__ void fbh_layer_role(const FbhParams& p, int l, int pa
         if (active && row < R) st_agent(L.spikes + ((size_t)t * R + row) * HP + cc, pk | tagw);  // data + tag: published
         if constexpr (COUNT) nspk += (unsigned)__builtin_popcount(pk);  // (bytes 0/1: a popcount)
     }
-    if (active && row < R) {
+    // (the mask is asked here, and the lane's 4 bytes of h[k & 1] are loaded again: nothing more stays live across the frames)
+    bool live = true;
+    if constexpr (HELD) {
+        live = !((held >> rowc) & 1u);
+        if (active && row < R && !live) st_agent(hnext + (size_t)row * HP + cc, *reinterpret_cast<const unsigned*>(hprev + (size_t)row * HP + cc));
+    }
+    if (HELD ? (live && active && row < R) : (active && row < R)) {
         *reinterpret_cast<v4f*>(L.c + (size_t)row * H + cc) = c;
         st_agent(hnext + (size_t)row * HP + cc, pk);
         if constexpr (COUNT) slots[((size_t)l * R + row) * (H >> 2) + (cc >> 2)] = nspk;
@@ -334,8 +351,10 @@ __device__ __forceinline__ void fbh_layer_role(const FbhParams& p, int l, int pa
 // ---------------------------------------------------------------------------------------------------------------------
 // projection + activation + deep filter of one (bin block, speaker).  LDS: [64 B][hb: 5 KB][cbuf: 16 rows x 2 df tiles x 16 floats]
 // ---------------------------------------------------------------------------------------------------------------------
-template <bool WAVE>
-__device__ __forceinline__ void fbh_proj_role(const FbhParams& p, int idx, char* smem) {
+// HELD: a held clip's bins leave as zeros (the enhanced granules too, with their tag: the inverse-STFT waves poll them) and its history
+// rows cross the launch parity as they are: hist[(k + 1) & 1] <- hist[k & 1], no shift, none of the new frames.
+template <bool WAVE, bool HELD = false>
+__device__ __forceinline__ void fbh_proj_role(const FbhParams& p, int idx, char* smem, [[maybe_unused]] unsigned held = 0u) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n = lane & 15, q = lane >> 4;
@@ -369,6 +388,8 @@ __device__ __forceinline__ void fbh_proj_role(const FbhParams& p, int idx, char*
     const bool mine = tid < 256 && rl < B && f < F;
     const int b_ = mine ? rl : 0, fc = mine ? f : 0;
     const bool fresh = fbh_fresh(p, b_);
+    [[maybe_unused]] bool sits = false;  // HELD: my clip sits this launch out
+    if constexpr (HELD) sits = (held >> b_) & 1u;
     const float* hrow = p.hist[p.launch & 1u] + ((size_t)b_ * F + fc) * D * 2;
     const float* irow = p.inp + ((size_t)b_ * F + fc) * hop * 2;
     bool ok = true;
@@ -422,6 +443,9 @@ __device__ __forceinline__ void fbh_proj_role(const FbhParams& p, int idx, char*
                 }
                 fbd_tap(yr, yi, xv, cbuf[(rl * ntl + d) * 16 + bi], cbuf[(rl * ntl + df + d) * 16 + bi]);
             }
+            if constexpr (HELD) {
+                if (sits) yr = yi = 0.0f;  // (whatever the taps gave, NaN included)
+            }
             const size_t o = (((size_t)rl * S + s_) * F + f) * hop + t;
             if constexpr (WAVE) {  // the enhanced bin to the inverse-STFT wave of (clip, speaker); the spectrum only on request
                 hop_put_cplx(p.enh_g + 4 * o, make_float2(yr, yi), tagw);
@@ -435,6 +459,12 @@ __device__ __forceinline__ void fbh_proj_role(const FbhParams& p, int idx, char*
     // the history the next launch reads (the other half of the double buffer): the last D of [history | new frames]
     if (mine && s_ == 0) {
         float* hnext = p.hist[(p.launch + 1u) & 1u] + ((size_t)rl * F + f) * D * 2;
+        if constexpr (HELD) {
+            if (sits) {  // (the rows as memory holds them, whether or not a restart is due: it is due in the next launch then)
+                for (int i = 0; i < D; ++i) *reinterpret_cast<float2*>(hnext + 2 * i) = *reinterpret_cast<const float2*>(hrow + 2 * i);
+                return;
+            }
+        }
         if constexpr (WAVE) {  // (the taps are in registers: history 1 .. D - 1, then the granule taken above)
 #pragma unroll
             for (int i = 0; i < FBH_DF_MAX - 1; ++i)
@@ -448,19 +478,24 @@ __device__ __forceinline__ void fbh_proj_role(const FbhParams& p, int idx, char*
 // ---------------------------------------------------------------------------------------------------------------------
 // waveform mode: the new frame's spectrum (block 0) and the enhanced frame back to samples (the last blocks); sfsn_hop_wave_dev.h
 // ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void fbh_stft_role(const FbhParams& p, char* smem) {
-    hop_wave_stft(p.wave_in, p.wave_state, p.window, p.spec_g, p.F, 0, p.B, hop_tag(p.launch) * 0x02020202u, smem,
-                  [&](int ln, int n) { return __ballot(ln < n && fbh_clip_k(p, ln) == -1); });
+// HELD (sfsn_hop_wave_dev.h's held forms): a held clip's wave_state does not move and a first call does not take the samples; its
+// samples out are zero, its done word is written all the same, its accumulator is not touched
+template <bool HELD = false>
+__device__ __forceinline__ void fbh_stft_role(const FbhParams& p, char* smem, [[maybe_unused]] unsigned held = 0u) {
+    hop_wave_stft_held<HELD>(p.wave_in, p.wave_state, p.window, p.spec_g, p.F, 0, p.B, hop_tag(p.launch) * 0x02020202u, smem,
+                             [&](int ln, int n) { return __ballot(ln < n && fbh_clip_k(p, ln) == -1); },
+                             [&](int ci) { return (bool)((held >> ci) & 1u); });
 }
-__device__ __forceinline__ void fbh_istft_role(const FbhParams& p, int wg, char* smem) {
-    hop_wave_istft(
+template <bool HELD = false>
+__device__ __forceinline__ void fbh_istft_role(const FbhParams& p, int wg, char* smem, [[maybe_unused]] unsigned held = 0u) {
+    hop_wave_istft_held<HELD>(
         p.ola_state, p.wave_out, p.window, p.enh_g, p.done, p.cnt, p.F, wg, p.B * p.S, hop_tag(p.launch) * 0x02020202u, p.launch + 1u, smem,
         [&](int pair, int& fi, bool& fresh, bool& mute) {
             fi = fbh_clip_k(p, pair / p.S);
             fresh = fi == 0;
             mute = fi < 2;
         },
-        [](bool&) {});
+        [](bool&) {}, [&](int pair) { return (bool)((held >> (pair / p.S)) & 1u); });
 }
 
 __global__ __launch_bounds__(HOP_THREADS) void fullband_stream_hop_kernel(const FbhParams p) {
@@ -528,6 +563,75 @@ __global__ __launch_bounds__(HOP_THREADS) void fullband_stream_hop_wave_kernel(c
         return;
     }
     fbh_istft_role(p, pi - p.nwg_proj, smem);
+}
+
+// one held launch of one workgroup: the role its block index selects, in the order of the three kernels above.  (They keep their own
+// dispatch: routed through this one with HELD = false, the spectrum kernel came out with a 624-byte private segment.)
+template <bool WAVE, bool COUNT>
+__device__ __forceinline__ void fbh_held_dispatch(const FbhParams& p, [[maybe_unused]] unsigned* slots, unsigned held, char* smem) {
+    const int bi = (int)blockIdx.x - (WAVE ? 1 : 0);
+    if constexpr (WAVE) {
+        if (bi < 0) {
+            fbh_stft_role<true>(p, smem, held);
+            return;
+        }
+    }
+    if (bi < p.nwg_in) {
+        fbh_input_role<WAVE>(p, smem);
+        return;
+    }
+    const int li = bi - p.nwg_in;
+    if (li < p.nl * p.wpl) {
+        const int l = li / p.wpl, part = li - l * p.wpl;
+        if (l == 0)
+            fbh_layer_role<true, COUNT, true>(p, 0, part, smem, slots, held);
+        else
+            fbh_layer_role<false, COUNT, true>(p, l, part, smem, slots, held);
+        return;
+    }
+    const int pi = li - p.nl * p.wpl;
+    if constexpr (WAVE) {
+        if (pi >= p.nwg_proj) {
+            fbh_istft_role<true>(p, pi - p.nwg_proj, smem, held);
+            return;
+        }
+    }
+    fbh_proj_role<WAVE, true>(p, pi, smem, held);
+}
+
+// The launches with held clips (sfsn_fullband_stream_hop_held / _wave_held): the same roles with the mask compiled in, then the origins.
+// clip_start[b] += 1 must come after every read of clip_start in this launch: each workgroup, its role done and nothing of it in flight
+// (every origin it asked for has arrived), counts itself in scratch word FBH_HELD_CNT as its last act; the workgroup that finds itself
+// last applies the + 1s and clears the word for the next held launch.  Nobody waits on that word.  Every workgroup gets here: a role
+// whose bounded wait expired runs on to its end, and the inverse-STFT waves without a pair only leave their role.  The launch boundary
+// orders the new origins before the next launch on the stream.  (stream_hop_held_kernel's protocol, sfsn_hop.hip.)
+__device__ __forceinline__ void fbh_held_finish(const FbhParams& p, unsigned held, char* smem) {
+    __builtin_amdgcn_s_waitcnt(0);  // vmcnt(0) expcnt(0) lgkmcnt(0): nothing of this wave's role is still in flight
+    __syncthreads();
+    unsigned* fin = p.cnt + FBH_HELD_CNT;
+    if (threadIdx.x == 0)
+        *reinterpret_cast<unsigned*>(smem) = __hip_atomic_fetch_add(fin, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    if (*reinterpret_cast<const unsigned*>(smem) != gridDim.x - 1u) return;
+    const int b = threadIdx.x;
+    if (b < p.B && ((held >> b) & 1u))
+        __hip_atomic_fetch_add(const_cast<unsigned*>(p.clip_start) + b, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (threadIdx.x == 0) st_agent(fin, 0u);
+}
+__global__ __launch_bounds__(HOP_THREADS) void fullband_stream_hop_held_kernel(const FbhParams p, unsigned held) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    fbh_held_dispatch<false, false>(p, nullptr, held, smem);
+    fbh_held_finish(p, held, smem);
+}
+__global__ __launch_bounds__(HOP_THREADS) void fullband_stream_hop_held_counted_kernel(const FbhParams p, unsigned* slots, unsigned held) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    fbh_held_dispatch<false, true>(p, slots, held, smem);
+    fbh_held_finish(p, held, smem);
+}
+__global__ __launch_bounds__(HOP_THREADS) void fullband_stream_hop_wave_held_kernel(const FbhParams p, unsigned held) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    fbh_held_dispatch<true, false>(p, nullptr, held, smem);
+    fbh_held_finish(p, held, smem);
 }
 
 #ifdef SFSN_FBH_ROLE_KERNELS
@@ -624,7 +728,7 @@ static int fbh_plan(FbhParams& p, size_t& lds, const sfsn_fullband_hop_desc* d, 
 extern "C" size_t sfsn_fullband_hop_scratch_bytes(const sfsn_fullband_hop_desc* desc) {
     FbhParams p;
     size_t lds;
-    return fbh_plan(p, lds, desc) == SFSN_OK ? 64 : 0;  // word 0: the error word
+    return fbh_plan(p, lds, desc) == SFSN_OK ? 64 : 0;  // word 0: the error word; word 3: the held launches' finishing count
 }
 
 static bool aligned8(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 7u) == 0; }
@@ -634,8 +738,10 @@ extern "C" size_t sfsn_fullband_hop_spike_slots(const sfsn_fullband_hop_desc* d)
     return (size_t)d->n_layers * d->B * (d->Hp / 4);
 }
 
-// the launch of every mode; w != nullptr: waveform mode (d = &w->hop); slots != nullptr: the counting spectrum launch
-static int fbh_launch(const sfsn_fullband_hop_desc* d, const sfsn_fullband_wave_desc* w, void* stream, unsigned* slots = nullptr) {
+// the launch of every mode; w != nullptr: waveform mode (d = &w->hop); slots != nullptr: the counting spectrum launch; held != 0: the
+// held kernels (the mask has passed fbh_held_mask)
+static int fbh_launch(const sfsn_fullband_hop_desc* d, const sfsn_fullband_wave_desc* w, void* stream, unsigned* slots = nullptr,
+                      unsigned held = 0u) {
     FbhParams p;
     size_t lds;
     const int rc = fbh_plan(p, lds, d, w != nullptr);
@@ -675,6 +781,13 @@ static int fbh_launch(const sfsn_fullband_hop_desc* d, const sfsn_fullband_wave_
     // every workgroup must be resident at once (consumers wait for producers): one per compute unit at most
     if (p.nblocks > cu_count()) return SFSN_EUNSUPPORTED;
     if (lds > 160 * 1024) return SFSN_EUNSUPPORTED;
+    if (held) {
+        const dim3 grid(p.nblocks), block(HOP_THREADS);
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        if (w) return launch_lds<fullband_stream_hop_wave_held_kernel>(grid, block, lds, st, p, held);
+        if (slots) return launch_lds<fullband_stream_hop_held_counted_kernel>(grid, block, lds, st, p, slots, held);
+        return launch_lds<fullband_stream_hop_held_kernel>(grid, block, lds, st, p, held);
+    }
     if (w) return launch_lds<fullband_stream_hop_wave_kernel>(dim3(p.nblocks), dim3(HOP_THREADS), lds, static_cast<hipStream_t>(stream), p);
     if (slots) return launch_lds<fullband_stream_hop_counted_kernel>(dim3(p.nblocks), dim3(HOP_THREADS), lds, static_cast<hipStream_t>(stream), p, slots);
     return launch_lds<fullband_stream_hop_kernel>(dim3(p.nblocks), dim3(HOP_THREADS), lds, static_cast<hipStream_t>(stream), p);
@@ -690,4 +803,31 @@ extern "C" int sfsn_fullband_stream_hop_counted(const sfsn_fullband_hop_desc* d,
 extern "C" int sfsn_fullband_stream_hop_wave(const sfsn_fullband_wave_desc* w, void* stream) {
     if (!w) return SFSN_EINVAL;
     return fbh_launch(&w->hop, w, stream);
+}
+
+// ---- held clips: the mask's own checks come first and need no device
+static int fbh_held_mask(const sfsn_fullband_hop_desc* d, unsigned held) {
+    if (!d) return SFSN_EINVAL;
+    if (d->B < 32 && (held >> (d->B > 0 ? d->B : 0)) != 0) return SFSN_EINVAL;  // a bit at or beyond B
+    if (!d->clip_start) return SFSN_EINVAL;                                      // a held clip needs an origin of its own
+    return SFSN_OK;
+}
+
+extern "C" int sfsn_fullband_stream_hop_held(const sfsn_fullband_hop_desc* d, unsigned* spike_slots, unsigned held_mask, void* stream) {
+    if (held_mask == 0) return spike_slots ? sfsn_fullband_stream_hop_counted(d, spike_slots, stream) : sfsn_fullband_stream_hop(d, stream);
+    int rc = fbh_held_mask(d, held_mask);
+    if (rc != SFSN_OK) return rc;
+    FbhParams p;
+    size_t lds;
+    if ((rc = fbh_plan(p, lds, d)) != SFSN_OK) return rc;  // (a descriptor the plain launch refuses: its code, before the slots are looked at)
+    if ((reinterpret_cast<uintptr_t>(spike_slots) & 3u) != 0) return SFSN_EINVAL;
+    return fbh_launch(d, nullptr, stream, spike_slots, held_mask);
+}
+
+extern "C" int sfsn_fullband_stream_hop_wave_held(const sfsn_fullband_wave_desc* w, unsigned held_mask, void* stream) {
+    if (held_mask == 0) return sfsn_fullband_stream_hop_wave(w, stream);
+    if (!w) return SFSN_EINVAL;
+    const int rc = fbh_held_mask(&w->hop, held_mask);
+    if (rc != SFSN_OK) return rc;
+    return fbh_launch(&w->hop, w, stream, nullptr, held_mask);
 }

@@ -51,6 +51,17 @@ after a stall or switches from a file to live input.  One launch each way on the
 fresh clip reads as zero state, so ``reset(clips); catch_up(prefix, clips)`` is the warm start from a recorded prefix (the sibling's
 ``prime``; its four method names are not defined here).
 
+Held ticks: ``tick(frames, clips)`` / ``tick_wave(samples, clips)`` / ``tick_wave_host(samples, clips)`` advance only the listed clips
+of the batch; every other clip is HELD: its input row may hold anything (NaN included), its output row is zero, and its state, spike
+counts, ``clip_frames()`` and ``clip_calls()`` stay what they were, so that its next active call continues its utterance bit for bit
+(tests/test_cirm_hold.py).  A server whose clips' frames arrive with jitter ticks with the clips that are ready.  The one-launch hop
+holds clips inside the one launch it makes anyway (``sfsn_fullband_stream_hop_held`` / ``_wave_held``: the mask travels by value in the
+kernel arguments, a held row's state stores are suppressed, ``h`` and the deep-filter history cross the launch parity unchanged, and the
+last workgroup to finish moves the held clips' origins on by one launch; no fill, no copy, no second kernel); the per-kernel sequence
+saves the held clips' rows of its state before the replay and puts them back after it.  ``clips=None`` or every clip listed is the call
+``step*`` makes; an empty list launches nothing.  These are names of their own beside ``step`` / ``step_wave`` / ``step_wave_host``,
+whose signatures stay (the sibling's sessions take ``clips=`` on ``step*`` itself); profiles/cirm_hold.md has the measurement.
+
 Not covered here: ``resident`` sessions, ``count_spikes`` together with ``waveform``, waveform sessions beyond 16 clips or with
 separate gate weights, and LSTM models.
 """
@@ -66,7 +77,7 @@ import torch
 
 from . import _lib
 from ._lib import MAX_COUNT_TENSORS, FullbandHopDesc, FullbandWaveDesc, RowCount, check
-from .clip_select import as_i32, check_frames, check_samples, clip_indices, runs, runs_by
+from .clip_select import as_i32, check_frames, check_samples, clip_indices, held_masks, runs, runs_by
 from .engine import SpikeSummary, _ptr
 from .fullband_engine import FullbandEngine
 
@@ -235,16 +246,21 @@ class FullbandStreamingSession:
         h["origin"].fill_(1)  # every clip's first call is launch 0: its frame 0 is launch 1
         h.update(wave=wv, wdesc=wd, wref=ctypes.byref(wd))
 
-    def _launch_wave(self, wave_in_ptr: int) -> None:
+    def _launch_wave(self, wave_in_ptr: int, held_mask: int = 0) -> None:
+        """One waveform launch; ``held_mask`` (tick_wave*): bit b = clip b is held -- the held entry point, still one launch."""
         h = self._hop
         if h["err_pending"] and int(h["err"][0]) != 0:  # written behind an earlier launch; no blocking here
             self.check_errors()
         d = h["desc"]
         h["wdesc"].wave_in = wave_in_ptr
         with torch.cuda.device(self.dev):  # the C ABI launches on the calling thread's current device
-            rc = self.eng.lib.sfsn_fullband_stream_hop_wave(h["wref"], ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream))
+            st = ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+            if held_mask:
+                rc = self.eng.lib.sfsn_fullband_stream_hop_wave_held(h["wref"], held_mask, st)
+            else:
+                rc = self.eng.lib.sfsn_fullband_stream_hop_wave(h["wref"], st)
         if rc:
-            check(rc, "sfsn_fullband_stream_hop_wave")
+            check(rc, "sfsn_fullband_stream_hop_wave_held" if held_mask else "sfsn_fullband_stream_hop_wave")
         d.launch_index = (d.launch_index + 1) & 0xFFFFFFFF
         self._count("hop")
         self._calls += 1
@@ -281,7 +297,12 @@ class FullbandStreamingSession:
         host["inp"].copy_(torch.as_tensor(samples, dtype=torch.float32).reshape(self.B, 128))
         target = (self._hop["desc"].launch_index + 1) & 0xFFFFFFFF
         self._launch_wave(host["inp"].data_ptr())
-        done, t_end, t_soft = host["done_np"], None, None
+        self._wait_done(target, timeout_s)
+        return host["out"]
+
+    def _wait_done(self, target: int, timeout_s: float) -> None:
+        """Spin until every (clip, speaker) completion word of a host_io session reads ``target`` (the launch's index + 1)."""
+        done, t_end, t_soft = self._hop["wave"]["host"]["done_np"], None, None
         while (int(done.min()) & 0xFFFFFFFF) != target or (int(done.max()) & 0xFFFFFFFF) != target:  # (uint32 compare: the index wraps)
             if t_end is None:
                 t_end = time.perf_counter() + timeout_s
@@ -293,9 +314,9 @@ class FullbandStreamingSession:
                 self.check_errors()
             elif time.perf_counter() > t_end:
                 raise RuntimeError("sfsn_fullband_stream_hop_wave: no completion word from the launch (see check_errors())")
-        return host["out"]
 
-    def _launch_hop(self, frames: torch.Tensor) -> None:
+    def _launch_hop(self, frames: torch.Tensor, held_mask: int = 0) -> None:
+        """One spectrum launch; ``held_mask`` (tick): bit b = clip b is held -- the held entry point, still one launch."""
         h = self._hop
         if h["err_pending"] and int(h["err"][0]) != 0:  # written behind an earlier launch; no blocking here
             self.check_errors()
@@ -303,12 +324,16 @@ class FullbandStreamingSession:
         d.inp_ri = frames.data_ptr()
         with torch.cuda.device(self.dev):  # the C ABI launches on the calling thread's current device
             st = ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
-            if h["slots"] is not None:
+            if held_mask:
+                slots = ctypes.c_void_p(h["slots"].data_ptr()) if h["slots"] is not None else None
+                rc = self.eng.lib.sfsn_fullband_stream_hop_held(h["ref"], slots, held_mask, st)
+            elif h["slots"] is not None:
                 rc = self.eng.lib.sfsn_fullband_stream_hop_counted(h["ref"], ctypes.c_void_p(h["slots"].data_ptr()), st)
             else:
                 rc = self.eng.lib.sfsn_fullband_stream_hop(h["ref"], st)
         if rc:
-            check(rc, "sfsn_fullband_stream_hop_counted" if h["slots"] is not None else "sfsn_fullband_stream_hop")
+            check(rc, "sfsn_fullband_stream_hop_held" if held_mask else
+                  "sfsn_fullband_stream_hop_counted" if h["slots"] is not None else "sfsn_fullband_stream_hop")
         d.launch_index = (d.launch_index + 1) & 0xFFFFFFFF
         self._count("hop")
         if (self.frames_done + self.hop) % 256 < self.hop:  # every ~256 frames the error word follows the launches into pinned memory
@@ -407,6 +432,125 @@ class FullbandStreamingSession:
         if copy:
             return e.clone(), (m.clone() if m is not None else None)
         return e, m
+
+    # ---- held ticks: a call that advances only some clips of the batch ------------------------------------------------------------
+    def _hold(self, clips, what: str):
+        """``clips`` of a tick: None where nobody is held (``clips=None`` or every clip listed); otherwise ``(active, held, mask)``
+        with bit b of ``mask`` set for a held clip b (clip_select.held_masks: duplicates merged, ``ValueError`` naming an index out of
+        range, ``TypeError`` for wrong types)."""
+        if clips is None:
+            return None
+        active, held, words = held_masks(clips, self.B, [(0, self.B)], what)
+        if not held:
+            return None
+        return active, held, words[0][0]  # (the mask is the one-launch tier's: B <= 16 there, one word)
+
+    def _held_bookkeeping(self, held) -> None:
+        """After a launch that held ``held``: their utterances began one hop (waveform: one call) later, so that ``clip_frames()`` /
+        ``clip_calls()`` stay what they were."""
+        self._clip_f0[held] += self.hop
+        if self.waveform:
+            self._clip_c0[held] += 1
+
+    def tick(self, frames: torch.Tensor, clips, copy: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """``step`` for a tick on which only ``clips`` (a sequence or 1-D tensor of clip indices; duplicates merged) have new frames:
+        they take the hop, every other clip is HELD -- its rows of ``frames`` may hold anything (NaN included), its output rows are
+        zero, and its state, spike counts and ``clip_frames()`` are what they were: its next active call continues its utterance
+        bit for bit.  Shapes do not change.  The one-launch tier holds the clips inside the one launch it makes anyway
+        (``sfsn_fullband_stream_hop_held``: the mask travels in the kernel arguments, no fill, no copy, no second kernel); the
+        per-kernel tier saves the held clips' rows of its state before the replay and puts them back after it (stream-ordered row
+        copies).  ``clips=None`` or every clip listed: exactly ``step(frames, copy)``.  An empty list advances nobody: nothing is
+        launched, nothing changes, zeros are returned.  ``ValueError``: an index out of range (named); ``TypeError``: wrong types."""
+        if self.waveform:
+            raise RuntimeError("this session was opened with waveform=True: use step_wave(samples)")
+        hold = self._hold(clips, "tick")
+        if hold is None:
+            return self.step(frames, copy)
+        if frames.device != self.dev or frames.dtype != torch.complex64 or tuple(frames.shape) != (self.B, self.F, self.hop):
+            raise RuntimeError(f"expected complex64 {(self.B, self.F, self.hop)} on {self.dev}, got {frames.dtype} {tuple(frames.shape)} "
+                               f"on {frames.device}")
+        active, held, mask = hold
+        if self._hop is not None:
+            e, m = self._hop["enh"], self._hop["mag"]
+        else:
+            e, m = self.enh[..., self.D:], (self.enh_mag[..., self.D:] if self.enh_mag is not None else None)
+        if not active:  # nobody advances
+            return torch.zeros_like(e), (torch.zeros_like(m) if m is not None else None)
+        if self._hop is not None:
+            if not (frames.is_contiguous() and frames.data_ptr() % 8 == 0):
+                self.inp.copy_(frames)
+                frames = self.inp
+            self._launch_hop(frames, mask)  # read in place; the held rows too, into nothing that stays
+        else:
+            # the held clips' rows of everything a step reads before it writes (export_state's sections) are put aside and put back
+            # behind the replay: stream-ordered row copies, the ones export_state / import_state of this tier make
+            sel = torch.tensor(held, dtype=torch.long).to(self.dev, non_blocking=True)
+            parts = self._state_parts()
+            saved = [t.index_select(0, sel) for _, t in parts]
+            self.inp.copy_(frames)
+            if self._graph is not None:
+                self._graph.replay()
+            else:
+                self.eng._errors.poll()
+                self._enqueue()
+            for k, v in self._last.items():
+                self.launches[k] = self.launches.get(k, 0) + v
+            for (_, t), rows in zip(parts, saved):
+                t.index_copy_(0, sel, rows)
+            e.index_fill_(0, sel, 0)
+            if m is not None:
+                m.index_fill_(0, sel, 0)
+        self.frames_done += self.hop
+        self._held_bookkeeping(held)
+        if copy:
+            return e.clone(), (m.clone() if m is not None else None)
+        return e, m
+
+    def tick_wave(self, samples: torch.Tensor, clips, copy: bool = True) -> torch.Tensor:
+        """``step_wave`` for a tick on which only ``clips`` have new samples: they make this call, every other clip is HELD -- its
+        row of ``samples`` is ignored (NaN included), it gets zeros, its state and ``clip_calls()`` stay, and its next active call
+        returns what that call would have returned (the three-call delay line counts the clip's OWN calls).  A clip may be held at
+        the session's first call and before it has ever run: it simply makes its first call later.  One
+        ``sfsn_fullband_stream_hop_wave_held`` launch.  ``clips=None`` or every clip listed: exactly ``step_wave(samples, copy)``;
+        an empty list launches nothing and returns zeros."""
+        if not self.waveform:
+            raise RuntimeError("open the session with waveform=True")
+        if self.host_io:
+            raise RuntimeError("this session was opened with host_io=True: use step_wave_host(samples)")
+        hold = self._hold(clips, "tick_wave")
+        if hold is None:
+            return self.step_wave(samples, copy)
+        if (samples.device != self.dev or samples.dtype != torch.float32 or tuple(samples.shape) != (self.B, 128) or not samples.is_contiguous()
+                or samples.data_ptr() % 8 != 0):
+            raise RuntimeError(f"expected contiguous float32 {(self.B, 128)} on {self.dev}, got {samples.dtype} {tuple(samples.shape)} on "
+                               f"{samples.device}")
+        active, held, mask = hold
+        out = self._hop["wave"]["out"]
+        if not active:  # nobody makes this call
+            return torch.zeros_like(out)
+        self._launch_wave(samples.data_ptr(), mask)
+        self._held_bookkeeping(held)
+        return out.clone() if copy else out
+
+    def tick_wave_host(self, samples, clips, timeout_s: float = 2.0) -> torch.Tensor:
+        """``step_wave_host`` with HELD clips (``tick_wave``'s rules, CPU tensors in and out): the launch writes the held clips'
+        completion words too, so the wait on the words ends as it always does.  ``clips=None`` or every clip listed: exactly
+        ``step_wave_host(samples, timeout_s)``; an empty list launches nothing and returns zeros."""
+        if not self.host_io:
+            raise RuntimeError("open the session with waveform=True, host_io=True")
+        hold = self._hold(clips, "tick_wave_host")
+        if hold is None:
+            return self.step_wave_host(samples, timeout_s)
+        active, held, mask = hold
+        host = self._hop["wave"]["host"]
+        if not active:  # nobody makes this call
+            return torch.zeros_like(host["out"])
+        host["inp"].copy_(torch.as_tensor(samples, dtype=torch.float32).reshape(self.B, 128))
+        target = (self._hop["desc"].launch_index + 1) & 0xFFFFFFFF
+        self._launch_wave(host["inp"].data_ptr(), mask)
+        self._held_bookkeeping(held)
+        self._wait_done(target, timeout_s)
+        return host["out"]
 
     def reset(self, clips=None) -> None:
         """Back to the start of an utterance: zero (h, c), zero history and zero spike counts.  ``clips`` (a sequence or 1-D tensor of

@@ -78,8 +78,9 @@ class Model(_EngineMixin, nn.Module):
         tensors through pinned host memory, no copy launch and no stream synchronisation.  ``count_spikes=True`` (spectrum sessions, both
         tiers): per-clip spike counts of every layer, kept on the device as the session runs, for ``session.spike_summary(clips)`` --
         ``metric.compute_synops(session.spike_summary([b]), [], shared_weights=...)`` is clip b's SynOPs; together with ``waveform``
-        it raises ``NotImplementedError`` (the waveform launch does not count).  ``resident`` is not built for this model.  GSN models
-        on a HIP device."""
+        it raises ``NotImplementedError`` (the waveform launch does not count).  A tick on which only some clips have input:
+        ``session.tick(frames, clips)`` / ``tick_wave`` / ``tick_wave_host`` hold every other clip inside the same one launch.
+        ``resident`` is not built for this model.  GSN models on a HIP device."""
         if self.fb_model.sequence_model_name == "LSTM":
             raise NotImplementedError("cIRM-GSN streaming covers the GSN sequence model: an LSTM model runs on ATen and has no session")
         if resident:
