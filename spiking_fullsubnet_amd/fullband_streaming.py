@@ -68,6 +68,7 @@ separate gate weights, and LSTM models.
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 import time
 import weakref
 from typing import Dict, Optional, Tuple
@@ -76,10 +77,12 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import MAX_COUNT_TENSORS, FullbandHopDesc, FullbandWaveDesc, RowCount, check
-from .clip_select import as_i32, check_frames, check_samples, clip_indices, held_masks, runs, runs_by
-from .engine import SpikeSummary, _ptr
+from ._lib import FullbandHopDesc, FullbandWaveDesc, check
+from .clip_select import check_frames, check_samples, clip_indices, held_masks, runs
+from .clip_state import ClipState, clip_list, fullband_sections, import_clips, layout_of, new_blob
+from .engine import SpikeSummary
 from .fullband_engine import FullbandEngine
+from .session_common import SessionCommon, row_count_jobs
 
 # what one_launch="auto" takes where sfsn_fullband_stream_hop covers the session: the tier that measured faster at the recipe
 # geometry, B = 1, hop = 1 (profiles/cirm_streaming.md)
@@ -120,7 +123,7 @@ def wave_refusal(engine: FullbandEngine, batch: int, hop: int, frame=None) -> Op
     return None
 
 
-class FullbandStreamingSession:
+class FullbandStreamingSession(SessionCommon):
     """``step(frames [B, F, hop] complex64) -> (enh_stft [B, S, F, hop], enh_mag [B, S, F, hop] or None when S > 1)``;
     ``waveform=True``: ``step_wave(samples [B, 128] float32) -> [B, S, 128]`` (``host_io=True``: ``step_wave_host``, CPU tensors);
     ``count_spikes=True``: ``spike_summary(clips)`` (spectrum sessions)."""
@@ -177,7 +180,7 @@ class FullbandStreamingSession:
             else:
                 self._build_sequence()
                 if graph:
-                    self._capture()
+                    self._capture(lambda: engine._errors.poll(block=True))  # (the warm-up launches' error words)
 
     def _count(self, what: str) -> None:
         self.launches[what] = self.launches.get(what, 0) + 1
@@ -246,27 +249,30 @@ class FullbandStreamingSession:
         h["origin"].fill_(1)  # every clip's first call is launch 0: its frame 0 is launch 1
         h.update(wave=wv, wdesc=wd, wref=ctypes.byref(wd))
 
-    def _launch_wave(self, wave_in_ptr: int, held_mask: int = 0) -> None:
-        """One waveform launch; ``held_mask`` (tick_wave*): bit b = clip b is held -- the held entry point, still one launch."""
+    def _launch(self, name: str, *args) -> None:
+        """One launch of the hop's entry point ``name`` (``args``: everything in front of the stream) on torch's current stream."""
         h = self._hop
         if h["err_pending"] and int(h["err"][0]) != 0:  # written behind an earlier launch; no blocking here
             self.check_errors()
-        d = h["desc"]
-        h["wdesc"].wave_in = wave_in_ptr
         with torch.cuda.device(self.dev):  # the C ABI launches on the calling thread's current device
-            st = ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
-            if held_mask:
-                rc = self.eng.lib.sfsn_fullband_stream_hop_wave_held(h["wref"], held_mask, st)
-            else:
-                rc = self.eng.lib.sfsn_fullband_stream_hop_wave(h["wref"], st)
+            rc = getattr(self.eng.lib, name)(*args, ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream))
         if rc:
-            check(rc, "sfsn_fullband_stream_hop_wave_held" if held_mask else "sfsn_fullband_stream_hop_wave")
+            check(rc, name)
+        d = h["desc"]
         d.launch_index = (d.launch_index + 1) & 0xFFFFFFFF
         self._count("hop")
+
+    def _launch_wave(self, wave_in_ptr: int, held_mask: int = 0) -> None:
+        """One waveform launch; ``held_mask`` (tick_wave*): bit b = clip b is held -- the held entry point, still one launch."""
+        h = self._hop
+        h["wdesc"].wave_in = wave_in_ptr
+        if held_mask:
+            self._launch("sfsn_fullband_stream_hop_wave_held", h["wref"], held_mask)
+        else:
+            self._launch("sfsn_fullband_stream_hop_wave", h["wref"])
         self._calls += 1
         if self._calls % 256 == 0:  # every 256 launches the error word follows them into pinned memory
-            h["err"].copy_(h["scratch"][:1], non_blocking=True)
-            h["err_pending"] = True
+            self._error_words_follow((h,))
 
     def step_wave(self, samples: torch.Tensor, copy: bool = True) -> torch.Tensor:
         """Waveform streaming (``waveform=True``): ``samples`` float32 [B, 128], contiguous, on the device -- the next 8 ms of every
@@ -277,12 +283,22 @@ class FullbandStreamingSession:
             raise RuntimeError("open the session with waveform=True")
         if self.host_io:
             raise RuntimeError("this session was opened with host_io=True: use step_wave_host(samples)")
+        return self._call_wave(samples, None, copy)
+
+    def _call_wave(self, samples: torch.Tensor, hold, copy: bool) -> torch.Tensor:
+        """``step_wave`` (``hold=None``) / ``tick_wave`` (``hold``: ``_hold``'s ``(active, held, mask)``) behind their refusals."""
         if (samples.device != self.dev or samples.dtype != torch.float32 or tuple(samples.shape) != (self.B, 128) or not samples.is_contiguous()
                 or samples.data_ptr() % 8 != 0):
             raise RuntimeError(f"expected contiguous float32 {(self.B, 128)} on {self.dev}, got {samples.dtype} {tuple(samples.shape)} on "
                                f"{samples.device}")
-        self._launch_wave(samples.data_ptr())
         out = self._hop["wave"]["out"]
+        if hold is None:
+            self._launch_wave(samples.data_ptr())
+        elif not hold[0]:  # nobody makes this call
+            return torch.zeros_like(out)
+        else:
+            self._launch_wave(samples.data_ptr(), hold[2])
+            self._held_bookkeeping(hold[1])
         return out.clone() if copy else out
 
     def step_wave_host(self, samples, timeout_s: float = 2.0) -> torch.Tensor:
@@ -293,10 +309,20 @@ class FullbandStreamingSession:
         call); same three-call delay as ``step_wave``."""
         if not self.host_io:
             raise RuntimeError("open the session with waveform=True, host_io=True")
+        return self._call_wave_host(samples, None, timeout_s)
+
+    def _call_wave_host(self, samples, hold, timeout_s: float) -> torch.Tensor:
+        """``step_wave_host`` (``hold=None``) / ``tick_wave_host`` (``hold``: ``_hold``'s) behind their refusal."""
         host = self._hop["wave"]["host"]
+        if hold is not None and not hold[0]:  # nobody makes this call
+            return torch.zeros_like(host["out"])
         host["inp"].copy_(torch.as_tensor(samples, dtype=torch.float32).reshape(self.B, 128))
         target = (self._hop["desc"].launch_index + 1) & 0xFFFFFFFF
-        self._launch_wave(host["inp"].data_ptr())
+        if hold is None:
+            self._launch_wave(host["inp"].data_ptr())
+        else:
+            self._launch_wave(host["inp"].data_ptr(), hold[2])
+            self._held_bookkeeping(hold[1])
         self._wait_done(target, timeout_s)
         return host["out"]
 
@@ -315,31 +341,6 @@ class FullbandStreamingSession:
             elif time.perf_counter() > t_end:
                 raise RuntimeError("sfsn_fullband_stream_hop_wave: no completion word from the launch (see check_errors())")
 
-    def _launch_hop(self, frames: torch.Tensor, held_mask: int = 0) -> None:
-        """One spectrum launch; ``held_mask`` (tick): bit b = clip b is held -- the held entry point, still one launch."""
-        h = self._hop
-        if h["err_pending"] and int(h["err"][0]) != 0:  # written behind an earlier launch; no blocking here
-            self.check_errors()
-        d = h["desc"]
-        d.inp_ri = frames.data_ptr()
-        with torch.cuda.device(self.dev):  # the C ABI launches on the calling thread's current device
-            st = ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
-            if held_mask:
-                slots = ctypes.c_void_p(h["slots"].data_ptr()) if h["slots"] is not None else None
-                rc = self.eng.lib.sfsn_fullband_stream_hop_held(h["ref"], slots, held_mask, st)
-            elif h["slots"] is not None:
-                rc = self.eng.lib.sfsn_fullband_stream_hop_counted(h["ref"], ctypes.c_void_p(h["slots"].data_ptr()), st)
-            else:
-                rc = self.eng.lib.sfsn_fullband_stream_hop(h["ref"], st)
-        if rc:
-            check(rc, "sfsn_fullband_stream_hop_held" if held_mask else
-                  "sfsn_fullband_stream_hop_counted" if h["slots"] is not None else "sfsn_fullband_stream_hop")
-        d.launch_index = (d.launch_index + 1) & 0xFFFFFFFF
-        self._count("hop")
-        if (self.frames_done + self.hop) % 256 < self.hop:  # every ~256 frames the error word follows the launches into pinned memory
-            h["err"].copy_(h["scratch"][:1], non_blocking=True)
-            h["err_pending"] = True
-
     # ---- the per-kernel sequence ----------------------------------------------------------------------------------------------------
     def _build_sequence(self) -> None:
         eng, spec, dev = self.eng, self.eng.spec, self.dev
@@ -357,50 +358,22 @@ class FullbandStreamingSession:
         self._row_jobs = []
         if self.count_spikes:  # the workspace's int8 spikes [Th][B][HP8], one row per clip; frames [D, D + hop) are this step's
             self._rows = torch.zeros((nl, B), dtype=torch.int64, device=dev)
-            for l0 in range(0, nl, MAX_COUNT_TENSORS):
-                arr = (RowCount * min(MAX_COUNT_TENSORS, nl - l0))()
-                for j in range(len(arr)):
-                    t = self._ws["s8"][l0 + j]
-                    arr[j].spikes_i8, arr[j].T, arr[j].R, arr[j].HP, arr[j].rows_per_clip = _ptr(t), t.shape[0], t.shape[1], t.shape[2], 1
-                    arr[j].counts = _ptr(self._rows[l0 + j])
-                self._row_jobs.append(arr)
+            self._row_jobs = row_count_jobs([(t, 1) for t in self._ws["s8"]], self._rows)
 
     def _enqueue(self) -> None:
         """One hop on torch's current stream: the history shift, then the offline forward's launches on frames [D, D + hop)."""
-        eng, B, F, D, hop = self.eng, self.B, self.F, self.D, self.hop
+        eng, B, D, hop = self.eng, self.B, self.D, self.hop
         with torch.cuda.device(self.dev):
+            st = ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
             ri = torch.view_as_real(self.hist)
-            if D + hop <= 16:  # history shift + append in one launch
-                st = ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
-                check(eng.lib.sfsn_hist_shift(_ptr(ri), _ptr(torch.view_as_real(self.inp)), B * F, D, hop, st), "sfsn_hist_shift")
-            else:
-                if D > 0:
-                    self._tmp[:, :, :D].copy_(self.hist[:, :, hop:hop + D])
-                    self.hist[:, :, :D].copy_(self._tmp[:, :, :D])
-                self.hist[:, :, D:].copy_(self.inp)
+            self._shift_history(ri, st)
             before = dict(eng.launches)
             eng._launch_frames(ri, B, self.Th, D, hop, self._stack, self._ws, self._x, self._states, [None] * len(self._states), None,
                                torch.view_as_real(self.enh), self.enh_mag)
             for arr in self._row_jobs:  # count_spikes: the new frames' spikes per clip (one launch up to 16 layers; capturable)
-                check(eng.lib.sfsn_spike_count_rows(arr, len(arr), D, hop, ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)),
-                      "sfsn_spike_count_rows")
+                check(eng.lib.sfsn_spike_count_rows(arr, len(arr), D, hop, st), "sfsn_spike_count_rows")
                 eng._count("spike_count")
             self._last = {k: v - before.get(k, 0) for k, v in eng.launches.items() if v != before.get(k, 0)}
-
-    def _capture(self) -> None:
-        side = torch.cuda.Stream(device=self.dev)
-        side.wait_stream(torch.cuda.current_stream(self.dev))
-        with torch.cuda.stream(side):
-            for _ in range(2):  # module loading, function attributes and allocator warm-up happen outside the capture
-                self._enqueue()
-        torch.cuda.current_stream(self.dev).wait_stream(side)
-        torch.cuda.synchronize(self.dev)
-        self.eng._errors.poll(block=True)  # (the warm-up launches' error words)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self._enqueue()
-        self._graph = g
-        self.reset()
 
     # ---- the session ----------------------------------------------------------------------------------------------------------------
     def step(self, frames: torch.Tensor, copy: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
@@ -409,16 +382,37 @@ class FullbandStreamingSession:
         reads ``frames`` in place, in stream order: do not overwrite it before the stream has passed this step."""
         if self.waveform:
             raise RuntimeError("this session was opened with waveform=True: use step_wave(samples)")
+        return self._call(frames, None, copy)
+
+    def _call(self, frames: torch.Tensor, hold, copy: bool) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """``step`` (``hold=None``) / ``tick`` (``hold``: ``_hold``'s ``(active, held, mask)``) behind their refusals."""
         if frames.device != self.dev or frames.dtype != torch.complex64 or tuple(frames.shape) != (self.B, self.F, self.hop):
             raise RuntimeError(f"expected complex64 {(self.B, self.F, self.hop)} on {self.dev}, got {frames.dtype} {tuple(frames.shape)} "
                                f"on {frames.device}")
-        if self._hop is not None:
+        h = self._hop
+        if h is not None:
+            e, m = h["enh"], h["mag"]
+        else:
+            e, m = self.enh[..., self.D:], (self.enh_mag[..., self.D:] if self.enh_mag is not None else None)
+        if hold is not None and not hold[0]:  # nobody advances
+            return torch.zeros_like(e), (torch.zeros_like(m) if m is not None else None)
+        if h is not None:
             if not (frames.is_contiguous() and frames.data_ptr() % 8 == 0):
                 self.inp.copy_(frames)
                 frames = self.inp
-            self._launch_hop(frames)  # read in place: no staging copy in front
-            e, m = self._hop["enh"], self._hop["mag"]
+            h["desc"].inp_ri = frames.data_ptr()  # read in place: no staging copy in front (the held rows too, into nothing that stays)
+            slots = h["slots"]
+            if hold is not None:  # the held entry point, still one launch: bit b of the mask = clip b is held
+                self._launch("sfsn_fullband_stream_hop_held", h["ref"], ctypes.c_void_p(slots.data_ptr()) if slots is not None else None,
+                             hold[2])
+            elif slots is not None:
+                self._launch("sfsn_fullband_stream_hop_counted", h["ref"], ctypes.c_void_p(slots.data_ptr()))
+            else:
+                self._launch("sfsn_fullband_stream_hop", h["ref"])
+            if (self.frames_done + self.hop) % 256 < self.hop:  # every ~256 frames the error word follows the launches into pinned memory
+                self._error_words_follow((h,))
         else:
+            saved = None if hold is None else self._save_held(hold[1])
             self.inp.copy_(frames)
             if self._graph is not None:
                 self._graph.replay()
@@ -427,8 +421,11 @@ class FullbandStreamingSession:
                 self._enqueue()
             for k, v in self._last.items():
                 self.launches[k] = self.launches.get(k, 0) + v
-            e, m = self.enh[..., self.D:], (self.enh_mag[..., self.D:] if self.enh_mag is not None else None)
+            if saved is not None:
+                self._restore_held(saved, (e, m))
         self.frames_done += self.hop
+        if hold is not None:
+            self._held_bookkeeping(hold[1])
         if copy:
             return e.clone(), (m.clone() if m is not None else None)
         return e, m
@@ -445,13 +442,6 @@ class FullbandStreamingSession:
             return None
         return active, held, words[0][0]  # (the mask is the one-launch tier's: B <= 16 there, one word)
 
-    def _held_bookkeeping(self, held) -> None:
-        """After a launch that held ``held``: their utterances began one hop (waveform: one call) later, so that ``clip_frames()`` /
-        ``clip_calls()`` stay what they were."""
-        self._clip_f0[held] += self.hop
-        if self.waveform:
-            self._clip_c0[held] += 1
-
     def tick(self, frames: torch.Tensor, clips, copy: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         """``step`` for a tick on which only ``clips`` (a sequence or 1-D tensor of clip indices; duplicates merged) have new frames:
         they take the hop, every other clip is HELD -- its rows of ``frames`` may hold anything (NaN included), its output rows are
@@ -463,48 +453,7 @@ class FullbandStreamingSession:
         launched, nothing changes, zeros are returned.  ``ValueError``: an index out of range (named); ``TypeError``: wrong types."""
         if self.waveform:
             raise RuntimeError("this session was opened with waveform=True: use step_wave(samples)")
-        hold = self._hold(clips, "tick")
-        if hold is None:
-            return self.step(frames, copy)
-        if frames.device != self.dev or frames.dtype != torch.complex64 or tuple(frames.shape) != (self.B, self.F, self.hop):
-            raise RuntimeError(f"expected complex64 {(self.B, self.F, self.hop)} on {self.dev}, got {frames.dtype} {tuple(frames.shape)} "
-                               f"on {frames.device}")
-        active, held, mask = hold
-        if self._hop is not None:
-            e, m = self._hop["enh"], self._hop["mag"]
-        else:
-            e, m = self.enh[..., self.D:], (self.enh_mag[..., self.D:] if self.enh_mag is not None else None)
-        if not active:  # nobody advances
-            return torch.zeros_like(e), (torch.zeros_like(m) if m is not None else None)
-        if self._hop is not None:
-            if not (frames.is_contiguous() and frames.data_ptr() % 8 == 0):
-                self.inp.copy_(frames)
-                frames = self.inp
-            self._launch_hop(frames, mask)  # read in place; the held rows too, into nothing that stays
-        else:
-            # the held clips' rows of everything a step reads before it writes (export_state's sections) are put aside and put back
-            # behind the replay: stream-ordered row copies, the ones export_state / import_state of this tier make
-            sel = torch.tensor(held, dtype=torch.long).to(self.dev, non_blocking=True)
-            parts = self._state_parts()
-            saved = [t.index_select(0, sel) for _, t in parts]
-            self.inp.copy_(frames)
-            if self._graph is not None:
-                self._graph.replay()
-            else:
-                self.eng._errors.poll()
-                self._enqueue()
-            for k, v in self._last.items():
-                self.launches[k] = self.launches.get(k, 0) + v
-            for (_, t), rows in zip(parts, saved):
-                t.index_copy_(0, sel, rows)
-            e.index_fill_(0, sel, 0)
-            if m is not None:
-                m.index_fill_(0, sel, 0)
-        self.frames_done += self.hop
-        self._held_bookkeeping(held)
-        if copy:
-            return e.clone(), (m.clone() if m is not None else None)
-        return e, m
+        return self._call(frames, self._hold(clips, "tick"), copy)
 
     def tick_wave(self, samples: torch.Tensor, clips, copy: bool = True) -> torch.Tensor:
         """``step_wave`` for a tick on which only ``clips`` have new samples: they make this call, every other clip is HELD -- its
@@ -517,20 +466,7 @@ class FullbandStreamingSession:
             raise RuntimeError("open the session with waveform=True")
         if self.host_io:
             raise RuntimeError("this session was opened with host_io=True: use step_wave_host(samples)")
-        hold = self._hold(clips, "tick_wave")
-        if hold is None:
-            return self.step_wave(samples, copy)
-        if (samples.device != self.dev or samples.dtype != torch.float32 or tuple(samples.shape) != (self.B, 128) or not samples.is_contiguous()
-                or samples.data_ptr() % 8 != 0):
-            raise RuntimeError(f"expected contiguous float32 {(self.B, 128)} on {self.dev}, got {samples.dtype} {tuple(samples.shape)} on "
-                               f"{samples.device}")
-        active, held, mask = hold
-        out = self._hop["wave"]["out"]
-        if not active:  # nobody makes this call
-            return torch.zeros_like(out)
-        self._launch_wave(samples.data_ptr(), mask)
-        self._held_bookkeeping(held)
-        return out.clone() if copy else out
+        return self._call_wave(samples, self._hold(clips, "tick_wave"), copy)
 
     def tick_wave_host(self, samples, clips, timeout_s: float = 2.0) -> torch.Tensor:
         """``step_wave_host`` with HELD clips (``tick_wave``'s rules, CPU tensors in and out): the launch writes the held clips'
@@ -538,19 +474,7 @@ class FullbandStreamingSession:
         ``step_wave_host(samples, timeout_s)``; an empty list launches nothing and returns zeros."""
         if not self.host_io:
             raise RuntimeError("open the session with waveform=True, host_io=True")
-        hold = self._hold(clips, "tick_wave_host")
-        if hold is None:
-            return self.step_wave_host(samples, timeout_s)
-        active, held, mask = hold
-        host = self._hop["wave"]["host"]
-        if not active:  # nobody makes this call
-            return torch.zeros_like(host["out"])
-        host["inp"].copy_(torch.as_tensor(samples, dtype=torch.float32).reshape(self.B, 128))
-        target = (self._hop["desc"].launch_index + 1) & 0xFFFFFFFF
-        self._launch_wave(host["inp"].data_ptr(), mask)
-        self._held_bookkeeping(held)
-        self._wait_done(target, timeout_s)
-        return host["out"]
+        return self._call_wave_host(samples, self._hold(clips, "tick_wave_host"), timeout_s)
 
     def reset(self, clips=None) -> None:
         """Back to the start of an utterance: zero (h, c), zero history and zero spike counts.  ``clips`` (a sequence or 1-D tensor of
@@ -560,10 +484,7 @@ class FullbandStreamingSession:
         if clips is not None:
             self._reset_clips(clips)
             return
-        owner = self._owner() if self._owner is not None else None
-        if owner is not None and owner.engine() is not self.eng:
-            raise RuntimeError("the module's parameters (or device) changed after this streaming session was created: its packed "
-                               "weights are stale -- create a new session with module.streaming(...)")
+        self._check_owner()
         if self._hop is not None:
             self.check_errors()
             h = self._hop
@@ -586,8 +507,6 @@ class FullbandStreamingSession:
         self._clip_f0[:] = 0
         self._calls = 0
         self._clip_c0[:] = 0
-
-    _as_i32 = staticmethod(as_i32)  # a launch index (uint32) as the int32 a fill writes
 
     def _reset_clips(self, clips) -> None:
         idx = clip_indices(clips, self.B, "reset", duplicates="merge", empty="ok")
@@ -687,12 +606,7 @@ class FullbandStreamingSession:
                 self.hist.index_copy_(0, sel, buf[:, :, T - self.Th:])  # the last D + hop frames of [history | new] (N >= hop)
                 if self._rows is not None:  # the new frames' spikes per clip, added to the clips' counts
                     tmp = torch.zeros((nl, n), dtype=torch.int64, device=dev)
-                    for l0 in range(0, nl, MAX_COUNT_TENSORS):
-                        jobs = (RowCount * min(MAX_COUNT_TENSORS, nl - l0))()
-                        for j in range(len(jobs)):
-                            t = ws["s8"][l0 + j]
-                            jobs[j].spikes_i8, jobs[j].T, jobs[j].R, jobs[j].HP, jobs[j].rows_per_clip = _ptr(t), T, n, HP8, 1
-                            jobs[j].counts = _ptr(tmp[l0 + j])
+                    for jobs in row_count_jobs([(t, 1) for t in ws["s8"]], tmp, T=T, R=n):
                         check(L.sfsn_spike_count_rows(jobs, len(jobs), D, N, st), "sfsn_spike_count_rows")
                         eng._count("spike_count")
                     self._rows.index_add_(1, sel, tmp)
@@ -787,7 +701,6 @@ class FullbandStreamingSession:
         cached = getattr(self, "_signature", None)
         if cached is not None:
             return cached
-        import dataclasses
         sig = [("model", "cirm_gsn"), ("tier", "one_launch" if self._hop is not None else "per_kernel"), ("hop", self.hop),
                ("waveform", self.waveform), ("count_spikes", self.count_spikes), ("F", self.F), ("Hp", self.eng.Hp)]
         sig += [(k, v) for k, v in dataclasses.asdict(self.eng.spec).items() if k != "bn"]
@@ -804,15 +717,7 @@ class FullbandStreamingSession:
             parts.append(("rows", self._rows.t()))
         return parts
 
-    def _state_layout(self):
-        """((section, start, stop), ...), bytes of one clip's blob in this session's tier (clip_state.py); fixed at construction."""
-        cached = getattr(self, "_layout", None)
-        if cached is None:
-            cached = self._layout = self._make_state_layout()
-        return cached
-
     def _make_state_layout(self):
-        from .clip_state import fullband_sections, layout_of
         if self._hop is None:
             return layout_of([(name, t.shape[1] * t.element_size()) for name, t in self._state_parts()])
         layout, nbytes = fullband_sections(self.eng.spec.layers, self.eng.Hp, self.count_spikes, self.F, self.D, self.waveform, self.S)
@@ -838,12 +743,10 @@ class FullbandStreamingSession:
         signature (``clip_state.py``).  (The warm start from a recorded prefix is ``reset(clips); catch_up(prefix, clips)``.)  The one-launch hop copies
         the state in one launch (``sfsn_fullband_hop_state_export``), the per-kernel sequence with stream-ordered row copies.  The
         session is not changed.  Ordered on torch's current stream, no synchronisation; may return before the copy has run."""
-        from .clip_state import ClipState, clip_list, gather_rows, new_blob
         idx = clip_list(clips, self.B, "export_state")
         layout, nbytes = self._state_layout()
         if self._hop is None:
-            sel = torch.tensor(idx, dtype=torch.long).to(self.dev, non_blocking=True)
-            blob = gather_rows(self._state_parts(), sel, nbytes, layout)
+            blob = self._export_rows(idx, nbytes, layout)
         else:
             blob = new_blob(len(idx), nbytes, layout, self.dev)
             slots, wstate, ola = self._state_pointers()
@@ -862,14 +765,11 @@ class FullbandStreamingSession:
         clips go on untouched.  Ordered on torch's current stream, no synchronisation.  The weights are NOT compared: importing
         into a session of another model of the same geometry is the caller's decision.  Refusals as for
         ``StreamingSession.import_state``."""
-        from .clip_state import import_clips, scatter_rows
         layout, nbytes = self._state_layout()
         idx = import_clips(state, clips, self.B, self.dev, self._state_signature(), layout, nbytes)
         blob = state.blob.contiguous()
         if self._hop is None:
-            sel = torch.tensor(idx, dtype=torch.long).to(self.dev, non_blocking=True)
-            scatter_rows(self._state_parts(), sel, blob, layout)
-            self._clip_f0[idx] = self.frames_done - state.frames
+            self._import_rows(idx, state, blob, layout)
             return
         h = self._hop
         slots, wstate, ola = self._state_pointers()
@@ -879,11 +779,7 @@ class FullbandStreamingSession:
                                                              ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream))
         if rc:
             check(rc, "sfsn_fullband_hop_state_import")
-        # the clips' origins (include/sfsn.h): the next launch gives each the frame index it had at export -- a waveform clip's is its
-        # calls minus one (-1: its first call is still to come).  Fills behind the queued launches, as in _reset_clips
-        ages = [int(state.calls[j]) - 1 if self.waveform else int(state.frames[j]) // self.hop for j in range(len(idx))]
-        for b0, m, age in runs_by(idx, ages):  # (one fill per run of consecutive clips of one age: clips that moved together)
-            h["origin"][b0:b0 + m].fill_(self._as_i32(h["desc"].launch_index - age))
+        self._fill_origins(h["origin"], h["desc"].launch_index, idx, state)  # (include/sfsn.h: the clips' origins)
         if self.waveform:
             self._clip_c0[idx] = self._calls - state.calls
         else:
@@ -905,14 +801,8 @@ class FullbandStreamingSession:
         ``metric.compute_synops(session.spike_summary([b]), [], shared_weights=...)`` is clip b's SynOPs.  The selected clips must
         have seen the same number of frames (``ValueError`` otherwise); the session must have been opened with ``count_spikes=True``
         (``RuntimeError``)."""
-        if not self.count_spikes:
-            raise RuntimeError("open the session with count_spikes=True to count spikes")
-        idx = clip_indices(clips, self.B, "clips", duplicates="merge", empty="refuse")
-        frames = self.clip_frames()[idx]
-        if (frames != frames[0]).any():
-            raise ValueError(f"spike_summary: the selected clips have seen different numbers of frames {frames.tolist()}; select "
-                             "clips whose utterances are equally long")
-        T, nb = int(frames[0]), len(idx)
+        idx, T = self._summary_clips(clips, self.clip_frames())
+        nb = len(idx)
         eng, nl = self.eng, self.eng.spec.layers
         if self._hop is not None:  # (include/sfsn.h: layer by layer, [B][Hp / 4])
             counts = self._hop["slots"].view(nl, self.B, -1)[:, idx].sum((1, 2), dtype=torch.int64)

@@ -70,18 +70,21 @@ per-kernel sequence adds a per-clip count launch (``sfsn_spike_count_rows``) to 
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 import math
 import os
 import time
+import weakref
 from typing import Optional, Tuple
 
 import numpy as np
 import torch
 
-from ._lib import (AdvanceSrc, DfGroup, HopDesc, HOP_MAX_GROUPS, HOP_MAX_LAYERS, MAX_COUNT_TENSORS, NORM_CUMLAPLACE, PrimeSrc, RowCount,
-                   SeedDst, check)
-from .clip_select import as_i32, check_frames, check_samples, clip_indices, held_masks, part_runs, runs, runs_by, slot_order
+from ._lib import AdvanceSrc, DfGroup, HopDesc, HOP_MAX_GROUPS, HOP_MAX_LAYERS, NORM_CUMLAPLACE, PrimeSrc, SeedDst, check
+from .clip_select import check_frames, check_samples, clip_indices, held_masks, part_runs, runs, slot_order
+from .clip_state import ClipState, clip_list, hop_sections, import_clips, layout_of, new_blob
 from .engine import Engine, NormStats, SpikeSummary, _ptr
+from .session_common import SessionCommon, row_count_jobs
 
 
 OFFLINE_NORM_MESSAGE = ("the frozen front-end's offline normalisation (model_low_freq.py:147-169, 205-218) divides by statistics of the "
@@ -97,7 +100,7 @@ def _raw_stream(device_index: int) -> int:
         return torch.cuda.current_stream(device_index).cuda_stream
 
 
-class StreamingSession:
+class StreamingSession(SessionCommon):
     """``step(frames [B, F, hop] complex64) -> (enh_stft [B, S, F, hop], enh_mag [B, S, F, hop])`` with state carried."""
 
     def __init__(self, engine: Engine, batch: int = 1, hop: int = 1, graph: bool = True, rows_per_wg=None, owner=None,
@@ -106,7 +109,6 @@ class StreamingSession:
         spec = engine.spec
         # the module the engine was packed from: reset() checks that its parameters have not changed since (the session's
         # captured graph holds pointers to THIS engine's packed weights)
-        import weakref
         self._owner = weakref.ref(owner) if owner is not None else None
         if batch < 1 or hop < 1:
             raise ValueError("batch and hop must be positive")
@@ -194,13 +196,7 @@ class StreamingSession:
             self._rows = torch.zeros((spec.fb_layers + ng * spec.sb_layers, B), dtype=torch.int64, device=dev)
             tens = [(self.fb["s8"][l][0], 1) for l in range(spec.fb_layers)] + \
                    [(self.sb["s8"][l][g], spec.units(g)) for g in range(ng) for l in range(spec.sb_layers)]
-            self._row_jobs = []
-            for i0 in range(0, len(tens), MAX_COUNT_TENSORS):
-                arr = (RowCount * len(tens[i0:i0 + MAX_COUNT_TENSORS]))()
-                for j, (t, rpc) in enumerate(tens[i0:i0 + MAX_COUNT_TENSORS]):
-                    arr[j].spikes_i8, arr[j].T, arr[j].R, arr[j].HP, arr[j].rows_per_clip = _ptr(t), t.shape[0], t.shape[1], t.shape[2], rpc
-                    arr[j].counts = _ptr(self._rows[i0 + j])
-                self._row_jobs.append(arr)
+            self._row_jobs = row_count_jobs(tens, self._rows)
         if self._hop is None and graph:
             self._capture()
 
@@ -399,7 +395,7 @@ class StreamingSession:
         words of the clips that sit this hop out (clip_select.held_masks); a part with a held clip is launched through
         sfsn_stream_hop_held (still one launch; a part held as a whole is launched too: every part carries the same launch index),
         a part without one through sfsn_stream_hop."""
-        idx = self._dev_index
+        idx, lib = self._dev_index, self.eng.lib
         st = ctypes.c_void_p(_raw_stream(idx))
         same = torch.cuda.current_device() == idx  # the C ABI launches on the calling thread's current device
         for pi, part in enumerate(self._hop["parts"]):
@@ -411,28 +407,20 @@ class StreamingSession:
             if frame_index is not None:
                 d.frame_index = frame_index
             if held is not None and any(held[pi]):
-                bits = (ctypes.c_uint64 * len(held[pi]))(*held[pi])
-                if same:
-                    rc = self.eng.lib.sfsn_stream_hop_held(part["ref"], bits, st)
-                else:
-                    with torch.cuda.device(self.dev):
-                        rc = self.eng.lib.sfsn_stream_hop_held(part["ref"], bits, st)
-                if rc:
-                    check(rc, "sfsn_stream_hop_held")
+                name, fn, args = "sfsn_stream_hop_held", lib.sfsn_stream_hop_held, (part["ref"], (ctypes.c_uint64 * len(held[pi]))(*held[pi]), st)
             else:
-                if same:
-                    rc = self.eng.lib.sfsn_stream_hop(part["ref"], st)
-                else:
-                    with torch.cuda.device(self.dev):
-                        rc = self.eng.lib.sfsn_stream_hop(part["ref"], st)
-                if rc:
-                    check(rc, "sfsn_stream_hop")
+                name, fn, args = "sfsn_stream_hop", lib.sfsn_stream_hop, (part["ref"], st)
+            if same:
+                rc = fn(*args)
+            else:
+                with torch.cuda.device(self.dev):
+                    rc = fn(*args)
+            if rc:
+                check(rc, name)
             d.launch_index += 1
         self.frames_done += self.hop
         if self.frames_done % 256 < self.hop:  # every ~256 frames the error words follow the launches into pinned memory
-            for part in self._hop["parts"]:
-                part["err"].copy_(part["scratch"][:1], non_blocking=True)
-                part["err_pending"] = True
+            self._error_words_follow(self._hop["parts"])
 
     # -----------------------------------------------------------------------------------------------------------------
     def reset(self, clips=None) -> None:
@@ -448,10 +436,7 @@ class StreamingSession:
         if clips is not None:
             self._reset_clips(clips)
             return
-        owner = self._owner() if self._owner is not None else None
-        if owner is not None and owner.engine() is not self.eng:
-            raise RuntimeError("the module's parameters (or device) changed after this streaming session was created: its packed "
-                               "weights are stale -- create a new session with module.streaming(...)")
+        self._check_owner()
         for d in (self.fb, self.sb):
             for layer in d["states"]:
                 for h, c in layer:
@@ -503,8 +488,6 @@ class StreamingSession:
             else:
                 mine.index_copy_(-1, sel, new)
 
-    _as_i32 = staticmethod(as_i32)  # a launch index (uint32) as the int32 a fill writes
-
     def _refuse_resident(self, what: str) -> None:
         if self.resident:
             raise NotImplementedError(f"{what}: not on a resident session (resident=True): its launch holds the state while it runs")
@@ -526,13 +509,6 @@ class StreamingSession:
         # (waveform: no clip is older than the session's call count, so step_wave's zeros for the first three calls stay right, and
         #  from then on the launch mutes each clip by its own frame index)
         return active, held, words
-
-    def _held_bookkeeping(self, held) -> None:
-        """After a hop that held ``held``: their utterances began one hop (waveform: one call) later, so that ``clip_frames`` /
-        ``clip_calls`` stay what they were."""
-        self._clip_f0[held] += self.hop
-        if self.waveform:
-            self._clip_c0[held] += 1
 
     def _first_wave_call(self, src: torch.Tensor, hold) -> None:
         """A waveform session's first call launches nothing: the samples of the clips that make it enter the STFT state (``src``:
@@ -933,7 +909,6 @@ class StreamingSession:
         cached = getattr(self, "_signature", None)
         if cached is not None:
             return cached
-        import dataclasses
         sig = [("model", "spiking_fullsubnet"), ("tier", "one_launch" if self._hop is not None else "per_kernel"), ("hop", self.hop),
                ("waveform", self.waveform), ("count_spikes", self.count_spikes), ("given_stats", self._stats is not None)]
         sig += [(k, tuple(v) if isinstance(v, list) else v) for k, v in dataclasses.asdict(self.eng.spec).items()
@@ -955,15 +930,7 @@ class StreamingSession:
             parts.append(("rows", self._rows.t()))
         return parts
 
-    def _state_layout(self):
-        """((section, start, stop), ...), bytes of one clip's blob in this session's tier (clip_state.py); fixed at construction."""
-        cached = getattr(self, "_layout", None)
-        if cached is None:
-            cached = self._layout = self._make_state_layout()
-        return cached
-
     def _make_state_layout(self):
-        from .clip_state import hop_sections, layout_of
         if self._hop is None:
             return layout_of([(name, t.shape[1] * t.element_size()) for name, t in self._state_parts()])
         spec, eng, d = self.eng.spec, self.eng, self._hop["desc"]
@@ -989,13 +956,11 @@ class StreamingSession:
         stream-ordered copies.  The session is not changed: the clips go on here as well unless the caller resets them.  Ordered on
         torch's current stream with no synchronisation, like ``reset(clips=...)``: the state is that behind every step queued so
         far, and the call may return before the copy has run.  Not on resident sessions (``NotImplementedError``)."""
-        from .clip_state import ClipState, clip_list, gather_rows, new_blob
         self._refuse_resident("export_state")
         idx = clip_list(clips, self.B, "export_state")
         layout, nbytes = self._state_layout()
         if self._hop is None:
-            sel = torch.tensor(idx, dtype=torch.long).to(self.dev, non_blocking=True)
-            blob = gather_rows(self._state_parts(), sel, nbytes, layout)
+            blob = self._export_rows(idx, nbytes, layout)
         else:
             blob = new_blob(len(idx), nbytes, layout, self.dev)
             st = ctypes.c_void_p(_raw_stream(self._dev_index))
@@ -1022,7 +987,6 @@ class StreamingSession:
         ``ValueError``: a signature mismatch (named), duplicate indices; ``IndexError``: an index out of range; ``TypeError``: wrong
         types; ``RuntimeError``: a state on another device (``state.to(...)`` first), a row count other than ``len(clips)``;
         ``NotImplementedError``: a resident session."""
-        from .clip_state import import_clips, scatter_rows
         self._refuse_resident("import_state")
         layout, nbytes = self._state_layout()
         idx = import_clips(state, clips, self.B, self.dev, self._state_signature(), layout, nbytes)
@@ -1030,9 +994,7 @@ class StreamingSession:
         if self._stats is not None:
             self.set_norm_stats(NormStats(*state.stats), clips=idx)
         if self._hop is None:
-            sel = torch.tensor(idx, dtype=torch.long).to(self.dev, non_blocking=True)
-            scatter_rows(self._state_parts(), sel, blob, layout)
-            self._clip_f0[idx] = self.frames_done - state.frames
+            self._import_rows(idx, state, blob, layout)
             return
         self._first_call_made(idx)
         st = ctypes.c_void_p(_raw_stream(self._dev_index))
@@ -1042,11 +1004,7 @@ class StreamingSession:
                 rc = self.eng.lib.sfsn_hop_state_import(part["ref"], arr, len(local), ctypes.c_void_p(blob.data_ptr()), j0, st)
             if rc:
                 check(rc, "sfsn_hop_state_import")
-            # the clips' origins (include/sfsn.h): the next launch gives each the frame index it had at export.  Fills behind the
-            # queued launches, as in _reset_clips
-            ages = [int(state.calls[j0 + i]) - 1 if self.waveform else int(state.frames[j0 + i]) // self.hop for i in range(len(local))]
-            for b0, m, age in runs_by(local, ages):  # (one fill per run of consecutive clips of one age: clips that moved together)
-                part["origin"][b0:b0 + m].fill_(self._as_i32(part["desc"].launch_index - age))
+            self._fill_origins(part["origin"], part["desc"].launch_index, local, state, j0)  # (include/sfsn.h: the clips' origins)
             part["desc"].clip_start = part["origin"].data_ptr()
         if self.waveform:
             self._clip_c0[idx] = self._wave_calls - state.calls
@@ -1079,14 +1037,8 @@ class StreamingSession:
         ``metric.compute_synops(*session.spike_summary([b]), shared_weights=...)`` is clip b's SynOPs.  The selected clips must
         have seen the same number of frames (``ValueError`` otherwise); the session must have been opened with
         ``count_spikes=True`` (``RuntimeError``)."""
-        if not self.count_spikes:
-            raise RuntimeError("open the session with count_spikes=True to count spikes")
-        idx = clip_indices(clips, self.B, "clips", duplicates="merge", empty="refuse")
-        frames = self.clip_frames[idx]
-        if (frames != frames[0]).any():
-            raise ValueError(f"spike_summary: the selected clips have seen different numbers of frames {frames.tolist()}; select "
-                             "clips whose utterances are equally long")
-        T, nb = int(frames[0]), len(idx)
+        idx, T = self._summary_clips(clips, self.clip_frames)
+        nb = len(idx)
         spec, eng = self.eng.spec, self.eng
         ng, nl_fb, nl_sb = spec.n_groups, spec.fb_layers, spec.sb_layers
         if self._hop is None:
@@ -1150,13 +1102,7 @@ class StreamingSession:
         B, F, D, hop, Th, S, ng = self.B, self.F, self.D, self.hop, self.Th, spec.num_spks, spec.n_groups
         st = ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
         ri = torch.view_as_real(self.hist)
-        if D + hop <= 16:  # history shift + append in one launch
-            check(L.sfsn_hist_shift(_ptr(ri), _ptr(torch.view_as_real(self.inp)), B * F, D, hop, st), "sfsn_hist_shift")
-        else:
-            if D > 0:
-                self._tmp[:, :, :D].copy_(self.hist[:, :, hop:hop + D])
-                self.hist[:, :, :D].copy_(self._tmp[:, :, :D])
-            self.hist[:, :, D:].copy_(self.inp)
+        self._shift_history(ri, st)
         # default: the engine's full-band setting, 16 rows per workgroup for the sub-band stack -- few rows per hop anyway, and
         # that geometry lets layers >= 1 take their input product inside the scan (three launches less per hop)
         rpw_fb, rpw_sb = (eng.rows_per_wg[0], 16) if self.rows_per_wg is None else self.rows_per_wg
@@ -1191,20 +1137,6 @@ class StreamingSession:
             for arr in self._row_jobs:
                 check(L.sfsn_spike_count_rows(arr, len(arr), D, hop, st), "sfsn_spike_count_rows")
 
-    def _capture(self) -> None:
-        side = torch.cuda.Stream(device=self.dev)
-        side.wait_stream(torch.cuda.current_stream(self.dev))
-        with torch.cuda.stream(side):
-            for _ in range(2):  # module loading, function attributes and allocator warm-up happen outside the capture
-                self._enqueue()
-        torch.cuda.current_stream(self.dev).wait_stream(side)
-        torch.cuda.synchronize(self.dev)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self._enqueue()
-        self._graph = g
-        self.reset()
-
     def step(self, frames: torch.Tensor, copy: bool = True, clips=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """``frames``: complex64 [B, F, hop] on the device.  Returns the enhanced frames and their magnitudes; with
         ``copy=False`` the returned tensors are views of the session's buffers, valid until the next ``step``.
@@ -1237,23 +1169,15 @@ class StreamingSession:
         e, m = self.enh[..., self.D:], self.enh_mag[..., self.D:]
         if hold is not None and not hold[0]:
             return torch.zeros_like(e), torch.zeros_like(m)
-        if hold is not None:
-            # the held clips' rows of everything a step reads before it writes (export_state's sections) are put aside and put back
-            # behind the replay: stream-ordered row copies, the ones export_state / import_state of this tier make
-            sel = torch.tensor(hold[1], dtype=torch.long).to(self.dev, non_blocking=True)
-            parts = self._state_parts()
-            saved = [t.index_select(0, sel) for _, t in parts]
+        saved = None if hold is None else self._save_held(hold[1])  # (put back behind the replay)
         self.inp.copy_(frames)
         if self._graph is not None:
             self._graph.replay()
         else:
             self._enqueue()
         self.frames_done += self.hop
-        if hold is not None:
-            for (_, t), rows in zip(parts, saved):
-                t.index_copy_(0, sel, rows)
-            e.index_fill_(0, sel, 0)
-            m.index_fill_(0, sel, 0)
+        if saved is not None:
+            self._restore_held(saved, (e, m))
             self._held_bookkeeping(hold[1])
         return (e.clone(), m.clone()) if copy else (e, m)
 

@@ -473,3 +473,30 @@ def test_what_a_tick_refuses():
     for sess in (ws, hs):
         sess.check_errors()
     assert "clips" not in inspect.signature(ws.step).parameters  # (tests/test_stream_hold.py pins it)
+
+
+# ---- 9. step and tick share one body: the refusals' order, and a tick of every clip IS the step -------------------------------------
+@pytest.mark.parametrize("mode", ["one_launch", "eager"])
+def test_the_clip_list_is_refused_first_and_a_tick_of_every_clip_is_the_step(mode):
+    m = model(**TINY)
+    X = _spectrum(B, 257, 4, 131)
+    stepped, ticked = session(m, B, mode), session(m, B, mode)
+
+    def feed(j):
+        return X[..., j:j + 1].contiguous()
+
+    def marks(s):
+        return dict(s.launches), (s._hop["desc"].launch_index if s.one_launch else None), s.frames_done
+
+    for j in range(4):
+        if j == 2:  # a wrong dtype AND an index out of range: the clip list's refusal wins, and nothing was launched or counted
+            before = marks(ticked)
+            with pytest.raises(ValueError, match="clip index 3 out of range for a session of 3 clips"):
+                ticked.tick(feed(j).to(torch.complex128), [0, 3])
+            assert marks(ticked) == before and before[2] == 2
+        assert same_out(stepped.step(feed(j)), ticked.tick(feed(j), range(B))), j
+    for s in (stepped, ticked):
+        s.check_errors()
+    assert torch.equal(stepped.export_state().blob, ticked.export_state().blob)
+    assert stepped.launches == ticked.launches and sum(stepped.launches.values()) >= 4
+    assert stepped.clip_frames().tolist() == ticked.clip_frames().tolist() == [4] * B
