@@ -810,6 +810,51 @@ int sfsn_hop_seed(const sfsn_hop_desc* desc /* host */, const int* clips /* host
 int sfsn_hop_advance(const sfsn_hop_desc* desc /* host */, const int* clips /* host */, int n_clips, const sfsn_advance_src* src /* host */,
                      void* stream);
 
+/* sfsn_hop_advance with a backlog of ITS OWN LENGTH per clip (csrc/sfsn_prime.hip): the offline kernels ran ONE padded forward of Nmax
+ * new frames behind lead = T - Nmax >= D frames of history (a ragged batch, the padding zeroed), clip b0 + i has N_b = frames[b0 + i]
+ * of them (device int32 [Bp], each a multiple of hop with hop <= N_b <= Nmax: the CALLER's check -- the launch holds a value outside
+ * [1, Nmax] inside that range, so that no index leaves the tensors, and promises nothing else about such a clip).  For clips[i], with
+ * k = desc->launch_index:
+ *   layer.h[k & 1] <- row N_b - 1 of spikes_i8; layer.c <- row N_b - 1 of `membrane`, the post-BatchNorm membrane of every frame
+ *                     (sfsn_scan_segment.membrane: the value that becomes c_state behind the last frame of a scan -- c_state itself is
+ *                     the membrane after the last PADDED frame and is not read);
+ *   hist_ri        <- the D frames that end with frame lead + N_b - 1 of stft_ri's row, [history | new]: N_b < D keeps the tail of the old
+ *                     history;
+ *   spike_slots    <- ADDED to over frames [0, N_b) only (a clip whose origin equals k: replaced);
+ *   wave_state     <- the 512 samples that end at sample 384 + 128 N_b of the clip's row of wave_ctx ([384 of context | new samples],
+ *                     the row sfsn_hop_seed began); ola_state <- continued in the hop's order through frame N_b - 1 only;
+ *                     wave_out[b0 + i][s][128 j ..] <- block j < N_b as sfsn_hop_advance writes it, zeros for N_b <= j < Nmax.
+ * The caller then moves clip_start[clips[i]] back by ITS OWN N_b / hop with a stream-ordered device operation behind the queued
+ * launches.  Everything else -- the untouched clips and scratch, fresh clips, clip_start == NULL, the exactness reservation (layer 0's
+ * membranes are the offline kernels') -- is sfsn_hop_advance's.  A descriptor with SFSN_NORM_CUMLAPLACE is refused
+ * (SFSN_EUNSUPPORTED): the sub-band running sums after a clip's own last frame are not available from a padded forward; make one
+ * sfsn_hop_advance call per length.
+ * SFSN_EINVAL, before the launch: as sfsn_hop_advance with Nmax in the place of N (Nmax % hop != 0, Nmax < hop, T < D + Nmax), a missing
+ * or misaligned pointer (membrane: 16 bytes; stft_ri, enh_ri, wave_out: 8; frames, spikes_i8, wave_ctx: 4), wave_stride < 384 +
+ * 128 Nmax.  SFSN_EUNSUPPORTED: as sfsn_hop_advance, and the cumulative norm.  (Added without an ABI bump: a new function and new
+ * structs only.) */
+typedef struct sfsn_ragged_layer {
+    const int8_t* spikes_i8; /* [Nmax][Bp * n_units][pad64(H)] the new frames' int8 spikes (bytes 0 / 1)  */
+    const float* membrane;   /* [Nmax][Bp * n_units][H] the new frames' post-BatchNorm membranes          */
+} sfsn_ragged_layer;
+typedef struct sfsn_ragged_seq {
+    sfsn_ragged_layer layer[SFSN_HOP_MAX_LAYERS];
+} sfsn_ragged_seq;
+typedef struct sfsn_advance_ragged_src {
+    int Bp, Nmax, b0;
+    int T;                   /* frames per row of stft_ri / enh_ri; the Nmax (padded) new frames are the last ones */
+    int wave_stride;         /* waveform mode: floats per row of wave_ctx (>= 384 + 128 Nmax)                      */
+    const int* frames;       /* DEVICE int32 [Bp]: N_b, the new frames clip b0 + i really has                      */
+    const float* stft_ri;    /* [Bp][F][T][2] [history | new | padding] (NULL if D == 0)                           */
+    const float* enh_ri;     /* waveform mode: [Bp][S][F][T][2] the enhanced frames                                */
+    const float* wave_ctx;   /* waveform mode: [Bp][wave_stride] 384 samples of context, then the new samples      */
+    float* wave_out;         /* waveform mode: [Bp][S][128 * Nmax] out                                             */
+    sfsn_ragged_seq fb;
+    sfsn_ragged_seq sb[SFSN_HOP_MAX_GROUPS];
+} sfsn_advance_ragged_src;
+int sfsn_hop_advance_ragged(const sfsn_hop_desc* desc /* host */, const int* clips /* host */, int n_clips,
+                            const sfsn_advance_ragged_src* src /* host */, void* stream);
+
 /* Moving a clip (csrc/sfsn_state.hip): the carried state of the listed clips out into a self-contained blob per clip, and from such a
  * blob into the listed clips of this or another descriptor of the same geometry -- ONE launch each way, ordered on `stream` like any
  * launch, plain stores, nothing waits inside it.  The state is COPIED, not recomputed, so a moved clip continues bit for bit, layer 0

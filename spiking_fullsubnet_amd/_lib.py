@@ -138,6 +138,19 @@ class AdvanceSrc(ctypes.Structure):  # sfsn_advance_src
                 ("fb", PrimeSeq), ("sb", PrimeSeq * HOP_MAX_GROUPS)]
 
 
+class RaggedLayer(ctypes.Structure):  # sfsn_ragged_layer
+    _fields_ = [("spikes_i8", _P), ("membrane", _P)]
+
+
+class RaggedSeq(ctypes.Structure):  # sfsn_ragged_seq
+    _fields_ = [("layer", RaggedLayer * HOP_MAX_LAYERS)]
+
+
+class AdvanceRaggedSrc(ctypes.Structure):  # sfsn_advance_ragged_src
+    _fields_ = [("Bp", _I), ("Nmax", _I), ("b0", _I), ("T", _I), ("wave_stride", _I), ("frames", _P), ("stft_ri", _P), ("enh_ri", _P),
+                ("wave_ctx", _P), ("wave_out", _P), ("fb", RaggedSeq), ("sb", RaggedSeq * HOP_MAX_GROUPS)]
+
+
 FULLBAND_HOP_MAX_LAYERS = 4
 
 
@@ -330,6 +343,8 @@ def lib() -> ctypes.CDLL:
     L.sfsn_hop_seed.argtypes = [ctypes.POINTER(HopDesc), ctypes.POINTER(_I), _I, ctypes.POINTER(SeedDst), _P]
     L.sfsn_hop_advance.restype = _I  # desc, clips, n_clips, src, stream
     L.sfsn_hop_advance.argtypes = [ctypes.POINTER(HopDesc), ctypes.POINTER(_I), _I, ctypes.POINTER(AdvanceSrc), _P]
+    L.sfsn_hop_advance_ragged.restype = _I  # desc, clips, n_clips, src, stream
+    L.sfsn_hop_advance_ragged.argtypes = [ctypes.POINTER(HopDesc), ctypes.POINTER(_I), _I, ctypes.POINTER(AdvanceRaggedSrc), _P]
     L.sfsn_hop_state_bytes.restype = ctypes.c_size_t  # per clip; 0: a descriptor the hop refuses (host only)
     L.sfsn_hop_state_bytes.argtypes = [ctypes.POINTER(HopDesc)]
     L.sfsn_hop_state_export.restype = _I  # desc, clips, n_clips, blob, stream
@@ -440,7 +455,7 @@ EXPORTS = ("sfsn_abi_version", "sfsn_source_hash", "sfsn_strerror", "sfsn_device
            "sfsn_hop_state_bytes", "sfsn_hop_state_export", "sfsn_hop_state_import", "sfsn_fullband_hop_state_bytes",
            "sfsn_fullband_hop_state_export", "sfsn_fullband_hop_state_import", "sfsn_hop_seed", "sfsn_hop_advance",
            "sfsn_fullband_hop_seed", "sfsn_fullband_hop_advance", "sfsn_stream_hop_held",
-           "sfsn_fullband_stream_hop_held", "sfsn_fullband_stream_hop_wave_held")
+           "sfsn_fullband_stream_hop_held", "sfsn_fullband_stream_hop_wave_held", "sfsn_hop_advance_ragged")
 
 
 def check(rc: int, what: str = "") -> None:

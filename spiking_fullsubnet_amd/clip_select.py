@@ -135,6 +135,36 @@ def check_frames(what: str, stft: torch.Tensor, n: int, F: int, dev, hop: int) -
     return N
 
 
+def clip_lengths(what: str, lengths, idx: Sequence[int], unit: int, unit_text: str, most: int, noun: str) -> List[int]:
+    """The per-clip lengths of a ragged backlog (``advance_ragged``: ``noun`` = "frames", ``unit`` = the session's hop;
+    ``advance_wave_ragged``: "samples", 128): a sequence or a CPU integer tensor with one value per listed clip ``idx[i]``, each a
+    positive multiple of ``unit`` (``unit_text``: how the message names it) and at most ``most``, what the tensor's rows hold.
+    ``ValueError`` naming the clip, in ``check_frames`` / ``check_samples``' wording for the same fault; returns the list of ints."""
+    if torch.is_tensor(lengths):
+        if lengths.device.type != "cpu":
+            raise ValueError(f"{what}: the lengths are a sequence or a CPU integer tensor (a device tensor would cost a "
+                             f"synchronisation), got a tensor on {lengths.device}")
+        if lengths.dim() != 1 or lengths.dtype.is_floating_point or lengths.dtype.is_complex or lengths.dtype == torch.bool:
+            raise ValueError(f"{what}: the lengths are a 1-D integer tensor, got {lengths.dtype} {tuple(lengths.shape)}")
+        lengths = lengths.tolist()
+    elif isinstance(lengths, (str, bytes)) or not hasattr(lengths, "__iter__"):
+        raise ValueError(f"{what}: the lengths are a sequence or a CPU integer tensor with one value per clip")
+    vals = list(lengths)
+    if len(vals) != len(idx):
+        raise ValueError(f"{what}: {len(vals)} lengths for {len(idx)} clips")
+    out = []
+    for b, v in zip(idx, vals):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{what}: clip {b}: the length {v!r} is not an integer")
+        v = int(v)
+        if v < unit or v % unit != 0:
+            raise ValueError(f"{what}: clip {b}: {v} {noun} is not a positive multiple of {unit_text}")
+        if v > most:
+            raise ValueError(f"{what}: clip {b}: {v} {noun}, the tensor's rows hold {most}")
+        out.append(v)
+    return out
+
+
 def check_samples(what: str, samples: torch.Tensor, n: int, dev) -> int:
     """``samples``: recorded samples of ``n`` clips, float32 [n, Ls] on ``dev`` with ``Ls`` a positive multiple of 128; returns Ls."""
     if samples.device != dev or samples.dtype != torch.float32:

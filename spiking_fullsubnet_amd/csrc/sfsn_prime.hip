@@ -1,6 +1,6 @@
 // sfsn_prime.hip -- the way between a streaming session (the one-launch hops of sfsn_hop.hip / sfsn_fullband_hop.hip) and the offline
 // kernels, one launch each way, for the listed clips of the session only (gfx950 only; include/sfsn.h: sfsn_hop_prime, sfsn_hop_seed,
-// sfsn_hop_advance, sfsn_fullband_hop_seed, sfsn_fullband_hop_advance).
+// sfsn_hop_advance, sfsn_hop_advance_ragged, sfsn_fullband_hop_seed, sfsn_fullband_hop_advance).
 //
 // A session that has streamed some frames of a clip holds: every layer's last spikes (double-buffered by launch parity) and membrane,
 // the running sums of the cumulative norm, the last D noisy frames, the spike counts per lane slot and, in waveform mode, the last
@@ -285,6 +285,186 @@ __global__ __launch_bounds__(PRIME_THREADS) void hop_take_kernel(const TakeParam
         take_hist<CONTINUE>(p, item);
     else
         take_wave(p, item);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The continuing TAKE launch with a length of its own per clip (sfsn_hop_advance_ragged): the offline kernels ran a padded batch of
+// Nmax new frames behind `lead` = T - Nmax frames of history, clip b0 + i has N_b = frames[b0 + i] of them and everything the launch
+// takes ends at the clip's own last frame.  The scans leave c_state after the last PADDED frame only, so the membranes come from the
+// per-frame membrane tap (sfsn_scan_segment.membrane: the post-BatchNorm value that becomes c_state), row N_b - 1.  The other roles
+// are hop_take_kernel<true>'s with N_b in the place of N; the cumulative norm is refused on the host (its running sums after a
+// clip's own last frame exist nowhere).  A kernel of its own: hop_take_kernel's two instantiations keep their code.
+struct TakeRaggedLayerDev {
+    int8_t* h;          // the half of the double buffer the next launch reads
+    float* c;
+    unsigned* slots;    // this layer's [R][H / 4] slots, or NULL
+    const int8_t* s8;   // [Nmax][Bp * units][HP]
+    const float* mem;   // [Nmax][Bp * units][H]
+};
+struct TakeRaggedSeqDev {
+    TakeRaggedLayerDev layer[SFSN_HOP_MAX_LAYERS];
+    int H, HP, units;
+};
+struct TakeRaggedParams {
+    TakeRaggedSeqDev seq[PRIME_MAX_SEQS];
+    SecDev sec[PRIME_MAX_SECS];
+    unsigned short clips[PRIME_MAX_CLIPS];
+    int nsec, n_clips, b0, Bp, Nmax, T;
+    int F, S, D, fcov, frame_index, ctx_stride;
+    unsigned k;
+    const int* frames;  // [Bp]
+    const float* stft;  // [Bp][F][T][2], the Nmax frames last
+    const float* enh;   // [Bp][S][F][T][2]
+    const float* ctx;   // [Bp][ctx_stride]: 384 samples of context, then the new samples
+    float* hist;
+    float* wave_state;
+    float* ola_state;
+    const float* window;
+    const unsigned* clip_start;
+    float* wave_out;    // [Bp][S][128 * Nmax]
+};
+static_assert(sizeof(TakeRaggedParams) <= 4096, "TakeRaggedParams travels as a kernel argument");
+
+// the clip's own frame count, held inside [1, Nmax] whatever the array says: no index below leaves the caller's tensors
+__device__ __forceinline__ int ragged_frames(const TakeRaggedParams& p, int i) {
+    const int n = p.frames[p.b0 + i];
+    return n < 1 ? 1 : (n > p.Nmax ? p.Nmax : n);
+}
+
+__device__ __forceinline__ void take_rows_ragged(const TakeRaggedParams& p, const SecDev& sd, int item) {
+    const TakeRaggedSeqDev& sq = p.seq[sd.seq];
+    const TakeRaggedLayerDev& L = sq.layer[sd.layer];
+    const int W = sq.H >> 2;
+    const int j = item % W, rr = item / W;
+    const int k = rr % sq.units, i = rr / sq.units;
+    const int N = ragged_frames(p, i);
+    const size_t Rs = (size_t)p.Bp * sq.units;
+    const size_t row_s = (size_t)(p.b0 + i) * sq.units + k, row_d = (size_t)p.clips[i] * sq.units + k;
+    const int8_t* sp = L.s8 + row_s * sq.HP + 4 * j;  // my word of the first new frame; a frame further every Rs * HP bytes
+    const size_t fs = Rs * sq.HP;
+    const unsigned last = *reinterpret_cast<const unsigned*>(sp + (size_t)(N - 1) * fs) & 0x01010101u;
+    const float4 c = *reinterpret_cast<const float4*>(L.mem + ((size_t)(N - 1) * Rs + row_s) * sq.H + 4 * j);
+    *reinterpret_cast<unsigned*>(L.h + row_d * sq.HP + 4 * j) = last;
+    *reinterpret_cast<float4*>(L.c + row_d * sq.H + 4 * j) = c;
+    if (!L.slots) return;
+    unsigned nspk = 0u;  // (a clip that begins here: the hop reads its slot as zero)
+    if (!clip_fresh(p.clip_start, p.k, 0u, p.clips[i])) nspk = L.slots[row_d * W + j];
+    for (int t0 = 0; t0 < N; t0 += 8) {  // eight independent loads in flight
+        unsigned w[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) w[u] = *reinterpret_cast<const unsigned*>(sp + (size_t)(t0 + u < N ? t0 + u : N - 1) * fs);
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+            if (t0 + u < N) nspk += __builtin_popcount(w[u] & 0x01010101u);
+    }
+    L.slots[row_d * W + j] = nspk;
+}
+
+// the D frames that end with the clip's own last one: frames lead + N_b - D .. lead + N_b - 1 of its row (lead >= D: N_b < D keeps the
+// tail of the old history)
+__device__ __forceinline__ void take_hist_ragged(const TakeRaggedParams& p, int item) {
+    const int D = p.D, T = p.T;
+    const int d = item % D, r = item / D;
+    const int f = r % p.fcov, i = r / p.fcov;
+    const int t = T - p.Nmax + ragged_frames(p, i) - D + d;
+    const float2 v = *reinterpret_cast<const float2*>(p.stft + (((size_t)(p.b0 + i) * p.F + f) * T + t) * 2);
+    *reinterpret_cast<float2*>(p.hist + (((size_t)p.clips[i] * p.F + f) * D + d) * 2) = v;
+}
+
+// the 512 samples that end with the clip's own last one: sample 384 + 128 N_b of its context row
+__device__ __forceinline__ void take_wave_ragged(const TakeRaggedParams& p, int item) {
+    const int n = item & (FFT_NFFT - 1), i = item >> 9;
+    const int end = SEED_CTX + 128 * ragged_frames(p, i);
+    p.wave_state[(size_t)p.clips[i] * FFT_NFFT + n] = p.ctx[(size_t)(p.b0 + i) * p.ctx_stride + end - FFT_NFFT + n];
+}
+
+// take_ola<true>'s recurrence over the clip's own N_b frames; the blocks behind them are written as zeros
+__device__ __forceinline__ void take_ola_ragged(const TakeRaggedParams& p, int blk, char* smem) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    float2* unit = reinterpret_cast<float2*>(smem);
+    float2(*fbuf)[FFT_N] = reinterpret_cast<float2(*)[FFT_N]>(smem + FFT_NFFT * 8);
+    float2(*xs)[264] = reinterpret_cast<float2(*)[264]>(smem + FFT_NFFT * 8 + PRIME_WAVES * FFT_N * 8);
+    fill_unit_table(unit, tid, PRIME_THREADS);
+    __syncthreads();
+    const int pair = blk * PRIME_WAVES + wave;
+    if (pair >= p.n_clips * p.S) return;
+    const int i = pair / p.S, s = pair - i * p.S, F = p.F, T = p.T, Nmax = p.Nmax;
+    const int N = ragged_frames(p, i);
+    const int clip = p.clips[i];
+    const int first = T - Nmax;  // the first frame fed
+    // a clip that begins here carries no sums
+    const int age = p.clip_start ? (int)(p.k - p.clip_start[clip]) : p.frame_index;
+    const bool fresh = p.clip_start && age == 0;
+    const int fi0 = fresh ? 0 : age;  // the frame index of the first new frame
+    const Twiddles tw = make_twiddles<true>(unit, lane);
+    float* os = p.ola_state + ((size_t)clip * p.S + s) * FFT_NFFT;
+    float2 win[4], wk[4], ola[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int n = 2 * (lane + 64 * r);
+        win[r] = make_float2(p.window[n], p.window[n + 1]);
+        wk[r] = unit_at<true>(unit, lane + 64 * r);
+        ola[r] = make_float2(0.0f, 0.0f);
+        if (!fresh) ola[r] = *reinterpret_cast<const float2*>(os + n);
+    }
+    const float* eg = p.enh + ((size_t)(p.b0 + i) * p.S + s) * F * T * 2 + (size_t)first * 2;
+    float* wo = p.wave_out + ((size_t)(p.b0 + i) * p.S + s) * 128 * Nmax;
+    const float sc = 1.0f / (float)FFT_N;
+    for (int t = 0; t < N; ++t) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) xs[wave][lane + 64 * r] = *reinterpret_cast<const float2*>(eg + ((size_t)(lane + 64 * r) * T + t) * 2);
+        if (lane == 0) xs[wave][FFT_N] = *reinterpret_cast<const float2*>(eg + ((size_t)FFT_N * T + t) * 2);
+        __builtin_amdgcn_wave_barrier();
+        float2 v[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int k = lane + 64 * r;
+            v[r] = irfft512_presplit(xs[wave][k], xs[wave][FFT_N - k], k, wk[r]);
+        }
+        fft256<true>(v, fbuf[wave], lane, tw);
+        float2 acc[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float2 res = make_float2(v[r].x * sc * win[r].x, v[r].y * sc * win[r].y);
+            acc[r] = make_float2(ola[r].x + res.x, ola[r].y + res.y);
+        }
+        const int fi = fi0 + t;
+        float2 env = make_float2(0.0f, 0.0f);
+#pragma unroll
+        for (int q = 3; q >= 0; --q)
+            if (fi - q >= 0) {
+                env.x += win[q].x * win[q].x;
+                env.y += win[q].y * win[q].y;
+            }
+        float2 out = make_float2(env.x > 1e-11f ? acc[0].x / env.x : 0.0f, env.y > 1e-11f ? acc[0].y / env.y : 0.0f);
+        if (fi < 2) out = make_float2(0.0f, 0.0f);  // (the part torch.istft trims)
+        *reinterpret_cast<float2*>(wo + (size_t)128 * t + 2 * lane) = out;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) ola[r] = r < 3 ? acc[r + 1] : make_float2(0.0f, 0.0f);
+        __builtin_amdgcn_wave_barrier();  // (this frame's reads of xs / fbuf before the next frame's writes)
+    }
+    for (int t = N; t < Nmax; ++t) *reinterpret_cast<float2*>(wo + (size_t)128 * t + 2 * lane) = make_float2(0.0f, 0.0f);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) *reinterpret_cast<float2*>(os + 2 * (lane + 64 * r)) = ola[r];
+}
+
+__global__ __launch_bounds__(PRIME_THREADS) void hop_take_ragged_kernel(const TakeRaggedParams p) {
+    __shared__ __attribute__((aligned(16))) char smem[FFT_NFFT * 8 + PRIME_WAVES * FFT_N * 8 + PRIME_WAVES * 264 * 8];
+    const SecDev& sd = p.sec[block_section(p.sec, p.nsec)];
+    const int blk = (int)blockIdx.x - sd.blk0;
+    if (sd.kind == SEC_OLA) {
+        take_ola_ragged(p, blk, smem);
+        return;
+    }
+    const int item = blk * PRIME_THREADS + (int)threadIdx.x;
+    if (item >= sd.items) return;
+    if (sd.kind == SEC_ROWS)
+        take_rows_ragged(p, sd, item);
+    else if (sd.kind == SEC_HIST)
+        take_hist_ragged(p, item);
+    else
+        take_wave_ragged(p, item);
 }
 
 // a clip whose origin is this launch index reads as zero, as it does in the hop
@@ -608,6 +788,54 @@ extern "C" int sfsn_hop_advance(const sfsn_hop_desc* desc, const int* clips, int
     TakeSrc t = take_src(*src, desc->n_groups);
     t.T = src->T; t.wave_out = src->wave_out;
     return take_launch(v, clips, n_clips, t, true, stream);
+}
+
+extern "C" int sfsn_hop_advance_ragged(const sfsn_hop_desc* desc, const int* clips, int n_clips, const sfsn_advance_ragged_src* src, void* stream) {
+    if (!desc || !clips || !src || n_clips <= 0) return SFSN_EINVAL;
+    HopView v;
+    int rc = view_of(desc, v);
+    if (rc != SFSN_OK) return rc;
+    for (int q = 0; q < v.nseq; ++q)
+        if (v.seq[q].cumulative) return SFSN_EUNSUPPORTED;  // (no running sums after a clip's own last frame: one sfsn_hop_advance per length)
+    TakeRaggedParams p;
+    memset(&p, 0, sizeof(p));
+    rc = check_clips(v.B, clips, n_clips, p.clips);
+    if (rc != SFSN_OK) return rc;
+    const int Nmax = src->Nmax, D = v.D;
+    if (Nmax < desc->hop || Nmax % desc->hop != 0 || src->T < Nmax + D) return SFSN_EINVAL;
+    if (src->Bp < 1 || src->b0 < 0 || n_clips > src->Bp - src->b0) return SFSN_EINVAL;
+    if (bad(src->frames, 4) || (D > 0 && bad(src->stft_ri, 8))) return SFSN_EINVAL;
+    if (v.wave && (bad(src->wave_ctx, 4) || src->wave_stride < SEED_CTX + 128 * Nmax || bad(src->enh_ri, 8) || bad(src->wave_out, 8))) return SFSN_EINVAL;
+    if (!state_ok(v, true)) return SFSN_EINVAL;
+    p.n_clips = n_clips; p.b0 = src->b0; p.Bp = src->Bp; p.Nmax = Nmax; p.T = src->T;
+    p.F = v.F; p.S = v.S; p.D = D; p.fcov = v.fcov; p.frame_index = v.frame_index; p.ctx_stride = src->wave_stride; p.k = v.k;
+    p.frames = src->frames; p.stft = src->stft_ri; p.enh = src->enh_ri; p.ctx = src->wave_ctx;
+    p.hist = v.hist; p.wave_state = v.wave_state; p.ola_state = v.ola_state; p.window = v.window;
+    p.clip_start = v.clip_start; p.wave_out = src->wave_out;
+    Sections secs{p.sec};
+    size_t slot0 = 0;
+    for (int q = 0; q < v.nseq; ++q) {
+        const SeqView& s = v.seq[q];
+        const sfsn_ragged_seq& rs = q == 0 ? src->fb : src->sb[q - 1];
+        TakeRaggedSeqDev& d = p.seq[q];
+        d.H = s.H; d.HP = (s.H + 63) / 64 * 64; d.units = s.units;
+        for (int l = 0; l < s.n_layers; ++l) {
+            const sfsn_ragged_layer& o = rs.layer[l];
+            if (bad(o.spikes_i8, 4) || bad(o.membrane, 16)) return SFSN_EINVAL;
+            d.layer[l].h = s.h[l]; d.layer[l].c = s.c[l]; d.layer[l].s8 = o.spikes_i8; d.layer[l].mem = o.membrane;
+            d.layer[l].slots = v.spike_slots ? v.spike_slots + slot0 : nullptr;
+            slot0 += (size_t)v.B * s.units * (s.H / 4);
+            secs.add(SEC_ROWS, q, l, n_clips * s.units * (s.H / 4));
+        }
+    }
+    if (D > 0 && v.fcov > 0) secs.add(SEC_HIST, 0, 0, n_clips * v.fcov * D);
+    if (v.wave) {
+        secs.add(SEC_WAVE, 0, 0, n_clips * FFT_NFFT);
+        secs.add(SEC_OLA, 0, 0, n_clips * v.S, PRIME_WAVES);
+    }
+    p.nsec = secs.nsec;
+    hipLaunchKernelGGL(hop_take_ragged_kernel, dim3(secs.blk), dim3(PRIME_THREADS), 0, static_cast<hipStream_t>(stream), p);
+    return hip_ok(hipGetLastError());
 }
 
 // The same two launches for the cIRM-GSN hop.  Waveform mode (wave_state != NULL) takes every frame index from desc->clip_start.

@@ -524,6 +524,7 @@ class _Forward:
     epi_chunk: Optional[tuple] = None  # (t0, nt) of the sub-band chunk whose epilogue ran inside its scan launch (_stage_scan_l01)
     lead: int = 0            # a forward with a start (_start_buffers): history frames in front of the new ones; the stages run behind them
     frames_before: int = 0   # ... and the frames the clips had seen before (cumulative_laplace_norm's denominator)
+    l0_alone: Optional[dict] = None  # per-clip ends: {tag: [(sequence model, rows of x as [T * R] indices, ascending)]} -- _l0_as_alone
 
     def link(self, src, dst) -> None:
         """dst waits for everything enqueued on src so far (no-op on the sequential path)."""
@@ -1161,11 +1162,12 @@ class Engine:
             out.append(row)
         return out
 
-    def _start_buffers(self, n: int, N: int, lead: int, frames_before: int = 0) -> dict:
+    def _start_buffers(self, n: int, N: int, lead: int, frames_before: int = 0, per_clip_ends: bool = False) -> dict:
         """The start of a forward that continues ``n`` running clips by ``N`` frames (``forward_stft(start["stft"], _end_state=start)``),
         for the caller to fill: ``fb`` / ``sb``: ``[l][i] = (h, c)`` of layer l, sequence model i as the scans take them (fp32 0 / 1
         spikes, membranes; views of ``state_flat``, the forward's state buffer); ``cum``: the running sums per sequence model
-        (cumulative_laplace_norm, else None); ``stft``: complex64 [n, F, lead + N], ``lead`` frames of history and the new frames."""
+        (cumulative_laplace_norm, else None); ``stft``: complex64 [n, F, lead + N], ``lead`` frames of history and the new frames.
+        ``per_clip_ends``: the forward will run with ``frames`` -- N is the longest clip's count (``forward_stft``)."""
         spec, dev = self.spec, self.device
         f32 = dict(dtype=torch.float32, device=dev)
         Rs = [n * spec.units(g) for g in range(spec.n_groups)]
@@ -1176,7 +1178,7 @@ class Engine:
                     sb=self._zero_states(Rs, self.sb[0].H, spec.sb_layers, flat[n_fb:]),
                     cum=[torch.empty((R,), **f32) for R in [n] + Rs] if spec.cum_laplace else None,
                     stft=torch.empty((n, spec.n_fft // 2 + 1, lead + N), dtype=torch.complex64, device=dev),
-                    lead=lead, frames_before=frames_before)
+                    lead=lead, frames_before=frames_before, per_clip_ends=per_clip_ends)
 
     def _alloc_stack(self, seqs, Rs, T, nt_max, want_layers, want_membrane, tag, state_flat=None, counts=None):
         """Per-forward tensors of a stack of sequence models sharing (H, L): API outputs are fresh, scratch is cached."""
@@ -1328,6 +1330,10 @@ class Engine:
         on frames ``[lead, lead + N)`` of it from the start's (h, c) per layer and sequence model, its cumulative sums and
         ``frames_before``, so that the deep filter reaches back into real history; the first feature launch does not zero the state
         buffer; the results are those of the N new frames.  Without a start the launches are exactly the same as ever.
+        A start made with ``per_clip_ends=True`` (internal: ``StreamingSession.advance_ragged``) runs WITH ``frames``: clip b has
+        ``frames[b]`` of the N new frames (``1 <= frames[b] <= N``), the forward runs with the membrane tap whatever
+        ``want_membrane`` says, and ``"end_state"`` carries the per-frame membranes (``mem``) from which the caller takes each clip's
+        own end (``_end_state_of``); not for the cumulative norm, whose running sums after a clip's own last frame exist nowhere.
 
         ``frames`` -- a ragged batch (``ragged.py``): a length-B sequence of ints, clip b has ``frames[b]`` frames
         (``1 <= frames[b] <= T``; ``ValueError`` otherwise) and the rest of its row is padding.  The launches of the model are the
@@ -1344,10 +1350,19 @@ class Engine:
             raise ValueError("return_norm_stats: this model computes no utterance statistics")
         if frames is not None:
             from . import ragged
-            if _end_state:
+            per_clip = isinstance(_end_state, dict) and bool(_end_state.get("per_clip_ends"))
+            if _end_state and not per_clip:
                 raise ValueError("_end_state: not with a ragged batch (the clips end at different frames)")
-            frames = ragged.check_frames(frames, stft.shape[0] if stft.dim() == 3 else -1, stft.shape[-1],
+            if per_clip and self.spec.cum_laplace:
+                raise NotImplementedError("_end_state with per-clip ends: not with cumulative_laplace_norm (no running sums after a "
+                                          "clip's own last frame)")
+            lead = int(_end_state["lead"]) if per_clip else 0
+            frames = ragged.check_frames(frames, stft.shape[0] if stft.dim() == 3 else -1, stft.shape[-1] - lead,
                                          gaussian=self.spec.gaussian and norm_stats is None)
+            if per_clip:  # (lengths within the [history | new] rows from here on; the membrane tap: every frame's c is kept)
+                frames, frames_dev, want_membrane = [lead + n for n in frames], None, True
+        elif isinstance(_end_state, dict) and _end_state.get("per_clip_ends"):
+            raise ValueError("_end_state: a start with per-clip ends needs frames")
         with torch.cuda.device(self.device):
             self._errors.poll()
             if frames is not None and frames_dev is None:
@@ -1392,14 +1407,12 @@ class Engine:
         lead = 0 if start is None else int(start["lead"])
         if start is not None and (stft.data_ptr() != start["stft"].data_ptr() or tuple(stft.shape) != tuple(start["stft"].shape) or T <= lead):
             raise ValueError("_end_state: a start runs on its own [history | new] buffer (Engine._start_buffers)")
-        plan = plan_forward(spec, B, T - lead, pipeline, self.n_cu, want_membrane, pipeline_default=self.pipeline_default,
-                            pipeline_chunk=self.pipeline_chunk, seq_chunk=self.seq_chunk, overlap_chunks=self.overlap_chunks,
-                            overlap_fracs=self.overlap_fracs, overlap_first=self.overlap_first, rows_per_wg=self.rows_per_wg,
-                            fuse_input=self.fuse_input, stack_scan=self.stack_scan, stack_rows_per_wg=self.stack_rows_per_wg,
-                            stack_wide=self.stack_wide, stack_rows_fb_auto=self.stack_rows_fb_auto, pair_scan=self.pair_scan)
+        plan = self._plan(B, T - lead, pipeline, want_membrane)
         if lead:  # the chunks of the N new frames, behind the history
             plan = plan._replace(bounds=tuple((t0 + lead, nt) for t0, nt in plan.bounds))
         f = self._alloc_forward(stft, plan, want_layers, want_membrane, want_counts, norm_stats, frames, frames_dev, start)
+        if start is not None and frames is not None and self._l0_hop is None:
+            f.l0_alone = self._l0_alone_rows(f)
         self._open_streams(f)
         fbm, sbm, gs_sb = f.fbm, f.sbm, f.gstreams[spec.fb_layers]
         if spec.laplace and norm_stats is None:
@@ -1430,13 +1443,72 @@ class Engine:
             out["end_state"] = self._end_state_of(f, want_counts)
         return out
 
+    def _plan(self, B: int, T: int, pipeline: Optional[bool], want_membrane: bool) -> ForwardPlan:
+        """``plan_forward`` with this engine's attributes."""
+        return plan_forward(self.spec, B, T, pipeline, self.n_cu, want_membrane, pipeline_default=self.pipeline_default,
+                            pipeline_chunk=self.pipeline_chunk, seq_chunk=self.seq_chunk, overlap_chunks=self.overlap_chunks,
+                            overlap_fracs=self.overlap_fracs, overlap_first=self.overlap_first, rows_per_wg=self.rows_per_wg,
+                            fuse_input=self.fuse_input, stack_scan=self.stack_scan, stack_rows_per_wg=self.stack_rows_per_wg,
+                            stack_wide=self.stack_wide, stack_rows_fb_auto=self.stack_rows_fb_auto, pair_scan=self.pair_scan)
+
+    def _l0_alone_rows(self, f: _Forward) -> dict:
+        """A ragged batch behind a start promises each clip the bits of ITS OWN forward (``StreamingSession.advance_ragged``: the
+        single-clip ``advance`` call).  One arithmetic of the forward depends on how many rows a launch has: the layer-0 input product
+        takes its bf16-split form from 64 row-frames per chunk on and the fp32 form below (include/sfsn.h, sfsn_input_proj_f32; every
+        schedule keeps to that rule: _stack_x_groups, sfsn_features_proj).  The batch has more row-frames than any clip alone, so
+        where a clip's own forward -- ``_plan(1, N_b)``'s chunks, ``units`` rows per frame -- stays below 64 the batch's product
+        is redone for those rows in the fp32 form (``_l0_as_alone``).  Returns the rows per model and sequence model."""
+        lead = f.lead
+        alone = [self._plan(1, end - lead, None, False).bounds for end in f.frames]  # the chunks of each clip's own forward
+        out = {}
+        for m in (f.fbm, f.sbm):
+            per_seq = []
+            for i, x in enumerate(m.xs):
+                R = x.shape[1]
+                u = R // len(f.frames)
+                rows = []
+                for b, bounds in enumerate(alone):
+                    for t0, nt in bounds:
+                        if nt * u < 64:
+                            rows.append(((lead + np.arange(t0, t0 + nt))[:, None] * R + (b * u + np.arange(u))[None, :]).ravel())
+                if rows:
+                    per_seq.append((i, np.sort(np.concatenate(rows))))
+            out[m.tag] = per_seq
+        return out
+
+    def _l0_as_alone(self, f: _Forward, m: _ModelRun, t0: int, nt: int, stream, st) -> None:
+        """Behind a chunk's layer-0 input product: the rows of ``f.l0_alone`` inside the chunk again, in calls below 64 rows (the fp32
+        form; a row's result depends on nothing but the row), into the chunk-local input term."""
+        for i, rows in f.l0_alone.get(m.tag, ()):
+            x, z, seq = m.xs[i], m.d["zin"][0][i], m.seqs[i]
+            R, I, cell = x.shape[1], seq.I, seq.cells[0]
+            mine = rows[(rows >= t0 * R) & (rows < (t0 + nt) * R)]
+            if not len(mine):
+                continue
+            G, H = cell.G, seq.H
+            P = ctypes.c_void_p
+            with torch.cuda.stream(stream):
+                idx = torch.from_numpy(mine.astype(np.int64)).pin_memory().to(self.device, non_blocking=True)
+                xr = x.view(-1, I).index_select(0, idx)
+                zr = torch.empty((len(mine), G * H), dtype=torch.float32, device=self.device)
+                for r0 in range(0, len(mine), 63):
+                    for g in range(G):
+                        check(self.lib.sfsn_input_proj_f32(P(xr.data_ptr() + r0 * I * 4), P(cell.w_ih_f32.data_ptr() + g * H * I * 4),
+                                                           P(cell.bias.data_ptr() + g * H * 4), P(zr.data_ptr() + (r0 * G + g) * H * 4),
+                                                           min(63, len(mine) - r0), I, H, G * H, st), "sfsn_input_proj_f32")
+                z.view(-1, G * H).index_copy_(0, idx - t0 * R, zr)
+
     def _end_state_of(self, f: _Forward, want_counts: bool) -> dict:
         """What a forward leaves behind its last frame, for a streaming session that goes on from there (``StreamingSession.prime``):
         ``fb`` / ``sb``: ``states[l][i] = (h, c)`` of layer l, sequence model i after the last frame (the ABI's h_state / c_state) and
         ``s8[l][i]`` the int8 spikes of every frame [T, R, pad64(H)] (row T - 1: the last frame's); ``cum``: the running sums of
         cumulative_laplace_norm per sequence model (full-band first), else None; ``counts``: with ``want_counts`` the spikes per
         (layer, clip), int64 [fb layers + groups x sb layers, B] in ``spike_summary``'s order, else None.  The states and the spikes
-        are the forward's own buffers, in stream order: the spikes are valid until the next forward on this stream."""
+        are the forward's own buffers, in stream order: the spikes are valid until the next forward on this stream.
+        A start with per-clip ends (a ragged batch behind a start): ``states`` are those after the last PADDED frame and of no use;
+        ``fb`` / ``sb`` also carry ``mem[l][i]``, the new frames' post-BatchNorm membranes [N, R, H] (row ``frames[b] - 1``: what c_state
+        would be had the scan stopped at clip b's own last frame), ``counts`` run over each clip's own frames and ``frames_dev`` holds
+        the clips' counts of NEW frames, int32 on the device."""
         spec, fb, sb = self.spec, f.fbm.d, f.sbm.d
         ng, nl_fb, nl_sb = spec.n_groups, spec.fb_layers, spec.sb_layers
         counts = None
@@ -1452,12 +1524,20 @@ class Engine:
                 for j, (t, rpc) in enumerate(part):
                     arr[j].spikes_i8, arr[j].T, arr[j].R, arr[j].HP, arr[j].rows_per_clip = t.data_ptr(), t.shape[0], t.shape[1], t.shape[2], rpc
                     arr[j].counts = counts.data_ptr() + 8 * (i0 + j) * B
-                check(self.lib.sfsn_spike_count_rows(arr, len(part), t0, T - t0, hm), "sfsn_spike_count_rows")
+                if f.frames is not None:  # (per-clip ends: frames_dev counts from the row's first frame, history included)
+                    check(self.lib.sfsn_spike_count_rows_ragged(arr, len(part), t0, T - t0, _ptr(f.frames_dev), B, hm), "sfsn_spike_count_rows_ragged")
+                else:
+                    check(self.lib.sfsn_spike_count_rows(arr, len(part), t0, T - t0, hm), "sfsn_spike_count_rows")
 
         def s8(d):  # (a forward with a start: the new frames' rows)
             return [[t[f.lead:] for t in row] for row in d["s8"]] if f.lead else d["s8"]
-        return dict(fb=dict(states=fb["states"], s8=s8(fb)), sb=dict(states=sb["states"], s8=s8(sb)),
-                    cum=None if f.cum is None else f.cum["state"], counts=counts)
+        es = dict(fb=dict(states=fb["states"], s8=s8(fb)), sb=dict(states=sb["states"], s8=s8(sb)),
+                  cum=None if f.cum is None else f.cum["state"], counts=counts)
+        if f.frames is not None:
+            for d, e in ((fb, es["fb"]), (sb, es["sb"])):
+                e["mem"] = [[t[f.lead:] for t in row] for row in d["mem"]]
+            es["frames_dev"] = f.frames_dev - f.lead
+        return es
 
     def _validate(self, stft):
         """(B, F, T) of a forward's input, or the error that says what is wrong with it."""
@@ -1679,6 +1759,8 @@ class Engine:
                         g.wait_event(gate_events[c])
                     if not self._features(f, m, t0, nt, f.hG[si], (rest, _pick(d["zin"][0], rest))) and rest:
                         self._stage_input(_pick(seqs, rest), 0, _pick(xs_, rest), _pick(d["zin"][0], rest), t0, nt, f.hG[si], tag)
+                    if f.l0_alone:
+                        self._l0_as_alone(f, m, t0, nt, g, f.hG[si])
                 else:
                     f.link(f.sstreams[si - 1], g)  # previous layer's scan of this chunk
                     if not fused:

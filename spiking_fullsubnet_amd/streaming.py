@@ -41,7 +41,10 @@ started from the state the session carries (``Engine.forward_stft(..., _end_stat
 in, D frames of history in front of the new ones) and their end state handed back.  The one-launch hop gives its state in one launch
 (``sfsn_hop_seed``) and takes the end state in one (``sfsn_hop_advance``: counts added to, the overlap-add accumulator continued),
 then the clips' origins move back by the backlog's launches; the per-kernel sequence uses row copies.  A fresh clip reads as zero:
-``advance`` on it equals ``prime``.  Not for resident sessions.
+``advance`` on it equals ``prime``.  Not for resident sessions.  ``advance_ragged(stft, frames, clips)`` /
+``advance_wave_ragged(samples, lengths, clips)`` take a backlog of ITS OWN length per clip in one call and equal the single-clip
+``advance`` calls bit for bit: one padded forward with per-clip lengths and the per-frame membranes, and a hand-back launch that takes
+every clip's rows at its own last frame (``sfsn_hop_advance_ragged``).
 
 Moving a clip: ``export_state(clips)`` copies the clips' carried state out of the session (a ``clip_state.ClipState``: one self-contained
 blob per clip) and ``import_state(state, clips)`` puts it into slots of this or another session of the same geometry and tier, where
@@ -80,8 +83,8 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from ._lib import AdvanceSrc, DfGroup, HopDesc, HOP_MAX_GROUPS, HOP_MAX_LAYERS, NORM_CUMLAPLACE, PrimeSrc, SeedDst, check
-from .clip_select import check_frames, check_samples, clip_indices, held_masks, part_runs, runs, slot_order
+from ._lib import AdvanceRaggedSrc, AdvanceSrc, DfGroup, HopDesc, HOP_MAX_GROUPS, HOP_MAX_LAYERS, NORM_CUMLAPLACE, PrimeSrc, SeedDst, check
+from .clip_select import check_frames, check_samples, clip_indices, clip_lengths, held_masks, part_runs, runs, slot_order
 from .clip_state import ClipState, clip_list, hop_sections, import_clips, layout_of, new_blob
 from .engine import Engine, NormStats, SpikeSummary, _ptr
 from .session_common import SessionCommon, row_count_jobs
@@ -627,15 +630,17 @@ class StreamingSession(SessionCommon):
             for g in range(ng):
                 src.sb[g].cum = es["cum"][1 + g].data_ptr()
 
-    def _offline_forward(self, stft, idx, end_state):
+    def _offline_forward(self, stft, idx, end_state, frames=None):
         """The offline forward of the clips ``idx``' frames ``stft`` with the session's statistics of those clips; ``end_state``:
-        True (from zero) or the start buffers it continues from."""
+        True (from zero) or the start buffers it continues from; ``frames``: the clips' own counts of new frames (a start made with
+        ``per_clip_ends``)."""
         eng = self.eng
         ns = None if self._stats is None else (self._stats if len(idx) == self.B else self._stats.select(idx))
         # (the per-kernel sequence's layer-0 membranes are those of ITS input product, the form below 64 rows: these frames take it too)
         eng._l0_hop = self.hop if self._hop is None else None
         try:
-            return eng.forward_stft(stft, want_layers=False, want_counts=self._rows is not None, norm_stats=ns, _end_state=end_state)
+            return eng.forward_stft(stft, want_layers=False, want_counts=self._rows is not None, norm_stats=ns, _end_state=end_state,
+                                    frames=frames)
         finally:
             eng._l0_hop = None
 
@@ -760,15 +765,17 @@ class StreamingSession(SessionCommon):
         return res
 
     # ---- a backlog on running clips: the offline kernels from the carried state, their end state back into the session -----------
-    def _advance_sorted(self, stft, idx, samples=None):
+    def _advance_sorted(self, stft, idx, samples=None, lens=None):
         """``stft``: complex64 [len(idx), F, N], or None in waveform mode, where ``samples`` float32 [len(idx), 128 * N] contiguous
         give the frames; ``idx`` ascending.  Returns (the forward of the N new frames, the waveform blocks or None).  Everything on
-        torch's current stream."""
+        torch's current stream.  ``lens`` (``advance_ragged``): clip ``idx[i]`` has ``lens[i]`` of the N frames, the rest of its row is
+        padding -- the same seed and forward, zeroed padding, and every clip's end taken at its own last frame
+        (``_take_ragged``)."""
         eng, spec = self.eng, self.eng.spec
         n, hop, D, ng, dev = len(idx), self.hop, self.D, spec.n_groups, self.dev
         N = stft.shape[-1] if samples is None else samples.shape[1] // 128
         T = D + N
-        start = eng._start_buffers(n, N, D, frames_before=int(self.clip_frames[idx[0]]))
+        start = eng._start_buffers(n, N, D, frames_before=int(self.clip_frames[idx[0]]), per_clip_ends=lens is not None)
         buf = start["stft"]
         units = [1] + [spec.units(g) for g in range(ng)]
         st = ctypes.c_void_p(_raw_stream(self._dev_index))
@@ -806,6 +813,14 @@ class StreamingSession(SessionCommon):
             wbuf[:, 384:].copy_(samples)
             # frame j of the backlog covers samples [128 j, 128 j + 512) of the buffer: the centred frame j + 2
             stft = spectral.stft(wbuf, 512, 128)[:, :, 2:2 + N]
+        if lens is not None:
+            from . import ragged
+            fdev = ragged.upload(lens, dev)  # (pinned, on the current stream: no synchronisation)
+            keep = torch.arange(N, device=dev).unsqueeze(0) < fdev.unsqueeze(1)
+            # the padding reads as zero whatever the caller left there: the scans run over it, and nothing of it may be NaN
+            buf[:, :, D:].copy_(torch.where(keep.unsqueeze(1), stft, torch.zeros((), dtype=stft.dtype, device=dev)))
+            out = self._offline_forward(buf, idx, start, frames=lens)
+            return out, self._take_ragged(out, buf, idx, lens, fdev, wbuf, st)
         buf[:, :, D:].copy_(stft)
         out = self._offline_forward(buf, idx, start)
         es = out["end_state"]
@@ -833,6 +848,59 @@ class StreamingSession(SessionCommon):
             for b0, m in self._chunk_launches("sfsn_hop_advance", part, chunks, src, st):
                 part["origin"][b0:b0 + m].sub_(N // hop)
         return out, res
+
+    def _take_ragged(self, out, buf, idx, lens, fdev, wbuf, st):
+        """The end of ``_advance_sorted`` with per-clip lengths: each clip ``idx[i]``'s state after ITS OWN last new frame
+        ``lens[i] - 1`` into the session -- the spikes' row, the membrane tap's row (the scans' c_state is the one after the last
+        padded frame), the history and the samples that end there, the counts over its own frames -- and its origin back by its own
+        launches.  One-launch tier: ``sfsn_hop_advance_ragged``; per-kernel tier: row gathers.  Returns the waveform blocks or None."""
+        spec = self.eng.spec
+        n, hop, D, ng, dev = len(idx), self.hop, self.D, spec.n_groups, self.dev
+        T = buf.shape[-1]
+        N = T - D
+        es = out["end_state"]
+        if self._hop is None:
+            last = (fdev - 1).long()
+            rows = torch.arange(n, device=dev)
+            units = [1] + [spec.units(g) for g in range(ng)]
+            ends = {}
+            for key, us in (("fb", units[:1]), ("sb", units[1:])):
+                e = es[key]
+                # (h as the scans take it: fp32 0 / 1 -- the int8 spikes of the clip's last frame, without the rows' padding columns)
+                ends[key] = dict(states=[[(s8.view(N, n, u, -1)[last, rows][..., :m.shape[-1]].reshape(n * u, -1).float(),
+                                           m.view(N, n, u, -1)[last, rows].reshape(n * u, -1))
+                                          for s8, m, u in zip(s8s, ms, us)] for s8s, ms in zip(e["s8"], e["mem"])])
+            self._put_states(ends, idx)
+            for j, b in enumerate(idx):  # the D + hop frames that end with the clip's own last one (lens[j] >= hop: the row has them)
+                self.hist[b].copy_(buf[j, :, D + lens[j] - self.Th:D + lens[j]])
+            if self._rows is not None:
+                self._rows.index_add_(1, torch.tensor(idx, dtype=torch.long).to(dev, non_blocking=True), es["counts"])
+            return None
+        src = AdvanceRaggedSrc()
+        src.Bp, src.Nmax, src.T = n, N, T
+        nd = es["frames_dev"]
+        src.frames = nd.data_ptr()
+        src.stft_ri = torch.view_as_real(buf).data_ptr()
+        for o, e, gi in [(src.fb, es["fb"], 0)] + [(src.sb[g], es["sb"], g) for g in range(ng)]:
+            for l in range(len(e["s8"])):
+                o.layer[l].spikes_i8, o.layer[l].membrane = e["s8"][l][gi].data_ptr(), e["mem"][l][gi].data_ptr()
+        res = None
+        if wbuf is not None:
+            enh = out["enh_stft"]  # (the new frames of the forward's [.., T] rows: the launch takes the rows)
+            src.enh_ri = enh.data_ptr() - D * enh.element_size()
+            res = torch.empty((n, spec.num_spks, 128 * N), dtype=torch.float32, device=dev)
+            src.wave_ctx, src.wave_stride, src.wave_out = wbuf.data_ptr(), wbuf.shape[1], res.data_ptr()
+        back = nd // hop if hop > 1 else nd  # each clip's own launches
+        for part, chunks in self._part_chunks(idx):
+            for j0, local in chunks:
+                src.b0 = j0
+                self._part_launch("sfsn_hop_advance_ragged", part, local, src, st)
+            # the clips' origins move back by their own launches, behind the queued launches (32-bit wrap-around, as in _advance_sorted)
+            for j0, local in chunks:
+                for b0, m in runs(local):
+                    part["origin"][b0:b0 + m].sub_(back[j0:j0 + m])
+                    j0 += m
+        return res
 
     def _advance_checks(self, what: str, idx) -> None:
         spec = self.eng.spec
@@ -901,6 +969,91 @@ class StreamingSession(SessionCommon):
         self._clip_c0[idx] -= Ls // 128
         self._primed = True  # the launch mutes each clip by its own frame index (see step_wave)
         return res
+
+    def _ragged_refusals(self, what: str, lens) -> None:
+        if self.eng.spec.cum_laplace:
+            raise NotImplementedError(f"{what}: with cumulative_laplace_norm the sub-band running sums after a clip's own last frame "
+                                      f"are not available from a padded forward (lengths {list(lens)}): make one `advance` call per length")
+
+    def advance_ragged(self, stft: torch.Tensor, frames, clips=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``advance`` with a backlog of ITS OWN LENGTH per clip, in one call: ``stft`` complex64 [len(clips), F, Nmax] on the device,
+        row i for ``clips[i]`` (``None``: every clip); ``frames``: a sequence or CPU int tensor, ``frames[i]`` the frames row i really
+        holds -- a positive multiple of ``hop``, at most ``Nmax`` (``ValueError`` naming the clip; a wrong count of lengths is a
+        ``ValueError`` too).  Whatever row i holds at frames ``>= frames[i]`` is ignored.
+
+        The call returns, and leaves behind, exactly what the single-clip calls ``advance(stft[i:i+1, :, :frames[i]],
+        clips=[clips[i]])`` would have: ``(enh_stft [.., S, F, Nmax], enh_mag)`` equal over each clip's own frames and zero past
+        them; ``clip_frames``, the spike counts and every section of ``export_state`` equal bit for bit, the layer-0 membranes
+        included (both sides run the offline kernels), in both tiers.  Unlisted clips are untouched, a fresh clip reads as zero state.
+
+        One seed launch, ONE padded forward from the carried state (``Engine.forward_stft(..., frames=, _end_state=start)`` with the
+        per-frame membrane tap: the scans' own end state is the one after the last padded frame) and one hand-back launch
+        (``sfsn_hop_advance_ragged``) that takes every clip's rows at its own last frame and moves its origin back by its own
+        launches; the per-kernel tier gathers the same rows.  The lengths go to the device from pinned memory: ordered on torch's
+        current stream, no synchronisation.  Equal lengths: the call IS ``advance``.  Refused: resident sessions and, where the
+        lengths differ, ``cumulative_laplace_norm`` models (``NotImplementedError``: one ``advance`` call per length); waveform
+        sessions (``RuntimeError``: ``advance_wave_ragged``).  Not for cIRM-GSN sessions."""
+        self._refuse_resident("advance_ragged")
+        if self.waveform:
+            raise RuntimeError("this session was opened with waveform=True: use advance_wave_ragged(samples, lengths)")
+        idx, order = self._prime_clips(clips, stft.shape[0] if isinstance(stft, torch.Tensor) and stft.dim() == 3 else -1, "advance_ragged")
+        if stft.device != self.dev or stft.dtype != torch.complex64 or stft.shape[1] != self.F:
+            raise RuntimeError(f"expected complex64 {(len(idx), self.F, 'Nmax')} on {self.dev}, got {stft.dtype} {tuple(stft.shape)} on {stft.device}")
+        Nmax = stft.shape[2]
+        lens = clip_lengths("advance_ragged", frames, idx, self.hop, f"the session's hop ({self.hop})", Nmax, "frames")
+        N = max(lens)
+
+        def padded(t):  # zeros behind the longest clip, up to the caller's Nmax
+            return t.contiguous() if N == Nmax else torch.nn.functional.pad(t, (0, Nmax - N))
+
+        if min(lens) == N:
+            enh, mag = self.advance(stft[..., :N], clips=clips)
+            return padded(enh), padded(mag)
+        self._ragged_refusals("advance_ragged", lens)
+        own = dict(zip(idx, lens))
+
+        def run(rows, slots):
+            out, _ = self._advance_sorted(rows, slots, lens=[own[b] for b in slots])
+            return out["enh_stft"], out["enh_mag"]
+
+        enh, mag = self._slot_ordered(stft[..., :N], idx, order, run)
+        self._clip_f0[idx] -= np.asarray(lens, dtype=self._clip_f0.dtype)
+        return padded(enh), padded(mag)
+
+    def advance_wave_ragged(self, samples: torch.Tensor, lengths, clips=None) -> torch.Tensor:
+        """``advance_ragged`` for waveform sessions (``host_io`` included; device tensors in and out): ``samples`` float32
+        [len(clips), 128 * cmax], ``lengths[i]`` the samples row i really holds, a positive multiple of 128 and at most
+        ``128 * cmax``.  Returns [.., S, 128 * cmax]: over each clip's own samples what ``advance_wave(samples[i:i+1, :lengths[i]],
+        clips=[clips[i]])`` returns, zeros behind; the session is left where those calls leave it (STFT state, overlap-add sums,
+        ``clip_calls`` included).  Every listed clip must have made at least one call in its current utterance (``ValueError``
+        naming the clip, as ``advance_wave``)."""
+        self._refuse_resident("advance_wave_ragged")
+        if not self.waveform:
+            raise RuntimeError("open the session with waveform=True")
+        idx, order = self._prime_clips(clips, samples.shape[0] if isinstance(samples, torch.Tensor) and samples.dim() == 2 else -1, "advance_wave_ragged")
+        if samples.device != self.dev or samples.dtype != torch.float32:
+            raise RuntimeError(f"expected float32 {(len(idx), '128 * cmax')} on {self.dev}, got {samples.dtype} {tuple(samples.shape)} on {samples.device}")
+        Lmax = samples.shape[1]
+        lens = clip_lengths("advance_wave_ragged", lengths, idx, 128, "128", Lmax, "samples")
+        Ls = max(lens)
+
+        def padded(t):
+            return t if Ls == Lmax else torch.nn.functional.pad(t, (0, Lmax - Ls))
+
+        if min(lens) == Ls:
+            return padded(self.advance_wave(samples[:, :Ls], clips=clips))
+        calls = self.clip_calls
+        for b in idx:
+            if calls[b] < 1:
+                raise ValueError(f"advance_wave_ragged: clip {b} has made no call in its current utterance (no STFT state to continue "
+                                 "from): start it with prime_wave")
+        self._ragged_refusals("advance_wave_ragged", lens)
+        own = dict(zip(idx, lens))
+        res, = self._slot_ordered(samples[:, :Ls], idx, order, lambda rows, slots: self._advance_sorted(
+            None, slots, samples=rows.contiguous(), lens=[own[b] // 128 for b in slots])[1:])
+        self._clip_c0[idx] -= np.asarray(lens, dtype=self._clip_c0.dtype) // 128
+        self._primed = True  # the launch mutes each clip by its own frame index (see step_wave)
+        return padded(res)
 
     # ---- moving a clip: its state out of its slot, and into a slot of this or another session ------------------------------------
     def _state_signature(self) -> tuple:
