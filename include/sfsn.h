@@ -1252,6 +1252,48 @@ int sfsn_fullband_hop_advance(const sfsn_fullband_hop_desc* desc /* host */, uns
                               float* wave_state /* nullable */, float* ola_state /* nullable */, const int* clips /* host */, int n_clips,
                               const sfsn_fullband_advance_src* src /* host */, void* stream);
 
+/* sfsn_fullband_hop_advance with a backlog of ITS OWN LENGTH per clip (csrc/sfsn_prime.hip; a kernel of its own): sfsn_hop_advance_ragged's
+ * contract on sfsn_fullband_hop_advance's state.  The offline kernels ran ONE padded forward of Nmax new frames behind T - Nmax >= D
+ * frames of history (the padding zeroed; sfsn_fullband_proj_deepfilter_ragged as the epilogue, the per-layer scans with the membrane
+ * tap), clip b0 + i has N_b = frames[b0 + i] of them (device int32 [Bp], each a multiple of hop with hop <= N_b <= Nmax: the CALLER's
+ * check -- the launch holds a value outside [1, Nmax] inside that range, so that no index leaves the tensors, and promises nothing else
+ * about such a clip).  For clips[i], with k = desc->launch_index:
+ *   layer.h[k & 1] <- row N_b - 1 of spikes_i8; layer.c <- row N_b - 1 of `membrane` (sfsn_scan_segment.membrane: c_state itself is the
+ *                     membrane after the last PADDED frame and is not read);
+ *   hist_ri[k & 1] <- the D frames that end with frame T - Nmax + N_b - 1 of stft_ri's row: N_b < D keeps the tail of the old history;
+ *   spike_slots    <- ADDED to over frames [0, N_b) only (a clip whose origin equals k: replaced);
+ *   wave_state     <- the 512 samples that end at sample 384 + 128 N_b of the clip's row of wave_ctx ([384 of context | new samples],
+ *                     the row sfsn_fullband_hop_seed began); ola_state <- continued in the hop's order through frame N_b - 1 only;
+ *                     wave_out[b0 + i][s][128 j ..] <- block j < N_b as sfsn_fullband_hop_advance writes it, zeros for N_b <= j < Nmax.
+ * Waveform mode, a clip WITHOUT A CALL (origin k + 1; the launch reads desc->clip_start): it carries no overlap-add sums, its first
+ * new frame has frame index 0, its N_b may be 0 (held inside [0, Nmax]; its backlog is its first call alone: zeros to h, c, hist_ri
+ * and ola_state, only wave_state taken) and its window of samples ends ONE HOP LATER, at sample 384 + 128 (N_b + 1) of its row -- its
+ * first 128 samples made no frame.  Rows of such clips hold wave_stride >= 384 + 128 (Nmax + 1) floats; the host cannot know a clip's
+ * kind, so the launch holds the window's end inside the row.
+ * The caller then moves clip_start[clips[i]] back by the clip's OWN launches replaced -- N_b / hop; waveform mode: N_b calls for a clip
+ * that had made a call, N_b + 1 for one that had not -- unsigned, wrap-safe, stream-ordered, behind the queued launches.  Everything
+ * else -- the untouched clips and scratch, exactness without a layer-0 reservation -- is sfsn_fullband_hop_advance's.  Plain vector
+ * loads and stores, no atomics, nothing waits.
+ * SFSN_EINVAL, before any launch: as sfsn_fullband_hop_advance with Nmax in the place of N (Nmax % hop != 0, Nmax < hop in either mode,
+ * T < D + Nmax), a missing or misaligned pointer (membrane: 16 bytes; stft_ri, enh_ri, wave_out: 8; frames, spikes_i8, wave_ctx,
+ * window: 4), wave_stride < 384 + 128 Nmax.  SFSN_EUNSUPPORTED: as sfsn_fullband_hop_advance.  (Added without an ABI bump: a new
+ * function and a new struct only.) */
+typedef struct sfsn_fullband_advance_ragged_src {
+    int Bp, Nmax, b0;
+    int T;                   /* frames per row of stft_ri / enh_ri; the Nmax (padded) new frames are the last ones */
+    int wave_stride;         /* waveform mode: floats per row of wave_ctx (>= 384 + 128 Nmax; see above)            */
+    const int* frames;       /* DEVICE int32 [Bp]: N_b, the new frames clip b0 + i really has                      */
+    const float* stft_ri;    /* [Bp][F][T][2] [history | new | padding] (NULL if D == 0)                           */
+    const float* enh_ri;     /* waveform mode: [Bp][S][F][T][2] the enhanced frames                                */
+    const float* wave_ctx;   /* waveform mode: [Bp][wave_stride] 384 samples of context, then the new samples      */
+    float* wave_out;         /* waveform mode: [Bp][S][128 * Nmax] out                                             */
+    const float* window;     /* waveform mode: [512] the session's window (sfsn_fullband_wave_desc)                */
+    sfsn_ragged_layer layer[SFSN_FULLBAND_HOP_MAX_LAYERS]; /* spikes_i8 [Nmax][Bp][pad64(Hp)], membrane [Nmax][Bp][Hp] */
+} sfsn_fullband_advance_ragged_src;
+int sfsn_fullband_hop_advance_ragged(const sfsn_fullband_hop_desc* desc /* host */, unsigned* spike_slots /* nullable */,
+                                     float* wave_state /* nullable */, float* ola_state /* nullable */, const int* clips /* host */,
+                                     int n_clips, const sfsn_fullband_advance_ragged_src* src /* host */, void* stream);
+
 /* ----------------------------------------------------------------------------------------------------
  * The intel_ndns recipe's training loss (recipes/intel_ndns/spiking_fullsubnet/trainer.py:24-48 on audiozen/loss.py) and its
  * gradient with respect to the estimate, in one call of two launches:

@@ -182,6 +182,11 @@ class FullbandAdvanceSrc(ctypes.Structure):  # sfsn_fullband_advance_src
                 ("window", _P), ("layer", PrimeLayer * FULLBAND_HOP_MAX_LAYERS)]
 
 
+class FullbandAdvanceRaggedSrc(ctypes.Structure):  # sfsn_fullband_advance_ragged_src
+    _fields_ = [("Bp", _I), ("Nmax", _I), ("b0", _I), ("T", _I), ("wave_stride", _I), ("frames", _P), ("stft_ri", _P), ("enh_ri", _P),
+                ("wave_ctx", _P), ("wave_out", _P), ("window", _P), ("layer", RaggedLayer * FULLBAND_HOP_MAX_LAYERS)]
+
+
 def _sources():
     """The files the library is made of, in the order the Makefile hashes them (SRCS)."""
     return [os.path.join(_HERE, "..", "include", "sfsn.h")] + [
@@ -400,6 +405,9 @@ def lib() -> ctypes.CDLL:
     L.sfsn_fullband_hop_advance.restype = _I  # desc, spike_slots, wave_state, ola_state | clips, n_clips | src, stream
     L.sfsn_fullband_hop_advance.argtypes = [ctypes.POINTER(FullbandHopDesc), _P, _P, _P, ctypes.POINTER(_I), _I,
                                             ctypes.POINTER(FullbandAdvanceSrc), _P]
+    L.sfsn_fullband_hop_advance_ragged.restype = _I  # desc, spike_slots, wave_state, ola_state | clips, n_clips | src, stream
+    L.sfsn_fullband_hop_advance_ragged.argtypes = [ctypes.POINTER(FullbandHopDesc), _P, _P, _P, ctypes.POINTER(_I), _I,
+                                                   ctypes.POINTER(FullbandAdvanceRaggedSrc), _P]
     L.sfsn_recipe_loss_scratch_bytes.restype = ctypes.c_size_t  # rows, n_samples; 0: refused (host only)
     L.sfsn_recipe_loss_scratch_bytes.argtypes = [_I, _I]
     L.sfsn_recipe_loss.restype = _I  # est, tgt | rows, n_samples | c_freq, c_mag, c_sdr | flags | terms, grad_est, scratch, stream
@@ -455,7 +463,8 @@ EXPORTS = ("sfsn_abi_version", "sfsn_source_hash", "sfsn_strerror", "sfsn_device
            "sfsn_hop_state_bytes", "sfsn_hop_state_export", "sfsn_hop_state_import", "sfsn_fullband_hop_state_bytes",
            "sfsn_fullband_hop_state_export", "sfsn_fullband_hop_state_import", "sfsn_hop_seed", "sfsn_hop_advance",
            "sfsn_fullband_hop_seed", "sfsn_fullband_hop_advance", "sfsn_stream_hop_held",
-           "sfsn_fullband_stream_hop_held", "sfsn_fullband_stream_hop_wave_held", "sfsn_hop_advance_ragged")
+           "sfsn_fullband_stream_hop_held", "sfsn_fullband_stream_hop_wave_held", "sfsn_hop_advance_ragged",
+           "sfsn_fullband_hop_advance_ragged")
 
 
 def check(rc: int, what: str = "") -> None:

@@ -1,6 +1,6 @@
 // sfsn_prime.hip -- the way between a streaming session (the one-launch hops of sfsn_hop.hip / sfsn_fullband_hop.hip) and the offline
 // kernels, one launch each way, for the listed clips of the session only (gfx950 only; include/sfsn.h: sfsn_hop_prime, sfsn_hop_seed,
-// sfsn_hop_advance, sfsn_hop_advance_ragged, sfsn_fullband_hop_seed, sfsn_fullband_hop_advance).
+// sfsn_hop_advance, sfsn_hop_advance_ragged, sfsn_fullband_hop_seed, sfsn_fullband_hop_advance, sfsn_fullband_hop_advance_ragged).
 //
 // A session that has streamed some frames of a clip holds: every layer's last spikes (double-buffered by launch parity) and membrane,
 // the running sums of the cumulative norm, the last D noisy frames, the spike counts per lane slot and, in waveform mode, the last
@@ -325,30 +325,56 @@ struct TakeRaggedParams {
 };
 static_assert(sizeof(TakeRaggedParams) <= 4096, "TakeRaggedParams travels as a kernel argument");
 
-// the clip's own frame count, held inside [1, Nmax] whatever the array says: no index below leaves the caller's tensors
-__device__ __forceinline__ int ragged_frames(const TakeRaggedParams& p, int i) {
-    const int n = p.frames[p.b0 + i];
-    return n < 1 ? 1 : (n > p.Nmax ? p.Nmax : n);
+// The ragged roles are one text for two parameter blocks: TakeRaggedParams (sfsn_hop_advance_ragged; NOCALL = false) and
+// FullbandTakeRaggedParams (sfsn_fullband_hop_advance_ragged; NOCALL = true: the cIRM-GSN waveform hop's clip WITHOUT A CALL, origin
+// k + 1 -- hop_take_kernel<true>'s `span`: no carried overlap-add sums, frame index 0 at its first new frame, an STFT-state window that
+// ends one hop later in its context row, and N_b = 0 where its backlog is its one first call).
+template <bool NOCALL, class P>
+__device__ __forceinline__ unsigned ragged_span(const P& p) {
+    if constexpr (NOCALL) return p.span;
+    return 0u;
 }
 
-__device__ __forceinline__ void take_rows_ragged(const TakeRaggedParams& p, const SecDev& sd, int item) {
-    const TakeRaggedSeqDev& sq = p.seq[sd.seq];
+// launch k is the clip's first call, still to come (the caller guarantees clip_start where span is set)
+template <bool NOCALL, class P>
+__device__ __forceinline__ bool ragged_nocall(const P& p, int i) {
+    if constexpr (NOCALL) return p.span && p.clip_start[p.clips[i]] - p.k == 1u;
+    return false;
+}
+
+// the clip's own frame count, held inside [1, Nmax] ([0, Nmax] for the clip without a call) whatever the array says: no index below
+// leaves the caller's tensors
+template <bool NOCALL, class P>
+__device__ __forceinline__ int ragged_frames(const P& p, int i) {
+    const int n = p.frames[p.b0 + i];
+    if constexpr (!NOCALL) {
+        return n < 1 ? 1 : (n > p.Nmax ? p.Nmax : n);
+    } else {
+        const int lo = ragged_nocall<NOCALL>(p, i) ? 0 : 1;
+        return n < lo ? lo : (n > p.Nmax ? p.Nmax : n);
+    }
+}
+
+template <bool NOCALL, class P>
+__device__ __forceinline__ void take_rows_ragged(const P& p, const SecDev& sd, int item) {
+    const auto& sq = p.seq[sd.seq];
     const TakeRaggedLayerDev& L = sq.layer[sd.layer];
     const int W = sq.H >> 2;
     const int j = item % W, rr = item / W;
     const int k = rr % sq.units, i = rr / sq.units;
-    const int N = ragged_frames(p, i);
+    const int N = ragged_frames<NOCALL>(p, i);
     const size_t Rs = (size_t)p.Bp * sq.units;
     const size_t row_s = (size_t)(p.b0 + i) * sq.units + k, row_d = (size_t)p.clips[i] * sq.units + k;
     const int8_t* sp = L.s8 + row_s * sq.HP + 4 * j;  // my word of the first new frame; a frame further every Rs * HP bytes
     const size_t fs = Rs * sq.HP;
-    const unsigned last = *reinterpret_cast<const unsigned*>(sp + (size_t)(N - 1) * fs) & 0x01010101u;
-    const float4 c = *reinterpret_cast<const float4*>(L.mem + ((size_t)(N - 1) * Rs + row_s) * sq.H + 4 * j);
+    const bool none = NOCALL && N == 0;  // (the clip without a call and no frame: zeros, which its frame 0 reads anyway)
+    const unsigned last = none ? 0u : *reinterpret_cast<const unsigned*>(sp + (size_t)(N - 1) * fs) & 0x01010101u;
+    const float4 c = none ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : *reinterpret_cast<const float4*>(L.mem + ((size_t)(N - 1) * Rs + row_s) * sq.H + 4 * j);
     *reinterpret_cast<unsigned*>(L.h + row_d * sq.HP + 4 * j) = last;
     *reinterpret_cast<float4*>(L.c + row_d * sq.H + 4 * j) = c;
     if (!L.slots) return;
     unsigned nspk = 0u;  // (a clip that begins here: the hop reads its slot as zero)
-    if (!clip_fresh(p.clip_start, p.k, 0u, p.clips[i])) nspk = L.slots[row_d * W + j];
+    if (!clip_fresh(p.clip_start, p.k, NOCALL ? ragged_span<NOCALL>(p) : 0u, p.clips[i])) nspk = L.slots[row_d * W + j];
     for (int t0 = 0; t0 < N; t0 += 8) {  // eight independent loads in flight
         unsigned w[8];
 #pragma unroll
@@ -362,24 +388,33 @@ __device__ __forceinline__ void take_rows_ragged(const TakeRaggedParams& p, cons
 
 // the D frames that end with the clip's own last one: frames lead + N_b - D .. lead + N_b - 1 of its row (lead >= D: N_b < D keeps the
 // tail of the old history)
-__device__ __forceinline__ void take_hist_ragged(const TakeRaggedParams& p, int item) {
+template <bool NOCALL, class P>
+__device__ __forceinline__ void take_hist_ragged(const P& p, int item) {
     const int D = p.D, T = p.T;
     const int d = item % D, r = item / D;
     const int f = r % p.fcov, i = r / p.fcov;
-    const int t = T - p.Nmax + ragged_frames(p, i) - D + d;
-    const float2 v = *reinterpret_cast<const float2*>(p.stft + (((size_t)(p.b0 + i) * p.F + f) * T + t) * 2);
+    const int t = T - p.Nmax + ragged_frames<NOCALL>(p, i) - D + d;
+    const bool none = NOCALL && ragged_frames<NOCALL>(p, i) == 0;  // (no frame: zero, as take_hist)
+    const float2 v = none ? make_float2(0.0f, 0.0f) : *reinterpret_cast<const float2*>(p.stft + (((size_t)(p.b0 + i) * p.F + f) * T + t) * 2);
     *reinterpret_cast<float2*>(p.hist + (((size_t)p.clips[i] * p.F + f) * D + d) * 2) = v;
 }
 
-// the 512 samples that end with the clip's own last one: sample 384 + 128 N_b of its context row
-__device__ __forceinline__ void take_wave_ragged(const TakeRaggedParams& p, int item) {
+// the 512 samples that end with the clip's own last one: sample 384 + 128 N_b of its context row -- one hop later for the clip
+// without a call, whose first 128 samples made no frame (held inside the row: the host cannot know the clip's kind)
+template <bool NOCALL, class P>
+__device__ __forceinline__ void take_wave_ragged(const P& p, int item) {
     const int n = item & (FFT_NFFT - 1), i = item >> 9;
-    const int end = SEED_CTX + 128 * ragged_frames(p, i);
+    int end = SEED_CTX + 128 * ragged_frames<NOCALL>(p, i);
+    if constexpr (NOCALL) {
+        if (ragged_nocall<NOCALL>(p, i)) end += 128;
+        if (end > p.ctx_stride) end = p.ctx_stride;
+    }
     p.wave_state[(size_t)p.clips[i] * FFT_NFFT + n] = p.ctx[(size_t)(p.b0 + i) * p.ctx_stride + end - FFT_NFFT + n];
 }
 
 // take_ola<true>'s recurrence over the clip's own N_b frames; the blocks behind them are written as zeros
-__device__ __forceinline__ void take_ola_ragged(const TakeRaggedParams& p, int blk, char* smem) {
+template <bool NOCALL, class P>
+__device__ __forceinline__ void take_ola_ragged(const P& p, int blk, char* smem) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     float2* unit = reinterpret_cast<float2*>(smem);
@@ -390,12 +425,12 @@ __device__ __forceinline__ void take_ola_ragged(const TakeRaggedParams& p, int b
     const int pair = blk * PRIME_WAVES + wave;
     if (pair >= p.n_clips * p.S) return;
     const int i = pair / p.S, s = pair - i * p.S, F = p.F, T = p.T, Nmax = p.Nmax;
-    const int N = ragged_frames(p, i);
+    const int N = ragged_frames<NOCALL>(p, i);
     const int clip = p.clips[i];
     const int first = T - Nmax;  // the first frame fed
-    // a clip that begins here carries no sums
+    // a clip that begins here carries no sums (NOCALL: nor does the clip whose first call is launch k -- age -1, as take_ola)
     const int age = p.clip_start ? (int)(p.k - p.clip_start[clip]) : p.frame_index;
-    const bool fresh = p.clip_start && age == 0;
+    const bool fresh = NOCALL ? p.clip_start && age <= 0 && age >= -(int)ragged_span<NOCALL>(p) : p.clip_start && age == 0;
     const int fi0 = fresh ? 0 : age;  // the frame index of the first new frame
     const Twiddles tw = make_twiddles<true>(unit, lane);
     float* os = p.ola_state + ((size_t)clip * p.S + s) * FFT_NFFT;
@@ -454,17 +489,61 @@ __global__ __launch_bounds__(PRIME_THREADS) void hop_take_ragged_kernel(const Ta
     const SecDev& sd = p.sec[block_section(p.sec, p.nsec)];
     const int blk = (int)blockIdx.x - sd.blk0;
     if (sd.kind == SEC_OLA) {
-        take_ola_ragged(p, blk, smem);
+        take_ola_ragged<false>(p, blk, smem);
         return;
     }
     const int item = blk * PRIME_THREADS + (int)threadIdx.x;
     if (item >= sd.items) return;
     if (sd.kind == SEC_ROWS)
-        take_rows_ragged(p, sd, item);
+        take_rows_ragged<false>(p, sd, item);
     else if (sd.kind == SEC_HIST)
-        take_hist_ragged(p, item);
+        take_hist_ragged<false>(p, item);
     else
-        take_wave_ragged(p, item);
+        take_wave_ragged<false>(p, item);
+}
+
+// The same launch for a cIRM-GSN session (sfsn_fullband_hop_advance_ragged): one sequence of up to SFSN_FULLBAND_HOP_MAX_LAYERS layers,
+// one row per clip, at most 16 clips, and in waveform mode the clip without a call (NOCALL above).  A kernel of its own:
+// hop_take_ragged_kernel keeps its code.
+struct FullbandTakeRaggedSeqDev {
+    TakeRaggedLayerDev layer[SFSN_FULLBAND_HOP_MAX_LAYERS];
+    int H, HP, units;
+};
+struct FullbandTakeRaggedParams {
+    FullbandTakeRaggedSeqDev seq[1];
+    SecDev sec[SFSN_FULLBAND_HOP_MAX_LAYERS + 3];
+    unsigned short clips[16];
+    int nsec, n_clips, b0, Bp, Nmax, T;
+    int F, S, D, fcov, frame_index, ctx_stride;
+    unsigned k, span;   // span 1 (waveform mode): origins k and k + 1 read as zero
+    const int* frames;  // [Bp]
+    const float* stft;  // [Bp][F][T][2], the Nmax frames last
+    const float* enh;   // [Bp][S][F][T][2]
+    const float* ctx;   // [Bp][ctx_stride]: 384 samples of context, then the new samples
+    float* hist;
+    float* wave_state;
+    float* ola_state;
+    const float* window;
+    const unsigned* clip_start;
+    float* wave_out;    // [Bp][S][128 * Nmax]
+};
+
+__global__ __launch_bounds__(PRIME_THREADS) void fullband_take_ragged_kernel(const FullbandTakeRaggedParams p) {
+    __shared__ __attribute__((aligned(16))) char smem[FFT_NFFT * 8 + PRIME_WAVES * FFT_N * 8 + PRIME_WAVES * 264 * 8];
+    const SecDev& sd = p.sec[block_section(p.sec, p.nsec)];
+    const int blk = (int)blockIdx.x - sd.blk0;
+    if (sd.kind == SEC_OLA) {
+        take_ola_ragged<true>(p, blk, smem);
+        return;
+    }
+    const int item = blk * PRIME_THREADS + (int)threadIdx.x;
+    if (item >= sd.items) return;
+    if (sd.kind == SEC_ROWS)
+        take_rows_ragged<true>(p, sd, item);
+    else if (sd.kind == SEC_HIST)
+        take_hist_ragged<true>(p, item);
+    else
+        take_wave_ragged<true>(p, item);
 }
 
 // a clip whose origin is this launch index reads as zero, as it does in the hop
@@ -867,4 +946,51 @@ extern "C" int sfsn_fullband_hop_advance(const sfsn_fullband_hop_desc* desc, uns
     t.stft = src->stft_ri; t.enh = src->enh_ri; t.tail = src->wave_tail; t.wave_out = src->wave_out;
     t.layer[0] = src->layer;
     return take_launch(v, clips, n_clips, t, true, stream);
+}
+
+extern "C" int sfsn_fullband_hop_advance_ragged(const sfsn_fullband_hop_desc* desc, unsigned* spike_slots, float* wave_state, float* ola_state,
+                                                const int* clips, int n_clips, const sfsn_fullband_advance_ragged_src* src, void* stream) {
+    if (!desc || !clips || !src || n_clips < 1) return SFSN_EINVAL;
+    if ((wave_state != nullptr) != (ola_state != nullptr)) return SFSN_EINVAL;
+    HopView v;
+    int rc = view_of(desc, spike_slots, wave_state, ola_state, src->window, v);
+    if (rc != SFSN_OK) return rc;
+    if (v.wave && !desc->clip_start) return SFSN_EINVAL;
+    if (n_clips > v.B) return SFSN_EINVAL;  // (distinct indices below B <= 16: FullbandTakeRaggedParams::clips holds them)
+    FullbandTakeRaggedParams p;
+    memset(&p, 0, sizeof(p));
+    unsigned short listed[PRIME_MAX_CLIPS];
+    rc = check_clips(v.B, clips, n_clips, listed);
+    if (rc != SFSN_OK) return rc;
+    for (int i = 0; i < n_clips; ++i) p.clips[i] = listed[i];
+    const int Nmax = src->Nmax, D = v.D;
+    if (Nmax < desc->hop || Nmax % desc->hop != 0 || src->T < Nmax + D) return SFSN_EINVAL;
+    if (src->Bp < 1 || src->b0 < 0 || n_clips > src->Bp - src->b0) return SFSN_EINVAL;
+    if (bad(src->frames, 4) || (D > 0 && bad(src->stft_ri, 8))) return SFSN_EINVAL;
+    if (v.wave && (bad(src->wave_ctx, 4) || src->wave_stride < SEED_CTX + 128 * Nmax || bad(src->enh_ri, 8) || bad(src->wave_out, 8))) return SFSN_EINVAL;
+    if (!state_ok(v, true)) return SFSN_EINVAL;
+    p.n_clips = n_clips; p.b0 = src->b0; p.Bp = src->Bp; p.Nmax = Nmax; p.T = src->T;
+    p.F = v.F; p.S = v.S; p.D = D; p.fcov = v.fcov; p.frame_index = v.frame_index; p.ctx_stride = src->wave_stride; p.k = v.k; p.span = v.span;
+    p.frames = src->frames; p.stft = src->stft_ri; p.enh = src->enh_ri; p.ctx = src->wave_ctx;
+    p.hist = v.hist; p.wave_state = v.wave_state; p.ola_state = v.ola_state; p.window = v.window;
+    p.clip_start = v.clip_start; p.wave_out = src->wave_out;
+    Sections secs{p.sec};
+    const SeqView& s = v.seq[0];
+    FullbandTakeRaggedSeqDev& d = p.seq[0];
+    d.H = s.H; d.HP = (s.H + 63) / 64 * 64; d.units = 1;
+    for (int l = 0; l < s.n_layers; ++l) {
+        const sfsn_ragged_layer& o = src->layer[l];
+        if (bad(o.spikes_i8, 4) || bad(o.membrane, 16)) return SFSN_EINVAL;
+        d.layer[l].h = s.h[l]; d.layer[l].c = s.c[l]; d.layer[l].s8 = o.spikes_i8; d.layer[l].mem = o.membrane;
+        d.layer[l].slots = v.spike_slots ? v.spike_slots + (size_t)l * v.B * (s.H / 4) : nullptr;
+        secs.add(SEC_ROWS, 0, l, n_clips * (s.H / 4));
+    }
+    if (D > 0) secs.add(SEC_HIST, 0, 0, n_clips * v.F * D);
+    if (v.wave) {
+        secs.add(SEC_WAVE, 0, 0, n_clips * FFT_NFFT);
+        secs.add(SEC_OLA, 0, 0, n_clips * v.S, PRIME_WAVES);
+    }
+    p.nsec = secs.nsec;
+    hipLaunchKernelGGL(fullband_take_ragged_kernel, dim3(secs.blk), dim3(PRIME_THREADS), 0, static_cast<hipStream_t>(stream), p);
+    return hip_ok(hipGetLastError());
 }

@@ -221,14 +221,18 @@ class FullbandEngine:
         self._errors.check()
 
     def _launch_frames(self, ri, B: int, T: int, t0: int, nt: int, stack: bool, ws: dict, x, states, spk, proj, enh, mag,
-                       frames_dev: Optional[torch.Tensor] = None) -> None:
+                       frames_dev: Optional[torch.Tensor] = None, mem=None, own_frames=None) -> None:
         """The launch sequence of the model on frames [t0, t0 + nt) of the spectrum ri [B, F, T, 2], on torch's current stream:
         features -> layer 0's input term -> the GSN layers from `states` (updated in place) -> projection + deep filter.
         forward_stft runs it on (0, T) from zero states; a streaming session (fullband_streaming.py) on the `hop` new frames behind
         its history, with the states carried.  x [T, B, F], spk[l] [T, B, Hp] or None, proj [T, B, P] or None, enh [B, S, F, T, 2],
         mag [B, S, F, T] or None are whole-spectrum buffers; ws = _make_workspace(B, nt, T, stack).  frames_dev (int32 [B] on the
         device): a ragged batch -- the last launch is the length-aware one: enh / mag are zero and proj is not written at frames
-        >= frames_dev[b].  The launches before it are the same: the model is causal."""
+        >= frames_dev[b].  The launches before it are the same: the model is causal.
+        mem (a session's ragged backlog, ``catch_up_ragged``): mem[l] [T, B, Hp], every frame's post-BatchNorm membrane of layer l
+        (sfsn_scan_segment.membrane) -- the per-layer launches (``stack`` False: the stack launch has no tap), with fp32 spikes in
+        spk[l], which the tap goes with.  own_frames (host ints, with mem): clip b has own_frames[b] <= nt of the new frames and is
+        promised the bits of ITS OWN call, so its rows of layer 0's input product take the form that call would (``_l0_as_alone``)."""
         spec, L, Hp, G, F = self.spec, self.lib, self.Hp, self.G, self.F
         st, dev, nl, S = self._stream(), self.device, spec.layers, spec.num_spks
         check(L.sfsn_fullband_features(_ptr(ri), B, F, T, spec.fdrc, _ptr(self.ln_w), _ptr(self.ln_b), 1e-5, _ptr(x), t0, nt, st),
@@ -247,7 +251,11 @@ class FullbandEngine:
             else:
                 check(rc, "sfsn_input_proj_f32")
                 self._count("inproj")
+                if own_frames is not None:
+                    self._l0_as_alone(args, x, z0, g, B, t0, nt, own_frames)
         s8_at = t0 * B * self.HP8  # frame t0 of an int8 spike buffer
+        if mem is not None and stack:
+            raise ValueError("the membrane tap runs on the per-layer launches (sfsn_gsn_stack_scan requires membrane == NULL)")
         if stack:
             segs = (ScanSegment * nl)()
             fin = (FusedInput * nl)()
@@ -277,7 +285,7 @@ class FullbandEngine:
                                                 ctypes.c_void_p(zin.data_ptr() + g * Hp * 4), nt * B, Hp, Hp, G * Hp, st), "sfsn_spike_proj")
                         self._count("spike_proj")
                 seg = (ScanSegment * 1)()
-                fill_segment(seg[0], self.layers[l], B, Hp, t0, zin, states[l], ws["s8"][l], spk[l])
+                fill_segment(seg[0], self.layers[l], B, Hp, t0, zin, states[l], ws["s8"][l], spk[l], None if mem is None else mem[l])
                 check(L.sfsn_gsn_layer_scan(seg, 1, nt, Hp, int(spec.shared), 0, st), "sfsn_gsn_layer_scan")
                 self._count("layer_scan")
         args = (_ptr(ri), _ptr(ws["s8"][-1]), Hp, _ptr(self.proj_q), _ptr(self.proj_dq), _ptr(self.proj_b), spec.act, B, F, T, S, spec.df,
@@ -288,6 +296,28 @@ class FullbandEngine:
         else:
             check(L.sfsn_fullband_proj_deepfilter_ragged(*args, _ptr(frames_dev), st), "sfsn_fullband_proj_deepfilter_ragged")
             self._count("projdf_ragged")
+
+    def _l0_as_alone(self, args, x, z0, g: int, B: int, t0: int, nt: int, own_frames) -> None:
+        """Behind sfsn_input_proj_f32 on the nt * B rows of a padded batch (K = F <= 192): that product is fp32 below 64 rows per
+        call and bf16-split from there on, and the two forms differ in the low bits (include/sfsn.h).  A clip alone has own_frames[b]
+        rows, the batch nt * B: where the batch took the split form, the rows of every clip whose own call stays below 64 are done
+        again in the fp32 form, in calls below 64 rows (a row's result depends on nothing but the row), as ``Engine`` does for
+        ``advance_ragged`` (engine.py, l0_alone).  A clip of 64 rows or more takes the split form alone and in any batch."""
+        if nt * B < 64:
+            return
+        rows = [np.arange(n) * B + b for b, n in enumerate(own_frames) if 0 < n < 64]
+        if not rows:
+            return
+        mine = np.sort(np.concatenate(rows))
+        F, Hp, G, P = self.F, self.Hp, self.G, ctypes.c_void_p
+        idx = torch.from_numpy(mine.astype(np.int64)).pin_memory().to(self.device, non_blocking=True)
+        xr = x[t0:t0 + nt].reshape(-1, F).index_select(0, idx)
+        zr = torch.empty((len(mine), Hp), dtype=torch.float32, device=self.device)
+        for r0 in range(0, len(mine), 63):
+            check(self.lib.sfsn_input_proj_f32(P(xr.data_ptr() + r0 * F * 4), args[1], args[2], P(zr.data_ptr() + r0 * Hp * 4),
+                                               min(63, len(mine) - r0), F, Hp, Hp, args[-1]), "sfsn_input_proj_f32")
+            self._count("inproj_alone")
+        z0.view(-1, G * Hp)[:, g * Hp:(g + 1) * Hp].index_copy_(0, idx, zr)
 
     @torch.no_grad()
     def forward_stft(self, noisy_cmp: torch.Tensor, want_layers: bool = False, want_counts: bool = False, frames=None,

@@ -51,6 +51,11 @@ after a stall or switches from a file to live input.  One launch each way on the
 fresh clip reads as zero state, so ``reset(clips); catch_up(prefix, clips)`` is the warm start from a recorded prefix (the sibling's
 ``prime``; its four method names are not defined here).
 
+A backlog of its own length per clip: ``catch_up_ragged(stft, frames, clips)`` / ``catch_up_wave_ragged(samples, lengths, clips)`` equal the
+single-clip ``catch_up`` / ``catch_up_wave`` calls bit for bit in one call: one padded forward on the per-layer scans with the per-frame
+membrane tap and the length-aware epilogue, and a hand-back launch that takes every clip's rows at its own last frame
+(``sfsn_fullband_hop_advance_ragged``; the per-kernel sequence gathers the same rows).
+
 Held ticks: ``tick(frames, clips)`` / ``tick_wave(samples, clips)`` / ``tick_wave_host(samples, clips)`` advance only the listed clips
 of the batch; every other clip is HELD: its input row may hold anything (NaN included), its output row is zero, and its state, spike
 counts, ``clip_frames()`` and ``clip_calls()`` stay what they were, so that its next active call continues its utterance bit for bit
@@ -76,9 +81,9 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ragged
 from ._lib import FullbandHopDesc, FullbandWaveDesc, check
-from .clip_select import check_frames, check_samples, clip_indices, held_masks, runs
+from .clip_select import check_frames, check_samples, clip_indices, clip_lengths, held_masks, runs
 from .clip_state import ClipState, clip_list, fullband_sections, import_clips, layout_of, new_blob
 from .engine import SpikeSummary
 from .fullband_engine import FullbandEngine
@@ -540,10 +545,13 @@ class FullbandStreamingSession(SessionCommon):
             ws = cache[key] = self.eng._make_workspace(n, max(N, 1), T, stack)
         return ws
 
-    def _catch_up_run(self, idx, stft=None, samples=None, nocall: bool = False):
+    def _catch_up_run(self, idx, stft=None, samples=None, nocall: bool = False, lens=None):
         """``idx``: distinct clip indices in the caller's order; ``stft`` complex64 [len(idx), F, N], or (waveform mode) ``samples``
         float32 [len(idx), 128 c] contiguous, ``nocall``: the clips have made no call in their utterance.  Returns (enh [n, S, F, N],
-        mag or None) or the waveform blocks [n, S, 128 c].  Everything on torch's current stream."""
+        mag or None) or the waveform blocks [n, S, 128 c].  Everything on torch's current stream.  ``lens`` (``catch_up_ragged``):
+        clip ``idx[i]`` has ``lens[i]`` of the N frames (waveform mode: of the c calls) and the rest of its row is padding -- the same
+        seed, the padding zeroed, one forward with the membrane tap and every clip's end taken at its own last frame
+        (``_take_ragged``)."""
         eng, spec, dev, L = self.eng, self.eng.spec, self.dev, self.eng.lib
         n, hop, D, F, S, nl, Hp, HP8 = len(idx), self.hop, self.D, self.F, self.S, spec.layers, eng.Hp, eng.HP8
         f32 = dict(dtype=torch.float32, device=dev)
@@ -591,6 +599,9 @@ class FullbandStreamingSession(SessionCommon):
                     # first call, whose samples make no frame, [128 (j + 1), ..): the centred frame j + 3
                     lead = 3 if nocall else 2
                     stft = spectral.stft(wbuf, 512, 128)[:, :, lead:lead + N]
+                if lens is not None:  # (N >= 1: the longest clip has a frame)
+                    return self._run_ragged(idx, [v - int(nocall) for v in lens] if samples is not None else lens, stft, buf, flat, wbuf,
+                                            sel if h is None else None, nocall)
                 buf[:, :, D:].copy_(stft)
                 stack = eng._use_stack(n)
                 ws = self._catch_up_workspace(n, N, T, stack)
@@ -640,11 +651,90 @@ class FullbandStreamingSession(SessionCommon):
             lead0 = torch.zeros((n, S, 128), **f32)  # (the first call's block)
             return torch.cat([lead0, wo], -1) if wo is not None else lead0
 
+    def _run_ragged(self, idx, own, stft, buf, flat, wbuf, sel, nocall: bool):
+        """The rest of ``_catch_up_run`` with per-clip lengths, behind the seed: ``own[i]`` new frames of clip ``idx[i]`` (0: a clip
+        without a call whose backlog is its first call alone) in rows of ``Nmax = stft.shape[-1]`` frames.  ``buf`` [n, F, D + Nmax]
+        holds the history, ``flat`` the clips' (h, c), ``wbuf`` the waveform context rows or None, ``sel`` the clips as a device index
+        (per-kernel tier).  The padding is zeroed whatever the caller left there (the scans run over it: nothing of it may be NaN);
+        ONE forward on the per-layer launches with the membrane tap and the length-aware epilogue; then every clip's rows at its own
+        last frame go back into the session -- ``sfsn_fullband_hop_advance_ragged`` on the one-launch tier, stream-ordered gathers
+        on the per-kernel tier -- and its origin moves back by its own launches."""
+        eng, spec, dev, L = self.eng, self.eng.spec, self.dev, self.eng.lib
+        n, hop, D, F, S, nl, Hp, HP8 = len(idx), self.hop, self.D, self.F, self.S, spec.layers, eng.Hp, eng.HP8
+        f32 = dict(dtype=torch.float32, device=dev)
+        N = stft.shape[-1]
+        T = D + N
+        h = self._hop
+        st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        fdev = ragged.upload(own, dev)  # (pinned, on the current stream: no synchronisation)
+        keep = torch.arange(N, device=dev).unsqueeze(0) < fdev.unsqueeze(1)
+        buf[:, :, D:].copy_(torch.where(keep.unsqueeze(1), stft, torch.zeros((), dtype=stft.dtype, device=dev)))
+        ws = self._catch_up_workspace(n, N, T, False)
+        x = torch.empty((T, n, F), **f32)
+        states = [(flat[l, 0], flat[l, 1]) for l in range(nl)]  # (left after the last PADDED frame: not read again)
+        spk = [torch.empty((T, n, Hp), **f32) for _ in range(nl)]
+        mem = [torch.empty((T, n, Hp), **f32) for _ in range(nl)]
+        enh = torch.empty((n, S, F, T, 2), **f32)
+        mag = torch.empty((n, S, F, T), **f32) if S == 1 else None
+        ends = fdev + D  # each clip's frames within its [history | new] row
+        if not torch.cuda.is_current_stream_capturing():
+            eng._errors.poll()
+        eng._launch_frames(torch.view_as_real(buf), n, T, D, N, False, ws, x, states, spk, None, enh, mag, frames_dev=ends, mem=mem,
+                           own_frames=own)
+        if h is None:
+            last = (ends - 1).long()  # (own >= hop >= 1 on spectrum sessions, the only ones of this tier)
+            rows = torch.arange(n, device=dev)
+            for l in range(nl):
+                self._flat[l, 0].index_copy_(0, sel, spk[l][last, rows])
+                self._flat[l, 1].index_copy_(0, sel, mem[l][last, rows])
+            for j, b in enumerate(idx):  # the D + hop frames that end with the clip's own last one
+                self.hist[b].copy_(buf[j, :, D + own[j] - self.Th:D + own[j]])
+            if self._rows is not None:  # each clip's own frames' spikes, added to its counts
+                tmp = torch.zeros((nl, n), dtype=torch.int64, device=dev)
+                for jobs in row_count_jobs([(t, 1) for t in ws["s8"]], tmp, T=T, R=n):
+                    check(L.sfsn_spike_count_rows_ragged(jobs, len(jobs), D, N, ctypes.c_void_p(ends.data_ptr()), n, st),
+                          "sfsn_spike_count_rows_ragged")
+                    eng._count("spike_count")
+                self._rows.index_add_(1, sel, tmp)
+            return torch.view_as_complex(enh)[..., D:].contiguous(), (mag[..., D:].contiguous() if mag is not None else None)
+        slots, wstate, ola = self._state_pointers()
+        src = _lib.FullbandAdvanceRaggedSrc()
+        src.Bp, src.Nmax, src.b0, src.T = n, N, 0, T
+        src.frames, src.stft_ri = fdev.data_ptr(), torch.view_as_real(buf).data_ptr()
+        for l in range(nl):  # (the new frames of the [T][n][.] buffers)
+            src.layer[l].spikes_i8, src.layer[l].membrane = ws["s8"][l].data_ptr() + D * n * HP8, mem[l].data_ptr() + D * n * Hp * 4
+        wo = None
+        if wbuf is not None:
+            wo = torch.empty((n, S, 128 * N), **f32)
+            src.wave_ctx, src.wave_stride, src.window = wbuf.data_ptr(), wbuf.shape[1], h["wave"]["window"].data_ptr()
+            src.enh_ri, src.wave_out = enh.data_ptr(), wo.data_ptr()
+        arr = (ctypes.c_int * n)(*idx)
+        rc = L.sfsn_fullband_hop_advance_ragged(h["ref"], slots, wstate, ola, arr, n, ctypes.byref(src), st)
+        if rc:
+            check(rc, "sfsn_fullband_hop_advance_ragged")
+        self._count("advance_ragged")
+        # every clip's origin moves back by ITS OWN launches replaced (32-bit wrap-around, as the launch's unsigned difference), behind
+        # the queued launches
+        back = ragged.upload([v + int(nocall) for v in own] if wbuf is not None else [v // hop for v in own], dev)
+        for i, b in enumerate(idx):
+            h["origin"][b:b + 1].sub_(back[i:i + 1])
+        if wbuf is None:
+            return torch.view_as_complex(enh)[..., D:].contiguous(), (mag[..., D:].contiguous() if mag is not None else None)
+        return torch.cat([torch.zeros((n, S, 128), **f32), wo], -1) if nocall else wo
+
     def _catch_up_clips(self, what: str, clips, given) -> list:
         idx = clip_indices(clips, self.B, what, duplicates="refuse", empty="refuse")
         if given != len(idx):
             raise RuntimeError(f"{what}: a backlog of {given} clips for {len(idx)} clip indices")
         return idx
+
+    _MIXED_KINDS = ("{what}: clip {none} has made no call in its current utterance and clip {some} has: they get different frame counts "
+                    "-- make one call per kind")
+
+    def _call_kinds(self, idx):
+        """The listed clips that have made no call in their utterance, and the ones that have (waveform sessions)."""
+        calls = self.clip_calls()
+        return [b for b in idx if calls[b] < 1], [b for b in idx if calls[b] >= 1]
 
     def catch_up(self, stft: torch.Tensor, clips=None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         """Run a BACKLOG of ``N`` frames on clips of a running session at the speed of the offline kernels: ``stft`` complex64
@@ -685,15 +775,79 @@ class FullbandStreamingSession(SessionCommon):
             raise RuntimeError("open the session with waveform=True")
         idx = self._catch_up_clips("catch_up_wave", clips, samples.shape[0] if isinstance(samples, torch.Tensor) and samples.dim() == 2 else -1)
         Ls = check_samples("catch_up_wave", samples, len(idx), self.dev)
-        calls = self.clip_calls()
-        none = [b for b in idx if calls[b] < 1]
-        some = [b for b in idx if calls[b] >= 1]
+        none, some = self._call_kinds(idx)
         if none and some:
-            raise ValueError(f"catch_up_wave: clip {none[0]} has made no call in its current utterance and clip {some[0]} has: they get "
-                             "different frame counts -- make one call per kind")
+            raise ValueError(self._MIXED_KINDS.format(what="catch_up_wave", none=none[0], some=some[0]))
         res = self._catch_up_run(idx, samples=samples.contiguous(), nocall=bool(none))
         self._clip_c0[idx] -= Ls // 128
         return res
+
+    def catch_up_ragged(self, stft: torch.Tensor, frames, clips=None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """``catch_up`` with a backlog of ITS OWN LENGTH per clip, in one call: ``stft`` complex64 [len(clips), F, Nmax] on the device,
+        row i for ``clips[i]`` (``None``: every clip; any order of distinct indices); ``frames``: a sequence or CPU int tensor,
+        ``frames[i]`` the frames row i really holds -- a positive multiple of ``hop``, at most ``Nmax`` (``ValueError`` naming the
+        clip; a wrong count of lengths is a ``ValueError`` too).  Whatever row i holds at frames ``>= frames[i]`` is ignored, NaN
+        included.
+
+        The call returns, and leaves behind, exactly what the single-clip calls ``catch_up(stft[i:i+1, :, :frames[i]],
+        clips=[clips[i]])`` would have: ``(enh_stft [.., S, F, Nmax], enh_mag`` or None``)`` equal over each clip's own frames and
+        zero past them; ``clip_frames()``, the spike counts and every section of ``export_state`` equal bit for bit, in both tiers.
+        Unlisted clips are untouched, a fresh clip reads as zero state.
+
+        One seed launch, ONE padded forward from the carried state -- the per-layer scans with the per-frame membrane tap (the
+        scans' own end state is the one after the last padded frame; ``sfsn_gsn_stack_scan`` has no tap) and the length-aware
+        epilogue (``sfsn_fullband_proj_deepfilter_ragged``) -- and one hand-back launch (``sfsn_fullband_hop_advance_ragged``) that
+        takes every clip's rows at its own last frame and moves its origin back by its own launches; the per-kernel tier gathers the
+        same rows.  Where layer 0's input product depends on the row count (``F <= 192``), each clip's rows take the form its own
+        call would have taken.  The lengths go to the device from pinned memory: ordered on torch's current stream, no
+        synchronisation.  Equal lengths: the call IS ``catch_up``, plus padding of the result.  One call costs about three
+        single-clip ``catch_up`` calls whatever the number of clips (profiles/cirm_catchup_ragged.md: 0.9 ms at the recipe), so it
+        pays from FOUR distinct lengths on (1.14 x at four, 2.4 x at eight); up to three, loop over ``catch_up``."""
+        if self.waveform:
+            raise RuntimeError("this session was opened with waveform=True: use catch_up_wave_ragged(samples, lengths)")
+        idx = self._catch_up_clips("catch_up_ragged", clips, stft.shape[0] if isinstance(stft, torch.Tensor) and stft.dim() == 3 else -1)
+        Nmax = check_frames("catch_up_ragged", stft, len(idx), self.F, self.dev, 1)
+        lens = clip_lengths("catch_up_ragged", frames, idx, self.hop, f"the session's hop ({self.hop})", Nmax, "frames")
+        N = max(lens)
+
+        def padded(t):  # zeros behind the longest clip, up to the caller's Nmax
+            return t if t is None or N == Nmax else torch.nn.functional.pad(t, (0, Nmax - N))
+
+        if min(lens) == N:
+            enh, mag = self.catch_up(stft[..., :N], clips=clips)
+        else:
+            enh, mag = self._catch_up_run(idx, stft=stft[..., :N], lens=lens)
+            self._clip_f0[idx] -= np.asarray(lens, dtype=self._clip_f0.dtype)
+        return padded(enh), padded(mag)
+
+    def catch_up_wave_ragged(self, samples: torch.Tensor, lengths, clips=None) -> torch.Tensor:
+        """``catch_up_ragged`` for waveform sessions (``host_io`` included; device tensors in and out): ``samples`` float32
+        [len(clips), 128 * cmax], ``lengths[i]`` the samples row i really holds, a positive multiple of 128 and at most
+        ``128 * cmax``.  Returns [.., S, 128 * cmax]: over each clip's own samples what ``catch_up_wave(samples[i:i+1, :lengths[i]],
+        clips=[clips[i]])`` returns, zeros behind; the session is left where those calls leave it (STFT state, overlap-add sums,
+        ``clip_calls()`` and ``clip_frames()`` included).  Both kinds of clip are taken, one kind per call as in ``catch_up_wave``
+        (the same ``ValueError`` for a mix): a clip that has made a call gets ``c_b = lengths[b] / 128`` frames; a clip that has made
+        no call yet gets ``c_b - 1`` frames behind a block of zeros and an STFT state that ends ``128 c_b`` samples into its row --
+        ``c_b = 1`` (no frame at all) is fine beside longer clips without a call."""
+        if not self.waveform:
+            raise RuntimeError("open the session with waveform=True")
+        idx = self._catch_up_clips("catch_up_wave_ragged", clips,
+                                   samples.shape[0] if isinstance(samples, torch.Tensor) and samples.dim() == 2 else -1)
+        Lmax = check_samples("catch_up_wave_ragged", samples, len(idx), self.dev)
+        lens = clip_lengths("catch_up_wave_ragged", lengths, idx, 128, "128", Lmax, "samples")
+        Ls = max(lens)
+
+        def padded(t):
+            return t if Ls == Lmax else torch.nn.functional.pad(t, (0, Lmax - Ls))
+
+        if min(lens) == Ls:
+            return padded(self.catch_up_wave(samples[:, :Ls], clips=clips))
+        none, some = self._call_kinds(idx)
+        if none and some:
+            raise ValueError(self._MIXED_KINDS.format(what="catch_up_wave", none=none[0], some=some[0]))
+        res = self._catch_up_run(idx, samples=samples[:, :Ls].contiguous(), nocall=bool(none), lens=[v // 128 for v in lens])
+        self._clip_c0[idx] -= np.asarray(lens, dtype=self._clip_c0.dtype) // 128
+        return padded(res)
 
     # ---- moving a clip: its state out of its slot, and into a slot of this or another session ------------------------------------
     def _state_signature(self) -> tuple:

@@ -992,7 +992,7 @@ class StreamingSession(SessionCommon):
         launches; the per-kernel tier gathers the same rows.  The lengths go to the device from pinned memory: ordered on torch's
         current stream, no synchronisation.  Equal lengths: the call IS ``advance``.  Refused: resident sessions and, where the
         lengths differ, ``cumulative_laplace_norm`` models (``NotImplementedError``: one ``advance`` call per length); waveform
-        sessions (``RuntimeError``: ``advance_wave_ragged``).  Not for cIRM-GSN sessions."""
+        sessions (``RuntimeError``: ``advance_wave_ragged``).  cIRM-GSN sessions: ``FullbandStreamingSession.catch_up_ragged``."""
         self._refuse_resident("advance_ragged")
         if self.waveform:
             raise RuntimeError("this session was opened with waveform=True: use advance_wave_ragged(samples, lengths)")
