@@ -16,6 +16,10 @@ by per-clip means of the whole utterance, which a stream does not have: they com
 --calibrate SECONDS of the file (Separator.norm_stats) and are handed to the session (streaming(norm_stats=...)).  The default, the
 whole file, reproduces the offline result model(wave) bit for bit; anything shorter is a modelling choice this project makes no
 accuracy claim about.
+
+--resample 3 takes a 48 kHz file and writes a 48 kHz file (384 samples per hop), --s16 hands the session the file's 16-bit samples as
+they are and writes what it returns: decimation, interpolation and both format conversions run inside the same one launch
+(streaming(resample=3, sample_format="s16"); --model fullsubnet and frozen).  The filters add 95 samples at 48 kHz to the lead-in.
 """
 import argparse
 import os
@@ -56,12 +60,21 @@ def main():
     ap.add_argument("--zoo", choices=("s", "m"), default="m", help="--model frozen: baseline_s or baseline_m")
     ap.add_argument("--calibrate", type=float, default=None, metavar="SECONDS", help="--model frozen: take the normalisation statistics "
                     "from an offline pass over the first SECONDS of the file (default: the whole file = the offline result)")
+    ap.add_argument("--resample", type=int, choices=(1, 3), default=1, help="3: the file is 48 kHz; it is decimated and the result "
+                    "interpolated back inside the hop's launch")
+    ap.add_argument("--s16", action="store_true", help="hand the session 16-bit PCM and take 16-bit PCM back (converted inside the launch)")
     args = ap.parse_args()
+    outer = args.resample != 1 or args.s16
+    if args.model == "cirm" and outer:
+        ap.error("--resample / --s16: built for --model fullsubnet and frozen (the cIRM-GSN sessions are a follow-up)")
+    rate, n = 16000 * args.resample, 128 * args.resample
+    io_kw = dict(resample=args.resample, sample_format="s16" if args.s16 else "f32") if outer else {}
     if args.model == "cirm" and args.synops:
         ap.error("--synops: cIRM-GSN streaming sessions do not count spikes (count_spikes is built for --model fullsubnet only)")
     with wave.open(args.inp, "rb") as w:
-        assert w.getnchannels() == 1 and w.getsampwidth() == 2 and w.getframerate() == 16000, "16 kHz mono 16-bit PCM expected"
-        x = np.frombuffer(w.readframes(w.getnframes()), dtype=np.int16).astype(np.float32) / 32768.0
+        assert w.getnchannels() == 1 and w.getsampwidth() == 2 and w.getframerate() == rate, f"{rate} Hz mono 16-bit PCM expected"
+        pcm = np.frombuffer(w.readframes(w.getnframes()), dtype=np.int16)
+        x = pcm.astype(np.float32) / 32768.0
     if args.model == "cirm":
         from spiking_fullsubnet_amd.modeling_cirm_gsn import Model as CirmGsn
         model = CirmGsn(**CIRM_GSN)
@@ -79,32 +92,38 @@ def main():
     if args.model == "cirm":
         sess = model.streaming(batch=1, waveform=True, host_io=True)
     elif args.model == "frozen":
-        n_cal = len(x) if args.calibrate is None else min(len(x), max(1024, int(args.calibrate * 16000)))
-        stats = model.norm_stats(torch.from_numpy(x[:n_cal].copy()).reshape(1, -1).to("cuda"))
+        x16 = x
+        if args.resample == 3:  # the statistics are the model's: taken at its own rate
+            from spiking_fullsubnet_amd import spectral
+            x16 = spectral.resample_down3(torch.from_numpy(x[:len(x) // 3 * 3].copy()).reshape(1, -1).to("cuda"))[0][0].cpu().numpy()
+        n_cal = len(x16) if args.calibrate is None else min(len(x16), max(1024, int(args.calibrate * 16000)))
+        stats = model.norm_stats(torch.from_numpy(x16[:n_cal].copy()).reshape(1, -1).to("cuda"))
         print(f"statistics from the first {n_cal / 16000:.2f} s: full-band mean {float(stats.mu_fb[0]):.6g}, "
               f"sub-band means {[round(v, 6) for v in stats.mu_sb[:, 0].tolist()]}")
-        sess = model.streaming(batch=1, waveform=True, host_io=True, count_spikes=args.synops, norm_stats=stats)
+        sess = model.streaming(batch=1, waveform=True, host_io=True, count_spikes=args.synops, norm_stats=stats, **io_kw)
     else:
-        sess = model.streaming(batch=1, waveform=True, host_io=True, count_spikes=args.synops)
-    n_hops = -(-len(x) // 128) + 3  # + the 3 hops of algorithmic delay
-    xp = np.zeros(n_hops * 128, np.float32)
-    xp[:len(x)] = x
-    y = np.zeros(n_hops * 128, np.float32)
+        sess = model.streaming(batch=1, waveform=True, host_io=True, count_spikes=args.synops, **io_kw)
+    lead = 3 * n + (95 if args.resample == 3 else 0)  # the 3 hops of algorithmic delay (+ the two filters' 47.5 samples each)
+    n_hops = -(-(len(x) + lead) // n)
+    src = pcm if args.s16 else x
+    xp = np.zeros(n_hops * n, src.dtype)
+    xp[:len(x)] = src
+    y = np.zeros(n_hops * n, src.dtype)
     lat = []
     for c in range(n_hops):
         t0 = time.perf_counter()
-        o = sess.step_wave_host(torch.from_numpy(xp[128 * c:128 * (c + 1)]).reshape(1, 128))
+        o = sess.step_wave_host(torch.from_numpy(xp[n * c:n * (c + 1)]).reshape(1, n))
         lat.append(time.perf_counter() - t0)
-        y[128 * c:128 * (c + 1)] = o[0, 0].numpy()
+        y[n * c:n * (c + 1)] = o[0, 0].numpy()
     sess.check_errors()
-    y = y[384:384 + len(x)]  # drop the lead-in
+    y = y[lead:lead + len(x)]  # drop the lead-in
     with wave.open(args.out, "wb") as w:
         w.setnchannels(1)
         w.setsampwidth(2)
-        w.setframerate(16000)
-        w.writeframes((np.clip(y, -1.0, 1.0) * 32767.0).astype(np.int16).tobytes())
+        w.setframerate(rate)
+        w.writeframes((y if args.s16 else (np.clip(y, -1.0, 1.0) * 32767.0).astype(np.int16)).tobytes())
     lat = np.sort(np.asarray(lat[10:])) * 1e6
-    print(f"{len(x) / 16000:.2f} s of audio, {n_hops} hops: per-hop latency p50 {lat[len(lat) // 2]:.1f} us, p99 {lat[int(len(lat) * 0.99)]:.1f} us "
+    print(f"{len(x) / rate:.2f} s of audio, {n_hops} hops: per-hop latency p50 {lat[len(lat) // 2]:.1f} us, p99 {lat[int(len(lat) * 0.99)]:.1f} us "
           f"({8000.0 / lat[len(lat) // 2]:.0f} x real time)")
     if args.synops:  # the utterance as streamed: every frame the session computed (the zero-padded tail included)
         from spiking_fullsubnet_amd import metric

@@ -682,6 +682,64 @@ int sfsn_stream_hop(const sfsn_hop_desc* desc /* host */, void* stream);
  * Not for the resident form.  The cIRM-GSN hop has its own held entries: sfsn_fullband_stream_hop_held / _wave_held. */
 int sfsn_stream_hop_held(const sfsn_hop_desc* desc /* host */, const uint64_t* held_bits /* host, ceil(B/64) words, bit b = clip b is held */, void* stream);
 
+/* ---- Outer samples: three times the model's rate and / or 16-bit PCM (additive exports; the ABI version stays 21) -------------------
+ * One linear-phase low-pass h[0 .. 95], given by the caller as float32 (the package: sinc((k - 47.5) / 3) / 3 * kaiser(96, 8)[k],
+ * normalised to sum 1 in float64, then rounded), serves both ways:
+ *   down (3 -> 1)   y[m] = sum_{k = 0 .. 95} taps[k] x[3 m + 2 - k],          x[n < 0] = the carried samples (zero at the start);
+ *   up   (1 -> 3)   z[3 m + p] = sum_{j = 0 .. 31} phase_taps[32 p + j] y[m - j],   phase_taps[32 p + j] = 3 h[3 j + p] (rounded once).
+ * Summation order (the stand-alone kernels and the hop give the same bits): ONE fp32 accumulator from 0.0f, fmaf, ascending k (j).
+ * Carried state: down, per row 96 floats -- the last 93 input samples as float32, oldest first, 3 words of padding (written zero);
+ *                up, per row 32 floats -- the last 31 values of y, oldest first, one word of padding.
+ * Formats: SFSN_SAMPLE_F32; SFSN_SAMPLE_S16 in: (float)s * 2^-15 (exact); out: clamp(rintf(v * 32768), -32768, 32767), ties to even,
+ * NaN -> 0.  Strides count samples of the buffer's own format. */
+#define SFSN_SAMPLE_F32 0
+#define SFSN_SAMPLE_S16 1
+/* in: B rows of 3 n_out samples of in_format, row b at in + b * in_stride samples (in_stride >= 3 n_out; what lies between rows is never
+ * read); out: float32 [B][n_out]; state: [B][96] read and updated in place, or NULL = zeros and nothing carried.  A signal fed in
+ * chunks with its state carried gives the bits of one call.  SFSN_EINVAL, in this order: an unknown format; a NULL in / taps / out,
+ * B or n_out < 1, in_stride < 3 n_out.  Both refusals are answered without a device. */
+int sfsn_resample_down3(const void* in, int in_format, int B, int n_out, long long in_stride, const float* taps /* [96] */,
+                        float* state /* [B][96], nullable */, float* out /* [B][n_out] */, void* stream);
+/* in: float32 [R][n_in]; out: R rows of 3 n_in samples of out_format, row r at out + r * out_stride samples (only those 3 n_in are
+ * written); state: [R][32] read and updated in place, or NULL.  Refusals as above (out_format first). */
+int sfsn_resample_up3(const float* in /* [R][n_in] */, int R, int n_in, const float* phase_taps /* [3][32] */, float* state /* [R][32], nullable */,
+                      void* out, int out_format, long long out_stride, void* stream);
+
+/* sfsn_stream_hop / sfsn_stream_hop_held for a waveform descriptor whose OUTER samples differ from the model's: the conversion runs in
+ * the launch's first and last stage, by the waves that build the frame and that finish the inverse STFT -- no further launch, wait,
+ * hand-off, tag or workgroup. */
+typedef struct {
+    int ratio;                /* outer rate / model rate: 1 or 3 (128 * ratio samples per clip and launch, each way)               */
+    int format;               /* SFSN_SAMPLE_*: the format of wave_in AND wave_out                                                 */
+    const void* wave_in;      /* [B][128 * ratio] the new outer samples (may be pinned host memory, like desc->wave_in)            */
+    void* wave_out;           /* [B][S][128 * ratio] out (may be pinned host memory)                                               */
+    float* dec_state;         /* [B][96]    the decimator's carried samples, in/out (zero = start of an utterance); ratio 3 only    */
+    float* int_state;         /* [B][S][32] the interpolator's carried samples, in/out; ratio 3 only                              */
+    const float* taps;        /* [96]; ratio 3 only                                                                                */
+    const float* phase_taps;  /* [3][32]; ratio 3 only                                                                             */
+} sfsn_hop_io;
+/* io == NULL IS sfsn_stream_hop_held(desc, held_bits, stream) (and with held_bits == NULL, sfsn_stream_hop).  Otherwise desc->wave_in and
+ * desc->wave_out are ignored and the launch
+ *   reads   io->wave_in; every clip's dec_state row (as zero in the clip's first call of an utterance, k == clip_start[b] - 1, which is
+ *           how a restart reaches the filter with no extra launch); every pair's int_state row; taps, phase_taps; all sfsn_stream_hop reads;
+ *   writes  io->wave_out: U3(the 128 samples sfsn_stream_hop would have written) in io->format, stored before the pair's done word;
+ *           ZERO while the pair's frame index is < 2 (with or without clip_start -- the two hops torch.istft trims), and int_state is
+ *           then written as zero: the interpolator sees the zeros its caller sees;
+ *           wave_state [B][512]: the last 512 samples at the MODEL's rate, D3(io->wave_in) appended; dec_state: the last 93 outer samples;
+ *           everything else sfsn_stream_hop writes.
+ *   held    (bit b of held_bits) as sfsn_stream_hop_held, and: dec_state and int_state of the clip are not touched, io->wave_out of the
+ *           clip is zero in io->format.
+ * ratio 1 with SFSN_SAMPLE_F32 launches the kernels of sfsn_stream_hop(_held) on io's buffers; the other three combinations have
+ * instantiations of their own, in which the plain kernels' code is unchanged.  Returns, in this order:
+ *   io->ratio not 1 or 3                                   SFSN_EINVAL
+ *   io->format unknown                                     SFSN_EINVAL
+ *   desc NULL or not a waveform descriptor (wave_state)    SFSN_EINVAL
+ *   desc->hop != 1                                         SFSN_EUNSUPPORTED
+ *   a NULL io->wave_in / wave_out; ratio 3: a NULL state or tap pointer   SFSN_EINVAL
+ * then whatever sfsn_stream_hop_held returns.  All of these are answered without a device.  Not for the resident form. */
+int sfsn_stream_hop_io(const sfsn_hop_desc* desc /* host */, const sfsn_hop_io* io /* host, nullable */, const uint64_t* held_bits /* nullable */,
+                       void* stream);
+
 /* The RESIDENT form of the waveform hop (BASELINE.json configs[4] names a "persistent kernel"; round 3).  One launch serves hop
  * after hop of a waveform session with host completion words (wave_in, wave_out and done in pinned host memory, hop == 1):
  * for hop k = 0, 1, ... the host writes the 128 samples per clip into wave_in, then stores k + 1 into the 32-bit `doorbell`

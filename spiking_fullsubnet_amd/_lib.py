@@ -107,6 +107,14 @@ class HopDesc(ctypes.Structure):
                 ("clip_start", _P), ("spike_slots", _P)]
 
 
+SAMPLE_F32, SAMPLE_S16 = 0, 1  # SFSN_SAMPLE_*
+
+
+class HopIo(ctypes.Structure):  # sfsn_hop_io
+    _fields_ = [("ratio", _I), ("format", _I), ("wave_in", _P), ("wave_out", _P), ("dec_state", _P), ("int_state", _P), ("taps", _P),
+                ("phase_taps", _P)]
+
+
 class PrimeLayer(ctypes.Structure):  # sfsn_prime_layer
     _fields_ = [("spikes_i8", _P), ("c", _P)]
 
@@ -190,8 +198,8 @@ class FullbandAdvanceRaggedSrc(ctypes.Structure):  # sfsn_fullband_advance_ragge
 def _sources():
     """The files the library is made of, in the order the Makefile hashes them (SRCS)."""
     return [os.path.join(_HERE, "..", "include", "sfsn.h")] + [
-        os.path.join(CSRC, f) for f in ("sfsn_scan_dev.h", "sfsn_scan3_dev.h", "sfsn_scan3i_dev.h", "sfsn_scan3x_dev.h", "sfsn_scan3w_dev.h", "sfsn_scan3j_dev.h", "sfsn_scan3g_dev.h", "sfsn_feat_dev.h", "sfsn_fft_dev.h", "sfsn_hop_dev.h", "sfsn_hop_wave_dev.h", "sfsn_fullband_dev.h", "sfsn_host.h", "sfsn_scan_host.h", "sfsn_pair_dev.h", "sfsn_projdf_dev.h", "sfsn_kernels.hip", "sfsn_stack.hip", "sfsn_hop.hip", "sfsn_fft.hip", "sfsn_train.hip",
-                                  "sfsn_featproj.hip", "sfsn_projdf.hip", "sfsn_fullband.hip", "sfsn_fullband_train.hip", "sfsn_fullband_hop.hip", "sfsn_loss.hip", "sfsn_pit.hip", "sfsn_ragged.hip", "sfsn_pair16.hip", "sfsn_pair16e.hip", "sfsn_prime.hip", "sfsn_state.hip", "sfsn_pack.cpp")]
+        os.path.join(CSRC, f) for f in ("sfsn_scan_dev.h", "sfsn_scan3_dev.h", "sfsn_scan3i_dev.h", "sfsn_scan3x_dev.h", "sfsn_scan3w_dev.h", "sfsn_scan3j_dev.h", "sfsn_scan3g_dev.h", "sfsn_feat_dev.h", "sfsn_fft_dev.h", "sfsn_hop_dev.h", "sfsn_hop_wave_dev.h", "sfsn_fullband_dev.h", "sfsn_host.h", "sfsn_scan_host.h", "sfsn_pair_dev.h", "sfsn_projdf_dev.h", "sfsn_resample_dev.h", "sfsn_kernels.hip", "sfsn_stack.hip", "sfsn_hop.hip", "sfsn_fft.hip", "sfsn_train.hip",
+                                  "sfsn_featproj.hip", "sfsn_projdf.hip", "sfsn_fullband.hip", "sfsn_fullband_train.hip", "sfsn_fullband_hop.hip", "sfsn_loss.hip", "sfsn_pit.hip", "sfsn_ragged.hip", "sfsn_pair16.hip", "sfsn_pair16e.hip", "sfsn_prime.hip", "sfsn_state.hip", "sfsn_resample.hip", "sfsn_hop_io.hip", "sfsn_pack.cpp")]
 
 
 def source_hash() -> str:
@@ -342,6 +350,12 @@ def lib() -> ctypes.CDLL:
     L.sfsn_stream_hop.argtypes = [ctypes.POINTER(HopDesc), _P]
     L.sfsn_stream_hop_held.restype = _I  # desc, held_bits (ceil(B / 64) words, bit b = clip b is held), stream
     L.sfsn_stream_hop_held.argtypes = [ctypes.POINTER(HopDesc), ctypes.POINTER(ctypes.c_uint64), _P]
+    L.sfsn_stream_hop_io.restype = _I  # desc, io (nullable), held_bits (nullable), stream
+    L.sfsn_stream_hop_io.argtypes = [ctypes.POINTER(HopDesc), ctypes.POINTER(HopIo), ctypes.POINTER(ctypes.c_uint64), _P]
+    L.sfsn_resample_down3.restype = _I  # in, in_format, B, n_out, in_stride | taps, state, out, stream
+    L.sfsn_resample_down3.argtypes = [_P, _I, _I, _I, ctypes.c_longlong, _P, _P, _P, _P]
+    L.sfsn_resample_up3.restype = _I  # in, R, n_in | phase_taps, state | out, out_format, out_stride, stream
+    L.sfsn_resample_up3.argtypes = [_P, _I, _I, _P, _P, _P, _I, ctypes.c_longlong, _P]
     L.sfsn_hop_prime.restype = _I
     L.sfsn_hop_prime.argtypes = [ctypes.POINTER(HopDesc), ctypes.POINTER(_I), _I, ctypes.POINTER(PrimeSrc), _P]
     L.sfsn_hop_seed.restype = _I  # desc, clips, n_clips, dst, stream
@@ -464,7 +478,7 @@ EXPORTS = ("sfsn_abi_version", "sfsn_source_hash", "sfsn_strerror", "sfsn_device
            "sfsn_fullband_hop_state_export", "sfsn_fullband_hop_state_import", "sfsn_hop_seed", "sfsn_hop_advance",
            "sfsn_fullband_hop_seed", "sfsn_fullband_hop_advance", "sfsn_stream_hop_held",
            "sfsn_fullband_stream_hop_held", "sfsn_fullband_stream_hop_wave_held", "sfsn_hop_advance_ragged",
-           "sfsn_fullband_hop_advance_ragged")
+           "sfsn_fullband_hop_advance_ragged", "sfsn_resample_down3", "sfsn_resample_up3", "sfsn_stream_hop_io")
 
 
 def check(rc: int, what: str = "") -> None:

@@ -1139,6 +1139,7 @@ static int hop_fits_device(int nblocks) {
     return nblocks > cus ? SFSN_EUNSUPPORTED : SFSN_OK;
 }
 
+#ifndef SFSN_HOP_IO_UNIT  // (sfsn_hop_io.hip includes this file for the roles and the plan: the exports and their kernels stay here)
 extern "C" size_t sfsn_hop_scratch_bytes(const sfsn_hop_desc* desc) {
     HopParams p;
     size_t lds;
@@ -1167,6 +1168,8 @@ extern "C" int sfsn_hop_stages(const sfsn_hop_desc* desc, int* out, int cap) {
     return p.nstage;
 }
 
+#endif  // SFSN_HOP_IO_UNIT
+
 // the mask of a held launch, checked: SFSN_OK with `any` = some clip is held
 static int hop_held_mask(HopHeld& hm, bool& any, const sfsn_hop_desc* desc, const uint64_t* held_bits) {
     memset(&hm, 0, sizeof(hm));
@@ -1182,6 +1185,7 @@ static int hop_held_mask(HopHeld& hm, bool& any, const sfsn_hop_desc* desc, cons
     return SFSN_OK;
 }
 
+#ifndef SFSN_HOP_IO_UNIT
 static int hop_launch(const sfsn_hop_desc* desc, const uint64_t* held_bits, void* stream) {
     HopParams local;
     size_t lds;
@@ -1251,3 +1255,4 @@ extern "C" int sfsn_stream_hop_resident(const sfsn_hop_desc* desc, void* doorbel
     return g2 ? launch_lds<stream_hop_resident_kernel<2, false>>(grid, block, lds, st, local, bell, polls)
               : launch_lds<stream_hop_resident_kernel<1, false>>(grid, block, lds, st, local, bell, polls);
 }
+#endif  // SFSN_HOP_IO_UNIT

@@ -66,7 +66,7 @@ class Model(_EngineMixin, nn.Module):
         return True  # (eval mode without gradients: the engine for GSN, _forward_lstm for LSTM -- both below)
 
     def streaming(self, batch: int = 1, hop: int = 1, graph: bool = True, one_launch="auto", waveform: bool = False,
-                  host_io: bool = False, resident: bool = False, count_spikes: bool = False):
+                  host_io: bool = False, resident: bool = False, count_spikes: bool = False, resample: int = 1, sample_format: str = "f32"):
         """Frame-by-frame session (``fullband_streaming.FullbandStreamingSession``): ``step(frames [B, F, hop])`` with the GSN states
         and ``df_order - 1`` frames of history kept on the device, bit-identical to the offline forward on the concatenated input.
         ``one_launch``: True = the whole hop in one ``sfsn_fullband_stream_hop`` launch (``NotImplementedError`` where it does not cover
@@ -80,7 +80,13 @@ class Model(_EngineMixin, nn.Module):
         ``metric.compute_synops(session.spike_summary([b]), [], shared_weights=...)`` is clip b's SynOPs; together with ``waveform``
         it raises ``NotImplementedError`` (the waveform launch does not count).  A tick on which only some clips have input:
         ``session.tick(frames, clips)`` / ``tick_wave`` / ``tick_wave_host`` hold every other clip inside the same one launch.
-        ``resident`` is not built for this model.  GSN models on a HIP device."""
+        ``resident`` is not built for this model, nor are ``resample`` / ``sample_format`` other than ``1`` / ``"f32"`` (outer samples at
+        48 kHz or as 16-bit PCM: the Spiking-FullSubNet sessions have them; the device bodies are shared, the host side is a follow-up).
+        GSN models on a HIP device."""
+        if resample != 1:
+            raise NotImplementedError(f"cIRM-GSN streaming: resample={resample!r} is not built (the Spiking-FullSubNet sessions have it)")
+        if sample_format != "f32":
+            raise NotImplementedError(f"cIRM-GSN streaming: sample_format={sample_format!r} is not built (the Spiking-FullSubNet sessions have it)")
         if self.fb_model.sequence_model_name == "LSTM":
             raise NotImplementedError("cIRM-GSN streaming covers the GSN sequence model: an LSTM model runs on ATen and has no session")
         if resident:

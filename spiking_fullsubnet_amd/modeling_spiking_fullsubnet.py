@@ -252,13 +252,17 @@ class _EngineMixin:
         return Engine(self._spec(), state_dict, device, weight_bits=self.weight_bits)
 
     def streaming(self, batch: int = 1, hop: int = 1, graph: bool = True, rows_per_wg=None, one_launch="auto", waveform: bool = False,
-                  host_io: bool = False, resident: bool = False, idle_ms: int = 1000, count_spikes: bool = False, norm_stats=None):
+                  host_io: bool = False, resident: bool = False, idle_ms: int = 1000, count_spikes: bool = False, norm_stats=None,
+                  resample: int = 1, sample_format: str = "f32"):
         """Frame-by-frame session (``streaming.StreamingSession``): state and deep-filter history stay on the device between
         calls; one launch per hop (``sfsn_stream_hop``) where the library covers the model, else the offline kernels replayed
         from a HIP graph.  ``waveform=True``: samples in, samples out (``step_wave``).  ``count_spikes=True``: per-clip spike
         counts for ``session.spike_summary()`` (SynOPs / NeuronOPs).  The live front-end and the frozen one with
         ``cumulative_laplace_norm`` stream as they are; the frozen one with an offline norm needs the clips' statistics,
-        ``norm_stats=`` (``engine.NormStats``; ``NotImplementedError`` without, ``ValueError`` where the model takes none)."""
+        ``norm_stats=`` (``engine.NormStats``; ``NotImplementedError`` without, ``ValueError`` where the model takes none).
+        Waveform sessions take their samples as a live source delivers them: ``resample=3`` -- 48 kHz in and out, 384 samples per
+        call -- and ``sample_format="s16"`` -- int16 tensors in and out; both conversions run inside the hop's one launch
+        (``StreamingSession.step_wave``)."""
         from .streaming import OFFLINE_NORM_MESSAGE, StreamingSession
         spec = self._spec()
         if norm_stats is not None and not spec.laplace:
@@ -268,7 +272,7 @@ class _EngineMixin:
         self._check_mode()
         return StreamingSession(self.engine(), batch=batch, hop=hop, graph=graph, rows_per_wg=rows_per_wg, owner=self, one_launch=one_launch,
                                 waveform=waveform, host_io=host_io, resident=resident, idle_ms=idle_ms, count_spikes=count_spikes,
-                                norm_stats=norm_stats)
+                                norm_stats=norm_stats, resample=resample, sample_format=sample_format)
 
     def _check_mode(self, x=None):
         """The inference kernels have no autograd graph and no training-mode BatchNorm: the entry points that use them

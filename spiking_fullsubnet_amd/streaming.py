@@ -83,9 +83,10 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from ._lib import AdvanceRaggedSrc, AdvanceSrc, DfGroup, HopDesc, HOP_MAX_GROUPS, HOP_MAX_LAYERS, NORM_CUMLAPLACE, PrimeSrc, SeedDst, check
+from ._lib import AdvanceRaggedSrc, AdvanceSrc, DfGroup, HopDesc, HopIo, HOP_MAX_GROUPS, HOP_MAX_LAYERS, NORM_CUMLAPLACE, PrimeSrc, SeedDst, check
 from .clip_select import check_frames, check_samples, clip_indices, clip_lengths, held_masks, part_runs, runs, slot_order
 from .clip_state import ClipState, clip_list, hop_sections, import_clips, layout_of, new_blob
+from . import spectral
 from .engine import Engine, NormStats, SpikeSummary, _ptr
 from .session_common import SessionCommon, row_count_jobs
 
@@ -106,10 +107,25 @@ def _raw_stream(device_index: int) -> int:
 class StreamingSession(SessionCommon):
     """``step(frames [B, F, hop] complex64) -> (enh_stft [B, S, F, hop], enh_mag [B, S, F, hop])`` with state carried."""
 
+    # the plain session's samples (the constructor replaces them for resample=3 / sample_format="s16")
+    resample, sample_format, _io, _outer, _fmt_code, _fmt_dtype = 1, "f32", False, 128, 0, torch.float32
+
     def __init__(self, engine: Engine, batch: int = 1, hop: int = 1, graph: bool = True, rows_per_wg=None, owner=None,
                  one_launch="auto", waveform: bool = False, host_io: bool = False, resident: bool = False, idle_ms: int = 1000,
-                 count_spikes: bool = False, norm_stats: Optional[NormStats] = None):
+                 count_spikes: bool = False, norm_stats: Optional[NormStats] = None, resample: int = 1, sample_format: str = "f32"):
         spec = engine.spec
+        # outer samples (waveform sessions): `resample` times the model's rate, as float32 or 16-bit PCM; (1, "f32") is the plain session
+        if resample not in (1, 3):
+            raise ValueError(f"resample must be 1 or 3 (the session's samples at the model's rate or at three times it), got {resample!r}")
+        self._fmt_code, self._fmt_dtype = spectral.format_of(sample_format)
+        self.resample, self.sample_format = int(resample), sample_format
+        self._outer = 128 * self.resample  # samples per clip and call, each way
+        self._io = self.resample != 1 or sample_format != "f32"
+        if self._io and not waveform:
+            raise ValueError("resample / sample_format go with waveform=True")
+        if self._io and resident:
+            raise NotImplementedError(f"resident=True with resample={resample!r}, sample_format={sample_format!r}: the resident launch takes "
+                                      "float32 samples at the model's rate only")
         # the module the engine was packed from: reset() checks that its parameters have not changed since (the session's
         # captured graph holds pointers to THIS engine's packed weights)
         self._owner = weakref.ref(owner) if owner is not None else None
@@ -322,6 +338,8 @@ class StreamingSession(SessionCommon):
             if self.waveform:
                 st.update(state=spool.zeros((nb, 512), torch.float32), ola=spool.zeros((nb, S, 512), torch.float32),
                           spec_g=spool.zeros((nb, F, 4), torch.float32), enh_g=spool.zeros((nb, S, F, 4), torch.float32))
+                if self.resample == 3:  # the two filters' carried samples (include/sfsn.h: sfsn_hop_io)
+                    st.update(dec=spool.zeros((nb, 96), torch.float32), int=spool.zeros((nb, S, 32), torch.float32))
             if a:
                 desc.inp_ri = desc.hist_ri = desc.enh_ri = desc.enh_mag = a
                 if self.waveform:
@@ -347,10 +365,11 @@ class StreamingSession(SessionCommon):
         per = -(-B // n_parts)
         enh = torch.zeros((B, S, F, hop, 2), dtype=torch.float32, device=dev)
         mag = torch.zeros((B, S, F, hop), dtype=torch.float32, device=dev)
-        wave_out = torch.zeros((B, S, 128), dtype=torch.float32, device=dev) if self.waveform else None
+        wave_out = torch.zeros((B, S, self._outer), dtype=self._fmt_dtype, device=dev) if self.waveform else None
         host = None
         if self.host_io:  # pinned host memory the kernel reads / writes directly (hipHostMalloc: device-reachable at the same address)
-            host = dict(inp=torch.zeros((B, 128), dtype=torch.float32).pin_memory(), out=torch.zeros((B, S, 128), dtype=torch.float32).pin_memory(),
+            host = dict(inp=torch.zeros((B, self._outer), dtype=self._fmt_dtype).pin_memory(),
+                        out=torch.zeros((B, S, self._outer), dtype=self._fmt_dtype).pin_memory(),
                         done=torch.zeros((B * S,), dtype=torch.int32).pin_memory())
             host["done_np"] = host["done"].numpy()
             host["bell"] = torch.zeros((16,), dtype=torch.int32).pin_memory()  # the resident kernel's doorbell (word 0)
@@ -371,6 +390,13 @@ class StreamingSession(SessionCommon):
                 desc.wave_in, desc.wave_out = probe.data_ptr(), ptr(wave_out[b0:])  # (wave_in: set per call)
                 if host is not None:
                     desc.wave_out, desc.done = ptr(host["out"][b0:]), ptr(host["done"][b0 * S:])
+            io = None
+            if self._io:  # the launch goes through sfsn_stream_hop_io: the descriptor's own sample pointers are ignored
+                io = HopIo()
+                io.ratio, io.format, io.wave_out = self.resample, self._fmt_code, desc.wave_out
+                if self.resample == 3:
+                    taps, phase_taps = spectral.resample_taps(dev)
+                    io.dec_state, io.int_state, io.taps, io.phase_taps = ptr(st["dec"]), ptr(st["int"]), ptr(taps), ptr(phase_taps)
             # the clips' origins (launch index of each clip's frame 0): written by stream-ordered fills, handed to the launches from
             # the first reset(clips) on (until then the session-wide counters serve); a resident session reads pinned host memory
             origin = torch.zeros((nb,), dtype=torch.int32, device=dev)
@@ -387,7 +413,7 @@ class StreamingSession(SessionCommon):
             scratch = torch.zeros((nbytes // 4 + 1,), dtype=torch.int32, device=dev)  # word 0: the error flag
             desc.scratch, desc.scratch_bytes = ptr(scratch), nbytes
             # the error word of a launch is looked at, without blocking, at a later step (pinned copy behind the launch)
-            parts.append(dict(desc=desc, ref=ctypes.byref(desc), b0=b0, nb=nb, st=st, spool=spool.buf, scratch=scratch, origin=origin, slots=slots,
+            parts.append(dict(desc=desc, ref=ctypes.byref(desc), io=io, io_ref=None if io is None else ctypes.byref(io), b0=b0, nb=nb, st=st, spool=spool.buf, scratch=scratch, origin=origin, slots=slots,
                               err=torch.zeros((1,), dtype=torch.int32).pin_memory(), err_pending=False))
         return dict(parts=parts, desc=parts[0]["desc"], scratch=parts[0]["scratch"], wpool=wpool.buf, enh=torch.view_as_complex(enh),
                     mag=mag, wave_out=wave_out, host=host, bounds=[(part["b0"], part["nb"]) for part in parts], held_before=False)
@@ -406,10 +432,13 @@ class StreamingSession(SessionCommon):
                 self.check_errors()  # (synchronises, clears the sticky words and raises)
             d = part["desc"]
             d.frames_before = self.frames_done
-            setattr(d, field, base_ptr + part["b0"] * stride_bytes)
+            setattr(d if part["io"] is None else part["io"], field, base_ptr + part["b0"] * stride_bytes)
             if frame_index is not None:
                 d.frame_index = frame_index
-            if held is not None and any(held[pi]):
+            if part["io"] is not None:  # (outer samples: waveform sessions only, field is "wave_in")
+                words = (ctypes.c_uint64 * len(held[pi]))(*held[pi]) if held is not None and any(held[pi]) else None
+                name, fn, args = "sfsn_stream_hop_io", lib.sfsn_stream_hop_io, (part["ref"], part["io_ref"], words, st)
+            elif held is not None and any(held[pi]):
                 name, fn, args = "sfsn_stream_hop_held", lib.sfsn_stream_hop_held, (part["ref"], (ctypes.c_uint64 * len(held[pi]))(*held[pi]), st)
             else:
                 name, fn, args = "sfsn_stream_hop", lib.sfsn_stream_hop, (part["ref"], st)
@@ -495,6 +524,11 @@ class StreamingSession(SessionCommon):
         if self.resident:
             raise NotImplementedError(f"{what}: not on a resident session (resident=True): its launch holds the state while it runs")
 
+    def _refuse_outer(self, what: str) -> None:
+        if self._io:
+            raise NotImplementedError(f"{what}: not on a session with resample={self.resample!r}, sample_format={self.sample_format!r} "
+                                      "(a recorded prefix or backlog in outer samples is a follow-up: open a plain session for it)")
+
     # ---- holding clips: a hop that advances only some clips of the batch ----------------------------------------------------------
     def _hold(self, clips, what: str):
         """``clips=`` (not None) of a step: None where every clip is listed; otherwise
@@ -521,7 +555,14 @@ class StreamingSession(SessionCommon):
         for part in self._hop["parts"]:
             b0, nb = part["b0"], part["nb"]
             for i0, m in runs([b - b0 for b in range(b0, b0 + nb) if b not in held]):
-                part["st"]["state"][i0:i0 + m, 384:].copy_(src[b0 + i0:b0 + i0 + m])
+                rows = src[b0 + i0:b0 + i0 + m]
+                if self._io:  # outer samples: what the launch's first stage does to them, by the stand-alone kernels (same bits)
+                    rows = rows.to(self.dev, non_blocking=True)
+                    if self.resample == 3:
+                        rows, _ = spectral.resample_down3(rows, state=part["st"]["dec"][i0:i0 + m])
+                    else:
+                        rows = rows.to(torch.float32) * (1.0 / 32768.0)
+                part["st"]["state"][i0:i0 + m, 384:].copy_(rows)
             for i0, m in runs([b - b0 for b in range(b0, b0 + nb) if b in held]):
                 part["origin"][i0:i0 + m].add_(1)
         if hold is not None:
@@ -736,6 +777,7 @@ class StreamingSession(SessionCommon):
         further frames torch.stft(center=True) makes of these samples look into samples not yet heard and are not used; ``c = 1``
         has no frame, its samples only enter the STFT state."""
         self._refuse_resident("prime_wave")
+        self._refuse_outer("prime_wave")
         if not self.waveform:
             raise RuntimeError("open the session with waveform=True")
         idx, order = self._prime_clips(clips, samples.shape[0] if isinstance(samples, torch.Tensor) and samples.dim() == 2 else -1)
@@ -955,6 +997,7 @@ class StreamingSession(SessionCommon):
         accumulator in the hop's order and with its envelope.  Every listed clip must have made at least one call in its current
         utterance (``ValueError`` naming the clip; start such a clip with ``prime_wave``).  Exactness as for ``advance``."""
         self._refuse_resident("advance_wave")
+        self._refuse_outer("advance_wave")
         if not self.waveform:
             raise RuntimeError("open the session with waveform=True")
         idx, order = self._prime_clips(clips, samples.shape[0] if isinstance(samples, torch.Tensor) and samples.dim() == 2 else -1, "advance_wave")
@@ -1028,6 +1071,7 @@ class StreamingSession(SessionCommon):
         ``clip_calls`` included).  Every listed clip must have made at least one call in its current utterance (``ValueError``
         naming the clip, as ``advance_wave``)."""
         self._refuse_resident("advance_wave_ragged")
+        self._refuse_outer("advance_wave_ragged")
         if not self.waveform:
             raise RuntimeError("open the session with waveform=True")
         idx, order = self._prime_clips(clips, samples.shape[0] if isinstance(samples, torch.Tensor) and samples.dim() == 2 else -1, "advance_wave_ragged")
@@ -1064,6 +1108,8 @@ class StreamingSession(SessionCommon):
             return cached
         sig = [("model", "spiking_fullsubnet"), ("tier", "one_launch" if self._hop is not None else "per_kernel"), ("hop", self.hop),
                ("waveform", self.waveform), ("count_spikes", self.count_spikes), ("given_stats", self._stats is not None)]
+        if self._io:  # (a plain session's signature is what it was: its states move to and from sessions made before these options)
+            sig += [("resample", self.resample), ("sample_format", self.sample_format)]
         sig += [(k, tuple(v) if isinstance(v, list) else v) for k, v in dataclasses.asdict(self.eng.spec).items()
                 if k not in ("bn", "proj_name")]
         self._signature = tuple(sig)
@@ -1092,7 +1138,23 @@ class StreamingSession(SessionCommon):
         fcov = max(d.sb[g].feat.lo + d.sb[g].feat.n_units * d.sb[g].fc for g in range(ng))
         layout, nbytes = hop_sections(seqs, spec.cum_laplace, self.count_spikes, fcov, self.D, self.waveform, spec.num_spks)
         assert nbytes == eng.lib.sfsn_hop_state_bytes(self._hop["parts"][0]["ref"]), "clip_state.hop_sections restates include/sfsn.h"
+        self._launch_bytes = nbytes  # what sfsn_hop_state_export / _import move: the row's head
+        if self.resample == 3:  # the two filters' carried samples behind it, moved by row copies beside the launch
+            layout = layout + (("dec", nbytes, nbytes + 96 * 4), ("int", nbytes + 96 * 4, nbytes + 96 * 4 + spec.num_spks * 32 * 4))
+            nbytes = layout[-1][2]
         return layout, nbytes
+
+    def _filter_rows(self, name: str, idx, put=None):
+        """The rows of clips ``idx`` (caller's order) of the carried filter samples ``name`` ("dec" / "int") as float32 [len(idx), n];
+        ``put``: such rows, written into the session instead.  Stream-ordered row copies, one per run of ``_part_runs``."""
+        rows = []
+        for part, j0, local in self._part_runs(idx):
+            t, sel = part["st"][name].view(part["nb"], -1), self._clip_rows(local)
+            if put is None:
+                rows.append(t.index_select(0, sel))
+            else:
+                t.index_copy_(0, sel, put[j0:j0 + len(local)])
+        return None if put is not None else torch.cat(rows, dim=0)
 
     def _part_runs(self, idx) -> list:
         """[part, first position, local clip indices] for runs of consecutive positions of ``idx`` that lie in one part, 256 at most
@@ -1115,14 +1177,17 @@ class StreamingSession(SessionCommon):
         if self._hop is None:
             blob = self._export_rows(idx, nbytes, layout)
         else:
-            blob = new_blob(len(idx), nbytes, layout, self.dev)
+            head = self._launch_bytes
+            blob = new_blob(len(idx), head, layout if head == nbytes else layout[:-2], self.dev)
             st = ctypes.c_void_p(_raw_stream(self._dev_index))
             for part, j0, local in self._part_runs(idx):
                 arr = (ctypes.c_int * len(local))(*local)
                 with torch.cuda.device(self.dev):
-                    rc = self.eng.lib.sfsn_hop_state_export(part["ref"], arr, len(local), ctypes.c_void_p(blob.data_ptr() + j0 * nbytes), st)
+                    rc = self.eng.lib.sfsn_hop_state_export(part["ref"], arr, len(local), ctypes.c_void_p(blob.data_ptr() + j0 * head), st)
                 if rc:
                     check(rc, "sfsn_hop_state_export")
+            if head != nbytes:
+                blob = torch.cat([blob] + [self._filter_rows(name, idx).view(torch.uint8).view(len(idx), -1) for name in ("dec", "int")], dim=1)
         stats = None
         if self._stats is not None:
             s = self._stats.select(idx)
@@ -1150,6 +1215,11 @@ class StreamingSession(SessionCommon):
             self._import_rows(idx, state, blob, layout)
             return
         self._first_call_made(idx)
+        if self._launch_bytes != nbytes:
+            head = self._launch_bytes
+            for name, a, b in layout[-2:]:
+                self._filter_rows(name, idx, blob[:, a:b].contiguous().view(torch.float32))
+            blob = blob[:, :head].contiguous()
         st = ctypes.c_void_p(_raw_stream(self._dev_index))
         for part, j0, local in self._part_runs(idx):
             arr = (ctypes.c_int * len(local))(*local)
@@ -1343,11 +1413,24 @@ class StreamingSession(SessionCommon):
 
         ``clips``: as for ``step`` -- only the listed clips make this call; a held clip's row of ``samples`` is ignored, it gets
         zeros, its ``clip_calls`` stays, and its next active call returns what that call would have returned (the three-call delay
-        line of its OWN calls).  A clip may be held at the session's first call, and before it has ever run."""
+        line of its OWN calls).  A clip may be held at the session's first call, and before it has ever run.
+
+        Outer samples (``resample=3`` and / or ``sample_format="s16"`` at ``model.streaming``): ``samples`` is ``[B, 128 * resample]`` of
+        float32 or int16 and the result ``[B, S, 128 * resample]`` of the same format -- 48 kHz and 16-bit PCM as a decoder or a sound
+        card delivers them, converted inside the same one launch (``sfsn_stream_hop_io``): int16 -> ``s * 2**-15``, a 96-tap low-pass
+        and decimation by 3 with carried samples (``D3``), the hop, interpolation by 3 with carried samples (``U3``), and
+        ``Q(v) = clamp(rint(v * 32768), -32768, 32767)`` (ties to even, NaN -> 0).  Call by call the result is
+        ``Q(U3(control(D3(x * 2**-15))))`` with ``control`` a plain float32 session of the same model on the same calls: bit for bit
+        what ``spectral.resample_down3``, that session and ``spectral.resample_up3`` give with their states carried.  The delay is
+        the three calls above plus 95 outer samples (47.5 each way through the linear-phase filter): 3 * 384 + 95 = 1247 samples at
+        48 kHz, 26 ms.  ``reset(clips)``, ``clips=`` holding and ``export_state`` / ``import_state`` (sections ``"dec"`` / ``"int"``)
+        carry the filters with the clip; ``prime_wave`` / ``advance_wave`` / ``advance_wave_ragged`` and ``resident=True`` are not
+        built for such sessions (``NotImplementedError``)."""
         if not self.waveform:
             raise RuntimeError("open the session with waveform=True")
-        if samples.device != self.dev or samples.dtype != torch.float32 or tuple(samples.shape) != (self.B, 128) or not samples.is_contiguous():
-            raise RuntimeError(f"expected contiguous float32 {(self.B, 128)} on {self.dev}, got {samples.dtype} {tuple(samples.shape)}")
+        if samples.device != self.dev or samples.dtype != self._fmt_dtype or tuple(samples.shape) != (self.B, self._outer) or not samples.is_contiguous():
+            what = "float32" if not self._io else f"{self._fmt_dtype} (resample={self.resample}, sample_format={self.sample_format!r})".replace("torch.", "")
+            raise RuntimeError(f"expected contiguous {what} {(self.B, self._outer)} on {self.dev}, got {samples.dtype} {tuple(samples.shape)}")
         h = self._hop
         out = h["wave_out"]
         hold = None if clips is None else self._hold(clips, "step_wave")
@@ -1358,7 +1441,7 @@ class StreamingSession(SessionCommon):
         if c == 0:  # no frame ends here yet (frame 0 covers samples [-256, 256)): the samples only enter the state
             self._first_wave_call(samples, hold)
             return torch.zeros_like(out)
-        self._launch_hops(samples.data_ptr(), 128 * 4, "wave_in", frame_index=c - 1, held=None if hold is None else hold[2])
+        self._launch_hops(samples.data_ptr(), self._outer * samples.element_size(), "wave_in", frame_index=c - 1, held=None if hold is None else hold[2])
         if hold is not None:
             self._held_bookkeeping(hold[1])
         if c < 3 and not self._primed:  # padded positions torch.istft trims (primed clips: the launch mutes each clip by its own index)
@@ -1431,7 +1514,14 @@ class StreamingSession(SessionCommon):
         hold = None if clips is None else self._hold(clips, "step_wave_host")
         if hold is not None and not hold[0]:  # nobody makes this call
             return torch.zeros_like(host["out"])
-        host["inp"].copy_(torch.as_tensor(samples, dtype=torch.float32).reshape(self.B, 128))
+        if self._io:
+            given = torch.as_tensor(samples)
+            if given.dtype != self._fmt_dtype or given.numel() != self.B * self._outer:
+                raise RuntimeError(f"expected {str(self._fmt_dtype).replace('torch.', '')} {(self.B, self._outer)} (resample={self.resample}, "
+                                   f"sample_format={self.sample_format!r}), got {given.dtype} {tuple(given.shape)}")
+            host["inp"].copy_(given.reshape(self.B, self._outer))
+        else:
+            host["inp"].copy_(torch.as_tensor(samples, dtype=torch.float32).reshape(self.B, 128))
         c = self._wave_calls
         self._wave_calls += 1
         if c == 0:
@@ -1442,7 +1532,8 @@ class StreamingSession(SessionCommon):
             target = self._ring_resident(c)
         else:
             target = h["parts"][0]["desc"].launch_index + 1
-            self._launch_hops(host["inp"].data_ptr(), 128 * 4, "wave_in", frame_index=c - 1, held=None if hold is None else hold[2])
+            self._launch_hops(host["inp"].data_ptr(), self._outer * host["inp"].element_size(), "wave_in", frame_index=c - 1,
+                              held=None if hold is None else hold[2])
             if hold is not None:
                 self._held_bookkeeping(hold[1])
         done, t_end, t_soft = host["done_np"], None, None
