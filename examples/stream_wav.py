@@ -19,7 +19,8 @@ accuracy claim about.
 
 --resample 3 takes a 48 kHz file and writes a 48 kHz file (384 samples per hop), --s16 hands the session the file's 16-bit samples as
 they are and writes what it returns: decimation, interpolation and both format conversions run inside the same one launch
-(streaming(resample=3, sample_format="s16"); --model fullsubnet and frozen).  The filters add 95 samples at 48 kHz to the lead-in.
+(streaming(resample=3, sample_format="s16"); --model cirm: Model.streaming_outer(resample=3, sample_format="s16")).  The filters add
+95 samples at 48 kHz to the lead-in.
 """
 import argparse
 import os
@@ -65,8 +66,6 @@ def main():
     ap.add_argument("--s16", action="store_true", help="hand the session 16-bit PCM and take 16-bit PCM back (converted inside the launch)")
     args = ap.parse_args()
     outer = args.resample != 1 or args.s16
-    if args.model == "cirm" and outer:
-        ap.error("--resample / --s16: built for --model fullsubnet and frozen (the cIRM-GSN sessions are a follow-up)")
     rate, n = 16000 * args.resample, 128 * args.resample
     io_kw = dict(resample=args.resample, sample_format="s16" if args.s16 else "f32") if outer else {}
     if args.model == "cirm" and args.synops:
@@ -90,7 +89,7 @@ def main():
         load_checkpoint(model, args.ckpt)
     model = model.to("cuda").eval()
     if args.model == "cirm":
-        sess = model.streaming(batch=1, waveform=True, host_io=True)
+        sess = model.streaming_outer(batch=1, host_io=True, **io_kw) if outer else model.streaming(batch=1, waveform=True, host_io=True)
     elif args.model == "frozen":
         x16 = x
         if args.resample == 3:  # the statistics are the model's: taken at its own rate

@@ -1218,6 +1218,36 @@ int sfsn_fullband_stream_hop_held(const sfsn_fullband_hop_desc* desc, unsigned* 
                                   unsigned held_mask /* bit b = clip b sits launch desc->launch_index out */, void* stream);
 int sfsn_fullband_stream_hop_wave_held(const sfsn_fullband_wave_desc* desc, unsigned held_mask, void* stream);
 
+/* sfsn_fullband_stream_hop_wave / _wave_held for OUTER samples that differ from the model's (sfsn_hop_io, as it stands above
+ * sfsn_stream_hop_io: three times the model's rate and / or 16-bit PCM): the conversion runs in the launch's first and last role, by the
+ * waves that build the frame and that finish the inverse STFT -- no further launch, wait, hand-off, tag or workgroup
+ * (csrc/sfsn_fullband_hop_io.hip; the device bodies are sfsn_stream_hop_io's, csrc/sfsn_hop_wave_dev.h).
+ * io == NULL IS sfsn_fullband_stream_hop_wave_held(desc, held_mask, stream) (and with held_mask == 0, sfsn_fullband_stream_hop_wave).
+ * Otherwise desc->wave_in and desc->wave_out are ignored and, with k = (int)(hop.launch_index - hop.clip_start[b]), the launch
+ *   reads   io->wave_in [B][128 ratio] (8-byte aligned, as wave_in is); every clip's dec_state row (as zero in the clip's first call,
+ *           k == -1, which is how a restart reaches the filter with no extra launch); every pair's int_state row; taps, phase_taps; all
+ *           sfsn_fullband_stream_hop_wave reads;
+ *   writes  io->wave_out [B][S][128 ratio] (8-byte aligned): U3(the 128 samples sfsn_fullband_stream_hop_wave would have written) in
+ *           io->format, stored before the pair's done word; ZERO while k < 2, and int_state is then written as zero: the interpolator
+ *           sees the zeros its caller sees;
+ *           wave_state [B][512]: the last 512 samples at the MODEL's rate, D3(io->wave_in) appended; dec_state: the last 93 outer samples;
+ *           everything else sfsn_fullband_stream_hop_wave writes.
+ *   held    (bit b of held_mask) as sfsn_fullband_stream_hop_wave_held, and: dec_state and int_state of the clip are not touched,
+ *           io->wave_out of the clip is zero in io->format.
+ * ratio 1 with SFSN_SAMPLE_F32 launches the kernels of sfsn_fullband_stream_hop_wave(_held) on io's buffers; the other three
+ * combinations have instantiations of their own (held and not), in which the plain kernels' code is unchanged.  The launch's dynamic
+ * LDS is the plain launch's or, with ratio 3, at least the STFT role's 40 KB with the decimator windows; the 160 KB refusal stays.
+ * Returns, in this order:
+ *   io->ratio not 1 or 3                                                   SFSN_EINVAL
+ *   io->format unknown                                                     SFSN_EINVAL
+ *   desc NULL or desc->wave_state NULL                                     SFSN_EINVAL
+ *   a NULL io->wave_in / wave_out; ratio 3: a NULL state or tap pointer    SFSN_EINVAL
+ *   with a bit of held_mask set: sfsn_fullband_stream_hop_held's mask checks (a bit at or beyond B, clip_start NULL: SFSN_EINVAL)
+ * then whatever sfsn_fullband_stream_hop_wave returns.  The refusals listed are answered without a device.
+ * (Added without an ABI bump: no existing struct or signature changed.) */
+int sfsn_fullband_stream_hop_wave_io(const sfsn_fullband_wave_desc* desc /* host */, const sfsn_hop_io* io /* host, nullable */,
+                                     unsigned held_mask, void* stream);
+
 /* Moving a clip of a cIRM-GSN session (csrc/sfsn_state.hip): sfsn_hop_state_export / sfsn_hop_state_import for sfsn_fullband_hop_desc --
  * the same launch, the same rules (one launch, plain stores, the half of h and hist_ri that launch launch_index reads, scratch and z0
  * untouched, the origin kept by the caller: clip_start[b'] = launch_index - age) and the same return codes.  What lives outside the

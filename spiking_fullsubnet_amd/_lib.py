@@ -199,7 +199,7 @@ def _sources():
     """The files the library is made of, in the order the Makefile hashes them (SRCS)."""
     return [os.path.join(_HERE, "..", "include", "sfsn.h")] + [
         os.path.join(CSRC, f) for f in ("sfsn_scan_dev.h", "sfsn_scan3_dev.h", "sfsn_scan3i_dev.h", "sfsn_scan3x_dev.h", "sfsn_scan3w_dev.h", "sfsn_scan3j_dev.h", "sfsn_scan3g_dev.h", "sfsn_feat_dev.h", "sfsn_fft_dev.h", "sfsn_hop_dev.h", "sfsn_hop_wave_dev.h", "sfsn_fullband_dev.h", "sfsn_host.h", "sfsn_scan_host.h", "sfsn_pair_dev.h", "sfsn_projdf_dev.h", "sfsn_resample_dev.h", "sfsn_kernels.hip", "sfsn_stack.hip", "sfsn_hop.hip", "sfsn_fft.hip", "sfsn_train.hip",
-                                  "sfsn_featproj.hip", "sfsn_projdf.hip", "sfsn_fullband.hip", "sfsn_fullband_train.hip", "sfsn_fullband_hop.hip", "sfsn_loss.hip", "sfsn_pit.hip", "sfsn_ragged.hip", "sfsn_pair16.hip", "sfsn_pair16e.hip", "sfsn_prime.hip", "sfsn_state.hip", "sfsn_resample.hip", "sfsn_hop_io.hip", "sfsn_pack.cpp")]
+                                  "sfsn_featproj.hip", "sfsn_projdf.hip", "sfsn_fullband.hip", "sfsn_fullband_train.hip", "sfsn_fullband_hop.hip", "sfsn_loss.hip", "sfsn_pit.hip", "sfsn_ragged.hip", "sfsn_pair16.hip", "sfsn_pair16e.hip", "sfsn_prime.hip", "sfsn_state.hip", "sfsn_resample.hip", "sfsn_hop_io.hip", "sfsn_fullband_hop_io.hip", "sfsn_pack.cpp")]
 
 
 def source_hash() -> str:
@@ -408,6 +408,8 @@ def lib() -> ctypes.CDLL:
     L.sfsn_fullband_stream_hop_held.argtypes = [ctypes.POINTER(FullbandHopDesc), _P, ctypes.c_uint, _P]
     L.sfsn_fullband_stream_hop_wave_held.restype = _I  # desc, held_mask, stream
     L.sfsn_fullband_stream_hop_wave_held.argtypes = [ctypes.POINTER(FullbandWaveDesc), ctypes.c_uint, _P]
+    L.sfsn_fullband_stream_hop_wave_io.restype = _I  # desc, io (nullable), held_mask, stream
+    L.sfsn_fullband_stream_hop_wave_io.argtypes = [ctypes.POINTER(FullbandWaveDesc), ctypes.POINTER(HopIo), ctypes.c_uint, _P]
     L.sfsn_fullband_hop_state_bytes.restype = ctypes.c_size_t  # desc, counted, wave; 0: not covered (host only)
     L.sfsn_fullband_hop_state_bytes.argtypes = [ctypes.POINTER(FullbandHopDesc), _I, _I]
     L.sfsn_fullband_hop_state_export.restype = _I  # desc, spike_slots, wave_state, ola_state | clips, n_clips | blob, stream
@@ -478,7 +480,8 @@ EXPORTS = ("sfsn_abi_version", "sfsn_source_hash", "sfsn_strerror", "sfsn_device
            "sfsn_fullband_hop_state_export", "sfsn_fullband_hop_state_import", "sfsn_hop_seed", "sfsn_hop_advance",
            "sfsn_fullband_hop_seed", "sfsn_fullband_hop_advance", "sfsn_stream_hop_held",
            "sfsn_fullband_stream_hop_held", "sfsn_fullband_stream_hop_wave_held", "sfsn_hop_advance_ragged",
-           "sfsn_fullband_hop_advance_ragged", "sfsn_resample_down3", "sfsn_resample_up3", "sfsn_stream_hop_io")
+           "sfsn_fullband_hop_advance_ragged", "sfsn_resample_down3", "sfsn_resample_up3", "sfsn_stream_hop_io",
+           "sfsn_fullband_stream_hop_wave_io")
 
 
 def check(rc: int, what: str = "") -> None:

@@ -498,6 +498,7 @@ __device__ __forceinline__ void fbh_istft_role(const FbhParams& p, int wg, char*
         [](bool&) {}, [&](int pair) { return (bool)((held >> (pair / p.S)) & 1u); });
 }
 
+#ifndef SFSN_FBH_IO_UNIT  // (sfsn_fullband_hop_io.hip includes this file for the roles, the plan and the checks: the kernels and the exports stay here)
 __global__ __launch_bounds__(HOP_THREADS) void fullband_stream_hop_kernel(const FbhParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int bi = (int)blockIdx.x;
@@ -564,6 +565,7 @@ __global__ __launch_bounds__(HOP_THREADS) void fullband_stream_hop_wave_kernel(c
     }
     fbh_istft_role(p, pi - p.nwg_proj, smem);
 }
+#endif  // SFSN_FBH_IO_UNIT
 
 // one held launch of one workgroup: the role its block index selects, in the order of the three kernels above.  (They keep their own
 // dispatch: routed through this one with HELD = false, the spectrum kernel came out with a 624-byte private segment.)
@@ -618,6 +620,7 @@ __device__ __forceinline__ void fbh_held_finish(const FbhParams& p, unsigned hel
         __hip_atomic_fetch_add(const_cast<unsigned*>(p.clip_start) + b, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     if (threadIdx.x == 0) st_agent(fin, 0u);
 }
+#ifndef SFSN_FBH_IO_UNIT
 __global__ __launch_bounds__(HOP_THREADS) void fullband_stream_hop_held_kernel(const FbhParams p, unsigned held) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     fbh_held_dispatch<false, false>(p, nullptr, held, smem);
@@ -633,6 +636,7 @@ __global__ __launch_bounds__(HOP_THREADS) void fullband_stream_hop_wave_held_ker
     fbh_held_dispatch<true, false>(p, nullptr, held, smem);
     fbh_held_finish(p, held, smem);
 }
+#endif  // SFSN_FBH_IO_UNIT
 
 #ifdef SFSN_FBH_ROLE_KERNELS
 // Each role as a kernel of its own, for the compile report only (never launched): the registers of one role, which the combined
@@ -684,6 +688,7 @@ __global__ __launch_bounds__(HOP_THREADS) void fbh_role_istft_kernel(const FbhPa
 // =====================================================================================================================
 // host side
 // =====================================================================================================================
+#ifndef SFSN_FBH_IO_UNIT
 extern "C" int sfsn_fullband_hop_check(int Hp, int n_layers, int F, int S, int df, int B, int hop, int D, int unshared) {
     if (Hp <= 0 || n_layers <= 0 || F <= 0 || S <= 0 || df <= 0 || B <= 0 || hop <= 0 || D != df - 1) return SFSN_EINVAL;
     if (unshared) return SFSN_EUNSUPPORTED;  // separate gate weights: twice the digits per agent
@@ -698,6 +703,7 @@ extern "C" int sfsn_fullband_wave_hop_check(int Hp, int n_layers, int F, int S, 
     if (rc != SFSN_OK) return rc;
     return F == FFT_F ? SFSN_OK : SFSN_EUNSUPPORTED;  // sfsn_fft_dev.h: 512-point frames, hop 128
 }
+#endif  // SFSN_FBH_IO_UNIT
 
 static int fbh_plan(FbhParams& p, size_t& lds, const sfsn_fullband_hop_desc* d, bool wave = false) {
     if (!d) return SFSN_EINVAL;
@@ -725,14 +731,17 @@ static int fbh_plan(FbhParams& p, size_t& lds, const sfsn_fullband_hop_desc* d, 
     return SFSN_OK;
 }
 
+#ifndef SFSN_FBH_IO_UNIT
 extern "C" size_t sfsn_fullband_hop_scratch_bytes(const sfsn_fullband_hop_desc* desc) {
     FbhParams p;
     size_t lds;
     return fbh_plan(p, lds, desc) == SFSN_OK ? 64 : 0;  // word 0: the error word; word 3: the held launches' finishing count
 }
+#endif  // SFSN_FBH_IO_UNIT
 
 static bool aligned8(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 7u) == 0; }
 
+#ifndef SFSN_FBH_IO_UNIT
 extern "C" size_t sfsn_fullband_hop_spike_slots(const sfsn_fullband_hop_desc* d) {
     if (!d || sfsn_fullband_hop_check(d->Hp, d->n_layers, d->F, d->S, d->df, d->B, d->hop, d->D, d->unshared) != SFSN_OK) return 0;
     return (size_t)d->n_layers * d->B * (d->Hp / 4);
@@ -804,6 +813,7 @@ extern "C" int sfsn_fullband_stream_hop_wave(const sfsn_fullband_wave_desc* w, v
     if (!w) return SFSN_EINVAL;
     return fbh_launch(&w->hop, w, stream);
 }
+#endif  // SFSN_FBH_IO_UNIT
 
 // ---- held clips: the mask's own checks come first and need no device
 static int fbh_held_mask(const sfsn_fullband_hop_desc* d, unsigned held) {
@@ -813,6 +823,7 @@ static int fbh_held_mask(const sfsn_fullband_hop_desc* d, unsigned held) {
     return SFSN_OK;
 }
 
+#ifndef SFSN_FBH_IO_UNIT
 extern "C" int sfsn_fullband_stream_hop_held(const sfsn_fullband_hop_desc* d, unsigned* spike_slots, unsigned held_mask, void* stream) {
     if (held_mask == 0) return spike_slots ? sfsn_fullband_stream_hop_counted(d, spike_slots, stream) : sfsn_fullband_stream_hop(d, stream);
     int rc = fbh_held_mask(d, held_mask);
@@ -831,3 +842,4 @@ extern "C" int sfsn_fullband_stream_hop_wave_held(const sfsn_fullband_wave_desc*
     if (rc != SFSN_OK) return rc;
     return fbh_launch(&w->hop, w, stream, nullptr, held_mask);
 }
+#endif  // SFSN_FBH_IO_UNIT

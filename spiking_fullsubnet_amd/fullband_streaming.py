@@ -67,8 +67,20 @@ saves the held clips' rows of its state before the replay and puts them back aft
 ``step*`` makes; an empty list launches nothing.  These are names of their own beside ``step`` / ``step_wave`` / ``step_wave_host``,
 whose signatures stay (the sibling's sessions take ``clips=`` on ``step*`` itself); profiles/cirm_hold.md has the measurement.
 
+Outer samples (``Model.streaming_outer(resample=3, sample_format="s16")``; the sibling's ``streaming(waveform=True, resample=...,
+sample_format=...)``): a waveform session whose samples are ``[B, 128 * resample]`` of float32 or int16, in and out -- 48 kHz and 16-bit
+PCM as a sound card delivers them, converted inside the same one launch (``sfsn_fullband_stream_hop_wave_io``,
+csrc/sfsn_fullband_hop_io.hip: the STFT role decimates in front of the frame, the inverse-STFT role interpolates and quantises behind
+it; the device bodies and the filters are the sibling's).  Call by call the result is ``Q(U3(control(D3(x * 2**-15))))`` with
+``control`` a plain waveform session on the same calls, bit for bit what ``spectral.resample_down3``, that session and
+``spectral.resample_up3`` give with their states carried per clip (tests/test_cirm_stream_io.py).  ``step_wave`` / ``tick_wave`` and
+their ``_host`` forms, ``reset(clips)`` (no extra launch: a clip's first call reads its decimator row as zero, a muted call writes
+its interpolator rows as zero), ``export_state`` / ``import_state`` (sections ``"dec"`` / ``"int"`` behind the launch's blob) and
+``catch_up_wave`` (the stand-alone resamplers around the model-rate backlog) carry the filters with the clip;
+``catch_up_wave_ragged`` refuses such sessions.  The delay is three calls plus 95 outer samples.
+
 Not covered here: ``resident`` sessions, ``count_spikes`` together with ``waveform``, waveform sessions beyond 16 clips or with
-separate gate weights, and LSTM models.
+separate gate weights, ragged backlogs in outer samples, and LSTM models.
 """
 from __future__ import annotations
 
@@ -81,8 +93,8 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 import torch
 
-from . import _lib, ragged
-from ._lib import FullbandHopDesc, FullbandWaveDesc, check
+from . import _lib, ragged, spectral
+from ._lib import FullbandHopDesc, FullbandWaveDesc, HopIo, check
 from .clip_select import check_frames, check_samples, clip_indices, clip_lengths, held_masks, runs
 from .clip_state import ClipState, clip_list, fullband_sections, import_clips, layout_of, new_blob
 from .engine import SpikeSummary
@@ -131,12 +143,26 @@ def wave_refusal(engine: FullbandEngine, batch: int, hop: int, frame=None) -> Op
 class FullbandStreamingSession(SessionCommon):
     """``step(frames [B, F, hop] complex64) -> (enh_stft [B, S, F, hop], enh_mag [B, S, F, hop] or None when S > 1)``;
     ``waveform=True``: ``step_wave(samples [B, 128] float32) -> [B, S, 128]`` (``host_io=True``: ``step_wave_host``, CPU tensors);
-    ``count_spikes=True``: ``spike_summary(clips)`` (spectrum sessions)."""
+    ``count_spikes=True``: ``spike_summary(clips)`` (spectrum sessions); ``resample=3`` / ``sample_format="s16"`` (waveform sessions,
+    ``Model.streaming_outer``): the samples are ``[B, 128 * resample]`` of float32 or int16, in and out."""
+
+    # the plain session's samples (the constructor replaces them for resample=3 / sample_format="s16")
+    resample, sample_format, _io, _outer, _fmt_code, _fmt_dtype = 1, "f32", False, 128, 0, torch.float32
 
     def __init__(self, engine: FullbandEngine, batch: int = 1, hop: int = 1, graph: bool = True, one_launch="auto", owner=None,
-                 waveform: bool = False, host_io: bool = False, frame=None, count_spikes: bool = False):
+                 waveform: bool = False, host_io: bool = False, frame=None, count_spikes: bool = False, resample: int = 1,
+                 sample_format: str = "f32"):
         if batch < 1 or hop < 1:
             raise ValueError("batch and hop must be positive")
+        # outer samples (waveform sessions): `resample` times the model's rate, as float32 or 16-bit PCM; (1, "f32") is the plain session
+        if resample not in (1, 3):
+            raise ValueError(f"resample must be 1 or 3 (the session's samples at the model's rate or at three times it), got {resample!r}")
+        self._fmt_code, self._fmt_dtype = spectral.format_of(sample_format)
+        self.resample, self.sample_format = int(resample), sample_format
+        self._outer = 128 * self.resample  # samples per clip and call, each way
+        self._io = self.resample != 1 or sample_format != "f32"
+        if self._io and not waveform:
+            raise ValueError("resample / sample_format go with waveform=True")
         if one_launch not in ("auto", True, False):
             raise ValueError("one_launch must be 'auto', True or False")
         self.waveform, self.host_io = bool(waveform), bool(host_io)
@@ -240,19 +266,29 @@ class FullbandStreamingSession(SessionCommon):
         """The waveform state, the granule scratch (zeroed once) and, with host_io, the pinned buffers the launch reads and writes."""
         B, F, S, dev, h = self.B, self.F, self.S, self.dev, self._hop
         f32 = dict(dtype=torch.float32, device=dev)
-        wv = dict(state=torch.zeros((B, 512), **f32), ola=torch.zeros((B, S, 512), **f32), out=torch.zeros((B, S, 128), **f32),
+        n, dt = self._outer, self._fmt_dtype
+        wv = dict(state=torch.zeros((B, 512), **f32), ola=torch.zeros((B, S, 512), **f32), out=torch.zeros((B, S, n), dtype=dt, device=dev),
                   window=torch.hann_window(512, **f32), spec_g=torch.zeros((B, F, 4), **f32), enh_g=torch.zeros((B, S, F, 4), **f32))
         wd.wave_state, wd.ola_state, wd.wave_out, wd.window = (wv[k].data_ptr() for k in ("state", "ola", "out", "window"))
         wd.spec_g, wd.enh_g = wv["spec_g"].data_ptr(), wv["enh_g"].data_ptr()
         wd.wave_in = wv["out"].data_ptr()  # (set per call)
         if self.host_io:  # pinned host memory the kernel reads / writes directly (device-reachable at the same address)
-            host = dict(inp=torch.zeros((B, 128), dtype=torch.float32).pin_memory(), out=torch.zeros((B, S, 128), dtype=torch.float32).pin_memory(),
+            host = dict(inp=torch.zeros((B, n), dtype=dt).pin_memory(), out=torch.zeros((B, S, n), dtype=dt).pin_memory(),
                         done=torch.zeros((B * S,), dtype=torch.int32).pin_memory())
             host["done_np"] = host["done"].numpy()
             wd.wave_in, wd.wave_out, wd.done = host["inp"].data_ptr(), host["out"].data_ptr(), host["done"].data_ptr()
             wv["host"] = host
+        io = None
+        if self._io:  # the launch goes through sfsn_fullband_stream_hop_wave_io: the descriptor's own sample pointers are ignored
+            io = HopIo()
+            io.ratio, io.format, io.wave_in, io.wave_out = self.resample, self._fmt_code, wd.wave_in, wd.wave_out
+            if self.resample == 3:  # the two filters' carried samples and taps (include/sfsn.h: sfsn_hop_io)
+                wv.update(dec=torch.zeros((B, 96), **f32), int=torch.zeros((B * S, 32), **f32))
+                wv["taps"], wv["phase_taps"] = spectral.resample_taps(dev)
+                io.dec_state, io.int_state = wv["dec"].data_ptr(), wv["int"].data_ptr()
+                io.taps, io.phase_taps = wv["taps"].data_ptr(), wv["phase_taps"].data_ptr()
         h["origin"].fill_(1)  # every clip's first call is launch 0: its frame 0 is launch 1
-        h.update(wave=wv, wdesc=wd, wref=ctypes.byref(wd))
+        h.update(wave=wv, wdesc=wd, wref=ctypes.byref(wd), io=io, io_ref=None if io is None else ctypes.byref(io))
 
     def _launch(self, name: str, *args) -> None:
         """One launch of the hop's entry point ``name`` (``args``: everything in front of the stream) on torch's current stream."""
@@ -270,11 +306,15 @@ class FullbandStreamingSession(SessionCommon):
     def _launch_wave(self, wave_in_ptr: int, held_mask: int = 0) -> None:
         """One waveform launch; ``held_mask`` (tick_wave*): bit b = clip b is held -- the held entry point, still one launch."""
         h = self._hop
-        h["wdesc"].wave_in = wave_in_ptr
-        if held_mask:
-            self._launch("sfsn_fullband_stream_hop_wave_held", h["wref"], held_mask)
+        if h["io"] is not None:  # outer samples: the io entry point, held or not -- still one launch
+            h["io"].wave_in = wave_in_ptr
+            self._launch("sfsn_fullband_stream_hop_wave_io", h["wref"], h["io_ref"], held_mask)
         else:
-            self._launch("sfsn_fullband_stream_hop_wave", h["wref"])
+            h["wdesc"].wave_in = wave_in_ptr
+            if held_mask:
+                self._launch("sfsn_fullband_stream_hop_wave_held", h["wref"], held_mask)
+            else:
+                self._launch("sfsn_fullband_stream_hop_wave", h["wref"])
         self._calls += 1
         if self._calls % 256 == 0:  # every 256 launches the error word follows them into pinned memory
             self._error_words_follow((h,))
@@ -283,7 +323,9 @@ class FullbandStreamingSession(SessionCommon):
         """Waveform streaming (``waveform=True``): ``samples`` float32 [B, 128], contiguous, on the device -- the next 8 ms of every
         clip, read in place in stream order.  Returns enhanced samples [B, S, 128]: call c of a clip's utterance returns the samples
         that entered with its call c - 3; a clip's first three calls return zeros.  One launch per call.  ``copy=False``: a view of the
-        session's buffer, valid until the next call."""
+        session's buffer, valid until the next call.  A session with outer samples (``Model.streaming_outer``) takes
+        ``[B, 128 * resample]`` of float32 or int16 and returns ``[B, S, 128 * resample]`` of the same format, converted inside the
+        same launch; a wrong shape or dtype is refused with a message that names the options."""
         if not self.waveform:
             raise RuntimeError("open the session with waveform=True")
         if self.host_io:
@@ -292,10 +334,10 @@ class FullbandStreamingSession(SessionCommon):
 
     def _call_wave(self, samples: torch.Tensor, hold, copy: bool) -> torch.Tensor:
         """``step_wave`` (``hold=None``) / ``tick_wave`` (``hold``: ``_hold``'s ``(active, held, mask)``) behind their refusals."""
-        if (samples.device != self.dev or samples.dtype != torch.float32 or tuple(samples.shape) != (self.B, 128) or not samples.is_contiguous()
-                or samples.data_ptr() % 8 != 0):
-            raise RuntimeError(f"expected contiguous float32 {(self.B, 128)} on {self.dev}, got {samples.dtype} {tuple(samples.shape)} on "
-                               f"{samples.device}")
+        if (samples.device != self.dev or samples.dtype != self._fmt_dtype or tuple(samples.shape) != (self.B, self._outer)
+                or not samples.is_contiguous() or samples.data_ptr() % 8 != 0):
+            raise RuntimeError(f"expected contiguous {self._sample_kind()} {(self.B, self._outer)} on {self.dev}, got {samples.dtype} "
+                               f"{tuple(samples.shape)} on {samples.device}")
         out = self._hop["wave"]["out"]
         if hold is None:
             self._launch_wave(samples.data_ptr())
@@ -305,6 +347,12 @@ class FullbandStreamingSession(SessionCommon):
             self._launch_wave(samples.data_ptr(), hold[2])
             self._held_bookkeeping(hold[1])
         return out.clone() if copy else out
+
+    def _sample_kind(self) -> str:
+        """The session's samples as an error message names them: the dtype, and for outer samples the options behind it."""
+        if not self._io:
+            return "float32"
+        return f"{self._fmt_dtype} (resample={self.resample}, sample_format={self.sample_format!r})".replace("torch.", "")
 
     def step_wave_host(self, samples, timeout_s: float = 2.0) -> torch.Tensor:
         """Waveform streaming with the samples on the HOST (``waveform=True, host_io=True``): ``samples`` = float32 [B, 128] CPU tensor
@@ -321,7 +369,14 @@ class FullbandStreamingSession(SessionCommon):
         host = self._hop["wave"]["host"]
         if hold is not None and not hold[0]:  # nobody makes this call
             return torch.zeros_like(host["out"])
-        host["inp"].copy_(torch.as_tensor(samples, dtype=torch.float32).reshape(self.B, 128))
+        if self._io:
+            given = torch.as_tensor(samples)
+            if given.dtype != self._fmt_dtype or given.numel() != self.B * self._outer:
+                raise RuntimeError(f"expected {str(self._fmt_dtype).replace('torch.', '')} {(self.B, self._outer)} (resample={self.resample}, "
+                                   f"sample_format={self.sample_format!r}), got {given.dtype} {tuple(given.shape)}")
+            host["inp"].copy_(given.reshape(self.B, self._outer))
+        else:
+            host["inp"].copy_(torch.as_tensor(samples, dtype=torch.float32).reshape(self.B, 128))
         target = (self._hop["desc"].launch_index + 1) & 0xFFFFFFFF
         if hold is None:
             self._launch_wave(host["inp"].data_ptr())
@@ -498,6 +553,9 @@ class FullbandStreamingSession(SessionCommon):
             if self.waveform:  # every clip's next call is its first (no frame yet): its frame 0 is the launch after the next
                 h["wave"]["state"].zero_()
                 h["wave"]["ola"].zero_()
+                if self.resample == 3:  # (a whole reset only: reset(clips) leaves the filters to the hop's first-call and mute rules)
+                    h["wave"]["dec"].zero_()
+                    h["wave"]["int"].zero_()
                 h["origin"].fill_(self._as_i32(h["desc"].launch_index + 1))
             else:
                 h["origin"].fill_(self._as_i32(h["desc"].launch_index))  # every clip's frame 0 is the next launch
@@ -770,10 +828,14 @@ class FullbandStreamingSession(SessionCommon):
         state, which makes no frame: ``c - 1`` frames (``c = 1`` writes only the STFT state).  The two kinds have different frame
         counts: all clips of one call must be of one kind (``ValueError`` naming the first clip of each).  The output blocks continue
         the clip's overlap-add accumulator in the hop's order and with its envelope; ``clip_calls()`` and ``clip_frames()`` advance
-        by ``c`` calls.  Bit for bit, as ``catch_up``."""
+        by ``c`` calls.  Bit for bit, as ``catch_up``.  On a session with outer samples (``Model.streaming_outer``) ``samples`` is
+        ``[len(clips), 128 * resample * c]`` of the session's dtype and the result ``[.., S, 128 * resample * c]`` of it
+        (``_catch_up_wave_outer``: both filters are left where the ``c`` calls would have left them)."""
         if not self.waveform:
             raise RuntimeError("open the session with waveform=True")
         idx = self._catch_up_clips("catch_up_wave", clips, samples.shape[0] if isinstance(samples, torch.Tensor) and samples.dim() == 2 else -1)
+        if self._io:
+            return self._catch_up_wave_outer(samples, idx)
         Ls = check_samples("catch_up_wave", samples, len(idx), self.dev)
         none, some = self._call_kinds(idx)
         if none and some:
@@ -781,6 +843,51 @@ class FullbandStreamingSession(SessionCommon):
         res = self._catch_up_run(idx, samples=samples.contiguous(), nocall=bool(none))
         self._clip_c0[idx] -= Ls // 128
         return res
+
+    def _catch_up_wave_outer(self, samples: torch.Tensor, idx) -> torch.Tensor:
+        """``catch_up_wave`` of a session with outer samples (``resample=3`` / ``sample_format="s16"``): ``samples``
+        [len(idx), 128 * resample * c] of the session's dtype -> [.., S, 128 * resample * c] of it, bit for bit the ``c`` calls of
+        ``step_wave``, both filters left where those calls leave them.  No kernel of its own: the backlog goes through
+        ``spectral.resample_down3`` from the clips' decimator rows (read as zero for clips without a call, as the hop reads them in a
+        first call), the model-rate samples through ``_catch_up_run``, its blocks through ``spectral.resample_up3`` from the clips'
+        interpolator rows -- read as zero for clips whose next call index is <= 2: the hop writes them as zero in every muted call,
+        and the muted blocks of the inner result are zero, so the interpolator sees what the hop's sees."""
+        n, S, r, dev, wv = len(idx), self.S, self.resample, self.dev, self._hop["wave"]
+        if samples.device != dev or samples.dtype != self._fmt_dtype:
+            raise RuntimeError(f"expected {self._sample_kind()} {(n, f'{self._outer} * c')} on {dev}, got {samples.dtype} {tuple(samples.shape)} "
+                               f"on {samples.device}")
+        Ls = samples.shape[1]
+        if Ls < self._outer or Ls % self._outer != 0:
+            raise ValueError(f"catch_up_wave: {Ls} samples is not a positive multiple of {self._outer} (resample={self.resample})")
+        none, some = self._call_kinds(idx)
+        if none and some:
+            raise ValueError(self._MIXED_KINDS.format(what="catch_up_wave", none=none[0], some=some[0]))
+        c, calls = Ls // self._outer, self.clip_calls()
+        x = samples.contiguous()
+        if r == 3:
+            sel = self._clip_rows(idx)
+            dec = wv["dec"].index_select(0, sel)
+            if none:
+                dec.zero_()
+            y, dec = spectral.resample_down3(x, dec)
+            wv["dec"].index_copy_(0, sel, dec)
+        else:
+            y = x.to(torch.float32) * (1.0 / 32768.0)  # (exact: sfsn_resample_dev.h's load of a 16-bit sample)
+        res = self._catch_up_run(idx, samples=y.contiguous(), nocall=bool(none))
+        self._clip_c0[idx] -= c
+        if r == 3:
+            pairs = self._clip_rows([b * S + s for b in idx for s in range(S)])
+            ist = wv["int"].index_select(0, pairs)
+            fresh = [i for i, b in enumerate(idx) if calls[b] <= 2]
+            if len(fresh) == n:
+                ist.zero_()
+            elif fresh:
+                ist.view(n, S * 32).index_fill_(0, self._clip_rows(fresh), 0.0)
+            z, ist = spectral.resample_up3(res.reshape(n * S, 128 * c), ist, sample_format=self.sample_format)
+            wv["int"].index_copy_(0, pairs, ist)
+            return z.view(n, S, 3 * 128 * c)
+        q = torch.round(res * 32768.0)  # (1, "s16"): sfsn_resample_dev.h's store -- rint, ties to even; NaN -> 0; clamped
+        return torch.clamp(torch.where(torch.isnan(q), torch.zeros_like(q), q), -32768.0, 32767.0).to(torch.int16)
 
     def catch_up_ragged(self, stft: torch.Tensor, frames, clips=None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         """``catch_up`` with a backlog of ITS OWN LENGTH per clip, in one call: ``stft`` complex64 [len(clips), F, Nmax] on the device,
@@ -831,6 +938,9 @@ class FullbandStreamingSession(SessionCommon):
         ``c_b = 1`` (no frame at all) is fine beside longer clips without a call."""
         if not self.waveform:
             raise RuntimeError("open the session with waveform=True")
+        if self._io:
+            raise NotImplementedError(f"catch_up_wave_ragged: not on a session with resample={self.resample!r}, sample_format="
+                                      f"{self.sample_format!r} (a ragged backlog in outer samples is a follow-up: loop over catch_up_wave)")
         idx = self._catch_up_clips("catch_up_wave_ragged", clips,
                                    samples.shape[0] if isinstance(samples, torch.Tensor) and samples.dim() == 2 else -1)
         Lmax = check_samples("catch_up_wave_ragged", samples, len(idx), self.dev)
@@ -857,6 +967,8 @@ class FullbandStreamingSession(SessionCommon):
             return cached
         sig = [("model", "cirm_gsn"), ("tier", "one_launch" if self._hop is not None else "per_kernel"), ("hop", self.hop),
                ("waveform", self.waveform), ("count_spikes", self.count_spikes), ("F", self.F), ("Hp", self.eng.Hp)]
+        if self._io:  # (a plain session's signature is what it was: its states move to and from sessions made before these options)
+            sig += [("resample", self.resample), ("sample_format", self.sample_format)]
         sig += [(k, v) for k, v in dataclasses.asdict(self.eng.spec).items() if k != "bn"]
         self._signature = tuple(sig)
         return self._signature
@@ -877,7 +989,20 @@ class FullbandStreamingSession(SessionCommon):
         layout, nbytes = fullband_sections(self.eng.spec.layers, self.eng.Hp, self.count_spikes, self.F, self.D, self.waveform, self.S)
         assert nbytes == self.eng.lib.sfsn_fullband_hop_state_bytes(self._hop["ref"], int(self.count_spikes), int(self.waveform)), \
             "clip_state.fullband_sections restates include/sfsn.h"
+        self._launch_bytes = nbytes  # what sfsn_fullband_hop_state_export / _import move: the row's head
+        if self.resample == 3:  # the two filters' carried samples behind it, moved by row copies beside the launch
+            layout = layout + (("dec", nbytes, nbytes + 96 * 4), ("int", nbytes + 96 * 4, nbytes + 96 * 4 + self.S * 32 * 4))
+            nbytes = layout[-1][2]
         return layout, nbytes
+
+    def _filter_rows(self, name: str, idx, put=None):
+        """The rows of clips ``idx`` (caller's order) of the carried filter samples ``name`` ("dec" / "int") as float32 [len(idx), n];
+        ``put``: such rows, written into the session instead.  Stream-ordered row copies."""
+        t, sel = self._hop["wave"][name].view(self.B, -1), self._clip_rows(idx)
+        if put is None:
+            return t.index_select(0, sel)
+        t.index_copy_(0, sel, put)
+        return None
 
     def _state_pointers(self):
         """(spike_slots, wave_state, ola_state) as the state launches take them (None: not part of this session)."""
@@ -902,7 +1027,8 @@ class FullbandStreamingSession(SessionCommon):
         if self._hop is None:
             blob = self._export_rows(idx, nbytes, layout)
         else:
-            blob = new_blob(len(idx), nbytes, layout, self.dev)
+            head = self._launch_bytes
+            blob = new_blob(len(idx), head, layout if head == nbytes else layout[:-2], self.dev)
             slots, wstate, ola = self._state_pointers()
             arr = (ctypes.c_int * len(idx))(*idx)  # (B <= 16: one launch)
             with torch.cuda.device(self.dev):
@@ -910,6 +1036,9 @@ class FullbandStreamingSession(SessionCommon):
                                                                  ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream))
             if rc:
                 check(rc, "sfsn_fullband_hop_state_export")
+            if head != nbytes:
+                blob = torch.cat([blob] + [self._filter_rows(name, idx).contiguous().view(torch.uint8).view(len(idx), -1) for name in ("dec", "int")],
+                                 dim=1)
         return ClipState(blob, self.clip_frames()[idx], self.clip_calls()[idx] if self.waveform else None, None, self._state_signature(),
                          layout)
 
@@ -926,6 +1055,10 @@ class FullbandStreamingSession(SessionCommon):
             self._import_rows(idx, state, blob, layout)
             return
         h = self._hop
+        if self._launch_bytes != nbytes:
+            for name, a, b in layout[-2:]:
+                self._filter_rows(name, idx, blob[:, a:b].contiguous().view(torch.float32))
+            blob = blob[:, :self._launch_bytes].contiguous()
         slots, wstate, ola = self._state_pointers()
         arr = (ctypes.c_int * len(idx))(*idx)
         with torch.cuda.device(self.dev):

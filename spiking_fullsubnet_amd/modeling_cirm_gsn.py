@@ -80,9 +80,9 @@ class Model(_EngineMixin, nn.Module):
         ``metric.compute_synops(session.spike_summary([b]), [], shared_weights=...)`` is clip b's SynOPs; together with ``waveform``
         it raises ``NotImplementedError`` (the waveform launch does not count).  A tick on which only some clips have input:
         ``session.tick(frames, clips)`` / ``tick_wave`` / ``tick_wave_host`` hold every other clip inside the same one launch.
-        ``resident`` is not built for this model, nor are ``resample`` / ``sample_format`` other than ``1`` / ``"f32"`` (outer samples at
-        48 kHz or as 16-bit PCM: the Spiking-FullSubNet sessions have them; the device bodies are shared, the host side is a follow-up).
-        GSN models on a HIP device."""
+        ``resident`` is not built for this model.  ``resample`` / ``sample_format`` other than ``1`` / ``"f32"`` raise
+        ``NotImplementedError`` HERE: outer samples at 48 kHz or as 16-bit PCM, converted inside the same one launch, come from a factory
+        of their own, ``streaming_outer(batch, host_io, resample=3, sample_format="s16")``.  GSN models on a HIP device."""
         if resample != 1:
             raise NotImplementedError(f"cIRM-GSN streaming: resample={resample!r} is not built (the Spiking-FullSubNet sessions have it)")
         if sample_format != "f32":
@@ -103,6 +103,33 @@ class Model(_EngineMixin, nn.Module):
         return FullbandStreamingSession(self.engine(), batch=batch, hop=hop, graph=graph, one_launch=one_launch, owner=self,
                                         waveform=waveform, host_io=host_io, frame=(self.n_fft, self.hop_length, self.win_length),
                                         count_spikes=count_spikes)
+
+    def streaming_outer(self, batch: int = 1, host_io: bool = False, resample: int = 3, sample_format: str = "s16"):
+        """A waveform session on the samples a sound card delivers: ``resample=3`` -- 48 kHz in and out, 384 samples per call -- and
+        ``sample_format="s16"`` -- int16 tensors in and out; ``(3, "s16")``, ``(3, "f32")`` and ``(1, "s16")`` exist.  The session is
+        ``streaming(waveform=True, host_io=host_io)``'s with ``step_wave`` / ``tick_wave`` / ``step_wave_host`` / ``tick_wave_host``
+        taking ``[B, 128 * resample]`` of the format and returning ``[B, S, 128 * resample]`` of it; decimation, interpolation and both
+        format conversions run inside the hop's one launch (``sfsn_fullband_stream_hop_wave_io``), and call by call the result is
+        ``Q(U3(control(D3(x * 2**-15))))`` with ``control`` the plain waveform session on the same calls, bit for bit
+        (``fullband_streaming``: outer samples).  The delay is three calls plus 95 outer samples.  ``ValueError``: ``resample`` not 1
+        or 3, an unknown format, or ``(1, "f32")``, which is ``streaming(waveform=True)``.  Everything else ``streaming(waveform=True)``
+        refuses is refused alike."""
+        from . import spectral
+        if resample not in (1, 3):
+            raise ValueError(f"resample must be 1 or 3 (the session's samples at the model's rate or at three times it), got {resample!r}")
+        spectral.format_of(sample_format)
+        if resample == 1 and sample_format == "f32":
+            raise ValueError("streaming_outer(resample=1, sample_format='f32'): the model's own samples are streaming(waveform=True)")
+        if self.fb_model.sequence_model_name == "LSTM":
+            raise NotImplementedError("cIRM-GSN streaming covers the GSN sequence model: an LSTM model runs on ATen and has no session")
+        self._check_mode()
+        if batch < 1:
+            raise ValueError("batch and hop must be positive")
+        if next(self.parameters()).device.type != "cuda":
+            raise NotImplementedError("waveform=True: cIRM-GSN streaming has no CPU path: move the module to a HIP device (`.to('cuda')`) first")
+        from .fullband_streaming import FullbandStreamingSession
+        return FullbandStreamingSession(self.engine(), batch=batch, hop=1, owner=self, waveform=True, host_io=host_io,
+                                        frame=(self.n_fft, self.hop_length, self.win_length), resample=resample, sample_format=sample_format)
 
     @torch.no_grad()
     def forward_stft(self, noisy_cmp, want_layers=False, want_counts=False, frames=None):
